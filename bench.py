@@ -28,6 +28,14 @@ Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + torch.cu
 front of the W warm-up steps the same schedule runs for >= --prewarm-s seconds (state restored afterwards; ``prewarm`` in the JSON line): an
 MI355X that idled through the set-up runs its first ~25 ms of work 10-15 % slow, and K = 20 steps are 5 ms (profiles/r05_experiments.md 10).
 
+A plain run (``python bench.py --gpus 1 --steps K --warmup W``) measures the headline only: set-up, pre-warm, W warm-up steps, the K timed
+steps, the JSON line (metric, value, unit, ms_per_step, ...).  Everything beside it -- the per-phase, drop-in and plug-in rates, the sustained
+region, the all-reduce timings, the rooflines, ``b_loop``, the frame-loop figures and the CPU baseline -- runs with ``--full`` (the
+``--no-*`` options still leave out single legs there).  ``--dump-outputs DIR`` writes what the timed path computed in its last step (the map
+and the camera poses after that step's update, and its loss) as DIR/<name>.npy (float32; at most 64 MB, a fixed seeded sample of Gaussian
+rows beyond that).  The scene is seeded and the last timed step starts from it (the map, the poses and the optimisers as set up), so that
+run after run, and build against build, that step sees the same inputs and its outputs can be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -119,12 +127,13 @@ def build_scene(name, dev, n_views, seed=0):
     return params, variables, frames, (N, W, H)
 
 
-def run_steps(params, variables, frames, bucket, rank, world, nsteps, opt_track, opt_map, track_state, start=0):
+def run_steps(params, variables, frames, bucket, rank, world, nsteps, opt_track, opt_map, track_state, start=0, last=None):
+    """`last`: a dict that receives the loss of the last step (``last['loss']``)."""
     from splatam_amd import slam
     n_views = len(frames) - 1
     for i in range(start, start + nsteps):
         if i % 5 < 2:
-            slam.tracking_iteration(params, frames[1], variables, 1, opt_track, track_state)
+            loss, _ = slam.tracking_iteration(params, frames[1], variables, 1, opt_track, track_state)
         else:
             view = 2 + (rank + i * world) % n_views
             data = frames[view]
@@ -136,7 +145,31 @@ def run_steps(params, variables, frames, bucket, rank, world, nsteps, opt_track,
             with torch.no_grad():
                 opt_map.step()
                 opt_map.zero_grad(set_to_none=True)
+        if last is not None and i == start + nsteps - 1:
+            last['loss'] = loss
     return variables
+
+
+DUMP_BUDGET_BYTES = (64 << 20) - (64 << 10)        # 64 MB in all, the .npy headers included
+
+
+def dump_outputs(dirpath, params, loss):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the map and the camera poses (``params``, updated in
+    place by that step) and the step's loss -- written as DIR/<name>.npy in float32.  Where the arrays would exceed 64 MB together, every
+    per-Gaussian array keeps the same fixed, seeded sample of rows (ascending), so that runs of the same workload stay comparable.  The
+    step starts from the seeded scene (main: the last timed step), so two runs agree to the rounding of the composites' float atomics."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in params.items()}
+    arrays["loss"] = np.array([float(loss)], dtype=np.float32)
+    n = params['means3D'].shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        per_row = sum(a.nbytes // n for a in arrays.values() if a.shape[:1] == (n,))
+        keep = max(1, (DUMP_BUDGET_BYTES - (total - per_row * n)) // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: (a[rows] if a.shape[:1] == (n,) else a) for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 SHARD_TRACKING = True       # --replicated-tracking clears it
@@ -786,6 +819,11 @@ def main():
     ap.add_argument("--launch-check", action="store_true", help="only exercise the N-rank launch (no GPU needed)")
     ap.add_argument("--replicated-tracking", action="store_true",
                     help="--gpus N > 1: every rank tracks the whole frame (no exchange) instead of sharding the frame's tile rows over the ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-phase / drop-in / plug-in rates, the sustained region, all-reduce "
+                         "timings, rooflines, b_loop, the frame-loop figures, the CPU baseline (default: the headline's K timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
     global SHARD_TRACKING
     SHARD_TRACKING = not args.replicated_tracking
@@ -824,18 +862,21 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    # the drop-in path works on its own copy of the map so that both engines start from the seeded scene
-    params_d = {k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}
-    bucket = sdist.GradBucket(params_d) if world > 1 else None
-    opt_track = slam.initialize_optimizer(params_d, slam.REPLICA_TRACKING['lrs'], tracking=True)
-    opt_map = slam.initialize_optimizer(params_d, slam.REPLICA_MAPPING['lrs'], tracking=False)
-    tstate = slam.TrackingState(params_d, 1)
+    full = args.full
+    # the drop-in path works on its own copy of the map so that both engines start from the seeded scene (the timed path of --engine
+    # dropin; beside the fused engine only --full's drop-in and plug-in figures use it)
+    if full or not fused:
+        params_d = {k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}
+        bucket = sdist.GradBucket(params_d) if world > 1 else None
+        opt_track = slam.initialize_optimizer(params_d, slam.REPLICA_TRACKING['lrs'], tracking=True)
+        opt_map = slam.initialize_optimizer(params_d, slam.REPLICA_MAPPING['lrs'], tracking=False)
+        tstate = slam.TrackingState(params_d, 1)
 
     # kernel-level figures are taken on the seeded initial map (before Adam moves it), so that they are
     # comparable from run to run and with scripts/kernel_driver.py
     roof = None
     mpix = ms_call = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and full and not args.no_roofline:
         # (BASELINE metric (i) first: the roofline leg below runs torch.profiler, and a process that has profiled once pays for it in every
         #  later autograd call -- the drop-in call is host-bound, it read 0.23 ms behind the profiler against 0.21 ms in a fresh process)
         mpix, ms_call = render_mpix(params_d, frames, shape, dev, reps=128)
@@ -851,6 +892,20 @@ def main():
         eng = FusedEngine(eparams, frames[1]['cam'], track_max_radius=variables['max_2D_radius'])
         eng.keep_map_grads = False      # (the loop discards a mapping iteration's gradients after the step, as the reference's zero_grad does)
         eng.begin_tracking(1)
+        start_state = {k: v.detach().clone() for k, v in eparams.items()}
+
+        def back_to_seeded(i):
+            """The map and the poses as seeded and a fresh optimiser for schedule step `i` (the mapping optimiser's moments for a mapping
+            step, the pose optimiser's state for a tracking step: neither reads the other's): the pre-warm's reset, whose kernels the
+            set-up and the pre-warm have loaded (torch's fused _foreach kernels cost ~20 ms at their first use and ~5 % of every later
+            step here), at most 12 small launches inside the clock."""
+            with torch.no_grad():
+                for k, v in eparams.items():
+                    v.copy_(start_state[k])
+            if i % 5 < 2 and not mode_c:
+                eng.begin_tracking(1)
+            else:
+                eng.reset_map_optimizer()
 
         def steps(n, start):
             if mode_c:
@@ -901,39 +956,50 @@ def main():
             raise SystemExit("instance lists overflowed during warm-up")
         barrier()
         t0 = time.perf_counter()
-        steps(args.steps, args.warmup)
+        steps(args.steps - 1, args.warmup)
+        # the LAST timed step starts from the seeded scene, so that what it computes (what --dump-outputs writes) is the same in every
+        # run with these arguments: the backward composites sum gradients with float atomics in a run-dependent order, and a chain of
+        # Adam steps turns that rounding into differences of a learning rate by ~60 steps.  The reset (one 14 MB device copy, the
+        # optimisers' moments zeroed) stays inside the clock, with or without --dump-outputs
+        back_to_seeded(args.warmup + args.steps - 1)
+        steps(1, args.warmup + args.steps - 1)
         barrier()
         elapsed = time.perf_counter() - t0
         if eng.check_overflow(grow=False):
             raise SystemExit("instance lists overflowed during the timed region: the result would be invalid")
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eparams, eng.loss())
         if world > 1:                       # every rank must agree on the length of the sustained region (it holds collectives)
             t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t[0])
-        # a sustained figure beside the K-step one: the same schedule for >= 6.5 s in ONE block (multiples of the 5-step mix period; the
-        # driver samples GPU utilisation every 5 s: at least one sample falls inside).  Tens of thousands of Adam steps on one synthetic
-        # view set would move the map until its lists outgrow the learnt buckets, so every 250 steps the map, the poses and the Adam
-        # state go back to their values at the start of the region (a 14 MB device copy: < 0.1 % of the block)
-        n_sus = max(args.steps, int(math.ceil(args.sustain_s * args.steps / max(elapsed, 1e-6) / 5.0)) * 5)
-        snapshot = {k: v.detach().clone() for k, v in eparams.items()}
-        barrier()
-        t1 = time.perf_counter()
-        done = 0
-        while done < n_sus:
-            nblk = min(250, n_sus - done)
-            steps(nblk, args.warmup + args.steps + done)
-            done += nblk
-            with torch.no_grad():
-                for k, v in eparams.items():
-                    v.copy_(snapshot[k])
-            eng.reset_map_optimizer()
-            eng.begin_tracking(1)
-        barrier()
-        sustained_s = time.perf_counter() - t1
-        sustained_ok = not eng.check_overflow(grow=False)
-        # the exchange step alone (rank-local average over 20 collectives of the flat gradient bucket)
+        n_sus = sustained_s = None
+        sustained_ok = True
         allreduce_ms = allreduce_small_ms = allreduce_small_folded_ms = None
-        if world > 1:
+        if full:
+            # a sustained figure beside the K-step one: the same schedule for >= 6.5 s in ONE block (multiples of the 5-step mix period;
+            # a sampler of GPU utilisation every 5 s sees at least one sample inside).  Tens of thousands of Adam steps on one synthetic
+            # view set would move the map until its lists outgrow the learnt buckets, so every 250 steps the map, the poses and the Adam
+            # state go back to their values at the start of the region (a 14 MB device copy: < 0.1 % of the block)
+            n_sus = max(args.steps, int(math.ceil(args.sustain_s * args.steps / max(elapsed, 1e-6) / 5.0)) * 5)
+            snapshot = {k: v.detach().clone() for k, v in eparams.items()}
+            barrier()
+            t1 = time.perf_counter()
+            done = 0
+            while done < n_sus:
+                nblk = min(250, n_sus - done)
+                steps(nblk, args.warmup + args.steps + done)
+                done += nblk
+                with torch.no_grad():
+                    for k, v in eparams.items():
+                        v.copy_(snapshot[k])
+                eng.reset_map_optimizer()
+                eng.begin_tracking(1)
+            barrier()
+            sustained_s = time.perf_counter() - t1
+            sustained_ok = not eng.check_overflow(grow=False)
+        # the exchange step alone (rank-local average over 20 collectives of the flat gradient bucket)
+        if full and world > 1:
             from splatam_amd.dist import all_reduce_sum_flat
             for _ in range(3):
                 all_reduce_sum_flat(eng.reduce_flat)
@@ -971,18 +1037,34 @@ def main():
             allreduce_small_folded_ms = 1e3 * (time.perf_counter() - t4) / 20
             eng.buf['sums'].zero_()
     else:
+        start_state = {k: v.detach().clone() for k, v in params_d.items()}
+        start_vars = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in variables.items()}
         variables = run_steps(params_d, variables, frames, bucket, rank, world, args.warmup, opt_track, opt_map, tstate, 0)
         barrier()
         t0 = time.perf_counter()
-        variables = run_steps(params_d, variables, frames, bucket, rank, world, args.steps, opt_track, opt_map, tstate, args.warmup)
+        last = {}
+        variables = run_steps(params_d, variables, frames, bucket, rank, world, args.steps - 1, opt_track, opt_map, tstate, args.warmup)
+        # the last timed step from the seeded scene, as on the fused engine (fresh optimisers and tracking state)
+        with torch.no_grad():
+            for k, v in params_d.items():
+                v.copy_(start_state[k])
+        opt_track.state.clear()
+        opt_map.state.clear()
+        tstate = slam.TrackingState(params_d, 1)
+        variables = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in start_vars.items()}
+        variables = run_steps(params_d, variables, frames, bucket, rank, world, 1, opt_track, opt_map, tstate, args.warmup + args.steps - 1, last)
         barrier()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, params_d, last['loss'].detach())
     if not fused:
         n_sus, sustained_s, allreduce_ms, allreduce_small_ms, allreduce_small_folded_ms, sustained_ok = args.steps, elapsed, None, None, None, True
     if world > 1:
-        t = torch.tensor([elapsed, sustained_s], device=dev, dtype=torch.float64)
+        t = torch.tensor([elapsed, elapsed if sustained_s is None else sustained_s], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, sustained_s = float(t[0]), float(t[1])
+        elapsed = float(t[0])
+        if sustained_s is not None:
+            sustained_s = float(t[1])
 
     def units(nsteps):
         """Work units of `nsteps` steps over all ranks.  Mix: a mapping step renders one view PER RANK (world iterations' worth
@@ -992,90 +1074,91 @@ def main():
         n_track = sum(1 for i in range(nsteps) if i % 5 < 2)        # (the schedule's phase is a multiple of 5 at every region start
         return n_track + (nsteps - n_track) * world                # when warmup and steps are; otherwise off by at most 2)
 
-    # per-phase rates (rank-local, informational)
-    n_phase = max(5, min(40, args.steps))
-    if fused:
-        track_rate = phase_rate(lambda: eng.tracking_iteration(frames[1], slam.REPLICA_TRACKING, shard=(rank, world) if (world > 1 and SHARD_TRACKING) else None,
-                                                               allreduce_sums=sdist.all_reduce_sum_flat), n_phase, dev)
-        map_rate = phase_rate(lambda: eng.mapping_iteration(frames[2], 2, slam.REPLICA_MAPPING), n_phase, dev)
+    if full:
+        # per-phase rates (rank-local, informational)
+        n_phase = max(5, min(40, args.steps))
+        if fused:
+            track_rate = phase_rate(lambda: eng.tracking_iteration(frames[1], slam.REPLICA_TRACKING, shard=(rank, world) if (world > 1 and SHARD_TRACKING) else None,
+                                                                   allreduce_sums=sdist.all_reduce_sum_flat), n_phase, dev)
+            map_rate = phase_rate(lambda: eng.mapping_iteration(frames[2], 2, slam.REPLICA_MAPPING), n_phase, dev)
 
-        # the tracking iteration with EVERY gradient the reference's backward() forms (dL/d rgb, opacity, scale too: the reference steps
-        # them with learning rate 0, configs/replica/splatam.py:71-79): the headline's tracking iterations leave them out
-        def track_full():
-            eng.loss_backward(frames[1], eng.track_time_idx, slam.REPLICA_TRACKING, tracking=True, map_grads=True,
-                              pose_adam=eng._pose_adam_args(slam.REPLICA_TRACKING))
-        track_rate_full = phase_rate(track_full, n_phase, dev) if world == 1 else None
-        # several ranks: the same tracking iteration replicated (every rank composites the whole frame, no exchange), and the mapping
-        # iteration with its gradient exchange -- beside the sharded / local rates above, so that a reader of the N-GPU line sees what
-        # each phase gains
-        track_rate_repl = map_rate_exch = None
-        if world > 1:
-            track_rate_repl = phase_rate(lambda: eng.tracking_iteration(frames[1], slam.REPLICA_TRACKING), n_phase, dev)
-            map_rate_exch = phase_rate(lambda: eng.mapping_iteration(frames[2], 2, slam.REPLICA_MAPPING, sdist.all_reduce_mean_flat), n_phase, dev)
-    n_drop = max(5, min(15, args.steps))
-    if fused:       # the drop-in path has not run yet: MIOpen / rocBLAS pick their kernels on the first calls
-        for _ in range(3):
-            slam.tracking_iteration(params_d, frames[1], variables, 1, opt_track, tstate)
-            slam.mapping_iteration(params_d, frames[2], variables, 2, opt_map)
-    track_rate_d = phase_rate(lambda: slam.tracking_iteration(params_d, frames[1], variables, 1, opt_track, tstate), n_drop, dev)
+            # the tracking iteration with EVERY gradient the reference's backward() forms (dL/d rgb, opacity, scale too: the reference steps
+            # them with learning rate 0, configs/replica/splatam.py:71-79): the headline's tracking iterations leave them out
+            def track_full():
+                eng.loss_backward(frames[1], eng.track_time_idx, slam.REPLICA_TRACKING, tracking=True, map_grads=True,
+                                  pose_adam=eng._pose_adam_args(slam.REPLICA_TRACKING))
+            track_rate_full = phase_rate(track_full, n_phase, dev) if world == 1 else None
+            # several ranks: the same tracking iteration replicated (every rank composites the whole frame, no exchange), and the mapping
+            # iteration with its gradient exchange -- beside the sharded / local rates above, so that a reader of the N-GPU line sees what
+            # each phase gains
+            track_rate_repl = map_rate_exch = None
+            if world > 1:
+                track_rate_repl = phase_rate(lambda: eng.tracking_iteration(frames[1], slam.REPLICA_TRACKING), n_phase, dev)
+                map_rate_exch = phase_rate(lambda: eng.mapping_iteration(frames[2], 2, slam.REPLICA_MAPPING, sdist.all_reduce_mean_flat), n_phase, dev)
+        n_drop = max(5, min(15, args.steps))
+        if fused:       # the drop-in path has not run yet: MIOpen / rocBLAS pick their kernels on the first calls
+            for _ in range(3):
+                slam.tracking_iteration(params_d, frames[1], variables, 1, opt_track, tstate)
+                slam.mapping_iteration(params_d, frames[2], variables, 2, opt_map)
+        track_rate_d = phase_rate(lambda: slam.tracking_iteration(params_d, frames[1], variables, 1, opt_track, tstate), n_drop, dev)
 
-    def map_once():
-        loss, _, _ = slam.get_loss(params_d, frames[2], variables, 2, slam.REPLICA_MAPPING['loss_weights'], False, 0.5, True, False, mapping=True)
-        loss.backward()
-        with torch.no_grad():
-            opt_map.step()
-            opt_map.zero_grad(set_to_none=True)
-    map_rate_d = phase_rate(map_once, n_drop, dev)
-    dropin_rate = 5.0 / (2.0 / track_rate_d + 3.0 / map_rate_d)
-    # the rasterizer's own share of a drop-in iteration (two forwards + two backwards through the autograd surface): HIP events around
-    # its C calls on the iteration's stream, summed over a few mapping iterations -- the rest is the reference's PyTorch glue
-    # (~100 small launches, MIOpen convolutions, boolean-mask indexing, torch.optim.Adam), which the library cannot shorten
-    spans = []
+        def map_once():
+            loss, _, _ = slam.get_loss(params_d, frames[2], variables, 2, slam.REPLICA_MAPPING['loss_weights'], False, 0.5, True, False, mapping=True)
+            loss.backward()
+            with torch.no_grad():
+                opt_map.step()
+                opt_map.zero_grad(set_to_none=True)
+        map_rate_d = phase_rate(map_once, n_drop, dev)
+        dropin_rate = 5.0 / (2.0 / track_rate_d + 3.0 / map_rate_d)
+        # the rasterizer's own share of a drop-in iteration (two forwards + two backwards through the autograd surface): HIP events around
+        # its C calls on the iteration's stream, summed over a few mapping iterations -- the rest is the reference's PyTorch glue
+        # (~100 small launches, MIOpen convolutions, boolean-mask indexing, torch.optim.Adam), which the library cannot shorten
+        spans = []
 
-    def timed(fn):
-        def wrapper(*a, **k):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn(*a, **k)
-            e1.record()
-            spans.append((e0, e1))
-            return out
-        return wrapper
-    saved_f, saved_b = rz.rasterize_forward, rz.rasterize_backward
-    rz.rasterize_forward, rz.rasterize_backward = timed(saved_f), timed(saved_b)
-    try:
-        torch.cuda.synchronize(dev)
-        for _ in range(5):
-            map_once()
-        torch.cuda.synchronize(dev)
-    finally:
-        rz.rasterize_forward, rz.rasterize_backward = saved_f, saved_b
-    dropin_raster_ms = sum(a.elapsed_time(b) for a, b in spans) / 5.0
-    rz.set_geometry_cache(False)
-    map_rate_d_nocache = phase_rate(map_once, n_drop, dev)
-    rz.set_geometry_cache(True)
-    # the SAME statements with splatam_amd.plugin installed (get_loss / initialize_optimizer of the module replaced at run time): what an
-    # unmodified scripts/splatam.py gets from the plug-in -- the fused iteration behind the reference's own loop statements
-    from splatam_amd import plugin
-    params_p = {k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}
-    vars_p = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in variables.items()}
-    with plugin.install(slam):
-        opt_track_p = slam.initialize_optimizer(params_p, slam.REPLICA_TRACKING['lrs'], tracking=True)
-        tstate_p = slam.TrackingState(params_p, 1)
-        for _ in range(3):
-            slam.tracking_iteration(params_p, frames[1], vars_p, 1, opt_track_p, tstate_p)
-        track_rate_p = phase_rate(lambda: slam.tracking_iteration(params_p, frames[1], vars_p, 1, opt_track_p, tstate_p), n_phase, dev)
-        opt_map_p = slam.initialize_optimizer(params_p, slam.REPLICA_MAPPING['lrs'], tracking=False)
-        for _ in range(3):
-            slam.mapping_iteration(params_p, frames[2], vars_p, 2, opt_map_p)
-        map_rate_p = phase_rate(lambda: slam.mapping_iteration(params_p, frames[2], vars_p, 2, opt_map_p), n_phase, dev)
-    plugin_rate = 5.0 / (2.0 / track_rate_p + 3.0 / map_rate_p)
-    if not fused:
-        track_rate, map_rate = track_rate_d, map_rate_d
+        def timed(fn):
+            def wrapper(*a, **k):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                out = fn(*a, **k)
+                e1.record()
+                spans.append((e0, e1))
+                return out
+            return wrapper
+        saved_f, saved_b = rz.rasterize_forward, rz.rasterize_backward
+        rz.rasterize_forward, rz.rasterize_backward = timed(saved_f), timed(saved_b)
+        try:
+            torch.cuda.synchronize(dev)
+            for _ in range(5):
+                map_once()
+            torch.cuda.synchronize(dev)
+        finally:
+            rz.rasterize_forward, rz.rasterize_backward = saved_f, saved_b
+        dropin_raster_ms = sum(a.elapsed_time(b) for a, b in spans) / 5.0
+        rz.set_geometry_cache(False)
+        map_rate_d_nocache = phase_rate(map_once, n_drop, dev)
+        rz.set_geometry_cache(True)
+        # the SAME statements with splatam_amd.plugin installed (get_loss / initialize_optimizer of the module replaced at run time): what an
+        # unmodified scripts/splatam.py gets from the plug-in -- the fused iteration behind the reference's own loop statements
+        from splatam_amd import plugin
+        params_p = {k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}
+        vars_p = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in variables.items()}
+        with plugin.install(slam):
+            opt_track_p = slam.initialize_optimizer(params_p, slam.REPLICA_TRACKING['lrs'], tracking=True)
+            tstate_p = slam.TrackingState(params_p, 1)
+            for _ in range(3):
+                slam.tracking_iteration(params_p, frames[1], vars_p, 1, opt_track_p, tstate_p)
+            track_rate_p = phase_rate(lambda: slam.tracking_iteration(params_p, frames[1], vars_p, 1, opt_track_p, tstate_p), n_phase, dev)
+            opt_map_p = slam.initialize_optimizer(params_p, slam.REPLICA_MAPPING['lrs'], tracking=False)
+            for _ in range(3):
+                slam.mapping_iteration(params_p, frames[2], vars_p, 2, opt_map_p)
+            map_rate_p = phase_rate(lambda: slam.mapping_iteration(params_p, frames[2], vars_p, 2, opt_map_p), n_phase, dev)
+        plugin_rate = 5.0 / (2.0 / track_rate_p + 3.0 / map_rate_p)
+        if not fused:
+            track_rate, map_rate = track_rate_d, map_rate_d
 
     result = None
     if rank == 0:
-        if mpix is None:
+        if full and mpix is None:
             mpix, ms_call = render_mpix(params_d, frames, shape, dev, reps=128)
         wl = (f"C: {N} Gaussians, {W}x{H}, mapping-only, a batch of 8 keyframe views per step sharded over the ranks, one gradient all-reduce"
               if mode_c else f"{args.workload}: {N} Gaussians, {W}x{H}, SplaTAM tracking+mapping loop (2:3 mix), isotropic map"
@@ -1099,10 +1182,13 @@ def main():
             # untimed work in front of the W warm-up steps (fused engine): the same schedule, state restored, so that the K timed steps do not
             # run inside the clock ramp of a GPU that idled through the set-up
             "prewarm": (prewarm if fused else None),
-            "sustained": ({"steps": n_sus, "seconds": round(sustained_s, 3), "iters_per_s": round(units(n_sus) / sustained_s, 3)} if sustained_ok
-                          else {"steps": n_sus, "invalid": "a per-tile list outgrew its bucket during the sustained region"}),
             "collectives": ("in-stream RCCL (splatam_amd.dist.InStreamRccl)" if sdist._instream is not None else
                             ("torch.distributed " + torch.distributed.get_backend() if world > 1 else None)),
+        }
+    if rank == 0 and full:
+        result.update({
+            "sustained": ({"steps": n_sus, "seconds": round(sustained_s, 3), "iters_per_s": round(units(n_sus) / sustained_s, 3)} if sustained_ok
+                          else {"steps": n_sus, "invalid": "a per-tile list outgrew its bucket during the sustained region"}),
             "allreduce_ms": None if allreduce_ms is None else round(allreduce_ms, 4),
             "allreduce_small_ms": None if allreduce_small_ms is None else round(allreduce_small_ms, 4),
             "allreduce_small_folded_ms": None if allreduce_small_folded_ms is None else round(allreduce_small_folded_ms, 4),
@@ -1124,7 +1210,7 @@ def main():
             "dropin_mapping_ms_per_iter": round(1e3 / map_rate_d, 3), "dropin_mapping_rasterizer_ms_per_iter": round(dropin_raster_ms, 3),
             "render_fwd_bwd_mpix_per_s": round(mpix, 2), "render_fwd_bwd_ms": round(ms_call, 4),
             "host_cores": os.cpu_count(),
-        }
+        })
         if roof is not None:
             result["roofline"] = roof
         if world == 1 and fused and args.workload == "B" and not mode_c and not args.no_b_loop:

@@ -27,7 +27,7 @@ LINK_GBS = 153.0
 
 def command(mode_args, rccl_args, n, steps, warmup):
     return [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", str(warmup),
-            "--no-cpu-baseline", "--no-slam-loop", "--sustain-s", "2"] + mode_args + (rccl_args if n > 1 else [])
+            "--full", "--no-cpu-baseline", "--no-slam-loop", "--sustain-s", "2"] + mode_args + (rccl_args if n > 1 else [])
 
 
 def last_json(text):

@@ -1,9 +1,9 @@
 """bench.py's cpu_baseline leg through the REFERENCE's own modules (scripts/cpu_baseline_reference.py): where /root/reference is present
 (this container) the leg imports utils/slam_helpers.py, utils/slam_external.py and runs get_loss / initialize_optimizer of
 scripts/splatam.py around the C oracle; elsewhere (the GPU box) it reports None and bench.py falls back to the mirror.  CPU only."""
+import json
 import os
 
-import pytest
 import torch
 
 import bench
@@ -36,12 +36,19 @@ def test_reference_leg_is_absent_without_the_reference(monkeypatch):
     assert bench.cpu_baseline_reference("A", params, frames) is None
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(bench.REFERENCE_DIR, "utils")), reason="the reference is not on this machine")
 def test_reference_leg_runs_the_references_own_get_loss():
     """One timed tracking iteration through the reference's modules; its first loss is the mirror's loss of the same inputs (the glue
-    the fused path is held to is the reference's, not only its mirror)."""
+    the fused path is held to is the reference's, not only its mirror).  The leg's first loss on this scene is recorded in
+    tests/golden/reference_facts.json (tests/golden/make_golden_reference_facts.py): the mirror is held to that record everywhere, the
+    leg itself runs wherever the reference tree is present."""
     params, frames, mirror_loss = _scene_a()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_facts.json")) as f:
+        recorded = json.load(f)["cpu_baseline_scene_a"]["first_loss"]
+    assert abs(recorded - mirror_loss) <= 1e-5 * abs(mirror_loss), (recorded, mirror_loss)
+    if not os.path.isdir(os.path.join(bench.REFERENCE_DIR, "utils")):
+        return
     out = bench.cpu_baseline_reference("A", params, frames, budget_s=5.0, max_iters=1)
     assert out is not None and out["kind"] == "reference glue + oracle" and out["value"] > 0
     assert "utils/slam_helpers.py" in out["sample"] and str(os.cpu_count()) in out["sample"]
     assert abs(out["first_loss"] - mirror_loss) <= 1e-5 * abs(mirror_loss), (out["first_loss"], mirror_loss)
+    assert abs(out["first_loss"] - recorded) <= 1e-5 * abs(recorded), (out["first_loss"], recorded)

@@ -1,13 +1,15 @@
 """CPU side of splatam_amd.plugin: the adapters keep the reference's signatures, and the loop statements that
-tests/test_gpu_plugin.py restates appear in the reference's source in that order (checked when /root/reference is present: the GPU
-box has no copy of it)."""
+tests/test_gpu_plugin.py restates appear in the reference's source in that order (recorded in tests/golden/reference_facts.json; the
+record is checked against the reference tree wherever that is present)."""
+import importlib.util
 import inspect
+import json
 import os
-import re
 
 import pytest
 
 REF = "/root/reference/scripts/splatam.py"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_adapter_signatures_match_the_reference_call_sites():
@@ -28,29 +30,35 @@ def test_install_refuses_a_module_without_the_loop_names():
         plugin.install(types.ModuleType("empty"))
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is not on this machine")
-def test_restated_loop_statements_follow_the_reference_source():
-    src = open(REF).read().splitlines()
+def _facts():
+    """tests/golden/reference_facts.json (tests/golden/make_golden_reference_facts.py): what these tests check about the reference's
+    scripts/splatam.py, recorded where the reference tree is present; wherever it is present the record is checked against it."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_facts.json")) as f:
+        return json.load(f)
 
-    def first(pattern, lo, hi):
-        for i in range(lo - 1, hi):
-            if re.search(pattern, src[i]):
-                return i + 1
-        raise AssertionError(f"{pattern!r} not found in lines {lo}-{hi}")
+
+def _golden_module():
+    spec = importlib.util.spec_from_file_location("make_golden_reference_facts", os.path.join(ROOT, "tests", "golden", "make_golden_reference_facts.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_restated_loop_statements_follow_the_reference_source():
+    rec = _facts()["loop_lines"]
+    if os.path.exists(REF):
+        assert _golden_module().loop_lines(open(REF).read().splitlines()) == rec
     # the reference's signatures the adapters mirror
-    assert re.search(r"def get_loss\(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_for_loss,", src[213])
-    assert "def initialize_optimizer(params, lrs_dict, tracking):" in src[159]
+    assert rec["get_loss_def"] == 214 and rec["initialize_optimizer_def"] == 160
     # tracking loop: optimizer per frame, then get_loss -> backward -> step -> zero_grad -> best candidate
-    t_opt = first(r"optimizer = initialize_optimizer\(params, config\['tracking'\]\['lrs'\], tracking=True\)", 670, 690)
-    t = [first(p, t_opt, 745) for p in (r"loss, variables, losses = get_loss\(params, tracking_curr_data, variables, iter_time_idx",
-                                         r"loss\.backward\(\)", r"optimizer\.step\(\)", r"optimizer\.zero_grad\(set_to_none=True\)",
-                                         r"if loss < current_min_loss")]
+    t_opt = rec["tracking"]["optimizer"]
+    t = [rec["tracking"][k] for k in ("get_loss", "backward", "step", "zero_grad", "best_candidate")]
+    assert 670 <= t_opt <= 690 and t_opt <= t[0] and t[-1] <= 745
     assert t == sorted(t), t
     # mapping loop: optimizer per frame, get_loss -> backward -> prune_gaussians -> step -> zero_grad
-    m_opt = first(r"optimizer = initialize_optimizer\(params, config\['mapping'\]\['lrs'\], tracking=False\)", 800, 830)
-    m = [first(p, m_opt, 895) for p in (r"loss, variables, losses = get_loss\(params, iter_data, variables, iter_time_idx",
-                                         r"loss\.backward\(\)", r"params, variables = prune_gaussians\(params, variables, optimizer, iter",
-                                         r"optimizer\.step\(\)", r"optimizer\.zero_grad\(set_to_none=True\)")]
+    m_opt = rec["mapping"]["optimizer"]
+    m = [rec["mapping"][k] for k in ("get_loss", "backward", "prune_gaussians", "step", "zero_grad")]
+    assert 800 <= m_opt <= 830 and m_opt <= m[0] and m[-1] <= 895
     assert m == sorted(m), m
 
 
@@ -76,14 +84,46 @@ def test_loss_scalars_read_through_their_report():
     assert isinstance(loss < other, torch.Tensor) and bool(loss < other)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="the reference tree is not on this machine")
 def test_install_patches_what_the_reference_loop_resolves():
     """``plugin.install`` on the REAL module (/root/reference/scripts/splatam.py imported as tests/golden/make_golden_loop.py imports
     it; in a subprocess -- the import shims are process wide): the two names are replaced; the loop looks both of them up as module
     globals at call time (so the replacement is what runs); every ``get_loss`` / ``initialize_optimizer`` call of ``rgbd_slam`` binds to
     the adapters' signatures; ``uninstall`` puts the reference's functions back.  No machine available to this repository has both the
     reference tree and a GPU, so the loop itself runs with the plug-in on the restated statements (tests/test_gpu_loop_golden.py),
-    which tests/test_loop_golden.py pins call by call to a recording of this very module."""
+    which tests/test_loop_golden.py pins call by call to a recording of this very module.  Without the reference tree the same checks
+    run on tests/golden/reference_facts.json (how ``rgbd_slam`` looks the names up, the shape of every call of them) with a stand-in
+    module holding the five names; where the tree is present the record is checked against it and the real module is patched as well."""
+    import types
+    from splatam_amd import plugin
+    rec = _facts()["rgbd_slam"]
+    edits = ("add_new_gaussians", "prune_gaussians", "densify")
+    assert rec["module_level"] and all(rec["global_lookup"][n] for n in ("get_loss", "initialize_optimizer") + edits), rec["global_lookup"]
+
+    def bind_all(names):
+        seen = {n: 0 for n in names}
+        for c in rec["calls"]:
+            if c["name"] in names:
+                inspect.signature(getattr(plugin, c["name"])).bind(*[None] * c["args"], **{k: None for k in c["keywords"]})
+                seen[c["name"]] += 1
+        return seen
+    assert bind_all(("get_loss", "initialize_optimizer")) == {"get_loss": 2, "initialize_optimizer": 2}
+    assert bind_all(edits) == {"add_new_gaussians": 1, "prune_gaussians": 1, "densify": 1}
+    S = types.ModuleType("splatam_stand_in")
+    for name in ("get_loss", "initialize_optimizer") + edits:
+        setattr(S, name, lambda *a, **k: None)
+    ref = {n: getattr(S, n) for n in ("get_loss", "initialize_optimizer") + edits}
+    handle = plugin.install(S)
+    assert S.get_loss is plugin.get_loss and S.initialize_optimizer is plugin.initialize_optimizer
+    assert all(getattr(S, n) is ref[n] for n in edits)
+    handle.uninstall()
+    assert all(getattr(S, n) is ref[n] for n in ref)
+    handle = plugin.install(S, map_edits=True)
+    assert all(getattr(S, n) is getattr(plugin, n) for n in edits) and S.get_loss is plugin.get_loss
+    handle.uninstall()
+    assert all(getattr(S, n) is ref[n] for n in ref)
+    if not os.path.exists(REF):
+        return
+    assert _golden_module().rgbd_slam_facts(open(REF).read()) == rec
     import subprocess
     import sys
     code = r'''

@@ -24,7 +24,7 @@ def test_dry_run_lists_every_launch():
     # mix and C, N = 1 once each (no collective), N = 2, 4, 8 over torch.distributed and in-stream RCCL
     assert len(cmds) == 2 * (1 + 3 * 2)
     assert sum("--instream-rccl" in c for c in cmds) == 6 and sum("--workload C" in c for c in cmds) == 7
-    assert all("--gpus" in c and "--no-slam-loop" in c for c in cmds)
+    assert all("--gpus" in c and "--full" in c and "--no-slam-loop" in c for c in cmds)     # (the table reads the figures of --full)
 
 
 def test_table_from_logs(tmp_path):
