@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 10       /* 10: group binning behind the reference API (SplatState.group_* in splat_preprocess_forward / splat_render_forward,
+#define SPLAT_ABI_VERSION 11       /* 11: SplatAdamMap.one_minus_beta1 / _beta2 (torch's 1 - beta, formed in double);
+                                      10: group binning behind the reference API (SplatState.group_* in splat_preprocess_forward / splat_render_forward,
                                       SPLAT_LAYOUT_GROUPS), SplatState.tile_recs (staged records handed from the forward to the backward composite), SplatCamera.bg == NULL = black, SplatGrads.flags (SPLAT_GRADS_UPSTREAM_SCALE), SplatState.status_host,
                                       SplatState.tile_order entries hold tile + 1 (a zeroed buffer is the natural order) and are laid out on request (SPLAT_LAYOUT_TILE_ORDER),
                                       SplatState.tile_queue (persistent composites: measured, not adopted, removed) is gone;
@@ -457,9 +458,12 @@ int splat_iter_loss_backward(const SplatCamera *cam, const SplatMap *map, const 
  * are formed by the caller in double, as torch does -- per group, because torch keeps a step count per parameter and a
  * parameter the caller re-created (pruning, opacity reset) restarts or skips its count.  Group order: means3D, rgb_colors,
  * unnorm_rotations, logit_opacities, log_scales.  exp_avg / exp_avg_sq have the shapes of the parameters.  gate: NULL, or
- * the d_cam of the iteration that formed the gradients -- the step is skipped while d_cam[12] (the capacity flag) is up. */
+ * the d_cam of the iteration that formed the gradients -- the step is skipped while d_cam[12] (the capacity flag) is up.
+ * one_minus_beta1 / one_minus_beta2: 1 - beta formed by the caller in double, as torch forms the weights of its moment updates
+ * (1.0f - 0.999f is 1.3e-5 away from float(1 - 0.999): every exp_avg_sq would be ~100 ulps off torch's). */
 typedef struct SplatAdamMap {
     float beta1, beta2, eps;
+    float one_minus_beta1, one_minus_beta2;
     float bc2_sqrt[5];
     float step_size[5];
     const float *grad[5];

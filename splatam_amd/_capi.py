@@ -18,7 +18,7 @@ SPLAT_MAX_CHANNELS = 8
 SPLAT_GRAD_STRIDE = 16
 SPLAT_COUNTER_STRIDE = 32
 SPLAT_GROUP_TILES = 2
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -81,7 +81,8 @@ class SplatIterWorkspace(C.Structure):
 
 
 class SplatAdamMap(C.Structure):
-    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("bc2_sqrt", C.c_float * 5),
+    _fields_ = [("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("one_minus_beta1", C.c_float),
+                ("one_minus_beta2", C.c_float), ("bc2_sqrt", C.c_float * 5),
                 ("step_size", C.c_float * 5), ("grad", _fp * 5), ("exp_avg", _fp * 5), ("exp_avg_sq", _fp * 5), ("gate", _fp)]
 
 

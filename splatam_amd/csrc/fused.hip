@@ -990,7 +990,8 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
                     const float gk = grads[gidx][k];
                     if ((gk == 0.f && mm == 0.f && vv == 0.f) || gate_up) continue;          // (see adam_map_kernel)
                     const size_t j = (size_t)i * kWidth[gidx] + k;
-                    params[gidx][j] = adam_update(olds[gidx][k], gk, mm, vv, opt.beta1, opt.beta2, opt.step_size[gidx], opt.bc2_sqrt[gidx], opt.eps);
+                    params[gidx][j] = adam_update_c(olds[gidx][k], gk, mm, vv, opt.one_minus_beta1, opt.beta2, opt.one_minus_beta2, opt.step_size[gidx],
+                                                     opt.bc2_sqrt[gidx], opt.eps);
                     opt.exp_avg[gidx][j] = mm;
                     opt.exp_avg_sq[gidx][j] = vv;
                 }
@@ -1055,7 +1056,8 @@ __global__ __launch_bounds__(kBlock) void adam_map_kernel(AdamArgs a, long long 
                 // isotropic map): the step leaves parameter and moments as they are -- nothing to write
                 if (gg == 0.f && mm == 0.f && vv == 0.f) return;
                 float *p = params[gidx];
-                p[j] = adam_update(p[j], gg, mm, vv, a.opt.beta1, a.opt.beta2, a.opt.step_size[gidx], a.opt.bc2_sqrt[gidx], a.opt.eps);
+                p[j] = adam_update_c(p[j], gg, mm, vv, a.opt.one_minus_beta1, a.opt.beta2, a.opt.one_minus_beta2, a.opt.step_size[gidx],
+                                     a.opt.bc2_sqrt[gidx], a.opt.eps);
                 a.opt.exp_avg[gidx][j] = mm;
                 a.opt.exp_avg_sq[gidx][j] = vv;
             }

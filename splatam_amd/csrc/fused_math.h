@@ -170,13 +170,19 @@ SPLAT_HD float ssim_pixel(float mu1, float mu2, float e11, float e22, float e12,
 }
 
 // Adam, one element (torch.optim.Adam, amsgrad=False, weight_decay=0): step_size = lr / (1 - beta1^t),
-// bc2_sqrt = sqrt(1 - beta2^t), both formed on the host in double as torch does.
-SPLAT_HD float adam_update(float param, float grad, float &m, float &v, float beta1, float beta2, float step_size,
-                           float bc2_sqrt, float eps) {
-    m = m + (1.0f - beta1) * (grad - m);
-    v = v * beta2 + (1.0f - beta2) * grad * grad;
+// bc2_sqrt = sqrt(1 - beta2^t), both formed on the host in double as torch does; omb1 / omb2 = 1 - beta1 / 1 - beta2 likewise
+// (torch's lerp weight and addcmul value)
+SPLAT_HD float adam_update_c(float param, float grad, float &m, float &v, float omb1, float beta2, float omb2, float step_size,
+                             float bc2_sqrt, float eps) {
+    m = m + omb1 * (grad - m);
+    v = v * beta2 + omb2 * grad * grad;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     return param - step_size * (m / denom);
+}
+
+SPLAT_HD float adam_update(float param, float grad, float &m, float &v, float beta1, float beta2, float step_size,
+                           float bc2_sqrt, float eps) {
+    return adam_update_c(param, grad, m, v, 1.0f - beta1, beta2, 1.0f - beta2, step_size, bc2_sqrt, eps);
 }
 
 }  // namespace splat

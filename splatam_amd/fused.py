@@ -779,6 +779,7 @@ class FusedEngine:
             steps = (self.map_step,) * 5
         o = _capi.SplatAdamMap()
         o.beta1, o.beta2, o.eps = beta1, beta2, eps
+        o.one_minus_beta1, o.one_minus_beta2 = 1.0 - beta1, 1.0 - beta2        # (in double, as torch forms them)
         for k, name in enumerate(PARAM_ORDER):
             t = max(int(steps[k]), 1)
             o.bc2_sqrt[k] = math.sqrt(1.0 - beta2 ** t)

@@ -188,25 +188,25 @@ class _Spy:
         return out
 
 
-def _cpu_case(params, frame, cam_args, dtype):
+def _cpu_case(params, frame, cam_args, dtype, time_idx=1):
     from splatam_amd import slam
     W, H, k = cam_args
     pc = {k_: torch.nn.Parameter(v.detach().cpu().to(dtype).clone()) for k_, v in params.items()}
     cam_c = slam.setup_camera(W, H, k, np.eye(4, dtype=np.float32), device="cpu")
-    frame_c = {'cam': cam_c, 'im': frame['im'].cpu().to(dtype), 'depth': frame['depth'].cpu().to(dtype), 'id': 1,
+    frame_c = {'cam': cam_c, 'im': frame['im'].cpu().to(dtype), 'depth': frame['depth'].cpu().to(dtype), 'id': time_idx,
                'w2c': torch.eye(4, dtype=dtype)}
     return pc, frame_c
 
 
-def _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch):
+def _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch, time_idx=1):
     """splatam_amd.slam.get_loss (pinned to /root/reference/scripts/splatam.py:214-347 by tests/golden/) on CPU tensors with the
     C oracle as its Renderer: returns (loss, [rgb render, depth/sil render], their autograd gradients)."""
     from splatam_amd import slam
     monkeypatch.setattr(slam, "Renderer", _Spy)
     _Spy.renders = []
-    pc, frame_c = _cpu_case(params, frame, cam_args, torch.float32)
+    pc, frame_c = _cpu_case(params, frame, cam_args, torch.float32, time_idx)
     vc = {k_: v.cpu().clone() for k_, v in variables.items()}
-    loss, _, _ = slam.get_loss(pc, frame_c, vc, 1, cfg['loss_weights'], cfg['use_sil_for_loss'], cfg['sil_thres'], cfg['use_l1'],
+    loss, _, _ = slam.get_loss(pc, frame_c, vc, time_idx, cfg['loss_weights'], cfg['use_sil_for_loss'], cfg['sil_thres'], cfg['use_l1'],
                                cfg['ignore_outlier_depth_loss'], tracking=tracking, mapping=not tracking)
     loss.backward()
     im, ds = _Spy.renders
@@ -214,13 +214,13 @@ def _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypa
     return float(loss.detach()), [im.detach(), ds.detach()], [im.grad, ds.grad if ds.grad is not None else zero]
 
 
-def _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, dtype, monkeypatch):
+def _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, dtype, monkeypatch, time_idx=1):
     """The oracle's two renders + two backward passes for GIVEN gradient planes (dL/drgb [3], dL/ddepth [1]) through the
     reference-shaped glue (transform_to_frame, render-variable assembly): gradients of every parameter."""
     from splatam_amd import slam
     monkeypatch.setattr(slam, "Renderer", c_ref.CRasterizer)
-    pc, frame_c = _cpu_case(params, frame, cam_args, dtype)
-    tg = slam.transform_to_frame(pc, 1, gaussians_grad=not tracking, camera_grad=tracking)
+    pc, frame_c = _cpu_case(params, frame, cam_args, dtype, time_idx)
+    tg = slam.transform_to_frame(pc, time_idx, gaussians_grad=not tracking, camera_grad=tracking)
     im, _, _ = slam.Renderer(raster_settings=frame_c['cam'])(**slam.transformed_params2rendervar(pc, tg))
     ds, _, _ = slam.Renderer(raster_settings=frame_c['cam'])(**slam.transformed_params2depthplussilhouette(pc, frame_c['w2c'], tg))
     pl = planes.to(dtype)
@@ -279,16 +279,23 @@ def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None):
     torch.cuda.synchronize()
     assert not eng.check_overflow(grow=False)
     what = f"fused {cfg_name}{'-aniso' if aniso else ''}{'-clustered' if region else ''} {'tracking' if tracking else 'mapping'}"
-    cam_args = (W, H, k)
-    loss_ref, renders, plane_grads = _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch)
+    g32, g64 = _fused_stages(eng, params, variables, frame, (W, H, k), c, cfg, tracking, what, monkeypatch)
+    return eng, g32, g64, what
+
+
+def _fused_stages(eng, params, variables, frame, cam_args, c, cfg, tracking, what, monkeypatch, time_idx=1):
+    """Stages (A)..(C) for an engine whose iteration on ``frame`` at pose ``time_idx`` has run; returns the oracle's float32 and
+    float64 gradients of stage (D) for the same gradient planes."""
+    from splatam_amd import slam
+    loss_ref, renders, plane_grads = _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch, time_idx)
     # (A) rendered planes
     imf, depthf, silf, dsqf = eng.rendered()
     nflip = 2e-4            # the fused glue rounds differently from torch's: a few more alpha >= 1/255 decisions flip than on the drop-in path
     got_im, got_ds = imf.cpu().numpy(), torch.cat([depthf, silf[None], dsqf]).cpu().numpy()
     # every pixel beyond 1e-4 explained by a decision the float64 oracle (float64 glue) finds within rounding of its threshold there
-    pc64, frame64 = _cpu_case(params, frame, cam_args, torch.float64)
+    pc64, frame64 = _cpu_case(params, frame, cam_args, torch.float64, time_idx)
     with torch.no_grad():
-        tg64 = slam.transform_to_frame(pc64, 1, gaussians_grad=False, camera_grad=False)
+        tg64 = slam.transform_to_frame(pc64, time_idx, gaussians_grad=False, camera_grad=False)
         b_im, _, _, _, n_im = oracle_flip_bounds(slam.transformed_params2rendervar(pc64, tg64), frame64['cam'])
         b_ds, _, _, _, n_ds = oracle_flip_bounds(slam.transformed_params2depthplussilhouette(pc64, frame64['w2c'], tg64), frame64['cam'])
     nbad = assert_outliers_explained(got_im, renders[0].numpy(), b_im[:3], 1e-4, noise=n_im[:3], what=f"{what} im")
@@ -298,7 +305,7 @@ def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None):
     # whose camera-space depths agree to float32 rounding are ordered by that rounding, and the in-kernel glue (FMA chain) rounds
     # z = (R X + t).z differently from torch's matmul -- a legitimate swap of two list neighbours, verified per pixel
     big = (np.abs(got_im - renders[0].numpy()).max(axis=0) > 0.03) | (np.abs(got_ds - renders[1].numpy()).max(axis=0) > 0.3)
-    eng.depth_tie_pixels = _assert_depth_ties_explain(big, params, c, what)
+    eng.depth_tie_pixels = _assert_depth_ties_explain(big, params, c, what, time_idx)
     # (B) loss
     loss_f = eng.loss()
     assert abs(loss_f - loss_ref) <= 1e-4 * abs(loss_ref), (what, loss_f, loss_ref)
@@ -312,9 +319,9 @@ def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None):
                           what=f"{what} dL/d(render) planes")
     assert float(planes[4:6].abs().max()) == 0.0 and float(plane_grads[1][1:3].abs().max()) == 0.0
     # (D) parameter / pose gradients for the SAME gradient planes, float32 and float64 oracle
-    g32 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float32, monkeypatch)
-    g64 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float64, monkeypatch)
-    return eng, g32, g64, what
+    g32 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float32, monkeypatch, time_idx)
+    g64 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float64, monkeypatch, time_idx)
+    return g32, g64
 
 
 @pytest.mark.parametrize("cfg_name,aniso", [('B', False), ('B', True), ('D', False), ('D', True), ('E', False), ('E', True)])
@@ -331,10 +338,10 @@ def test_fused_mapping_vs_oracle(cfg_name, aniso, monkeypatch):
         assert float(eng.grads["unnorm_rotations"].abs().max()) == 0.0
 
 
-def _check_pose_gradient(eng, g32, g64, what):
+def _check_pose_gradient(eng, g32, g64, what, time_idx=1):
     d = eng.buf['d_cam'].cpu().numpy().astype(np.float64)
-    gq32, gt32 = g32['cam_unnorm_rots'][0, :, 1], g32['cam_trans'][0, :, 1]
-    gq64, gt64 = g64['cam_unnorm_rots'][0, :, 1], g64['cam_trans'][0, :, 1]
+    gq32, gt32 = g32['cam_unnorm_rots'][0, :, time_idx], g32['cam_trans'][0, :, time_idx]
+    gq64, gt64 = g64['cam_unnorm_rots'][0, :, time_idx], g64['cam_trans'][0, :, time_idx]
     print(what, "pose gradient", d[0:7], "oracle f32", gq32, gt32, "oracle f64", gq64, gt64)
     for got, r32, r64 in ((d[0:4], gq32, gq64), (d[4:7], gt32, gt64)):
         tol = max(1e-4 * np.abs(r64).max(), 2.0 * np.abs(r32 - r64).max())

@@ -224,3 +224,111 @@ def assert_grad_outliers_explained(got, ref, flagged, xy, radii, rel=1e-3, what=
           f"({100 * frac:.3f} % of the pixels are flagged), {len(missing)} do not")
     assert not missing, f"{what}: gradient rows {missing[:8]} differ by more than {rel:g} of max with no decision flip under them"
     return int(rows.size)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# a multi-view mapping scene: one map, 8 keyframe poses that see different parts of it
+# ----------------------------------------------------------------------------------------------------------------------------------
+
+MULTIVIEW_SIZES = {
+    'B': dict(n=300_000, W=1200, H=680, fx=600.0, fy=600.0, cx=599.5, cy=339.5),       # = CONFIGS['B'] of tests/test_gpu_configs.py
+    'small': dict(n=20_000, W=320, H=240, fx=300.0, fy=300.0, cx=159.5, cy=119.5),
+}
+# keyframe poses (time indices 1..8; 0 stays the identity the map was made at): rotation (degrees about x, about y), translation (m).
+# Every pose turns or moves the camera towards +x, so a strip of the map on that side is seen by no keyframe; x rotations of both
+# signs make the top and bottom rows come and go; view 8 moves 1.4 m forward: the near part of the map (z < ~1.6) is behind the
+# 0.2 near plane and much of the rest projects far outside the image (the 1.3 tan(fov) clamp of the projection's Jacobian).
+MULTIVIEW_POSES = (
+    ((0.0, 8.0), (0.10, 0.00, 0.00)),
+    ((5.0, 14.0), (0.15, -0.05, 0.05)),
+    ((12.0, 6.0), (0.10, 0.12, 0.05)),
+    ((-15.0, 9.0), (0.12, -0.15, 0.10)),
+    ((-10.0, 20.0), (0.20, 0.10, 0.10)),       # the most rotated view
+    ((16.0, 12.0), (0.15, 0.20, 0.15)),
+    ((3.0, 5.0), (0.30, 0.00, 0.00)),
+    ((0.0, 6.0), (0.08, 0.00, -1.40)),         # the forward view
+)
+MOST_ROTATED_VIEW, FORWARD_VIEW = 5, 8
+
+
+def pose_quat(rx_deg, ry_deg):
+    """(w, x, y, z) of R = R_y(ry) R_x(rx) (world-to-camera)."""
+    ax, ay = np.radians(rx_deg) / 2, np.radians(ry_deg) / 2
+    qx = np.array([np.cos(ax), np.sin(ax), 0.0, 0.0])
+    qy = np.array([np.cos(ay), 0.0, np.sin(ay), 0.0])
+    w1, x1, y1, z1 = qy
+    w2, x2, y2, z2 = qx
+    return np.array([w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2, w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2,
+                     w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
+
+
+def frame_at_pose(params, cam, w2c_first, q, t):
+    """'Ground-truth' RGB-D frame: the map rendered (HIP drop-in rasterizer) from the world-to-camera pose (q, t) -- what
+    splatam_amd.slam.synthetic_frame does for its fixed small perturbation of the identity."""
+    from splatam_amd import slam
+    with torch.no_grad():
+        fake = dict(params)
+        dev = params['means3D'].device
+        fake['cam_unnorm_rots'] = torch.as_tensor(np.asarray(q), dtype=torch.float32, device=dev).reshape(1, 4, 1)
+        fake['cam_trans'] = torch.as_tensor(np.asarray(t), dtype=torch.float32, device=dev).reshape(1, 3, 1)
+        tg = slam.transform_to_frame(fake, 0, gaussians_grad=False, camera_grad=False)
+        rv = slam.transformed_params2rendervar(fake, tg)
+        im, _, _ = slam.Renderer(raster_settings=cam)(**{k: v.detach() for k, v in rv.items()})
+        dv = slam.transformed_params2depthplussilhouette(fake, w2c_first, tg)
+        ds, _, _ = slam.Renderer(raster_settings=cam)(**{k: v.detach() for k, v in dv.items()})
+        sil = ds[1:2]
+        depth = torch.where(sil > 0.5, ds[0:1] / sil.clamp_min(1e-6), torch.zeros_like(sil))
+    return im.contiguous(), depth.contiguous()
+
+
+def multiview_scene(size, seed=0, aniso=False):
+    """One seeded map (splatam_amd.slam.synthetic_params at the identity pose), the 8 keyframe poses of MULTIVIEW_POSES in
+    ``cam_unnorm_rots`` / ``cam_trans`` [..., 1..8], and per keyframe a frame rendered from a pose 0.4 deg / 1 cm off the keyframe's
+    (so that the loss has a real gradient), with the noise and the invalid-depth patch of the single-view tests.
+    Returns (params, variables, cam, k, views = [(frame, time_idx), ...], c)."""
+    from splatam_amd import slam
+    c = MULTIVIEW_SIZES[size]
+    n, W, H = c['n'], c['W'], c['H']
+    params, variables = slam.synthetic_params(n, W, H, c['fx'], c['fy'], c['cx'], c['cy'], num_frames=1 + len(MULTIVIEW_POSES), seed=seed,
+                                              device="cuda", anisotropic=aniso)
+    k = [[c['fx'], 0, c['cx']], [0, c['fy'], c['cy']], [0, 0, 1]]
+    w2c = torch.eye(4, device="cuda")
+    cam = slam.setup_camera(W, H, k, np.eye(4, dtype=np.float32), device="cuda")
+    g = torch.Generator().manual_seed(seed + 1)
+    views = []
+    for i, ((rx, ry), t) in enumerate(MULTIVIEW_POSES, start=1):
+        q = pose_quat(rx, ry)
+        with torch.no_grad():
+            params['cam_unnorm_rots'][0, :, i] = torch.as_tensor(q, dtype=torch.float32, device="cuda")
+            params['cam_trans'][0, :, i] = torch.as_tensor(t, dtype=torch.float32, device="cuda")
+        im, depth = frame_at_pose(params, cam, w2c, pose_quat(rx + 0.3, ry - 0.4), np.asarray(t) + np.array([0.01, -0.005, 0.005]))
+        im = (im + 0.03 * torch.randn(im.shape, generator=g).cuda()).clamp(0, 1).contiguous()
+        depth = (depth * (1 + 0.01 * torch.randn(depth.shape, generator=g).cuda())).contiguous()
+        depth[:, : H // 8, : W // 8] = 0.0                  # a patch of invalid depth (mask path)
+        views.append(({'cam': cam, 'im': im, 'depth': depth, 'id': i, 'w2c': w2c}, i))
+    return params, variables, cam, k, views, c
+
+
+def camera_depths(params, time_idx):
+    """float64 camera-space z of every Gaussian centre at pose ``time_idx``."""
+    q = params['cam_unnorm_rots'][0, :, time_idx].detach().double().cpu().numpy()
+    t = params['cam_trans'][0, :, time_idx].detach().double().cpu().numpy()
+    w, x, y, z = q / np.linalg.norm(q)
+    row2 = np.array([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)])
+    return params['means3D'].detach().double().cpu().numpy() @ row2 + t[2]
+
+
+def view_partition(radii_per_view, params, forward_view, min_frac=0.03, what=""):
+    """Rows of the map by how many keyframe views see them (radii > 0 of the reference renders): every view, some only, none; and
+    the rows the near plane (z <= 0.2) culls in ``forward_view``.  Each group must hold at least ``min_frac`` of the map, so that
+    no comparison over a group passes on an empty set."""
+    seen = np.stack([np.asarray(r) > 0 for r in radii_per_view])           # [V, P]
+    count = seen.sum(axis=0)
+    P = seen.shape[1]
+    groups = {'every view': count == seen.shape[0], 'some views': (count > 0) & (count < seen.shape[0]), 'no view': count == 0,
+              'behind the near plane (forward view)': camera_depths(params, forward_view) <= 0.2}
+    print(f"{what} partition of {P} rows: " + ", ".join(f"{k} {int(v.sum())} ({100 * v.mean():.1f} %)" for k, v in groups.items()))
+    for k, v in groups.items():
+        assert v.mean() >= min_frac, (what, k, int(v.sum()))
+    assert not seen[forward_view - 1][groups['behind the near plane (forward view)']].any(), "a row behind the near plane was rendered"
+    return groups, seen
