@@ -43,6 +43,13 @@ extern "C" {
                                       5: SplatState.group_count / group_recs / group_stride (group binning), splat_iter_mapping_step; 4: densification (splat_iter_means2d_accumulate, splat_map_densify_select / _duplicate);
                                       3: SplatState.keys_alt / long_base (multi-workgroup sort of lists beyond LDS); 2: map edits,
                                       splat_iter_render / _tracking_step, outlier scratch in SplatIterWorkspace */
+/* the words of SplatState.status */
+#define SPLAT_STATUS_INSTANCES 0   /* num_rendered */
+#define SPLAT_STATUS_OVERFLOW 1    /* overflow flag (num_rendered > capacity) */
+#define SPLAT_STATUS_LONGEST 2     /* longest tile list */
+#define SPLAT_STATUS_STALE_HINT 3  /* a list longer than the wave-sort limit met a stale max_list_hint that had skipped the long-list
+                                      sort kernel (the lists are then NOT sorted: re-run) */
+
 #define SPLAT_TILE 16            /* tile edge in pixels (one 256-thread workgroup per tile, one wave64 per 8x8 quadrant) */
 #define SPLAT_MAX_CHANNELS 8     /* colour channels per call: 3 for the reference API, up to 8 for fused passes */
 #define SPLAT_GRAD_STRIDE 16     /* floats per Gaussian in the backward accumulator (one 64-byte line) */
@@ -167,10 +174,7 @@ typedef struct SplatState {
     /* per-pixel */
     float *final_T;              /* [H][W] */
     int32_t *n_contrib;          /* [H][W] 1-based list position of the last contributor */
-    /* status words: [0] num_rendered  [1] overflow flag (num_rendered > capacity)
-     *               [2] longest tile list  [3] a list longer than the wave-sort limit met a stale max_list_hint
-     *               that had skipped the long-list sort kernel (the lists are then NOT sorted: re-run) */
-    int32_t *status;             /* [4] */
+    int32_t *status;             /* [4] the SPLAT_STATUS_* words */
     /* optional (NULL: none): ONE int32 in pinned HOST memory that the group-binning kernels set to 1 whenever they raise status[1] or
      * status[3] -- a caller that never waits for the device between the forward and the backward pass reads it (after an event that
      * follows the forward composite) without queueing a copy.  The caller zeroes it before the call. */
@@ -357,6 +361,23 @@ typedef struct SplatLossConfig {
 #define SPLAT_ITER_SUMS 32       /* doubles per copy of the partial sums */
 #define SPLAT_ITER_SUM_COPIES 64 /* copies: workgroups spread their atomics over them (one hot cache line otherwise) */
 #define SPLAT_ITER_DCAM 32       /* floats of SplatIterWorkspace.d_cam */
+/* the slots of SplatIterWorkspace.d_cam, the iteration's report (written by its last kernel; 10 spare) */
+#define SPLAT_REPORT_DROT 0        /* [0..3] dL/dcam_unnorm_rots[..., t] */
+#define SPLAT_REPORT_DTRANS 4      /* [4..6] dL/dcam_trans[..., t] */
+#define SPLAT_REPORT_LOSS 7
+#define SPLAT_REPORT_SUMS 8        /* [8..11] the raw sums [0..3] of this iteration */
+#define SPLAT_REPORT_FLAG 12       /* STICKY "lists overflowed / unsorted" flag (set by any iteration whose status OVERFLOW or STALE_HINT
+                                      was set; cleared by the host).  While it is up the Adam steps of this ABI (inside
+                                      splat_iter_tracking_step / _mapping_step / _finish, splat_iter_adam_pose, and splat_iter_adam_map
+                                      with SplatAdamMap.gate) leave parameters, moments and the best-candidate record untouched: an
+                                      iteration on truncated lists never moves the map */
+#define SPLAT_REPORT_MEDIAN 13     /* the median depth error of this iteration when ignore_outlier_depth_loss is set */
+#define SPLAT_REPORT_DEPTH_TERM 14 /* loss_weights['depth'] * the depth term, and ... */
+#define SPLAT_REPORT_IM_TERM 15    /* ... loss_weights['im'] * the image term of the loss (weighted_losses['depth' / 'im'] of
+                                      /root/reference/scripts/splatam.py:339) */
+#define SPLAT_REPORT_STATUS 16     /* [16..19] int32 bit patterns of st.status[0..3] as this iteration left them */
+#define SPLAT_REPORT_FLAGGED 20    /* int32: 1 when THIS iteration was flagged */
+#define SPLAT_REPORT_SKIPPED 21    /* int32: iterations whose Adam step was skipped since the host last cleared it */
 
 /* Device scratch + outputs of one fused iteration; every array is caller-owned.  The caller ZERO-INITIALISES sums,
  * st.tile_count, accum and dL_dout6 once; each iteration leaves them zeroed again (the kernels that consume a buffer
@@ -378,21 +399,7 @@ typedef struct SplatIterWorkspace {
     float *d_unnorm_rotations;   /* [P][4] */
     float *d_logit_opacities;    /* [P] */
     float *d_log_scales;         /* [P][1|3] */
-    float *d_cam;                /* [SPLAT_ITER_DCAM] the iteration's report, written by its last kernel:
-                                    [0..3] dL/dcam_unnorm_rots[...,t], [4..6] dL/dcam_trans[...,t], [7] loss,
-                                    [8..11] the raw sums [0..3] of this iteration,
-                                    [12] STICKY "lists overflowed / unsorted" flag (set by any iteration whose status[1] or
-                                         status[3] was set; cleared by the host).  While it is up the Adam steps of this ABI
-                                         (inside splat_iter_tracking_step / _mapping_step / _finish, splat_iter_adam_pose, and
-                                         splat_iter_adam_map with SplatAdamMap.gate) leave parameters, moments and the
-                                         best-candidate record untouched: an iteration on truncated lists never moves the map,
-                                    [13] the median depth error of this iteration when ignore_outlier_depth_loss is set,
-                                    [14] loss_weights['depth'] * the depth term, [15] loss_weights['im'] * the image term of [7]
-                                         (weighted_losses['depth' / 'im'] of /root/reference/scripts/splatam.py:339),
-                                    [16..19] int32 bit patterns of st.status[0..3] as this iteration left them (instances,
-                                         overflow, longest list, stale hint),
-                                    [20] int32: 1 when THIS iteration was flagged, [21] int32: iterations whose Adam step was
-                                         skipped since the host last cleared it, 10 spare */
+    float *d_cam;                /* [SPLAT_ITER_DCAM] the iteration's report: the SPLAT_REPORT_* slots */
     /* only read when cfg->ignore_outlier_depth_loss (/root/reference/scripts/splatam.py:266-268), NULL otherwise */
     float *outlier_err;          /* [H*W] scratch: depth error per pixel */
     uint32_t *outlier_scratch;   /* splat_map_scratch_words(H*W) words: histograms of the radix selection of torch.median */

@@ -36,8 +36,8 @@ CLAUSES = [
     ("K7", "back to front from n_contrib: T = T / (1 - alpha)", "T = T / (1.f - alpha);", RH, "const float Tn = Tr * rcp;                     // transmittance in front of this Gaussian"),
     ("K7", "accum = last_alpha last_colour + (1 - last_alpha) accum; dL/dalpha += (colour - accum) dL/dC  (the product carries the same recursion as the running sum R)", "accum[ch] = last_alpha * last_col[ch] + (1.f - last_alpha) * accum[ch];", RH, "const float dL_dalpha = fmaf(cdot, Tn, -(R * rcp));"),
     ("K7", "dL/dalpha += -T_final / (1 - alpha) * sum_ch bg dL/dC", "dL_dalpha += (-T_final / (1.f - alpha)) * bgdot;", RH, "if constexpr (BG) R += Tfin * bg_of(cam, ch) * dpix[ch];"),
-    ("K7", "dL/dG = opacity dL/dalpha; dL/dmean2D (NDC) = dL/dG dG/dd 0.5 (W, H)", "a[0] += (double)(dL_dG * dG_ddx * 0.5f * W);", PH, "g_ndc[0] = -(co.x * acc[0] + co.y * acc[1]) * 0.5f * c.W;"),
-    ("K7", "dL/dconic = (-0.5 gdx dx, -gdx dy [the two symmetric halves], -0.5 gdy dy) dL/dG", "a[3] += (double)(-gdx * dy * dL_dG);", PH, "const float g_conic[3] = {-0.5f * acc[2], -acc[3], -0.5f * acc[4]};"),
+    ("K7", "dL/dG = opacity dL/dalpha; dL/dmean2D (NDC) = dL/dG dG/dd 0.5 (W, H)", "a[0] += (double)(dL_dG * dG_ddx * 0.5f * W);", M, "g_ndc[0] = -(a * S[0] + b * S[1]) * 0.5f * W;"),
+    ("K7", "dL/dconic = (-0.5 gdx dx, -gdx dy [the two symmetric halves], -0.5 gdy dy) dL/dG", "a[3] += (double)(-gdx * dy * dL_dG);", M, "g_conic[0] = -0.5f * S[2];"),
     ("K7", "dL/dopacity += G dL/dalpha; dL/dcolour += alpha T dL/dC", "a[5] += (double)(G * dL_dalpha);", RH, "const float ww = al * Tn;"),
     ("K8", "conic -> cov2D with 1 / (det^2 + 1e-7)", "real d2 = 1.f / (det * det + 0.0000001f);", M, "const float d2 = 1.0f / (det * det + 0.0000001f);"),
     ("K8", "dL/da, dL/dc, dL/db of the 2x2 covariance", "real dLb = d2 * (2.f * cb * cc * gcx - (det + 2.f * cb * cb) * gcy + 2.f * ca * cb * gcz);", M, "const float dLb = d2 * (2.f * b * cc * g_conic[0] - (det + 2.f * b * b) * g_conic[1] + 2.f * a * b * g_conic[2]);"),

@@ -133,6 +133,20 @@ SPLAT_LAYOUT_SH, SPLAT_LAYOUT_LONG_LISTS, SPLAT_LAYOUT_BACKWARD, SPLAT_LAYOUT_SS
 SPLAT_LAYOUT_GROUPS, SPLAT_LAYOUT_TILE_ORDER, SPLAT_LAYOUT_RECS = 32, 64, 128
 SPLAT_GRADS_UPSTREAM_SCALE, SPLAT_GRADS_POISON_IF_FLAGGED, SPLAT_GRADS_ACCUM_ZEROED = 1, 2, 4
 SPLAT_LAYOUT_MAX_ARRAYS = 48
+SPLAT_STATUS_INSTANCES, SPLAT_STATUS_OVERFLOW, SPLAT_STATUS_LONGEST, SPLAT_STATUS_STALE_HINT = 0, 1, 2, 3
+SPLAT_REPORT_DROT, SPLAT_REPORT_DTRANS, SPLAT_REPORT_LOSS, SPLAT_REPORT_SUMS = 0, 4, 7, 8
+SPLAT_REPORT_FLAG, SPLAT_REPORT_MEDIAN, SPLAT_REPORT_DEPTH_TERM, SPLAT_REPORT_IM_TERM = 12, 13, 14, 15
+SPLAT_REPORT_STATUS, SPLAT_REPORT_FLAGGED, SPLAT_REPORT_SKIPPED = 16, 20, 21
+
+
+def lists_sorted_by_composite(max_list_hint: int) -> bool:
+    """The library's test (splat_device.h): lists known to be at most this long are sorted by the composite kernel itself."""
+    return 0 < max_list_hint and max_list_hint + max_list_hint // 4 <= 1024
+
+
+# staged records handed from the forward to the backward composite (SplatState.tile_recs) pay where a tile's list is several
+# 255-entry batches long and cost where it is one (profiles/r06_experiments.md 2): they are bound for lists longer than this
+RECS_MIN_LIST = 400
 
 EXPORTS = (
     "splat_error_string", "splat_abi_version", "splat_sizeof", "splat_num_tiles",

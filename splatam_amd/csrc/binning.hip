@@ -25,7 +25,7 @@ constexpr int kSortWaves = 16, kSortBlock = 64 * kSortWaves;
 // returning atomic on the tile cursor (a fabric round trip of a few microseconds under
 // load), so a lane keeps up to four of them in flight instead of chaining them.
 __global__ __launch_bounds__(kBlock) void scatter_kernel(SplatGaussians g, SplatState st, int gx) {
-    if ((long long)st.status[0] > st.capacity) return;      // lists would not fit: host re-sizes and retries
+    if ((long long)st.status[SPLAT_STATUS_INSTANCES] > st.capacity) return;      // lists would not fit: host re-sizes and retries
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= g.P) return;
     if (st.radii[i] <= 0) return;
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(kBlock) void scatter_kernel(SplatGaussians g, Splat
 // returning atomic per instance).
 __global__ __launch_bounds__(kDenseThreads) void scatter_dense_kernel(SplatGaussians g, SplatState st, int gx, int T) {
     extern __shared__ unsigned s_tile[];
-    if ((long long)st.status[0] > st.capacity) return;      // lists would not fit: host re-sizes and retries
+    if ((long long)st.status[SPLAT_STATUS_INSTANCES] > st.capacity) return;      // lists would not fit: host re-sizes and retries
     const int tid = threadIdx.x;
     for (int t = tid; t < T; t += kDenseThreads) s_tile[t] = 0u;
     __syncthreads();
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kDenseThreads) void scatter_dense_kernel(SplatGauss
 //    of LDS; beyond that the multi-workgroup kernels further down, or in place in HBM without their scratch.
 constexpr int kSortWave = 1024;
 
-// The host may know the longest list (status[2] of an earlier iteration).  The long-list kernel is skipped only when that
+// The host may know the longest list (status[SPLAT_STATUS_LONGEST] of an earlier iteration).  The long-list kernel is skipped only when that
 // hint leaves a 1.5x margin (the margin the bucket stride uses): lists grow a little from iteration to iteration.
 __host__ __device__ inline bool long_sort_skipped(int max_list_hint) {
     return max_list_hint > 0 && max_list_hint + max_list_hint / 2 <= kSortWave;
@@ -111,8 +111,8 @@ __global__ __launch_bounds__(64) void tile_sort_wave_kernel(SplatState st) {
     __shared__ __attribute__((aligned(8))) unsigned s_hist[256];
     const int tile = blockIdx.x, tid = threadIdx.x;
     if (st.tile_stride == 0) {
-        if ((long long)st.status[0] > st.capacity) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) st.status[1] = 1;
+        if ((long long)st.status[SPLAT_STATUS_INSTANCES] > st.capacity) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) st.status[SPLAT_STATUS_OVERFLOW] = 1;
             return;
         }
     }
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64) void tile_sort_wave_kernel(SplatState st) {
         // list is that long and skipped that launch.  Then flag it so that the host re-runs, and publish the ids
         // UNSORTED so that the composite kernels of this (invalid) iteration still read valid Gaussian indices.
         if (long_sort_skipped(st.max_list_hint)) {
-            if (tid == 0) atomicOr((unsigned *)&st.status[3], 1u);
+            if (tid == 0) atomicOr((unsigned *)&st.status[SPLAT_STATUS_STALE_HINT], 1u);
             for (int i = tid; i < n; i += 64) st.point_list[lo + i] = (uint32_t)st.keys[lo + i];
         }
         return;
@@ -145,12 +145,12 @@ __global__ __launch_bounds__(64) void tile_sort_wave_kernel(SplatState st) {
 }
 
 // `long_launched`: the host launches the multi-workgroup kernels below in this call (it decides from its list-length hint, which may
-// be stale: a list beyond LDS that nobody is going to sort is flagged -- status[3], the host repeats the iteration -- and published
+// be stale: a list beyond LDS that nobody is going to sort is flagged -- status[SPLAT_STATUS_STALE_HINT], the host repeats the iteration -- and published
 // unsorted, so that the composites of the invalid iteration still read valid Gaussian indices).
 __global__ __launch_bounds__(kSortBlock) void tile_sort_block_kernel(SplatState st, bool long_launched, int T) {
     __shared__ __attribute__((aligned(16))) uint64_t s_keys[kSortLds + 1024], s_alt[kSortLds + 1024];
     __shared__ __attribute__((aligned(8))) unsigned s_scratch[400];
-    if (st.tile_stride == 0 && (long long)st.status[0] > st.capacity) return;
+    if (st.tile_stride == 0 && (long long)st.status[SPLAT_STATUS_INSTANCES] > st.capacity) return;
     const int tid = threadIdx.x;
     // (2 x (kSortLds + 1024) keys + scratch = ~83 KB of LDS: one workgroup per CU -- a fixed grid walks the tiles, most of which have
     //  nothing for this kernel)
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kSortBlock) void tile_sort_block_kernel(SplatState 
             bitonic_sort(gk, n, tid, kSortBlock);
             for (int i = tid; i < n; i += kSortBlock) st.point_list[lo + i] = (uint32_t)gk[i];
         } else if (!long_launched) {
-            if (tid == 0) atomicOr((unsigned *)&st.status[3], 1u);
+            if (tid == 0) atomicOr((unsigned *)&st.status[SPLAT_STATUS_STALE_HINT], 1u);
             for (int i = tid; i < n; i += kSortBlock) st.point_list[lo + i] = (uint32_t)gk[i];
         }
     }
@@ -203,7 +203,7 @@ __host__ __device__ inline int long_passes(long long n) {      // merge passes a
 __global__ __launch_bounds__(1024) void long_scan_kernel(SplatState st, int T) {
     __shared__ unsigned wave_tot[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool dead = st.tile_stride == 0 && (long long)st.status[0] > st.capacity;      // lists were published empty
+    const bool dead = st.tile_stride == 0 && (long long)st.status[SPLAT_STATUS_INSTANCES] > st.capacity;      // lists were published empty
     const int per = (T + 1023) / 1024;
     const int lo = tid * per, hi = min(T, lo + per);
     auto items_of = [&](int t) -> unsigned {
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(kSortBlock) void long_run_sort_kernel(SplatState st
 __global__ __launch_bounds__(kBlock) void long_merge_kernel(SplatState st, int T, int pass) {
     __shared__ uint64_t s_in[kItemKeys];
     const long long L = (long long)kRun << pass;               // run length going into this pass
-    if (st.tile_stride == 0 && L >= (long long)st.status[2]) return;      // (exact lists: the scan knows the longest list of this iteration)
+    if (st.tile_stride == 0 && L >= (long long)st.status[SPLAT_STATUS_LONGEST]) return;      // (exact lists: the scan knows the longest list of this iteration)
     const unsigned total = st.long_base[T];
     const int Li = (int)L, tid = threadIdx.x;
     for (unsigned item = blockIdx.x; item < total; item += gridDim.x) {
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(kBlock) void long_merge_kernel(SplatState st, int T
 }
 
 // `passes`: merge passes the host launched (from its bound on the list length).  A list that needed more (stale hint) is flagged
-// -- status[3], the host repeats the iteration -- and published from the buffer its LAST LAUNCHED pass wrote: half merged, but valid ids.
+// -- status[SPLAT_STATUS_STALE_HINT], the host repeats the iteration -- and published from the buffer its LAST LAUNCHED pass wrote: half merged, but valid ids.
 __global__ __launch_bounds__(kBlock) void long_publish_kernel(SplatState st, int T, int passes) {
     const unsigned total = st.long_base[T];
     for (unsigned item = blockIdx.x; item < total; item += gridDim.x) {
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void long_publish_kernel(SplatState st, int
         int done = long_passes(n);
         if (done > passes) {
             done = passes;
-            if (chunk == 0 && threadIdx.x == 0) atomicOr((unsigned *)&st.status[3], 1u);
+            if (chunk == 0 && threadIdx.x == 0) atomicOr((unsigned *)&st.status[SPLAT_STATUS_STALE_HINT], 1u);
         }
         const uint64_t *buf = ((done & 1) ? st.keys_alt : st.keys) + lo;
 #pragma unroll
@@ -388,7 +388,7 @@ hipError_t launch_bin_forward(const SplatCamera &cam, const SplatGaussians &g, S
     }
     if (T > 0 && sort) {
         hipLaunchKernelGGL(tile_sort_wave_kernel, dim3(T), dim3(64), 0, s, st);
-        // the host may know the longest list (status[2]); only then can the long-list kernels be skipped
+        // the host may know the longest list (status[SPLAT_STATUS_LONGEST]); only then can the long-list kernels be skipped
         if (!long_sort_skipped(st.max_list_hint)) {
             const long long hint = st.max_list_hint > 0 ? (long long)st.max_list_hint + st.max_list_hint / 2 : (long long)1 << 40;
             const bool long_path = st.keys_alt && st.long_base && hint > kSortLds && st.capacity > kSortLds;

@@ -267,7 +267,7 @@ int splat_iter_time_kernel(int fn, int iters, const SplatCamera *cam, int32_t P,
     // fn 3: forward and backward composite ALTERNATING, as the iteration issues them (the forward one in its sorting form when the
     // state allows it): time(fn 3) - time(fn 2 or 0) is the backward composite between other kernels -- 30 launches of it in a row
     // read ~10 % longer than rocprofv3's per-kernel average of the loop
-    const bool can_sort = st.tile_stride > 0 && st.max_list_hint > 0 && st.max_list_hint + st.max_list_hint / 4 <= 1024;
+    const bool can_sort = st.tile_stride > 0 && lists_sorted_by_composite(st);
     if (fn == 2 || (fn == 3 && can_sort)) {
         if (!can_sort) return SPLAT_E_INVALID;
         sort_form = true;
@@ -279,8 +279,8 @@ int splat_iter_time_kernel(int fn, int iters, const SplatCamera *cam, int32_t P,
     (void)hipEventRecord(e0, s);
     for (int i = 0; i < iters && err == hipSuccess; ++i) {
         if (fn != 1 && fn != 4) err = launch_render_forward_feat8(*cam, ws->feat8, st, ws->out6, sort_form, s);
-        if ((fn == 1 || fn == 3) && err == hipSuccess) err = launch_render_backward_feat8(*cam, ws->feat8, st, ws->dL_dout6, ws->accum, P, false, true, s);
-        if (fn == 4) err = launch_render_backward_feat8(*cam, ws->feat8, st, ws->dL_dout6, ws->accum, P, false, false, s, false);     // tracking form
+        if ((fn == 1 || fn == 3) && err == hipSuccess) err = launch_render_backward_feat8(*cam, ws->feat8, st, ws->dL_dout6, ws->accum, P, false, IterSums::MapRgb, s);
+        if (fn == 4) err = launch_render_backward_feat8(*cam, ws->feat8, st, ws->dL_dout6, ws->accum, P, false, IterSums::Track, s);
     }
     (void)hipEventRecord(e1, s);
     // the timed backward launches accumulated into ws->accum: restore the workspace invariant (every iteration leaves the

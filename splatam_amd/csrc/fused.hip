@@ -144,7 +144,7 @@ __global__ __launch_bounds__(BLOCK) void fused_preprocess_kernel(FusedArgs a) {
     if (i == 0 && a.ws.st.tile_stride > 0) {
         // bucketed lists have no scan kernel: the per-iteration status words are reset here and re-accumulated by the
         // kernel that consumes the tile counters (fused_backward_kernel); [1] (overflow) stays sticky for the host
-        a.ws.st.status[0] = 0; a.ws.st.status[2] = 0; a.ws.st.status[3] = 0;
+        a.ws.st.status[SPLAT_STATUS_INSTANCES] = 0; a.ws.st.status[SPLAT_STATUS_LONGEST] = 0; a.ws.st.status[SPLAT_STATUS_STALE_HINT] = 0;
     }
     SplatState &st = a.ws.st;
     Projected o{};
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) void fused_preprocess_kernel(FusedArgs a) {
                 else spilled = true;
             }
     }
-    if (spilled) st.status[1] = 1;
+    if (spilled) st.status[SPLAT_STATUS_OVERFLOW] = 1;
 }
 
 // F1 for LONG bucketed lists of a map in ANY order (BASELINE config E: millions of Gaussians on a few hundred tiles).  One returning
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(kDenseBlock) void fused_preprocess_dense_kernel(Fus
     load_cam(c, a.cam);
     const int T = c.gx * c.gy;
     for (int t = tid; t < T; t += kDenseBlock) s_tile[t] = 0u;
-    if (blockIdx.x == 0 && tid == 0) { a.ws.st.status[0] = 0; a.ws.st.status[2] = 0; a.ws.st.status[3] = 0; }     // (see fused_preprocess_kernel)
+    if (blockIdx.x == 0 && tid == 0) { a.ws.st.status[SPLAT_STATUS_INSTANCES] = 0; a.ws.st.status[SPLAT_STATUS_LONGEST] = 0; a.ws.st.status[SPLAT_STATUS_STALE_HINT] = 0; }     // (see fused_preprocess_kernel)
     __syncthreads();
     const SplatState &st = a.ws.st;
     unsigned r0[kDensePerThread], r1[kDensePerThread], dbits[kDensePerThread];
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(kDenseBlock) void fused_preprocess_dense_kernel(Fus
                 else spilled = true;
             }
     }
-    if (spilled) st.status[1] = 1;
+    if (spilled) st.status[SPLAT_STATUS_OVERFLOW] = 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(kBlock) void track_loss_kernel(FusedArgs a, int HW)
     const float *o = a.ws.out6;
     float *g = a.ws.dL_dout6;
     const bool masked_im = a.cfg.use_sil_for_loss || a.cfg.ignore_outlier_depth_loss;
-    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[13] : 0.f;
+    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     float acc[2] = {0.f, 0.f};
     const int nvec = HW / V;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < nvec; i += gridDim.x * kBlock) {
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W
         load_px4<VEC>(Y, y0 + hr, x0 + hc, W, H, own_y);
     }
     __syncthreads();
-    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[13] : 0.f;
+    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};        // depth L1 (masked), image L1, mask count, SSIM map sum
     if (tid < kCItems) {                        // horizontal pass: 14 columns of sums feed 4 output pixels
         f2 oA[4], oB[4];
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(kBlock) void map_loss_backward_kernel(FusedArgs a, 
     __syncthreads();
     if (tid >= kCItems) return;
     const float inv_n = 1.0f / (3.0f * (float)HW);
-    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[13] : 0.f;
+    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     const float count = s_count;
     f2 oA[4];
     float oC[4];
@@ -804,9 +804,9 @@ __global__ __launch_bounds__(256) void pose_finish_kernel(FusedArgs a, int HW, P
         if (pa.state) pose_adam_load(a.map, a.frame.time_idx, pa, adam);
 #pragma unroll
         for (int k = 0; k < 4; ++k) stat[k] = a.ws.st.status[k];
-        flagged = stat[1] | stat[3];
-        sticky = a.ws.d_cam[12];
-        skipped = reinterpret_cast<const int *>(a.ws.d_cam)[21];
+        flagged = stat[SPLAT_STATUS_OVERFLOW] | stat[SPLAT_STATUS_STALE_HINT];
+        sticky = a.ws.d_cam[SPLAT_REPORT_FLAG];
+        skipped = reinterpret_cast<const int *>(a.ws.d_cam)[SPLAT_REPORT_SKIPPED];
     }
     // (all eight loads first, then the resets: a store between two loads makes the second wait for the first)
     double part_sum[8];
@@ -834,8 +834,8 @@ __global__ __launch_bounds__(256) void pose_finish_kernel(FusedArgs a, int HW, P
         for (int k = 0; k < kPoseSums; ++k) sums[k] = (float)S[8 + k];
         pose_backward(P, sums, dq, dt);
     }
-    for (int k = 0; k < 4; ++k) out[k] = dq[k];
-    for (int k = 0; k < 3; ++k) out[4 + k] = dt[k];
+    for (int k = 0; k < 4; ++k) out[SPLAT_REPORT_DROT + k] = dq[k];
+    for (int k = 0; k < 3; ++k) out[SPLAT_REPORT_DTRANS + k] = dt[k];
     float loss, w_depth_term, w_im_term;
     const float l_depth = a.cfg.use_l1 ? (float)S[0] : 0.f;
     if (a.cfg.tracking) {
@@ -848,16 +848,16 @@ __global__ __launch_bounds__(256) void pose_finish_kernel(FusedArgs a, int HW, P
         w_im_term = a.cfg.w_im * l_im;
     }
     loss = w_depth_term + w_im_term;
-    out[7] = loss;
-    for (int k = 0; k < 4; ++k) out[8 + k] = (float)S[k];       // raw sums, for inspection
+    out[SPLAT_REPORT_LOSS] = loss;
+    for (int k = 0; k < 4; ++k) out[SPLAT_REPORT_SUMS + k] = (float)S[k];       // raw sums, for inspection
     const bool gate_up = flagged != 0 || sticky != 0.f;
-    if (flagged != 0) out[12] = 1.0f;     // sticky until the host clears it
-    out[14] = w_depth_term;
-    out[15] = w_im_term;
+    if (flagged != 0) out[SPLAT_REPORT_FLAG] = 1.0f;     // sticky until the host clears it
+    out[SPLAT_REPORT_DEPTH_TERM] = w_depth_term;
+    out[SPLAT_REPORT_IM_TERM] = w_im_term;
     int *outi = reinterpret_cast<int *>(out);
-    for (int k = 0; k < 4; ++k) outi[16 + k] = stat[k];
-    outi[20] = flagged != 0 ? 1 : 0;
-    if (gate_up) outi[21] = skipped + 1;  // an iteration on truncated / unsorted lists: no Adam step moves anything (see SplatIterWorkspace.d_cam)
+    for (int k = 0; k < 4; ++k) outi[SPLAT_REPORT_STATUS + k] = stat[k];
+    outi[SPLAT_REPORT_FLAGGED] = flagged != 0 ? 1 : 0;
+    if (gate_up) outi[SPLAT_REPORT_SKIPPED] = skipped + 1;  // an iteration on truncated / unsorted lists: no Adam step moves anything (see SplatIterWorkspace.d_cam)
     if (pa.state && !gate_up) {
         float g[7];
         for (int k = 0; k < 4; ++k) g[k] = dq[k];
@@ -897,13 +897,13 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
         Pose P;
         load_pose(a.map, a.frame.time_idx, P);
         const float w2c_row2[4] = {a.frame.w2c[8], a.frame.w2c[9], a.frame.w2c[10], a.frame.w2c[11]};
-        // (MAPGRADS = false, camera tracking: the backward composite's tracking form publishes S1..S5 and the depth channel's colour sum
-        //  in slots 0..5 -- render.hip kTrackSlots --: half the accumulator line is read and cleared)
-        //  (MAPGRADS = true: the fused iteration's backward composites carry gradient in r, g, b, z only -- launch_render_backward_feat8,
-        //  the full-gradient tracking composite -- i.e. S1..S6 and four colour sums in slots 0..9: three quarters of the line; slots 10..15
-        //  are never written on this path and stay at the zero they were allocated with)
-        constexpr int kRow4 = MAPGRADS ? 3 : 2;
-        static_assert(SPLAT_GRAD_STRIDE >= 12, "slots 0..9 live in the first three float4 of the accumulator row");
+        // the accumulator row (splat_math.h) in the form the backward composite took: the tracking form exactly when no map gradient is
+        // wanted (iter_sums), else a mapping form -- with or without the r, g, b sums, laid out alike.  The tracking form fills half the
+        // line, a mapping form three quarters (the slots behind it are never written on this path and stay at the zero they were
+        // allocated with)
+        constexpr bool kTrack = !MAPGRADS;
+        constexpr int kRow4 = acc_row4(kTrack ? kAccTrackMask : 0xFu, !kTrack);
+        static_assert(kTrack || (acc_row4(kAccTrackMask, true) == kRow4 && acc_colour_slot(false, 5) < 4 * kRow4), "one row for both mapping forms");
         float acc[SPLAT_GRAD_STRIDE];
 #pragma unroll
         for (int k = 0; k < SPLAT_GRAD_STRIDE; ++k) acc[k] = 0.f;
@@ -917,9 +917,9 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
         load_gaussian(a.map, i, p, u, logit, ls);
         const float4 co = reinterpret_cast<const float4 *>(ws.st.conic_opacity)[i];
         // the Adam step is skipped while a capacity flag is up (this iteration's lists, or an earlier iteration's the host has not
-        // dealt with yet: SplatIterWorkspace.d_cam[12]); wave-uniform
+        // dealt with yet: SPLAT_REPORT_FLAG); wave-uniform
         bool gate_up = false;
-        if constexpr (ADAM) gate_up = (ws.st.status[1] | ws.st.status[3]) != 0 || ws.d_cam[12] != 0.f;
+        if constexpr (ADAM) gate_up = (ws.st.status[SPLAT_STATUS_OVERFLOW] | ws.st.status[SPLAT_STATUS_STALE_HINT]) != 0 || ws.d_cam[SPLAT_REPORT_FLAG] != 0.f;
         // the row is consumed: the next iteration's K7 accumulates from zero without a memset.  (Unconditional -- rows outside the view
         // are zero already -- and AFTER every load above: a store the compiler can neither sink nor prove disjoint pins them up here,
         // ahead of the visibility test.)
@@ -933,15 +933,15 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
             glue_forward(P, w2c_row2, p, u, logit, ls, iso, G);
             float S6[6];
             cov3d_from_scale_rot(G.s, c.scale_modifier, G.rq, S6);
-            const float g_ndc[2] = {-(co.x * acc[0] + co.y * acc[1]) * 0.5f * c.W, -(co.z * acc[1] + co.y * acc[0]) * 0.5f * c.H};
-            const float g_conic[3] = {-0.5f * acc[2], -acc[3], -0.5f * acc[4]};
+            float g_ndc[2], g_conic[3];
+            screen_grads(acc, co.x, co.y, co.z, c.W, c.H, g_ndc, g_conic);
             float dXc[3], dS6[6], ds[3] = {0.f, 0.f, 0.f}, drq[4] = {0.f, 0.f, 0.f, 0.f};
             project_gaussian_backward(c, G.Xc, S6, g_ndc, g_conic, dXc, dS6);
             if constexpr (MAPGRADS || !ISO) cov3d_backward(G.s, c.scale_modifier, G.rq, dS6, ds, drq);
-            // colour channels: 6..8 rgb, 9 z, 10 silhouette (constant), 11 z^2
-            drgb[0] = acc[6]; drgb[1] = acc[7]; drgb[2] = acc[8];
-            const float dz = MAPGRADS ? acc[9] + 2.f * G.z * acc[11] : acc[5];     // (tracking form: the depth channel's sum sits in slot 5)
-            glue_backward(P, w2c_row2, p, iso, G, dXc, dz, MAPGRADS ? acc[5] : 0.f, ds, drq, dp, du, &dlogit, dls, pose);
+            // colour channels: 0..2 rgb (used by the mapping forms only), 3 z, 4 silhouette (constant), 5 z^2
+            drgb[0] = acc[acc_colour_slot(false, 0)]; drgb[1] = acc[acc_colour_slot(false, 1)]; drgb[2] = acc[acc_colour_slot(false, 2)];
+            const float dz = kTrack ? acc[acc_colour_slot(true, 3)] : acc[acc_colour_slot(false, 3)] + 2.f * G.z * acc[acc_colour_slot(false, 5)];
+            glue_backward(P, w2c_row2, p, iso, G, dXc, dz, kTrack ? 0.f : acc[kAccOpacity], ds, drq, dp, du, &dlogit, dls, pose);
         }
         constexpr int kWidth[5] = {3, 3, 4, 1, ISO ? 1 : 3};
         // (the moments: one more round trip, all 27 loads at once, issued ahead of the gradient stores; holding them across the adjoint
@@ -1019,11 +1019,11 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
         }
         if (blockIdx.x * kBlock < T) {              // uniform per block; later blocks hold no tile
             for (int m = 32; m >= 1; m >>= 1) { sum += (unsigned)__shfl_xor((int)sum, m, 64); mx = max(mx, (unsigned)__shfl_xor((int)mx, m, 64)); }
-            if ((threadIdx.x & 63) == 0 && sum) { atomicAdd((unsigned *)&ws.st.status[0], sum); atomicMax((unsigned *)&ws.st.status[2], mx); }
+            if ((threadIdx.x & 63) == 0 && sum) { atomicAdd((unsigned *)&ws.st.status[SPLAT_STATUS_INSTANCES], sum); atomicMax((unsigned *)&ws.st.status[SPLAT_STATUS_LONGEST], mx); }
         }
     }
     // a band of tile rows (the other ranks hold the other bands): this rank's capacity flags travel with the partial sums
-    if (a.cfg.defer_finish && i == 0 && (ws.st.status[1] | ws.st.status[3]) != 0) atomicAdd(ws.sums + kFlagSum, 1.0);
+    if (a.cfg.defer_finish && i == 0 && (ws.st.status[SPLAT_STATUS_OVERFLOW] | ws.st.status[SPLAT_STATUS_STALE_HINT]) != 0) atomicAdd(ws.sums + kFlagSum, 1.0);
     if (a.cfg.camera_grad) block_sum_to<kPoseSums>(sum_copy(ws.sums) + 8, pose, s_part);
 }
 
@@ -1039,7 +1039,7 @@ struct AdamArgs {
 __global__ __launch_bounds__(kBlock) void adam_map_kernel(AdamArgs a, long long total) {
     const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (e >= total) return;
-    if (a.opt.gate && a.opt.gate[12] != 0.f) return;            // the iteration that formed these gradients ran on truncated lists
+    if (a.opt.gate && a.opt.gate[SPLAT_REPORT_FLAG] != 0.f) return;            // the iteration that formed these gradients ran on truncated lists
     float *params[5] = {a.map.means3D, a.map.rgb_colors, a.map.unnorm_rotations, a.map.logit_opacities, a.map.log_scales};
     const int width[5] = {3, 3, 4, 1, a.map.isotropic ? 1 : 3};
     long long off = 0;
@@ -1089,9 +1089,9 @@ __global__ __launch_bounds__(256) void fold_sums_kernel(double *sums) {
 __global__ void adam_pose_kernel(SplatMap map, int time_idx, const float *d_cam, float *state, float beta1, float beta2,
                                  float eps, float bc2_sqrt, float ss_rot, float ss_trans) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (d_cam[12] != 0.f) return;                               // (see SplatIterWorkspace.d_cam[12])
+    if (d_cam[SPLAT_REPORT_FLAG] != 0.f) return;                // (see SPLAT_REPORT_FLAG)
     const PoseAdam pa{state, beta1, beta2, eps, bc2_sqrt, ss_rot, ss_trans};
-    pose_adam_step(map, time_idx, d_cam, d_cam[7], pa);
+    pose_adam_step(map, time_idx, d_cam + SPLAT_REPORT_DROT, d_cam[SPLAT_REPORT_LOSS], pa);
 }
 
 }  // namespace
@@ -1106,6 +1106,13 @@ static bool group_binning(const SplatState &st, const SplatCamera &cam) { return
 // (whole frames only: a band of tile rows is composited in the natural order)
 static int finish_blocks(const SplatState &st) {
     return (st.tile_work && st.tile_order && st.tile_row_end <= st.tile_row_begin) ? 9 : 1;
+}
+
+// which sums the backward composite forms -- what a stored gradient or a stepped group needs -- and with them the form of the
+// accumulator rows F6 reads: the tracking form exactly when no map gradient is wanted (fused_backward_kernel<.., MAPGRADS = false>)
+static IterSums iter_sums(const SplatIterWorkspace &ws, const SplatAdamMap *map_adam) {
+    if (!map_adam && !ws.d_means3D && !ws.d_rgb_colors && !ws.d_unnorm_rotations && !ws.d_logit_opacities && !ws.d_log_scales) return IterSums::Track;
+    return ws.d_rgb_colors || (map_adam && map_adam->grad[1]) ? IterSums::MapRgb : IterSums::Map;
 }
 
 // F1 in the mode the state asks for
@@ -1163,17 +1170,17 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
     // (map gradients wanted as well -- the reference's backward() forms dL/d(rgb, opacity, scale) in tracking too --: the same kernel
     //  with the backward composite's mapping form inside)
     const bool one_kernel = fuse_loss && sort_in_k6 && cfg.fused_composite != 0;
-    const bool full_sums = ws.d_rgb_colors != nullptr || ws.d_logit_opacities != nullptr;
+    const IterSums sums = iter_sums(ws, map_adam);
     if (one_kernel) {
-        e = launch_render_track_fused(cam, ws.feat8, ws.st, ws.out6, ws.accum, ep, cfg.fused_composite == 2, s, full_sums);
+        e = launch_render_track_fused(cam, ws.feat8, ws.st, ws.out6, ws.accum, ep, cfg.fused_composite == 2, s, sums);
         if (e != hipSuccess) return e;
     } else {
         e = launch_render_forward_feat8(cam, ws.feat8, ws.st, ws.out6, sort_in_k6, s, fuse_loss ? &ep : nullptr, fuse_loss ? &loss_done : nullptr);
         if (e != hipSuccess) return e;
         if (cfg.ignore_outlier_depth_loss) {
-            // torch.median of the depth error (exact radix selection, mapedit.hip) -> d_cam[13] (its bits through counts[4])
+            // torch.median of the depth error (exact radix selection, mapedit.hip) -> SPLAT_REPORT_MEDIAN (its bits through counts[4])
             e = launch_depth_error_median(ws.out6, frame.depth, ws.outlier_err, ws.outlier_scratch, HW,
-                                          reinterpret_cast<int32_t *>(ws.d_cam) + 9, s);
+                                          reinterpret_cast<int32_t *>(ws.d_cam) + SPLAT_REPORT_MEDIAN - 4, s);
             if (e != hipSuccess) return e;
         }
         if (cfg.tracking && loss_done) {
@@ -1197,10 +1204,7 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
                 hipLaunchKernelGGL(map_loss_backward_kernel<false>, grid, dim3(kBlock), 0, s, a, W, H);
             }
         }
-        // (which sums the backward composite forms: what a stored gradient or a stepped group needs)
-        e = launch_render_backward_feat8(cam, ws.feat8, ws.st, ws.dL_dout6, ws.accum, P, false,
-                                         ws.d_rgb_colors != nullptr || (map_adam && map_adam->grad[1]), s,
-                                         ws.d_logit_opacities != nullptr || (map_adam && map_adam->grad[3]));
+        e = launch_render_backward_feat8(cam, ws.feat8, ws.st, ws.dL_dout6, ws.accum, P, false, sums, s);
         if (e != hipSuccess) return e;
     }
     PoseAdam pa{};
@@ -1209,7 +1213,7 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
                       pose_adam->step_size_trans};
     if (P > 0) {
         const bool iso = map.isotropic != 0;
-        const bool mapgrads = ws.d_means3D || ws.d_rgb_colors || ws.d_unnorm_rotations || ws.d_logit_opacities || ws.d_log_scales;
+        const bool mapgrads = sums != IterSums::Track;
         const SplatAdamMap opt = map_adam ? *map_adam : SplatAdamMap{};
         const dim3 grid(gblocks), block(kBlock);
         if (map_adam && iso) hipLaunchKernelGGL((fused_backward_kernel<true, true, true>), grid, block, 0, s, a, opt);
@@ -1267,21 +1271,26 @@ hipError_t launch_iter_render(const SplatCamera &cam, const SplatMap &map, const
 
 namespace {
 // accumulate_mean2d_gradient (/root/reference/utils/slam_external.py:100-104) from the colour-only sums S1, S2 of a Gaussian:
-// dL/dmeans2D (NDC, as the rasterizer returns it) = -(conic . S) * 0.5 * (W, H)   (K8: splat_math.h / fused_backward_kernel)
+// dL/dmeans2D (NDC, as the rasterizer returns it) = -(conic . S) * 0.5 * (W, H)   (splat_math.h: screen_grads)
 __global__ __launch_bounds__(kBlock) void means2d_accumulate_kernel(SplatIterWorkspace ws, int P, int W, int H, float *gaccum, float *denom, float *out) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= P) return;
     float gx = 0.f, gy = 0.f;
     const bool seen = ws.st.radii[i] > 0;
     if (seen) {
+        constexpr int kRow4 = acc_row4(0x0u, false);           // the colour pass' form: S1..S5 alone (launch_render_backward_rgb_only)
+        float acc[4 * kRow4];
         float4 *a4 = reinterpret_cast<float4 *>(ws.accum + (size_t)i * SPLAT_GRAD_STRIDE);
-        const float4 s0 = a4[0], s1 = a4[1];
-        a4[0] = make_float4(0.f, 0.f, 0.f, 0.f);               // consumed (slots 0..4 were written)
-        a4[1] = make_float4(0.f, 0.f, 0.f, 0.f);
-        (void)s1;
+        for (int k = 0; k < kRow4; ++k) {
+            const float4 v = a4[k];
+            acc[4 * k] = v.x; acc[4 * k + 1] = v.y; acc[4 * k + 2] = v.z; acc[4 * k + 3] = v.w;
+        }
+        for (int k = 0; k < kRow4; ++k) a4[k] = make_float4(0.f, 0.f, 0.f, 0.f);        // consumed
         const float4 co = reinterpret_cast<const float4 *>(ws.st.conic_opacity)[i];
-        gx = -(co.x * s0.x + co.y * s0.y) * 0.5f * (float)W;
-        gy = -(co.z * s0.y + co.y * s0.x) * 0.5f * (float)H;
+        float g_ndc[2], g_conic[3];
+        screen_grads(acc, co.x, co.y, co.z, (float)W, (float)H, g_ndc, g_conic);
+        gx = g_ndc[0];
+        gy = g_ndc[1];
         if (gaccum) {                       // (NULL: the caller only wants the gradient itself, splatam_amd.plugin)
             gaccum[i] += sqrtf(gx * gx + gy * gy);
             denom[i] += 1.0f;

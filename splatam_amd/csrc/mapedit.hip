@@ -523,7 +523,7 @@ __global__ __launch_bounds__(kBlock) void fold_tile_counters_kernel(SplatState s
         mx = max(mx, cnt);
     }
     for (int m = 32; m >= 1; m >>= 1) { sum += (unsigned)__shfl_xor((int)sum, m, 64); mx = max(mx, (unsigned)__shfl_xor((int)mx, m, 64)); }
-    if ((threadIdx.x & 63) == 0 && sum) { atomicAdd((unsigned *)&st.status[0], sum); atomicMax((unsigned *)&st.status[2], mx); }
+    if ((threadIdx.x & 63) == 0 && sum) { atomicAdd((unsigned *)&st.status[SPLAT_STATUS_INSTANCES], sum); atomicMax((unsigned *)&st.status[SPLAT_STATUS_LONGEST], mx); }
 }
 
 MapArrays map_arrays(const SplatMapStore &st) {

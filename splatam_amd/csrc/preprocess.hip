@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_forward_kernel(SplatCamera 
 // front end of the fused iteration, splat_device.h file_group_records): one 16-byte record per touched group of 2 x 2 tiles instead of a
 // count per tile now and a scatter later -- no tile scan, no scatter pass, no sort launch (K2-K4), and nothing the host must read
 // before it may launch the composite.  The caller knows (from an earlier call on this scene: SplatState.max_list_hint) that the lists
-// are short; a list that has outgrown the hint is flagged (status[1] / status[3]) by the composite and the call must be repeated on
+// are short; a list that has outgrown the hint is flagged (status[SPLAT_STATUS_OVERFLOW] / status[SPLAT_STATUS_STALE_HINT]) by the composite and the call must be repeated on
 // exact lists.
 __global__ __launch_bounds__(kGroupBlock) void preprocess_forward_group_kernel(SplatCamera cam, SplatGaussians g, SplatState st) {
     extern __shared__ unsigned s_grp[];
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(kScanBlock) void tile_scan_finish_kernel(SplatState
     before = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
     all = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
     mx = max(max(s_red[2][0], s_red[2][1]), max(s_red[2][2], s_red[2][3]));
-    // lists that do not fit the caller's buffers are published as EMPTY (and flagged in status[1]): a composite
+    // lists that do not fit the caller's buffers are published as EMPTY (and flagged in status[SPLAT_STATUS_OVERFLOW]): a composite
     // launched behind an overflowing binning must never index past keys / point_list
     const bool overflow = (long long)all > st.capacity;
     const int t = blockIdx.x * kScanBlock + threadIdx.x;
@@ -210,15 +210,15 @@ __global__ __launch_bounds__(kScanBlock) void tile_scan_finish_kernel(SplatState
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         st.tile_base[T] = overflow ? 0u : all;
-        st.status[0] = (int)all;
-        st.status[1] = overflow ? 1 : 0;
-        st.status[2] = (int)mx;
-        st.status[3] = 0;
+        st.status[SPLAT_STATUS_INSTANCES] = (int)all;
+        st.status[SPLAT_STATUS_OVERFLOW] = overflow ? 1 : 0;
+        st.status[SPLAT_STATUS_LONGEST] = (int)mx;
+        st.status[SPLAT_STATUS_STALE_HINT] = 0;
     }
 }
 
-// K8+K9 fused: from the per-Gaussian partial sums of the backward composite
-// (accum[i] = {S1..S6, colour sums}) to every dL/d(input).
+// K8+K9 fused: from the per-Gaussian partial sums of the backward composite (the accumulator row of splat_math.h in the
+// reference API's form: S1..S6 and the colour sums of every channel) to every dL/d(input).
 __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(SplatCamera cam, SplatGaussians g, SplatState st,
                                                                     SplatGrads gr) {
     const int i = blockIdx.x * kBlock + threadIdx.x;
@@ -248,10 +248,8 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(SplatCamera
             cov3d_from_scale_rot(s, c.scale_modifier, q, S6);
         }
         const float4 co = reinterpret_cast<const float4 *>(st.conic_opacity)[i];
-        // S1 = sum q*G*dx, S2 = sum q*G*dy, S3 = sum q*G*dx*dx, S4 = sum q*G*dx*dy, S5 = sum q*G*dy*dy
-        g_ndc[0] = -(co.x * acc[0] + co.y * acc[1]) * 0.5f * c.W;
-        g_ndc[1] = -(co.z * acc[1] + co.y * acc[0]) * 0.5f * c.H;
-        const float g_conic[3] = {-0.5f * acc[2], -acc[3], -0.5f * acc[4]};
+        float g_conic[3];
+        screen_grads(acc, co.x, co.y, co.z, c.W, c.H, g_ndc, g_conic);
         project_gaussian_backward(c, p, S6, g_ndc, g_conic, dmean, dS6);
         if (gr.dL_dscales && g.scales) {
             const float s[3] = {g.scales[3 * i], g.scales[3 * i + 1], g.scales[3 * i + 2]};
@@ -274,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(SplatCamera
             float *dsh = gr.dL_dshs + (size_t)i * g.sh_coeffs * 3;
             float ddir[3] = {0.f, 0.f, 0.f};
             for (int ch = 0; ch < 3; ++ch) {
-                const float gc = st.clamped[3 * i + ch] ? 0.f : acc[6 + ch];
+                const float gc = st.clamped[3 * i + ch] ? 0.f : acc[acc_colour_slot(false, ch)];
                 for (int k = 0; k < nb; ++k) {
                     dsh[3 * k + ch] = basis[k] * gc;
                     const float w = sh[3 * k + ch] * gc;
@@ -296,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(SplatCamera
             for (int k = 0; k < g.sh_coeffs * 3; ++k) dsh[k] = 0.f;
         }
     }
-    if ((gr.flags & SPLAT_GRADS_POISON_IF_FLAGGED) && st.tile_stride > 0 && (st.status[1] | st.status[3]) != 0) {
+    if ((gr.flags & SPLAT_GRADS_POISON_IF_FLAGGED) && st.tile_stride > 0 && (st.status[SPLAT_STATUS_OVERFLOW] | st.status[SPLAT_STATUS_STALE_HINT]) != 0) {
         // the forward pass ran on truncated lists and nobody has looked (SplatGrads.flags): nothing plausible leaves this call
         const float nan = __int_as_float(0x7fc00000);
         for (int k = 0; k < 3; ++k) dmean[k] = nan;
@@ -312,10 +310,10 @@ __global__ __launch_bounds__(kBlock) void preprocess_backward_kernel(SplatCamera
     gr.dL_dmeans2D[3 * i] = g_ndc[0];
     gr.dL_dmeans2D[3 * i + 1] = g_ndc[1];
     gr.dL_dmeans2D[3 * i + 2] = 0.f;
-    const bool poisoned = acc[5] != acc[5] && g_ndc[0] != g_ndc[0];     // (see above: a poisoned row is NaN whether or not the Gaussian was seen)
-    gr.dL_dopacities[i] = (vis || poisoned) ? acc[5] : 0.f;
+    const bool poisoned = acc[kAccOpacity] != acc[kAccOpacity] && g_ndc[0] != g_ndc[0];     // (see above: a poisoned row is NaN whether or not the Gaussian was seen)
+    gr.dL_dopacities[i] = (vis || poisoned) ? acc[kAccOpacity] : 0.f;
     if (gr.dL_dcolors)
-        for (int ch = 0; ch < C; ++ch) gr.dL_dcolors[(size_t)i * C + ch] = (vis || poisoned) ? acc[6 + ch] : 0.f;
+        for (int ch = 0; ch < C; ++ch) gr.dL_dcolors[(size_t)i * C + ch] = (vis || poisoned) ? acc[acc_colour_slot(false, ch)] : 0.f;
     if (gr.dL_dcov3D)
         for (int k = 0; k < 6; ++k) gr.dL_dcov3D[6 * i + k] = dS6[k];
 }

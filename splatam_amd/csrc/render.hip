@@ -489,6 +489,10 @@ template <int C, int CS, bool WITH_DEPTH>
 constexpr bool forward_compact6() { return C == 6 && CS == 8 && !WITH_DEPTH; }
 template <int C, int CS, bool WITH_DEPTH>
 constexpr int forward_fp() { return forward_compact6<C, CS, WITH_DEPTH>() ? 4 : (C + (WITH_DEPTH ? 1 : 0) + 3) / 4 * 4; }
+// the forward composite leaves its staged records in SplatState.tile_recs (one 48-byte record holds four features): a backward
+// composite re-stages from them only behind a forward form that writes them (launch_bwd), else it gathers
+template <int C, int CS, bool WITH_DEPTH>
+constexpr bool forward_writes_recs() { return forward_fp<C, CS, WITH_DEPTH>() == 4; }
 
 // The forward composite of ONE tile up to its per-pixel results (the kernels below add their epilogues): builds / reads the tile's list,
 // stages it batch by batch into B and composites front to back.  Returns the index of the LAST batch it staged (the one B still holds;
@@ -566,13 +570,13 @@ __device__ __forceinline__ int forward_tile(const float *colors, SplatState &st,
             if (tid == 0) {
                 // (a count that is flagged below is published CLAMPED: the backward composite must not walk past the published ids)
                 st.tile_count[(size_t)tile * SPLAT_COUNTER_STRIDE] = (unsigned)min(n, min(st.tile_stride, kFusedSortMax));
-                if (n > st.tile_stride) raise_status(st, 1);      // the published list would not fit its bucket
+                if (n > st.tile_stride) raise_status(st, SPLAT_STATUS_OVERFLOW);      // the published list would not fit its bucket
             }
             n = min(n, st.tile_stride);
         }
         if (n > kFusedSortMax) {        // the host's list-length hint was stale: flag it (the host repeats the iteration)
             if (tid == 0) {
-                raise_status(st, 3);
+                raise_status(st, SPLAT_STATUS_STALE_HINT);
                 if (st.tile_stride > 0) st.tile_count[(size_t)tile * SPLAT_COUNTER_STRIDE] = (unsigned)kFusedSortMax;    // (see above)
             }
             n = kFusedSortMax;
@@ -597,7 +601,7 @@ __device__ __forceinline__ int forward_tile(const float *colors, SplatState &st,
             __syncthreads();                        // every wave has finished reading the previous batch; this batch's list counts are in
             commit(B, pre, tid, wdone ? 1u : 0u, bi & 1);
             staged = bi;
-            if constexpr (FP == 4 && WRITE_RECS) {
+            if constexpr (forward_writes_recs<C, CS, WITH_DEPTH>() && WRITE_RECS) {
                 // the staged record goes to memory as well (SplatState.tile_recs): the backward composite re-stages the list from ONE
                 // coalesced 48-byte read per entry instead of the id -> conic / centre / colour gathers and the culling tests.  The
                 // spare word carries the quadrant mask (a quadrant is visited when one of its four blocks is)
@@ -818,16 +822,6 @@ __global__ __launch_bounds__(256, ((forward_compact6<C, CS, WITH_DEPTH>() || (SP
 // DMASK: channels whose incoming gradient can be non-zero (the others are not even loaded);
 // SMASK: channels whose colour sums (dL/dcolour) the caller needs.  The reference API uses all C for both; the fused
 // iteration knows that the silhouette and depth^2 planes carry no gradient, and that tracking never reads dL/drgb.
-constexpr int popcount_c(unsigned m) { return m == 0 ? 0 : (int)(m & 1u) + popcount_c(m >> 1); }
-constexpr int highest_set_bit(unsigned m) { int h = -1; for (int i = 0; i < 32; ++i) if ((m >> i) & 1u) h = i; return h; }
-constexpr int nth_set_bit(unsigned m, int n) {      // index of the n-th (0-based) set bit
-    int idx = 0;
-    while (true) {
-        if (m & 1u) { if (n == 0) return idx; --n; }
-        m >>= 1; ++idx;
-        if (idx > 31) return -1;
-    }
-}
 
 
 // ---------------------------------------------------------------------------
@@ -941,12 +935,8 @@ __device__ __forceinline__ void backward_core(const float *colors, const SplatSt
     const unsigned lo = st.tile_stride > 0 ? (unsigned)tile * (unsigned)st.tile_stride : st.tile_base[tile];
     const int nb = (int)((tmax + kBatchEntries - 1) / kBatchEntries);
 
-    // accumulator slot of published value k: S1..S5 (S6) -> 0..5, colour sums -> 6 + channel.  The camera-tracking form (no opacity sum,
-    // the depth channel's colour sum only) puts that one sum in the free slot 5: everything tracking publishes then lies in the first
-    // half of the accumulator line, and the per-Gaussian kernel behind it reads and clears 32 bytes per Gaussian instead of 64
-    // (fused.hip: fused_backward_kernel<.., MAPGRADS = false>)
-    constexpr bool kTrackSlots = !OPAC && SMASK == 0x8u;
-    auto slot_of = [](int k) { return k < NB ? k : (kTrackSlots ? 5 : 6 + nth_set_bit(SMASK, k - NB)); };
+    // accumulator slot of published value k (splat_math.h: the backward accumulator row)
+    auto slot_of = [](int k) { return acc_slot(SMASK, OPAC, k); };
     int doff_own = 0, doff_x = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k)
@@ -1404,7 +1394,7 @@ __device__ __forceinline__ void track_fused_body(const TrackFusedArgs &args) {
         return;
     }
     if constexpr (FULL) backward_core<C, CS, 0xFu, 0xFu, true, (DBG & 14)>(feat8, st, accum, B, PB, s_wmax, tile, tx, ty, tid, inside, Tfin, last, dpix, 0.f, staged);
-    else backward_core<C, CS, 0xFu, 0x8u, false, (DBG & 14)>(feat8, st, accum, B, PB, s_wmax, tile, tx, ty, tid, inside, Tfin, last, dpix, 0.f, staged);
+    else backward_core<C, CS, 0xFu, kAccTrackMask, false, (DBG & 14)>(feat8, st, accum, B, PB, s_wmax, tile, tx, ty, tid, inside, Tfin, last, dpix, 0.f, staged);
     // what the next launch's order is built from (SplatState.tile_work): the quadrants' deepest contributors, as the core left them
     if (st.tile_work && tid == 0) st.tile_work[tile] = s_wmax[0] + s_wmax[1] + s_wmax[2] + s_wmax[3];
 }
@@ -1436,11 +1426,12 @@ static void launch_fwd(const SplatCamera &cam, const float *colors, SplatState &
     hipLaunchKernelGGL(k, dim3(8 * per), dim3(256), 0, s,
                        FwdArgs{cam, colors, st, oc, od, T, per, TrackLossEpilogue{}});
 }
-template <int C, int CS, unsigned DMASK = (1u << C) - 1u, unsigned SMASK = (1u << C) - 1u, bool OPAC = true, bool BG = true>
-static void launch_bwd(const SplatCamera &cam, const float *colors, const SplatState &st, const float *dl, float *acc, int T,
-                       hipStream_t s) {
+// WITH_DEPTH: of the forward composite this pass follows (render_forward_kernel<C, CS, WITH_DEPTH, ..>)
+template <int C, int CS, bool WITH_DEPTH, unsigned DMASK = (1u << C) - 1u, unsigned SMASK = (1u << C) - 1u, bool OPAC = true, bool BG = true>
+static void launch_bwd(const SplatCamera &cam, const float *colors, SplatState st, const float *dl, float *acc, int T, hipStream_t s) {
     const int per = (T + 7) / 8;
-    if constexpr (C == 6 && CS == 8 && DMASK == 0xFu && !BG && (SMASK == 0xFu || (SMASK == 0x8u && !OPAC))) {
+    if (!forward_writes_recs<C, CS, WITH_DEPTH>()) st.tile_recs = nullptr;
+    if constexpr (C == 6 && CS == 8 && DMASK == 0xFu && !BG && (SMASK == 0xFu || acc_tracking(SMASK, OPAC))) {
         if (g_debug_k7_bits != 0) {
             constexpr bool W5 = popcount_c(SMASK) <= 2;
             auto go = [&](auto D) {
@@ -1513,18 +1504,18 @@ hipError_t launch_render_backward(const SplatCamera &cam, const SplatGaussians &
     }
     if (T == 0 || g.P == 0) return hipSuccess;
     if (!cam.bg && g.channels == 3) {           // black background (SplatCamera.bg == NULL): the background term of dL/dalpha falls away at compile time
-        launch_bwd<3, 3, 7u, 7u, true, false>(cam, col, st, gr.dL_dcolor, gr.accum, T, s);
+        launch_bwd<3, 3, true, 7u, 7u, true, false>(cam, col, st, gr.dL_dcolor, gr.accum, T, s);
         return hipGetLastError();
     }
     switch (g.channels) {
-        case 1: launch_bwd<1, 1>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 2: launch_bwd<2, 2>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 3: launch_bwd<3, 3>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 4: launch_bwd<4, 4>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 5: launch_bwd<5, 5>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 6: launch_bwd<6, 6>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 7: launch_bwd<7, 7>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
-        case 8: launch_bwd<8, 8>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 1: launch_bwd<1, 1, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 2: launch_bwd<2, 2, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 3: launch_bwd<3, 3, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 4: launch_bwd<4, 4, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 5: launch_bwd<5, 5, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 6: launch_bwd<6, 6, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 7: launch_bwd<7, 7, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
+        case 8: launch_bwd<8, 8, true>(cam, col, st, gr.dL_dcolor, gr.accum, T, s); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1567,7 +1558,7 @@ hipError_t launch_render_forward_feat8(const SplatCamera &cam, const float *feat
 // The tracking iteration's composites as ONE launch (render_track_fused_kernel): lists short enough for the composite's own sort, a
 // pixel-local loss (no outlier rejection).  keep_planes: also write out6 / final_T / n_contrib / dL_dout6.
 hipError_t launch_render_track_fused(const SplatCamera &cam, const float *feat8, SplatState &st_in, float *out6, float *accum,
-                                     const TrackLossEpilogue &ep, bool keep_planes, hipStream_t s, bool full_sums) {
+                                     const TrackLossEpilogue &ep, bool keep_planes, hipStream_t s, IterSums sums) {
     const int T = launch_tiles(cam, st_in);
     if (T == 0) return hipSuccess;
     const int per = (T + 7) / 8;
@@ -1583,7 +1574,7 @@ hipError_t launch_render_track_fused(const SplatCamera &cam, const float *feat8,
         }
         return hipGetLastError();
     }
-    if (full_sums) {
+    if (sums != IterSums::Track) {           // (one kernel holds the tracking form or the full mapping form: any map gradient takes the latter)
         if (keep_planes) hipLaunchKernelGGL((render_track_fused_full_kernel<true>), dim3(8 * per), dim3(256), 0, s, TrackFusedArgs{cam, feat8, st, out6, accum, T, per, ep});
         else hipLaunchKernelGGL((render_track_fused_full_kernel<false>), dim3(8 * per), dim3(256), 0, s, TrackFusedArgs{cam, feat8, st, out6, accum, T, per, ep});
         return hipGetLastError();
@@ -1599,7 +1590,7 @@ hipError_t launch_render_track_fused(const SplatCamera &cam, const float *feat8,
 }
 
 hipError_t launch_render_backward_feat8(const SplatCamera &cam, const float *feat8, const SplatState &st, const float *dL_dout6,
-                                        float *accum, int P, bool zero_accum, bool rgb_sums, hipStream_t s, bool opacity_sum) {
+                                        float *accum, int P, bool zero_accum, IterSums sums, hipStream_t s) {
     const int T = launch_tiles(cam, st);
     if (zero_accum) {
         hipError_t e = hipMemsetAsync(accum, 0, sizeof(float) * SPLAT_GRAD_STRIDE * (size_t)P, s);
@@ -1609,9 +1600,9 @@ hipError_t launch_render_backward_feat8(const SplatCamera &cam, const float *fea
     // channels r, g, b, z carry gradient; the silhouette and depth^2 planes never do.  dL/drgb is only summed on request
     // (tracking does not read it: LR 0 in /root/reference/configs/*/splatam.py, optimizer discarded after the frame).
     // (zero background: FusedEngine refuses anything else, as setup_camera builds it)
-    if (rgb_sums) launch_bwd<6, 8, 0xFu, 0xFu, true, false>(cam, feat8, st, dL_dout6, accum, T, s);
-    else if (opacity_sum) launch_bwd<6, 8, 0xFu, 0x8u, true, false>(cam, feat8, st, dL_dout6, accum, T, s);
-    else launch_bwd<6, 8, 0xFu, 0x8u, false, false>(cam, feat8, st, dL_dout6, accum, T, s);      // camera tracking: no dL/dopacity wanted
+    if (sums == IterSums::MapRgb) launch_bwd<6, 8, false, 0xFu, 0xFu, true, false>(cam, feat8, st, dL_dout6, accum, T, s);
+    else if (sums == IterSums::Map) launch_bwd<6, 8, false, 0xFu, 0x8u, true, false>(cam, feat8, st, dL_dout6, accum, T, s);
+    else launch_bwd<6, 8, false, 0xFu, kAccTrackMask, false, false>(cam, feat8, st, dL_dout6, accum, T, s);      // camera tracking: no dL/dopacity wanted
     return hipGetLastError();
 }
 

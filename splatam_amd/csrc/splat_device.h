@@ -31,6 +31,8 @@ constexpr int kDenseThreads = 1024, kDenseGaussians = 4096, kDenseMaxTilesLds = 
 inline bool dense_exact_lists(const SplatState &st, int P, int T) {
     return st.tile_stride == 0 && st.sub_bins > 1 && P >= 8 * kDenseGaussians && T <= kDenseMaxTilesLds;
 }
+static_assert(4 * acc_row4((1u << SPLAT_MAX_CHANNELS) - 1u, true) <= SPLAT_GRAD_STRIDE, "every form's sums fit the accumulator row");
+
 // lists known (host hint, possibly stale: then flagged) to be short are sorted by the composite kernel itself
 inline bool lists_sorted_by_composite(const SplatState &st) { return st.max_list_hint > 0 && st.max_list_hint + st.max_list_hint / 4 <= 1024; }
 // group binning (SplatState.group_count) needs bucketed lists that the composite sorts itself, and one LDS counter per group
@@ -62,10 +64,14 @@ struct TrackLossEpilogue {
 // *ep_done tells the caller whether the epilogue ran (generation-3 kernels) or the separate loss kernel is still needed.
 hipError_t launch_render_forward_feat8(const SplatCamera &cam, const float *feat8, SplatState &st, float *out6, bool sort_in_kernel,
                                        hipStream_t s, const TrackLossEpilogue *ep = nullptr, bool *ep_done = nullptr);
+// the sums the fused iteration's backward composite forms (fused.hip: iter_sums), and with them the layout of the accumulator rows F6
+// reads (splat_math.h): Track, the tracking form (the depth channel's colour sum alone, no opacity sum); Map, S1..S6 and the depth
+// channel's colour sum; MapRgb, the colour sums of r, g, b too
+enum class IterSums { Track, Map, MapRgb };
 hipError_t launch_render_track_fused(const SplatCamera &cam, const float *feat8, SplatState &st, float *out6, float *accum,
-                                     const TrackLossEpilogue &ep, bool keep_planes, hipStream_t s, bool full_sums = false);
+                                     const TrackLossEpilogue &ep, bool keep_planes, hipStream_t s, IterSums sums);
 hipError_t launch_render_backward_feat8(const SplatCamera &cam, const float *feat8, const SplatState &st, const float *dL_dout6,
-                                        float *accum, int P, bool zero_accum, bool rgb_sums, hipStream_t s, bool opacity_sum = true);
+                                        float *accum, int P, bool zero_accum, IterSums sums, hipStream_t s);
 hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map, const SplatFrameData &frame,
                                      const SplatLossConfig &cfg, SplatIterWorkspace &ws, hipStream_t s, const SplatPoseAdam *pose_adam = nullptr,
                                      const SplatAdamMap *map_adam = nullptr);
@@ -574,7 +580,7 @@ __device__ __forceinline__ void group_hist_reset(unsigned *s_grp, int num_groups
 }
 
 // step 1 (every thread of the workgroup): one 16-byte record (Gaussian id, depth bits, tile rectangle) per touched group of Gaussian i,
-// whose tile rectangle is [x0, x1) x [y0, y1) (`filed`: it has one).  A record that finds its group's bucket full raises status[1].
+// whose tile rectangle is [x0, x1) x [y0, y1) (`filed`: it has one).  A record that finds its group's bucket full raises status[SPLAT_STATUS_OVERFLOW].
 template <int BLOCK>
 __device__ __forceinline__ void file_group_records(const SplatState &st, unsigned *s_grp, int i, bool filed, int x0, int y0, int x1, int y1, float depth,
                                                    int ggx, int num_groups) {
@@ -614,7 +620,7 @@ __device__ __forceinline__ void file_group_records(const SplatState &st, unsigne
         if (slot < gstride) recs[(size_t)g * gstride + slot] = rec;
         else spilled = true;
     }
-    if (spilled) raise_status(st, 1);
+    if (spilled) raise_status(st, SPLAT_STATUS_OVERFLOW);
 }
 
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {

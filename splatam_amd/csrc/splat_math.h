@@ -330,4 +330,44 @@ SPLAT_HD void sh_basis(int deg, const float *d, float *basis, float (*db)[16]) {
     }
 }
 
+constexpr int popcount_c(unsigned m) { return m == 0 ? 0 : (int)(m & 1u) + popcount_c(m >> 1); }
+constexpr int highest_set_bit(unsigned m) { int h = -1; for (int i = 0; i < 32; ++i) if ((m >> i) & 1u) h = i; return h; }
+constexpr int nth_set_bit(unsigned m, int n) {      // index of the n-th (0-based) set bit
+    int idx = 0;
+    while (true) {
+        if (m & 1u) { if (n == 0) return idx; --n; }
+        m >>= 1; ++idx;
+        if (idx > 31) return -1;
+    }
+}
+
+// ---- the backward accumulator row: SPLAT_GRAD_STRIDE floats per Gaussian ----
+// The backward composite (render.hip backward_core) adds the sums of every visit of a Gaussian into its row; K8
+// (preprocess_backward_kernel), F6 (fused.hip fused_backward_kernel) and means2d_accumulate_kernel turn the row into gradients.
+// What a composite publishes is its FORM: smask, the colour channels whose sums it forms, and opac, whether it forms the opacity sum.
+//   slots 0..4   S1..S5 = sum q G dx, q G dy, q G dx^2, q G dx dy, q G dy^2   (q = opacity * dL/dalpha)
+//   slot 5       S6, the opacity sum
+//   slot 6 + ch  the colour sum of channel ch
+// The TRACKING form (no opacity sum; the colour sum of channel 3 alone: z of the fused iteration's r, g, b, z, 1, z^2) puts that one
+// sum in the free slot 5: everything it publishes lies in the first half of the row, and F6 reads and clears 32 bytes, not 64.
+constexpr int kAccOpacity = 5, kAccColour = 6;
+constexpr unsigned kAccTrackMask = 0x8u;
+constexpr bool acc_tracking(unsigned smask, bool opac) { return !opac && smask == kAccTrackMask; }
+constexpr int acc_colour_slot(bool tracking, int ch) { return tracking ? kAccOpacity : kAccColour + ch; }
+// the slot of the k-th value a form publishes: S1..S5 (S6), then the colour sums of the channels in smask, lowest channel first
+constexpr int acc_slot(unsigned smask, bool opac, int k) {
+    return k < (opac ? 6 : 5) ? k : acc_colour_slot(acc_tracking(smask, opac), nth_set_bit(smask, k - (opac ? 6 : 5)));
+}
+// float4 at the front of the row that hold everything a form publishes: what its consumer reads and clears
+constexpr int acc_row4(unsigned smask, bool opac) { return acc_slot(smask, opac, (opac ? 5 : 4) + popcount_c(smask)) / 4 + 1; }
+
+// dL/dmeans2D (NDC) and dL/dconic of a Gaussian from S1..S5 of its row (S: slots 0..4; a, b, c: its conic)
+SPLAT_HD void screen_grads(const float *S, float a, float b, float c, float W, float H, float g_ndc[2], float g_conic[3]) {
+    g_ndc[0] = -(a * S[0] + b * S[1]) * 0.5f * W;
+    g_ndc[1] = -(c * S[1] + b * S[0]) * 0.5f * H;
+    g_conic[0] = -0.5f * S[2];
+    g_conic[1] = -S[3];
+    g_conic[2] = -0.5f * S[4];
+}
+
 }  // namespace splat

@@ -27,6 +27,10 @@ from .rasterizer import _cached_contiguous
 PARAM_ORDER = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
 VARIABLE_KEYS = ("max_2D_radius", "means2D_gradient_accum", "denom", "timestep")
 _FLAG_SLOTS = 16        # floats ahead of the flat gradient bucket (one 64-byte line): slot 0 = capacity flag of the exchange
+# the iteration report's slots and the status words (include/splat_hip.h), bound once for the host paths
+_REPORT_FLAG, _REPORT_STATUS, _REPORT_SKIPPED = _capi.SPLAT_REPORT_FLAG, _capi.SPLAT_REPORT_STATUS, _capi.SPLAT_REPORT_SKIPPED
+_STATUS_INSTANCES, _STATUS_OVERFLOW = _capi.SPLAT_STATUS_INSTANCES, _capi.SPLAT_STATUS_OVERFLOW
+_STATUS_LONGEST, _STATUS_STALE_HINT = _capi.SPLAT_STATUS_LONGEST, _capi.SPLAT_STATUS_STALE_HINT
 
 
 class FusedEngine:
@@ -640,17 +644,16 @@ class FusedEngine:
         st.tile_count, st.tile_base, st.tile_cursor = b['tile_count'].data_ptr(), b['tile_base'].data_ptr(), b['tile_cursor'].data_ptr()
         st.keys, st.point_list, st.capacity = b['keys'].data_ptr(), b['point_list'].data_ptr(), self.capacity
         st.keys_alt, st.long_base = b['keys_alt'].data_ptr(), b['long_base'].data_ptr()
-        # staged records handed from the forward to the backward composite: pays where a tile's list is several batches long (every batch
-        # but the last is re-staged: B-loop, mapping +1.4 %) and costs where it is one (B: the forward composite's 34 MB of extra stores,
-        # mapping -1.4 %): profiles/r06_experiments.md 2.  SPLAT_TILE_RECS=1 / 0 forces it on / off
-        recs_on = self.use_recs == 1 or (self.use_recs == 2 and self.max_list_hint > 400)
+        # staged records handed from the forward to the backward composite (B-loop, mapping +1.4 %; B: the forward composite's 34 MB of
+        # extra stores, mapping -1.4 %).  SPLAT_TILE_RECS=1 / 0 forces them on / off
+        recs_on = self.use_recs == 1 or (self.use_recs == 2 and self.max_list_hint > _capi.RECS_MIN_LIST)
         st.tile_recs = b['tile_recs'].data_ptr() if (recs_on and b.get('tile_recs') is not None) else None
         st.long_items = b['long_items'].data_ptr()
         st.max_list_hint = self.max_list_hint
         st.tile_stride = self.tile_stride
         st.tile_row_begin, st.tile_row_end = self._tile_rows if self._tile_rows else (0, 0)
         st.group_count, st.group_recs, st.group_stride = b['group_count'].data_ptr(), None, 0
-        if self.group_bins and self.tile_stride > 0 and 0 < self.max_list_hint and self.max_list_hint * 5 // 4 <= 1024:
+        if self.group_bins and self.tile_stride > 0 and _capi.lists_sorted_by_composite(self.max_list_hint):
             gs = _capi.SPLAT_GROUP_TILES ** 2 * self.tile_stride
             need = self.num_groups * gs * 4
             if need <= 1 << 30:                       # (int32 words; 4 GiB of records)
@@ -773,7 +776,7 @@ class FusedEngine:
         """The next step of torch.optim.Adam(param_groups, lr=0.0, eps=1e-15) over the five Gaussian groups
         (/root/reference/scripts/splatam.py:160-166).  Bias corrections in double on the host, as torch forms them; ``steps``:
         the step count of each group AFTER this step (torch counts per parameter: a parameter the caller re-created restarts),
-        default: the engine's own count for all five.  The step is gated on the iteration's capacity flag (d_cam[12])."""
+        default: the engine's own count for all five.  The step is gated on the iteration's capacity flag (SPLAT_REPORT_FLAG)."""
         if steps is None:
             self.map_step += 1
             steps = (self.map_step,) * 5
@@ -904,12 +907,12 @@ class FusedEngine:
     def exchange_gradients(self, all_reduce, flat=None):
         """The gradient exchange of a multi-rank mapping step: ``all_reduce`` (sum or mean, in place) over the flat gradient bucket WITH
         this rank's capacity flag in its header.  Ranks render different views, so typically only some overflow their lists; the
-        flag of ANY rank comes back non-zero on EVERY rank and is made this rank's sticky flag (``d_cam[12]``) before the Adam step
+        flag of ANY rank comes back non-zero on EVERY rank and is made this rank's sticky flag (SPLAT_REPORT_FLAG) before the Adam step
         that follows, so the replicas skip the same steps and stay bit-identical (the reduced gradient of such an iteration holds a
         truncated-list contribution: nobody may step on it).  ``flat``: another buffer laid out like ``_exchange_flat`` (mapping_batch's
         accumulator)."""
         flat = self._exchange_flat if flat is None else flat
-        flag = self.buf['d_cam'][12:13]
+        flag = self.buf['d_cam'][_REPORT_FLAG:_REPORT_FLAG + 1]
         flat[0:1].copy_(flag)
         all_reduce(flat)
         torch.maximum(flag, (flat[0:1] != 0.0).to(flag.dtype), out=flag)
@@ -922,7 +925,7 @@ class FusedEngine:
 
     # ------------------------------------------------------------------ read-backs (host sync)
     def loss(self):
-        return float(self.buf['d_cam'][7])
+        return float(self.buf['d_cam'][_capi.SPLAT_REPORT_LOSS])
 
     def check_overflow(self, grow=True):
         """Lists are fixed-size; an iteration whose instances did not fit rendered truncated / empty lists and flagged
@@ -933,22 +936,23 @@ class FusedEngine:
         scatter pass) and the long-list sort launch is skipped while lists stay short."""
         stat = self.buf['status'].tolist()
         rep = self.buf['d_cam'].cpu()
-        return self._digest(stat, float(rep[12]) != 0.0, int(rep.view(torch.int32)[21]), grow)
+        return self._digest(stat, float(rep[_REPORT_FLAG]) != 0.0, int(rep.view(torch.int32)[_REPORT_SKIPPED]), grow)
 
     def digest_report(self, report, grow=True):
         """check_overflow() from a HOST copy of an iteration's report (``buf['d_cam']``, SPLAT_ITER_DCAM floats: the status words
-        the iteration left are in [16..19]) -- for callers that fetch the report asynchronously (splatam_amd.plugin): no
+        the iteration left are at SPLAT_REPORT_STATUS) -- for callers that fetch the report asynchronously (splatam_amd.plugin): no
         blocking read here.  Only valid for reports of whole iterations (their last kernel writes the snapshot)."""
         ints = report.view(torch.int32)
-        return self._digest(ints[16:20].tolist(), float(report[12]) != 0.0, int(ints[21]), grow, hysteresis=True)
+        return self._digest(ints[_REPORT_STATUS:_REPORT_STATUS + 4].tolist(), float(report[_REPORT_FLAG]) != 0.0, int(ints[_REPORT_SKIPPED]), grow,
+                            hysteresis=True)
 
     def _digest(self, stat, sticky, skipped, grow, hysteresis=False):
-        bad = sticky or stat[1] != 0 or stat[3] != 0 or (self.tile_stride == 0 and stat[0] > self.capacity)
+        bad = sticky or stat[_STATUS_OVERFLOW] != 0 or stat[_STATUS_STALE_HINT] != 0 or (self.tile_stride == 0 and stat[_STATUS_INSTANCES] > self.capacity)
         self.skipped_iterations = 0
         if bad:
             self.skipped_iterations = max(int(skipped), 1)
-            self.buf['d_cam'][12] = 0.0
-            self.buf['d_cam'][21] = 0.0             # (an int32 counter: the bit pattern of 0.0 is 0)
+            self.buf['d_cam'][_REPORT_FLAG] = 0.0
+            self.buf['d_cam'][_REPORT_SKIPPED] = 0.0    # (an int32 counter: the bit pattern of 0.0 is 0)
             self.buf['status'].zero_()
             self.buf['tile_count'].zero_()
             self.buf['group_count'].zero_()
@@ -958,12 +962,12 @@ class FusedEngine:
             if grow:
                 if self.tile_stride > 0:            # a bucket overflowed: back to exact lists, re-learn
                     self.tile_stride = 0
-                if stat[0] > self.capacity:
-                    self._alloc_lists(int(stat[0] * 1.5) + 65536)
+                if stat[_STATUS_INSTANCES] > self.capacity:
+                    self._alloc_lists(int(stat[_STATUS_INSTANCES] * 1.5) + 65536)
             return True
         if self._stats_partial:                 # the last iteration composited a band of tile rows: its statistics are not the frame's
             return False
-        longest = int(stat[2])
+        longest = int(stat[_STATUS_LONGEST])
         self.max_list_hint = longest            # short lists: sorted inside the composite, no sort launch
         self._learnt_P = self.P
         self._set_sub_bins(16 if longest > 2048 else 1)

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import slam
+from . import _capi, slam
 
 
 # --------------------------------------------------------------------------
@@ -278,7 +278,7 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     ``plugin.install(map_edits=True)`` (the two map edits are adapters too: the engine owns the map and edits it in place).
 
     Per-tile list overflow (fused): a flagged iteration and every iteration after it take NO Adam step on the device
-    (include/splat_hip.h, d_cam[12]); at the end of a phase ``check_overflow()`` says how many, the lists are re-sized and exactly
+    (include/splat_hip.h, SPLAT_REPORT_FLAG); at the end of a phase ``check_overflow()`` says how many, the lists are re-sized and exactly
     that many iterations are run again -- the pose / the map never saw a bad gradient, so nothing has to be restored.
 
     With ``torch.distributed`` initialised (one process per GPU, splatam_amd.dist.init_from_env) the loop runs on every rank
@@ -490,7 +490,7 @@ def _track_frame(params, variables, curr_data, time_idx, tcfg, eng, stats):
                 continue
         if it == num_iters and tcfg.get('use_depth_loss_thres', False) and not doubled:
             # the value the reference compares is the LAST iteration's weighted depth loss (scripts/splatam.py:728): no extra evaluation
-            depth_loss = float(eng.buf['d_cam'][14]) if eng is not None else float(state.last_losses['depth'].detach())
+            depth_loss = float(eng.buf['d_cam'][_capi.SPLAT_REPORT_DEPTH_TERM]) if eng is not None else float(state.last_losses['depth'].detach())
             if depth_loss >= tcfg['depth_loss_thres']:
                 doubled, todo = True, num_iters
     if eng is not None:

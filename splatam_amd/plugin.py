@@ -29,7 +29,7 @@ replaces the tensors the engine is RE-BOUND (``FusedEngine.rebind``): workspace,
 that moves the row count by less than 10 %.
 
 No blocking read per iteration.  The per-tile lists have a fixed capacity; an iteration whose lists did not fit raises a flag ON THE
-DEVICE and every Adam kernel skips while it is up (include/splat_hip.h, ``SplatIterWorkspace.d_cam[12]``), so a bad iteration never
+DEVICE and every Adam kernel skips while it is up (include/splat_hip.h, ``SPLAT_REPORT_FLAG``), so a bad iteration never
 moves the map or the pose.  The host learns of it
   * from the iteration's 128-byte report, copied to pinned memory asynchronously after every ``get_loss`` and looked at (event
     query, no wait) at the start of later calls: the lists are then re-sized and the loop goes on (mapping: the skipped iterations
@@ -61,6 +61,11 @@ import torch
 
 from . import _capi
 from .fused import PARAM_ORDER, FusedEngine
+
+# the iteration report's slots (include/splat_hip.h), bound once for the host paths
+_LOSS, _DEPTH_TERM, _IM_TERM = _capi.SPLAT_REPORT_LOSS, _capi.SPLAT_REPORT_DEPTH_TERM, _capi.SPLAT_REPORT_IM_TERM
+_FLAG, _STATUS, _SKIPPED = _capi.SPLAT_REPORT_FLAG, _capi.SPLAT_REPORT_STATUS, _capi.SPLAT_REPORT_SKIPPED
+_FLAGS_OF_STATUS = [_STATUS + _capi.SPLAT_STATUS_OVERFLOW, _STATUS + _capi.SPLAT_STATUS_STALE_HINT]
 
 _POSE_KEYS = ("cam_unnorm_rots", "cam_trans")
 _ALL_KEYS = PARAM_ORDER + _POSE_KEYS
@@ -95,7 +100,7 @@ class _FusedLoss(torch.Tensor):
         rep = getattr(self, "_report", None)
         if rep is None:
             return float(self.as_subclass(torch.Tensor))
-        return _session.value_of(rep, getattr(self, "_slot", 7))
+        return _session.value_of(rep, getattr(self, "_slot", _LOSS))
 
     def item(self):
         return self._value()
@@ -129,12 +134,11 @@ class _FusedLoss(torch.Tensor):
 
 
 def _report_values(host):
-    """The report as Python numbers: float slots as floats, the int32 slots [16..21] (status words, flagged bit, skipped count) as
+    """The report as Python numbers: float slots as floats, the int32 slots STATUS..SKIPPED (status words, flagged bit, skipped count) as
     ints read THROUGH AN int32 VIEW -- their bit patterns are denormal as floats and would flush to zero under FTZ / DAZ
     (torch.set_flush_denormal, a library built with -ffast-math) if they travelled as floats."""
     vals = host.tolist()
-    ints = host.view(torch.int32)[16:22].tolist()
-    vals[16:22] = ints
+    vals[_STATUS:_SKIPPED + 1] = host.view(torch.int32)[_STATUS:_SKIPPED + 1].tolist()
     return vals
 
 
@@ -276,16 +280,16 @@ class _Session:
         if host is None:
             host = rep.host_tensor
         # a flagged report: the iterations of this engine that were launched behind it (their reports are still in flight) were gated on
-        # the device too -- every one of them raised the skipped count d_cam[21], and the host-side step counts advanced with every
+        # the device too -- every one of them raised the skipped count (SPLAT_REPORT_SKIPPED), and the host-side step counts advanced with every
         # step().  The NEWEST of those reports carries the total: wait for it BEFORE the flag is cleared (digest_report queues the
         # clear behind them), so that all of them are taken back, not just the first
-        flagged = float(host[12]) != 0.0 or any(int(v) != 0 for v in host.view(torch.int32)[[17, 19]].tolist())
+        flagged = float(host[_FLAG]) != 0.0 or any(int(v) != 0 for v in host.view(torch.int32)[_FLAGS_OF_STATUS].tolist())
         skipped_in_flight = 0
         if flagged:
             for e2, r2, h2, ev2 in reversed(self.pending):
                 if e2 is eng and r2 is not rep:
                     ev2.synchronize()
-                    skipped_in_flight = int(h2.view(torch.int32)[21])
+                    skipped_in_flight = int(h2.view(torch.int32)[_SKIPPED])
                     break
         if eng.digest_report(host):
             skipped = max(eng.skipped_iterations, skipped_in_flight)
@@ -358,7 +362,7 @@ class _Session:
             fresh_t = eng.buf['d_cam'].cpu()
             fresh = _report_values(fresh_t)
             self.stats["repeats"] += 1
-            if fresh[12] == 0.0:
+            if fresh[_FLAG] == 0.0:
                 rep.dev.copy_(eng.buf['d_cam'])
                 rep.host, rep.host_tensor = fresh, fresh_t
                 return
@@ -396,10 +400,10 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
     s.post(eng, rep)
     s.stats["iterations"] += 1
     s.current = (eng, bound, rep)
-    loss = _scalar(rep, 7)
-    losses = {'im': _scalar(rep, 15), 'loss': loss}
+    loss = _scalar(rep, _LOSS)
+    losses = {'im': _scalar(rep, _IM_TERM), 'loss': loss}
     if use_l1:
-        losses['depth'] = _scalar(rep, 14)
+        losses['depth'] = _scalar(rep, _DEPTH_TERM)
     if variables is not None:
         variables['seen'] = eng.seen
         variables['means2D'] = _Means2D(eng, rep, tracking)
@@ -514,9 +518,10 @@ class FusedOptimizer(torch.optim.Adam):
         (decided on the device: the values after the step are kept only where the report's flag is down; no host read)."""
         by_name = {g['name']: g for g in self.param_groups}
         t = rep.args[2]
-        ok = rep.dev[12] == 0
+        ok = rep.dev[_FLAG] == 0
         pose, before = [], []
-        for name, lo, hi in (('cam_unnorm_rots', 0, 4), ('cam_trans', 4, 7)):
+        for name, lo, hi in (('cam_unnorm_rots', _capi.SPLAT_REPORT_DROT, _capi.SPLAT_REPORT_DROT + 4),
+                             ('cam_trans', _capi.SPLAT_REPORT_DTRANS, _capi.SPLAT_REPORT_DTRANS + 3)):
             p = by_name[name]['params'][0]
             g = torch.zeros_like(p)
             g[0, :, t] = rep.dev[lo:hi]

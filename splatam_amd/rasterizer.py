@@ -295,7 +295,7 @@ USE_TILE_RECS = None
 def _want_recs(will_backward: bool, longest) -> bool:
     if not will_backward or USE_TILE_RECS is False:
         return False
-    return bool(USE_TILE_RECS) or (longest is not None and longest > 400)
+    return bool(USE_TILE_RECS) or (longest is not None and longest > _capi.RECS_MIN_LIST)
 
 
 def _alloc_lists(pk: _Pack, dev, capacity: int, longest=None, recs=False):
@@ -644,16 +644,16 @@ def _rasterize_forward_once(settings, means3D, colors, opacities, scales, rotati
             pk.st.capacity = 1 << 62
             _capi.check(L.splat_preprocess_forward(C.byref(pk.cam), C.byref(pk.g), C.byref(pk.st), stream), "splat_preprocess_forward")
             stat = status.tolist()
-            num_rendered = int(stat[0])
-            _longest_seen[hint_key] = int(stat[2])
-            _scene_stats[scene] = {'longest': int(stat[2]), 'since_exact': 0}
+            num_rendered, longest = int(stat[_capi.SPLAT_STATUS_INSTANCES]), int(stat[_capi.SPLAT_STATUS_LONGEST])
+            _longest_seen[hint_key] = longest
+            _scene_stats[scene] = {'longest': longest, 'since_exact': 0}
             fast_path_stats["exact"] += 1
             if _SYNC_MODE != "lazy":
-                _alloc_lists(pk, dev, num_rendered, longest=int(stat[2]), recs=_want_recs(will_backward, int(stat[2])))
-                pk.st.max_list_hint = int(stat[2])        # lets the library skip the long-list sort kernel
+                _alloc_lists(pk, dev, num_rendered, longest=longest, recs=_want_recs(will_backward, longest))
+                pk.st.max_list_hint = longest             # lets the library skip the long-list sort kernel
             else:                                         # lazy, first call for this shape: learn the size
                 _capacity_hint[hint_key] = int(num_rendered * 1.5) + 1024
-                _alloc_lists(pk, dev, _capacity_hint[hint_key], recs=_want_recs(will_backward, int(stat[2])))
+                _alloc_lists(pk, dev, _capacity_hint[hint_key], recs=_want_recs(will_backward, longest))
             pk.num_rendered = num_rendered
         else:
             _alloc_lists(pk, dev, cap, recs=_want_recs(will_backward, _longest_seen.get(hint_key)))
@@ -689,10 +689,10 @@ def resolve_lazy(pk) -> None:
     host, ev = pend
     ev.synchronize()
     pk.pending_status = None
-    n = int(host[0])
+    n = int(host[_capi.SPLAT_STATUS_INSTANCES])
     pk.num_rendered = n
     _capacity_hint[pk.hint_key] = max(_capacity_hint.get(pk.hint_key, 0), int(n * 1.5) + 1024)
-    if int(host[1]) != 0 or n > pk.st.capacity:
+    if int(host[_capi.SPLAT_STATUS_OVERFLOW]) != 0 or n > pk.st.capacity:
         raise LazyOverflow(
             f"lazy sync mode: {n} (Gaussian, tile) instances did not fit the {pk.st.capacity}-entry lists; "
             "the capacity hint has been raised -- re-run the forward (or use set_sync_mode('exact'))")

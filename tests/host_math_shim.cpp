@@ -8,6 +8,16 @@ using namespace splat;
 
 extern "C" {
 
+// the backward accumulator row of a composite form (smask, opac): slot[k] of its k-th published value (-1 past the last), the float4
+// its consumer reads, and where a consumer reads the colour sum of channel ch (colour[ch]) and the opacity sum
+int hm_acc_form(unsigned smask, int opac, int *slot, int *colour) {
+    const int nv = (opac ? 6 : 5) + popcount_c(smask);
+    for (int k = 0; k < 16; ++k) slot[k] = k < nv ? acc_slot(smask, opac != 0, k) : -1;
+    for (int ch = 0; ch < 8; ++ch) colour[ch] = acc_colour_slot(acc_tracking(smask, opac != 0), ch);
+    return acc_row4(smask, opac != 0);
+}
+int hm_acc_opacity_slot() { return kAccOpacity; }
+
 // live_tile_rect (group binning files only the tiles that can blend): rect[4] = x0, y0, x1, y1 in, tightened in place
 void hm_live_tile_rect(int P, const float *conic, const float *opacity, const float *xy, int *rect) {
     for (int i = 0; i < P; ++i)

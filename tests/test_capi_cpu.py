@@ -59,8 +59,12 @@ def test_sizeof_of_an_unknown_struct_is_zero():
 
 def test_constants_match_header():
     from splatam_amd import _capi
-    for k in ("SPLAT_TILE", "SPLAT_MAX_CHANNELS", "SPLAT_GRAD_STRIDE", "SPLAT_COUNTER_STRIDE"):
+    for k in ("SPLAT_TILE", "SPLAT_MAX_CHANNELS", "SPLAT_GRAD_STRIDE", "SPLAT_COUNTER_STRIDE",
+              "SPLAT_STATUS_INSTANCES", "SPLAT_STATUS_OVERFLOW", "SPLAT_STATUS_LONGEST", "SPLAT_STATUS_STALE_HINT",
+              "SPLAT_REPORT_DROT", "SPLAT_REPORT_DTRANS", "SPLAT_REPORT_LOSS", "SPLAT_REPORT_SUMS", "SPLAT_REPORT_FLAG", "SPLAT_REPORT_MEDIAN",
+              "SPLAT_REPORT_DEPTH_TERM", "SPLAT_REPORT_IM_TERM", "SPLAT_REPORT_STATUS", "SPLAT_REPORT_FLAGGED", "SPLAT_REPORT_SKIPPED"):
         assert getattr(_capi, k) == int(re.search(rf"#define {k} (\d+)", HEADER).group(1))
+    assert _capi.SPLAT_REPORT_SKIPPED < _capi.SPLAT_ITER_DCAM
 
 
 def test_invalid_arguments_return_codes_not_crashes():

@@ -520,6 +520,89 @@ def test_mapping_step_without_gradient_stores_moves_the_map_the_same(aniso):
         assert float((a.exp_avg[k] - b.exp_avg[k]).abs().max()) <= 1e-4 * float(a.exp_avg[k].abs().max()) + 1e-12, k
 
 
+def _bind_only(eng, only):
+    """The engine's workspaces with only the map-gradient buffer ``only`` bound; a C caller may leave any of the five NULL
+    (include/splat_hip.h: each is written when non-NULL)."""
+    workspace = eng._workspace
+
+    def bound(*args, **kw):
+        ws = workspace(*args, **kw)
+        for f in ('d_means3D', 'd_rgb_colors', 'd_unnorm_rotations', 'd_logit_opacities', 'd_log_scales'):
+            if f != only:
+                setattr(ws, f, None)
+        return ws
+    eng._workspace = bound
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,only", [("mapping", "d_means3D"), ("mapping", "d_log_scales"), ("one-kernel tracking", "d_means3D")])
+def test_one_map_gradient_buffer_gives_what_all_five_give(mode, only):
+    """splat_iter_loss_backward with ONE map-gradient buffer bound: the backward composite forms its sums in the form the per-Gaussian
+    kernel reads them in (fused.hip: iter_sums), so the requested gradient and the report's pose gradient and loss equal those of the
+    run with all five (anisotropic map: the scales' adjoint goes through the rotation)."""
+    from splatam_amd import slam
+    from splatam_amd.fused import FusedEngine
+    params, variables, frame, cam = _scene(20000, 320, 240, aniso=True, seed=57)
+    out = {}
+    for keep in (None, only):
+        eng = FusedEngine({k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}, cam)
+        eng.loss_backward(frame, 1, slam.REPLICA_MAPPING, tracking=False)
+        assert not eng.check_overflow() and eng.tile_stride > 0
+        if keep is not None:
+            _bind_only(eng, keep)
+        if mode == "mapping":
+            eng.loss_backward(frame, 1, slam.REPLICA_MAPPING, tracking=False, do_ba=True)
+        else:
+            assert eng.track_fused and eng.track_fused_full and 0 < eng.max_list_hint <= 400     # (the one-kernel form with map gradients)
+            eng.begin_tracking(1)
+            eng.loss_backward(frame, 1, slam.REPLICA_TRACKING, tracking=True, map_grads=True)
+        torch.cuda.synchronize()
+        assert not eng.check_overflow(grow=False)
+        out[keep] = dict(d=eng.buf['d_cam'].clone(), grads={k: v.clone() for k, v in eng.grads.items()})
+    a, b = out[only], out[None]
+    assert abs(float(a['d'][7]) - float(b['d'][7])) <= 1e-6 * abs(float(b['d'][7]))
+    assert float((a['d'][:7] - b['d'][:7]).abs().max()) <= 2e-5 * float(b['d'][:7].abs().max()), (a['d'][:7], b['d'][:7])
+    if mode == "mapping":
+        k = only[2:]
+        sc = float(b['grads'][k].abs().max())
+        assert sc > 0 and float((a['grads'][k] - b['grads'][k]).abs().max()) <= 5e-5 * sc, k
+
+
+@pytest.mark.gpu
+def test_mapping_step_without_colour_and_opacity_gradients_moves_the_rest_the_same():
+    """splat_iter_mapping_step with SplatAdamMap.grad[1] and grad[3] NULL (torch skips parameters that have no gradient): means,
+    rotations and scales and their moments move as in the step over all five groups; colours, opacities and their moments stay as
+    they were, bit for bit."""
+    from splatam_amd import slam
+    from splatam_amd.fused import FusedEngine
+    params, variables, frame, cam = _scene(20000, 320, 240, aniso=True, seed=61)
+    cfg = slam.REPLICA_MAPPING
+    engs = []
+    for skip in (False, True):
+        eng = FusedEngine({k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}, cam)
+        for _ in range(3):
+            eng.loss_backward(frame, 1, cfg, tracking=False)
+            if not eng.check_overflow():
+                break
+        o = eng._adam_map_args(cfg['lrs'])
+        if skip:
+            o.grad[1] = o.grad[3] = None
+        eng.loss_backward(frame, 1, cfg, tracking=False, map_adam=o, map_grads="step only")
+        torch.cuda.synchronize()
+        assert not eng.check_overflow(grow=False)
+        engs.append(eng)
+    a, b = engs
+    for k in ('means3D', 'unnorm_rotations', 'log_scales'):
+        moved = float((a.params[k].detach() - params[k]).abs().max())
+        assert moved > 0.0, k
+        assert float((a.params[k].detach() - b.params[k].detach()).abs().max()) <= 2e-3 * moved + 1e-9, k
+        assert float((a.exp_avg[k] - b.exp_avg[k]).abs().max()) <= 1e-4 * float(a.exp_avg[k].abs().max()) + 1e-12, k
+    for k in ('rgb_colors', 'logit_opacities'):
+        assert float((a.params[k].detach() - params[k]).abs().max()) > 0.0, k
+        assert torch.equal(b.params[k].detach(), params[k].detach().cuda()), k
+        assert float(b.exp_avg[k].abs().max()) == 0.0 and float(b.exp_avg_sq[k].abs().max()) == 0.0, k
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["one batch", "several batches", "exact lists"])
 def test_staged_records_handed_to_the_backward_composite_change_nothing_but_speed(case):

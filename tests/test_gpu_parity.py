@@ -4,6 +4,8 @@ the C ABI underneath) against the oracle.  Tolerances are the north star's:
 gradients; integer / index outputs (radii, tile ranges, sorted lists,
 n_contrib) must match exactly up to float32 threshold flips, which are counted
 and bounded."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -178,6 +180,50 @@ def test_channel_counts(C_):
     oc, orad, od, og, _ = _c_oracle(cam, rv, gout)
     flips = _check_forward(gc, gr, gd, oc, orad, od, W * H, cam, rv)
     _check_grads(gg, og, flips=flips)
+
+
+def test_four_channels_on_a_state_bound_with_staged_records():
+    """A C caller that binds SPLAT_LAYOUT_RECS (SplatState.tile_recs) on a drop-in state of 4 channels: the forward composite of
+    4 channels + depth writes no staged records, so the backward composite must gather what it re-stages (render.hip:
+    forward_writes_recs) -- checked against the oracle as test_channel_counts checks it."""
+    from splatam_amd import _capi
+    from splatam_amd import rasterizer as rz
+    L = _capi.lib()
+    C_, W, H = 4, 112, 80
+    cam, rv = scene(2500, W, H, 100.0, seed=C_)
+    g = torch.Generator().manual_seed(C_)
+    rv['colors_precomp'] = torch.rand(rv['means3D'].shape[0], C_, generator=g)
+    cam = cam._replace(bg=torch.rand(C_, generator=g))
+    gout = torch.randn(C_, H, W, generator=g)
+    d = {k: v.detach().cuda().contiguous() for k, v in rv.items()}
+    P, none = d['means3D'].shape[0], torch.empty(0, device="cuda")
+    pk = rz._build_pack(_to_cuda_settings(cam), d['means3D'], d['colors_precomp'], d['opacities'], d['scales'], d['rotations'], none, none)
+    cap = 256 * P
+    lay = _capi.state_layout(P, W, H, 1, cap, _capi.SPLAT_LAYOUT_BACKWARD | _capi.SPLAT_LAYOUT_RECS | _capi.SPLAT_LAYOUT_LONG_LISTS)
+    slab = torch.empty(lay.total, dtype=torch.uint8, device="cuda")
+    st, gr = pk.st, _capi.SplatGrads()
+    assert L.splat_state_bind(C.byref(st), C.byref(gr), slab.data_ptr(), lay.arrays, lay.n, 1, cap) == 0 and st.tile_recs
+    slab[lay.offset["tile_recs"]:lay.offset["tile_recs"] + lay.bytes["tile_recs"]].zero_()     # (records never written: nothing blends)
+    color, depth = torch.empty(C_, H, W, device="cuda"), torch.empty(1, H, W, device="cuda")
+    dl = gout.cuda().contiguous()
+    grads = {k: torch.empty_like(d[k2]) for k, k2 in (('means3D', 'means3D'), ('colors_precomp', 'colors_precomp'),
+                                                     ('opacities', 'opacities'), ('scales', 'scales'), ('rotations', 'rotations'))}
+    grads['means2D'] = torch.empty(P, 3, device="cuda")
+    gr.dL_dcolor, gr.dL_dmeans3D, gr.dL_dmeans2D = dl.data_ptr(), grads['means3D'].data_ptr(), grads['means2D'].data_ptr()
+    gr.dL_dcolors, gr.dL_dopacities = grads['colors_precomp'].data_ptr(), grads['opacities'].data_ptr()
+    gr.dL_dscales, gr.dL_drotations = grads['scales'].data_ptr(), grads['rotations'].data_ptr()
+    cs, gs = C.byref(pk.cam), C.byref(pk.g)
+    assert L.splat_preprocess_forward(cs, gs, C.byref(st), None) == 0
+    assert L.splat_bin_forward(cs, gs, C.byref(st), None) == 0
+    assert L.splat_render_forward(cs, gs, C.byref(st), color.data_ptr(), depth.data_ptr(), None) == 0
+    assert L.splat_backward(cs, gs, C.byref(st), C.byref(gr), None) == 0
+    torch.cuda.synchronize()
+    status = slab[lay.offset["status"]:lay.offset["status"] + 16].view(torch.int32).tolist()
+    assert status[_capi.SPLAT_STATUS_OVERFLOW] == 0 and 0 < status[_capi.SPLAT_STATUS_INSTANCES] <= cap
+    radii = slab[lay.offset["radii"]:lay.offset["radii"] + 4 * P].view(torch.int32).cpu().numpy()
+    oc, orad, od, og, _ = _c_oracle(cam, rv, gout)
+    flips = _check_forward(color.cpu().numpy(), radii, depth.cpu().numpy(), oc, orad, od, W * H, cam, rv)
+    _check_grads({k: v.cpu().numpy() for k, v in grads.items()}, og, flips=flips)
 
 
 def test_depth_silhouette_pass():

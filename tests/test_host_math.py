@@ -250,3 +250,32 @@ def test_live_tile_rect_at_the_blend_threshold(shim):
     shim.hm_live_tile_rect(2, _p(conic), _p(op), _p(xy), _p(rect, C.c_int))
     assert rect[0, 0] <= 1 < rect[0, 2] and rect[0, 1] <= 2 < rect[0, 3], rect[0]
     assert rect[1, 2] == rect[1, 0] and rect[1, 3] == rect[1, 1], rect[1]
+
+
+# the forms of the backward composite (smask, opacity sum) the library launches: the reference API's (all C channels), the fused
+# iteration's mapping forms (r, g, b, z / z alone), its tracking form (z alone, no opacity sum), and the colour pass' (S1..S5 alone)
+_ACC_FORMS = [((1 << c) - 1, True) for c in range(1, 9)] + [(0xF, True), (0x8, True), (0x8, False), (0x0, False)]
+
+
+@pytest.mark.parametrize("smask,opac", _ACC_FORMS)
+def test_accumulator_row_producer_and_consumers_agree(shim, smask, opac):
+    """splat_math.h, the backward accumulator row: the slot where the backward composite publishes each value of a form is where K8,
+    F6 and means2d_accumulate_kernel read it, inside the part of the row they read and clear."""
+    from splatam_amd import _capi
+    slot, colour = np.zeros(16, np.int32), np.zeros(8, np.int32)
+    row4 = shim.hm_acc_form(smask, int(opac), _p(slot, C.c_int), _p(colour, C.c_int))
+    nb = 6 if opac else 5
+    chans = [ch for ch in range(8) if smask >> ch & 1]
+    pub = slot[:nb + len(chans)]
+    assert (slot[nb + len(chans):] == -1).all()
+    assert list(pub[:nb]) == list(range(nb))                        # S1..S5 (S6 = the opacity sum)
+    assert len(set(pub.tolist())) == len(pub) and pub.max() < 4 * row4 <= _capi.SPLAT_GRAD_STRIDE
+    assert row4 == pub.max() // 4 + 1
+    for n, ch in enumerate(chans):                                  # a channel's colour sum is read where it was published
+        assert pub[nb + n] == colour[ch], (ch, pub, colour)
+    if opac:
+        assert pub[5] == shim.hm_acc_opacity_slot() and shim.hm_acc_opacity_slot() not in colour[chans]
+    if (smask, opac) in ((0xF, True), (0x8, True)):                # F6's mapping branch reads both alike: r, g, b, z and z^2 in 3 float4
+        slot_f, colour_f = np.zeros(16, np.int32), np.zeros(8, np.int32)
+        assert shim.hm_acc_form(0xF, 1, _p(slot_f, C.c_int), _p(colour_f, C.c_int)) == row4 == 3
+        assert (colour_f == colour).all() and colour[5] < 4 * row4
