@@ -133,10 +133,13 @@ typedef struct SplatState {
     /* group binning (fused iteration, bucketed lists short enough for the composite's own sort): the per-Gaussian kernel
      * files ONE record per touched GROUP of SPLAT_GROUP_TILES x SPLAT_GROUP_TILES tiles (slots taken per (workgroup, group)
      * through an LDS histogram: ~1 global atomic per Gaussian in random row order, far fewer in creation order, instead of one
-     * per (Gaussian, tile) instance); the forward
+     * per (Gaussian, tile) instance; sixteen groups' counters share 64 bytes, so that a wave's atomics coalesce); the forward
      * composite of a tile filters its group's records by their tile rectangle, sorts, and publishes point_list / tile_count
      * exactly as the per-tile buckets would have held them.  NULL / group_stride 0: per-tile buckets */
-    uint32_t *group_count;       /* [G * SPLAT_COUNTER_STRIDE] records per group, G = ceil(tiles_x / 2) * ceil(tiles_y / 2); zero between iterations */
+    uint32_t *group_count;       /* [G * SPLAT_COUNTER_STRIDE] records per group, G = ceil(tiles_x / 2) * ceil(tiles_y / 2): the LIVE counter of
+                                    group g is word 16 + g % 16 of line g / 16 (sixteen consecutive groups in the upper 64 bytes of a
+                                    line), zero between iterations; word 1 of line g keeps the count of the last fused iteration; every
+                                    other word stays zero */
     uint32_t *group_recs;        /* [G * group_stride][4] (Gaussian id, float bits of depth, rect word 0, rect word 1) */
     int32_t max_list_hint;       /* longest tile list if the host knows it (status[2] of an earlier read), 0 = unknown */
     int32_t order_hint;          /* fused iteration, bucketed lists: non-zero = the map is (mostly) in creation order (neighbouring rows

@@ -262,8 +262,10 @@ int splat_iter_time_kernel(int fn, int iters, const SplatCamera *cam, int32_t P,
     if (fn == 1 || fn == 4) st.tile_recs = nullptr;
     // fn 2: the forward composite in the form the iteration launches when the lists are short -- it filters its group's records (or
     // reads its bucket), sorts and publishes the tile's list itself.  The iteration's last kernel left the groups' record counts in
-    // word 1 of their counter lines and the tiles' counts in the cursor words; the re-published lists and counts are the same values
+    // word 1 of their counter lines (group_kept: the live counters are set from them for the timed launches and zeroed again) and the
+    // tiles' counts in the cursor words; the re-published lists and counts are the same values
     bool sort_form = false;
+    int live_groups = 0;
     // fn 3: forward and backward composite ALTERNATING, as the iteration issues them (the forward one in its sorting form when the
     // state allows it): time(fn 3) - time(fn 2 or 0) is the backward composite between other kernels -- 30 launches of it in a row
     // read ~10 % longer than rocprofv3's per-kernel average of the loop
@@ -271,11 +273,12 @@ int splat_iter_time_kernel(int fn, int iters, const SplatCamera *cam, int32_t P,
     if (fn == 2 || (fn == 3 && can_sort)) {
         if (!can_sort) return SPLAT_E_INVALID;
         sort_form = true;
-        if (st.group_stride > 0 && st.group_count && st.group_recs) st.group_count = st.group_count + 1;
+        if (st.group_stride > 0 && st.group_count && st.group_recs) live_groups = tile_groups(cam->image_width, cam->image_height);
         else st.group_stride = 0;
     } else {
         st.group_stride = 0;
     }
+    if (live_groups) err = launch_group_counters_restore(st, live_groups, true, s);
     (void)hipEventRecord(e0, s);
     for (int i = 0; i < iters && err == hipSuccess; ++i) {
         if (fn != 1 && fn != 4) err = launch_render_forward_feat8(*cam, ws->feat8, st, ws->out6, sort_form, s);
@@ -283,6 +286,10 @@ int splat_iter_time_kernel(int fn, int iters, const SplatCamera *cam, int32_t P,
         if (fn == 4) err = launch_render_backward_feat8(*cam, ws->feat8, st, ws->dL_dout6, ws->accum, P, false, IterSums::Track, s);
     }
     (void)hipEventRecord(e1, s);
+    if (live_groups) {                          // (whatever the launches returned: the next iteration's per-Gaussian kernel starts from zero)
+        const hipError_t e = launch_group_counters_restore(st, live_groups, false, s);
+        if (err == hipSuccess) err = e;
+    }
     // the timed backward launches accumulated into ws->accum: restore the workspace invariant (every iteration leaves the
     // accumulator zeroed; fused_backward_kernel relies on it) outside the timed bracket
     if ((fn == 1 || fn == 3 || fn == 4) && err == hipSuccess && P > 0) err = hipMemsetAsync(ws->accum, 0, sizeof(float) * SPLAT_GRAD_STRIDE * (size_t)P, s);

@@ -1011,8 +1011,7 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
             if (t < G) {
                 // (the group's record count stays in word 1 of its counter line for a later pass over the same records:
                 //  splat_iter_time_kernel times the sorting form of the forward composite on it)
-                ws.st.group_count[(size_t)t * SPLAT_COUNTER_STRIDE + 1] = ws.st.group_count[(size_t)t * SPLAT_COUNTER_STRIDE];
-                ws.st.group_count[(size_t)t * SPLAT_COUNTER_STRIDE] = 0;
+                group_counter_fold(ws.st, t);
             }
             sum += cnt;
             mx = max(mx, cnt);

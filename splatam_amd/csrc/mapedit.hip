@@ -515,15 +515,19 @@ __global__ __launch_bounds__(kBlock) void fold_tile_counters_kernel(SplatState s
         const unsigned cnt = st.tile_count[(size_t)t * SPLAT_COUNTER_STRIDE];
         st.tile_count[(size_t)t * SPLAT_COUNTER_STRIDE] = 0;
         st.tile_cursor[(size_t)t * SPLAT_COUNTER_STRIDE] = cnt;
-        if (st.group_count && t < G) {                                                          // (G <= T)
-            st.group_count[(size_t)t * SPLAT_COUNTER_STRIDE + 1] = st.group_count[(size_t)t * SPLAT_COUNTER_STRIDE];    // kept, see fused_backward_kernel
-            st.group_count[(size_t)t * SPLAT_COUNTER_STRIDE] = 0;
-        }
+        if (st.group_count && t < G) group_counter_fold(st, t);                                 // (G <= T; kept, see fused_backward_kernel)
         sum += cnt;
         mx = max(mx, cnt);
     }
     for (int m = 32; m >= 1; m >>= 1) { sum += (unsigned)__shfl_xor((int)sum, m, 64); mx = max(mx, (unsigned)__shfl_xor((int)mx, m, 64)); }
     if ((threadIdx.x & 63) == 0 && sum) { atomicAdd((unsigned *)&st.status[SPLAT_STATUS_INSTANCES], sum); atomicMax((unsigned *)&st.status[SPLAT_STATUS_LONGEST], mx); }
+}
+
+// a pass over the last iteration's group records OUTSIDE an iteration (splat_iter_time_kernel): the live counters from the kept counts
+// (`live`), and back to zero afterwards
+__global__ __launch_bounds__(kBlock) void group_counters_restore_kernel(SplatState st, int G, int live) {
+    const int g = blockIdx.x * kBlock + threadIdx.x;
+    if (g < G) st.group_count[group_counter(g)] = live ? st.group_count[group_kept(g)] : 0u;
 }
 
 MapArrays map_arrays(const SplatMapStore &st) {
@@ -627,6 +631,11 @@ hipError_t launch_map_duplicate(const SplatMapStore &st, const SplatDensifyArgs 
     const int P = st.map.P;
     const int nblocks = (P + kPerBlock - 1) / kPerBlock;
     if (P > 0) hipLaunchKernelGGL(duplicate_rows_kernel, dim3(nblocks), dim3(kBlock), 0, s, st, a, st.counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_counters_restore(const SplatState &st, int G, bool live, hipStream_t s) {
+    if (G > 0) hipLaunchKernelGGL(group_counters_restore_kernel, dim3((G + kBlock - 1) / kBlock), dim3(kBlock), 0, s, st, G, live ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -542,7 +542,7 @@ __device__ __forceinline__ int forward_tile(const float *colors, SplatState &st,
                 const int i = k * 256 + tid;
                 r[k] = i < st.group_stride ? recs[i] : make_uint4(0u, 0u, 0u, 0u);
             }
-            const int cnt = min((int)st.group_count[(size_t)grp * SPLAT_COUNTER_STRIDE], st.group_stride);
+            const int cnt = min((int)st.group_count[group_counter(grp)], st.group_stride);
 #pragma unroll
             for (int k = 2; k < kChunks; ++k) {
                 const int i = k * 256 + tid;

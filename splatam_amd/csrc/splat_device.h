@@ -91,6 +91,7 @@ hipError_t launch_iter_means2d_accumulate(const SplatCamera &cam, const SplatMap
                                           float *means2D_grad, hipStream_t s);
 hipError_t launch_render_backward_rgb_only(const SplatCamera &cam, const float *feat8, const SplatState &st, const float *dL_dout6,
                                            float *accum, int P, hipStream_t s);
+hipError_t launch_group_counters_restore(const SplatState &st, int G, bool live, hipStream_t s);
 size_t map_scratch_words(long long n);
 int map_row_floats(const SplatMapStore &st);
 extern int g_debug_skip_count;
@@ -557,12 +558,19 @@ __device__ __forceinline__ uint64_t *radix_sort_lds_private(uint64_t *buf_a, uin
 
 // ---------------------------------------------------------------------------------------------------------------------
 // GROUP BINNING (SplatState.group_count / group_recs; the per-Gaussian kernels of both paths: fused.hip F1, preprocess.hip K1): the
-// kGroupBlock Gaussians of a workgroup count their records per GROUP of 2 x 2 tiles in an LDS histogram (one counter per group of the
-// frame: dynamic LDS, 4 bytes x groups), the workgroup takes ONE returning global atomic per non-empty group, and a record's slot is the
-// group's base + its LDS rank: ~1.0 global atomics per Gaussian in ANY row order (1.56 records per Gaussian over 836 groups at workload B)
-// instead of 2.36 per-tile ones, far fewer for a map in creation order.
-// Measured at B (iterations/s, tracking / mapping): per-tile buckets 3 700 / 2 945; groups with 256-Gaussian workgroups 3 900 / 3 025,
-// 512: 4 120 / 3 165, 1 024: 3 990 / 3 090 (fewer atomics, but one workgroup per CU leaves its phases unoverlapped).
+// Gaussians of a workgroup count their records per GROUP of 2 x 2 tiles in an LDS histogram (one counter per group of the frame: dynamic
+// LDS, 4 bytes x groups), the workgroup takes ONE returning global atomic per non-empty group, and a record's slot is the group's base +
+// its LDS rank.  A workgroup of 512 random Gaussians of workload B (1.56 records per Gaussian over 836 groups) leaves ~515 groups
+// non-empty: ~1.0 lane atomics per Gaussian in ANY row order instead of 2.36 per-tile ones, far fewer for a map in creation order.
+// The live counters of sixteen consecutive groups share 64 bytes (group_counter) and consecutive lanes reserve for consecutive groups: an
+// atomic instruction of a wave leaves for L2 as 4 requests of up to sixteen lanes instead of 64 of one.  Measured (profiles/group_filing_ab.md):
+// the reservation alone (scripts/micro/group_reserve_bench.hip), one counter per 128-byte line 15.7 us -> 12.3 us; F1 at B 25.7 -> 17.9 us,
+// K1 24.8 -> 16.0 us; nothing at B-loop, whose creation-order workgroups leave few groups non-empty.
+// Measured at B before that (iterations/s, tracking / mapping): per-tile buckets 3 700 / 2 945; groups with 256-Gaussian workgroups
+// 3 900 / 3 025, 512: 4 120 / 3 165, 1 024: 3 990 / 3 090 (fewer atomics, but one workgroup per CU leaves its phases unoverlapped).
+// Two or four Gaussians per thread of a 512-thread workgroup (half / a quarter of the workgroups and of the requests; the reservation
+// alone 6.6 / 4.3 us) lost as well: F1 at B 18.9 / 21.0 us, at B-loop 26.7 / 29.2 against 25.9 -- the kernel lasts as long as one
+// thread's chain of dependent work, and that chain doubles.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kGroupBlock = 512;
 constexpr int kGroupPerLane = 4;            // groups a lane files through the histogram; a Gaussian's further groups take own atomics
@@ -571,6 +579,25 @@ static_assert(kGT == 2, "the group index is tile >> 1");
 
 __host__ __device__ inline int tile_groups_x(int W) { return (((W + SPLAT_TILE - 1) / SPLAT_TILE) + kGT - 1) / kGT; }
 __host__ __device__ inline int tile_groups(int W, int H) { return tile_groups_x(W) * ((((H + SPLAT_TILE - 1) / SPLAT_TILE) + kGT - 1) / kGT); }
+
+// The words of SplatState.group_count (one SPLAT_COUNTER_STRIDE-word line per group) that mean something:
+//   group_counter(g)  the LIVE counter of group g, records filed in this iteration: sixteen consecutive groups in the upper 64 bytes of
+//                     line g / 16 (which exists: g / 16 < G).  Zero between iterations.
+//   group_kept(g)     word 1 of line g: the count of the last iteration, left by the kernel that resets the live counter
+//                     (group_counter_fold) for a later pass over the same records.
+// Every other word stays zero.
+constexpr int kGroupCountersPerLine = 16;
+static_assert(2 * kGroupCountersPerLine <= SPLAT_COUNTER_STRIDE, "the live counters fill the upper half of a line; word 1 is in the lower");
+__host__ __device__ inline size_t group_counter(int g) {
+    return (size_t)(g / kGroupCountersPerLine) * SPLAT_COUNTER_STRIDE + (SPLAT_COUNTER_STRIDE - kGroupCountersPerLine) + (size_t)(g % kGroupCountersPerLine);
+}
+__host__ __device__ inline size_t group_kept(int g) { return (size_t)g * SPLAT_COUNTER_STRIDE + 1; }
+
+// the iteration is over for group g (one thread per group): keep its count, reset the live counter
+__device__ __forceinline__ void group_counter_fold(const SplatState &st, int g) {
+    st.group_count[group_kept(g)] = st.group_count[group_counter(g)];
+    st.group_count[group_counter(g)] = 0;
+}
 
 // step 0 (every thread of the workgroup, BEFORE the projection work, which hides the barrier): the histogram starts at zero
 template <int BLOCK>
@@ -596,11 +623,18 @@ __device__ __forceinline__ void file_group_records(const SplatState &st, unsigne
             rank[t] = atomicAdd(&s_grp[(gy0 + yy) * ggx + gx0 + xx], 1u);
         }
     __syncthreads();
-    // (one returning atomic per non-empty group; two in flight per lane -- with a zero added where one of a lane's two groups is
-    //  empty -- was measured: 27.4 -> 34.1 us, the kernel is bound by the NUMBER of L2 atomics, not by their latency)
-    for (int g = (int)threadIdx.x; g < num_groups; g += BLOCK) {
-        const unsigned cnt = s_grp[g];
-        if (cnt) s_grp[g] = atomicAdd(&st.group_count[(size_t)g * SPLAT_COUNTER_STRIDE], cnt);
+    // One returning atomic per non-empty group: consecutive lanes, consecutive groups, contiguous counters.  A lane whose group is empty
+    // stays masked: adding zero is a request too (with a zero added where one of a lane's two groups was empty, on one counter per line:
+    // 27.4 -> 34.1 us -- the kernel is bound by the NUMBER of L2 atomic requests).  A lane's two groups (836 groups, 512 lanes) are
+    // requested before the first answer is used, each under its own mask: F1 at B 17.9 / 18.0 -> 17.2 / 16.6 us, B-loop unchanged.
+    for (int g0 = (int)threadIdx.x; g0 < num_groups; g0 += 2 * BLOCK) {
+        const int g1 = g0 + BLOCK;
+        const unsigned c0 = s_grp[g0], c1 = g1 < num_groups ? s_grp[g1] : 0u;
+        unsigned b0 = 0u, b1 = 0u;
+        if (c0) b0 = atomicAdd(&st.group_count[group_counter(g0)], c0);
+        if (c1) b1 = atomicAdd(&st.group_count[group_counter(g1)], c1);
+        if (c0) s_grp[g0] = b0;
+        if (c1) s_grp[g1] = b1;
     }
     __syncthreads();
     const uint4 rec = make_uint4((unsigned)i, __float_as_uint(depth), (unsigned)x0 | ((unsigned)y0 << 16), (unsigned)x1 | ((unsigned)y1 << 16));
@@ -615,7 +649,7 @@ __device__ __forceinline__ void file_group_records(const SplatState &st, unsigne
             const unsigned r = t == 0 ? rank[0] : (t == 1 ? rank[1] : (t == 2 ? rank[2] : rank[3]));
             slot = s_grp[g] + r;
         } else {
-            slot = atomicAdd(&st.group_count[(size_t)g * SPLAT_COUNTER_STRIDE], 1u);
+            slot = atomicAdd(&st.group_count[group_counter((int)g)], 1u);
         }
         if (slot < gstride) recs[(size_t)g * gstride + slot] = rec;
         else spilled = true;
