@@ -313,7 +313,7 @@ class FusedEngine:
         ``rendered()``.  The render of add_new_gaussians (/root/reference/scripts/splatam.py:381-385)."""
         self._check_cam(curr_data)
         fr = _capi.SplatFrameData()
-        w2c = curr_data['w2c'] if curr_data['w2c'].is_contiguous() else curr_data['w2c'].contiguous()
+        w2c = self._frame_w2c(curr_data)
         fr.im, fr.depth, fr.w2c, fr.time_idx = None, None, w2c.data_ptr(), int(time_idx)
         self._frame_keep = (w2c,)
         self._tile_rows, self._stats_partial = None, False         # a whole-frame render: its list statistics are the frame's
@@ -622,6 +622,18 @@ class FusedEngine:
                                "(build one engine per camera / resolution)")
         self._cam_ok[id(cam)] = cam          # keeps the tuple alive, so the id stays unique
 
+    def _frame_w2c(self, curr_data):
+        """curr_data['w2c'] as the kernels read it: 16 contiguous floats on the engine's device (row 2 is the depth channel of
+        the depth / silhouette render).  Anything else -- float64 from an inverse taken in double, a CPU tensor, a batch of
+        matrices -- would be read as 16 floats of something else; the reference's own matmul raises a RuntimeError for a dtype or
+        device mismatch (/root/reference/utils/slam_helpers.py:196-213), and so does this, before anything is launched.
+        Attribute reads only; a non-contiguous view is made contiguous."""
+        w2c = curr_data['w2c']
+        if not (isinstance(w2c, torch.Tensor) and w2c.dtype == torch.float32 and w2c.device == self.dev and tuple(w2c.shape) == (4, 4)):
+            got = f"{w2c.dtype}, {tuple(w2c.shape)}, {w2c.device}" if isinstance(w2c, torch.Tensor) else type(w2c).__name__
+            raise RuntimeError(f"curr_data['w2c'] must be a float32 tensor of shape [4, 4] on {self.dev} (got {got})")
+        return w2c if w2c.is_contiguous() else w2c.contiguous()
+
     def _map_struct(self):
         p = self.params
         if self.managed:          # the backing arrays (a zero-row view has no data pointer)
@@ -722,9 +734,9 @@ class FusedEngine:
         self._check_cam(curr_data)
         fr = _capi.SplatFrameData()
         im, depth = curr_data['im'], curr_data['depth']
-        w2c = curr_data['w2c']
-        if not (im.is_contiguous() and depth.is_contiguous() and w2c.is_contiguous()):
-            im, depth, w2c = im.contiguous(), depth.contiguous(), w2c.contiguous()
+        w2c = self._frame_w2c(curr_data)
+        if not (im.is_contiguous() and depth.is_contiguous()):
+            im, depth = im.contiguous(), depth.contiguous()
         fr.im, fr.depth, fr.w2c, fr.time_idx = im.data_ptr(), depth.data_ptr(), w2c.data_ptr(), int(time_idx)
         self._frame_keep = (im, depth, w2c)
         if keep_planes is None:

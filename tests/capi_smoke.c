@@ -4,7 +4,8 @@
  * splat_state_layout, hipMalloc ONE slab, splat_state_bind, then splat_preprocess_forward -> (read status[0]) -> splat_bin_forward ->
  * splat_render_forward -> splat_backward on 1 000 Gaussians, and compare every output with the CPU oracle through ITS C entry
  * points (oracle/raster_ref.c; test infrastructure: the checker, linked here only because this is a test).  Part 2: the same call with
- * group binning (no host read between the calls); part 3: the fused iteration through splat_iter_workspace_layout / _bind.
+ * group binning (no host read between the calls); part 3: the fused iteration through splat_iter_workspace_layout / _bind, at the
+ * identity and at a general first-frame matrix (w2c[16] and a camera to match).
  *
  * Built by tests/test_gpu_capi_c.py (gcc, no hipcc needed):
  *   gcc -std=c99 -O1 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tests/capi_smoke.c \
@@ -220,20 +221,44 @@ int main(void) {
 
     /* ---- part 3: the FUSED iteration through splat_iter_workspace_layout / _bind: ONE slab, zeroed as a binding would zero
      *      it (a superset of what the layout marks zero_init -- the launch order among it: a zeroed tile_order IS the natural order), a
-     *      render, one mapping iteration (which writes the launch order), the render again: bit-identical, and equal to the oracle ---- */
-    {
-        static float logit[P], logsc[P * 3], camq[4] = {1.f, 0.f, 0.f, 0.f}, camt[3] = {0.f, 0.f, 0.f}, w2c[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+     *      render, one mapping iteration (which writes the launch order), the render again: bit-identical, and equal to the oracle.
+     *      Twice: at the identity, and with frame.w2c = a GENERAL rigid matrix M (0.35 rad about (1, 2, 3): no off-diagonal pair of R is
+     *      symmetric; three distinct translation components), the camera built from M as setup_camera builds it and the map moved by
+     *      M^-1 -- the depth plane is then row 2 of w2c at work, the oracle's is the view matrix's: a column read for the row, a
+     *      dropped translation or a transposed view matrix cannot pass ---- */
+    for (int pose = 0; pose < 2; pose++) {
+        static float logit[P], logsc[P * 3], camq[4] = {1.f, 0.f, 0.f, 0.f}, camt[3] = {0.f, 0.f, 0.f}, means_w[P * 3], view[16], proj[16];
+        static const float w2c_all[2][16] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1},
+                                             {0.94370323f, -0.26626885f, 0.19627815f, 0.1f, 0.2835909f, 0.9566948f, -0.06566017f, -0.07f,
+                                              -0.17029503f, 0.11762641f, 0.9783474f, 0.2f, 0.f, 0.f, 0.f, 1.f}};
+        const float *w2c = w2c_all[pose];
         static float zeros6[6];
         for (int i = 0; i < P; i++) {
             logit[i] = logf(opac[i] / (1.f - opac[i]));
             for (int k = 0; k < 3; k++) logsc[3 * i + k] = logf(scales[3 * i + k]);
+            /* the map in the world frame: X_w = R^T (X_c - t) */
+            for (int k = 0; k < 3; k++) {
+                float acc = 0.f;
+                for (int r = 0; r < 3; r++) acc += w2c[4 * r + k] * (means[3 * i + r] - w2c[4 * r + 3]);
+                means_w[3 * i + k] = acc;
+            }
+        }
+        /* viewmatrix = w2c^T, projmatrix = (P w2c)^T, flattened row-major (/root/reference/utils/recon_helpers.py:8-13) */
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) {
+            float acc = 0.f;
+            for (int k = 0; k < 4; k++) acc += Pm[4 * c + k] * w2c[4 * k + r];
+            view[4 * r + c] = w2c[4 * c + r];
+            proj[4 * r + c] = acc;
         }
         SplatCamera cam0 = cam;
         cam0.bg = (const float *)to_device(zeros6, sizeof zeros6);          /* the fused iteration renders on black */
+        cam0.viewmatrix = (const float *)to_device(view, sizeof view);
+        cam0.projmatrix = (const float *)to_device(proj, sizeof proj);
+        if (!cam0.bg || !cam0.viewmatrix || !cam0.projmatrix) return 2;
         SplatMap map;
         memset(&map, 0, sizeof map);
         map.P = P; map.isotropic = 0; map.num_frames = 1;
-        map.means3D = (float *)to_device(means, sizeof means); map.rgb_colors = (float *)to_device(colors, sizeof colors);
+        map.means3D = (float *)to_device(means_w, sizeof means_w); map.rgb_colors = (float *)to_device(colors, sizeof colors);
         map.unnorm_rotations = (float *)to_device(rot, sizeof rot); map.logit_opacities = (float *)to_device(logit, sizeof logit);
         map.log_scales = (float *)to_device(logsc, sizeof logsc);
         map.cam_unnorm_rots = (float *)to_device(camq, sizeof camq); map.cam_trans = (float *)to_device(camt, sizeof camt);
@@ -252,7 +277,7 @@ int main(void) {
         if (!ws.st.tile_order || !ws.st.tile_work || !ws.out6 || !ws.ssim_maps) { fprintf(stderr, "iteration layout: missing arrays\n"); return 1; }
         SplatFrameData frame;
         memset(&frame, 0, sizeof frame);
-        frame.w2c = (const float *)to_device(w2c, sizeof w2c);
+        frame.w2c = (const float *)to_device(w2c, sizeof w2c_all[pose]);
         frame.time_idx = 0;
         SPLAT(splat_iter_render(&cam0, &map, &frame, &ws, stream));
         static float r_a[6 * H * W], r_b[6 * H * W], o_black[C * H * W], o_bdepth[H * W];
@@ -281,9 +306,12 @@ int main(void) {
         size_t written = 0;
         for (size_t i = 0; i < order_words; i++) written += order[i] != 0;
         int same = memcmp(r_a, r_b, sizeof r_a) == 0;
-        if (ref_forward(ref, P, C, W, H, zeros6, means, colors, opac, scales, 1.f, rot, NULL, view, proj, tanx, tany, o_black, o_bdepth, o_bradii)) return 4;
-        printf("capi_smoke (fused iteration through the layout, slab %zu bytes): loss %.6f, flag %.0f, %zu of %zu order words written, renders %s\n",
-               total3, d_cam[7], d_cam[12], written, order_words, same ? "bit-identical" : "DIFFER");
+        if (ref_forward(ref, P, C, W, H, zeros6, means_w, colors, opac, scales, 1.f, rot, NULL, view, proj, tanx, tany, o_black, o_bdepth, o_bradii)) return 4;
+        int visible = 0;
+        for (int i = 0; i < P; i++) visible += o_bradii[i] > 0;
+        printf("capi_smoke (fused iteration through the layout, %s, slab %zu bytes): %d Gaussians visible, loss %.6f, flag %.0f, %zu of %zu order words written, renders %s\n",
+               pose ? "a general first-frame matrix" : "identity", total3, visible, d_cam[7], d_cam[12], written, order_words, same ? "bit-identical" : "DIFFER");
+        fail += visible < 9 * P / 10;
         fail += !same || !(d_cam[7] > 0.f) || d_cam[12] != 0.f || written != order_words;
         fail += compare("rgb planes", r_b, o_black, (size_t)C * H * W, 1e-4f, 0.f, 2);
         fail += compare("depth plane", r_b + 3 * H * W, o_bdepth, (size_t)H * W, 1e-4f, 1e-4f, 2);

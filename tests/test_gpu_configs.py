@@ -188,23 +188,32 @@ class _Spy:
         return out
 
 
-def _cpu_case(params, frame, cam_args, dtype, time_idx=1):
+def _world_matrices(first_w2c=None, frame_w2c=None):
+    """(camera matrix, curr_data['w2c']) as float32 numpy 4x4: the identity by default; ``first_w2c`` alone: both (the frame loop's
+    usage); ``frame_w2c`` too: a depth channel that disagrees with the camera (/root/reference/scripts/post_splatam_opt.py:275,307)."""
+    cam_m = np.eye(4, dtype=np.float32) if first_w2c is None else np.ascontiguousarray(np.asarray(first_w2c, dtype=np.float32))
+    frame_m = cam_m if frame_w2c is None else np.ascontiguousarray(np.asarray(frame_w2c, dtype=np.float32))
+    return cam_m, frame_m
+
+
+def _cpu_case(params, frame, cam_args, dtype, time_idx=1, first_w2c=None, frame_w2c=None):
     from splatam_amd import slam
     W, H, k = cam_args
     pc = {k_: torch.nn.Parameter(v.detach().cpu().to(dtype).clone()) for k_, v in params.items()}
-    cam_c = slam.setup_camera(W, H, k, np.eye(4, dtype=np.float32), device="cpu")
+    cam_m, frame_m = _world_matrices(first_w2c, frame_w2c)
+    cam_c = slam.setup_camera(W, H, k, cam_m, device="cpu")
     frame_c = {'cam': cam_c, 'im': frame['im'].cpu().to(dtype), 'depth': frame['depth'].cpu().to(dtype), 'id': time_idx,
-               'w2c': torch.eye(4, dtype=dtype)}
+               'w2c': torch.tensor(frame_m).to(dtype)}             # (the float32 matrix the kernels read, widened exactly)
     return pc, frame_c
 
 
-def _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch, time_idx=1):
+def _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch, time_idx=1, first_w2c=None, frame_w2c=None):
     """splatam_amd.slam.get_loss (pinned to /root/reference/scripts/splatam.py:214-347 by tests/golden/) on CPU tensors with the
     C oracle as its Renderer: returns (loss, [rgb render, depth/sil render], their autograd gradients)."""
     from splatam_amd import slam
     monkeypatch.setattr(slam, "Renderer", _Spy)
     _Spy.renders = []
-    pc, frame_c = _cpu_case(params, frame, cam_args, torch.float32, time_idx)
+    pc, frame_c = _cpu_case(params, frame, cam_args, torch.float32, time_idx, first_w2c, frame_w2c)
     vc = {k_: v.cpu().clone() for k_, v in variables.items()}
     loss, _, _ = slam.get_loss(pc, frame_c, vc, time_idx, cfg['loss_weights'], cfg['use_sil_for_loss'], cfg['sil_thres'], cfg['use_l1'],
                                cfg['ignore_outlier_depth_loss'], tracking=tracking, mapping=not tracking)
@@ -214,12 +223,12 @@ def _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypa
     return float(loss.detach()), [im.detach(), ds.detach()], [im.grad, ds.grad if ds.grad is not None else zero]
 
 
-def _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, dtype, monkeypatch, time_idx=1):
+def _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, dtype, monkeypatch, time_idx=1, first_w2c=None, frame_w2c=None):
     """The oracle's two renders + two backward passes for GIVEN gradient planes (dL/drgb [3], dL/ddepth [1]) through the
     reference-shaped glue (transform_to_frame, render-variable assembly): gradients of every parameter."""
     from splatam_amd import slam
     monkeypatch.setattr(slam, "Renderer", c_ref.CRasterizer)
-    pc, frame_c = _cpu_case(params, frame, cam_args, dtype, time_idx)
+    pc, frame_c = _cpu_case(params, frame, cam_args, dtype, time_idx, first_w2c, frame_w2c)
     tg = slam.transform_to_frame(pc, time_idx, gaussians_grad=not tracking, camera_grad=tracking)
     im, _, _ = slam.Renderer(raster_settings=frame_c['cam'])(**slam.transformed_params2rendervar(pc, tg))
     ds, _, _ = slam.Renderer(raster_settings=frame_c['cam'])(**slam.transformed_params2depthplussilhouette(pc, frame_c['w2c'], tg))
@@ -228,9 +237,10 @@ def _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, dtyp
     return {k_: (None if v.grad is None else v.grad.numpy()) for k_, v in pc.items()}
 
 
-def _assert_depth_ties_explain(big, params, c, what, time_idx=1, max_pixels=400):
+def _assert_depth_ties_explain(big, params, c, what, time_idx=1, max_pixels=400, first_w2c=None):
     """Every pixel of the boolean image `big` lies under two Gaussians whose float64 camera-space depths differ by less than
-    4 float32 ulps (a depth tie: their order is decided by rounding)."""
+    4 float32 ulps (a depth tie: their order is decided by rounding).  With a first-frame matrix M the camera sees
+    M @ pose_t @ X: the depth the lists are sorted by is that product's z."""
     ys, xs = np.nonzero(big)
     print(f"{what}: {ys.size} pixels beyond the one-decision bound")
     if ys.size == 0:
@@ -244,6 +254,9 @@ def _assert_depth_ties_explain(big, params, c, what, time_idx=1, max_pixels=400)
                    [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
                    [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
     X = params['means3D'].detach().double().cpu().numpy() @ Rm.T + t
+    if first_w2c is not None:
+        M = np.asarray(first_w2c, dtype=np.float32).astype(np.float64)
+        X = X @ M[:3, :3].T + M[:3, 3]
     zc = X[:, 2]
     u, v = c['fx'] * X[:, 0] / zc + c['cx'], c['fy'] * X[:, 1] / zc + c['cy']
     for py, px in zip(ys, xs):
@@ -254,7 +267,9 @@ def _assert_depth_ties_explain(big, params, c, what, time_idx=1, max_pixels=400)
     return int(ys.size)
 
 
-def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None):
+def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None, first_w2c=None, frame_w2c=None):
+    """``first_w2c`` (default: the identity): the matrix the camera is built from and -- unless ``frame_w2c`` names another --
+    curr_data['w2c']; the map made at the identity is moved by its inverse (as tests/util.py: scene does), so it still fills the frame."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
     c = CONFIGS[cfg_name]
@@ -262,8 +277,13 @@ def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None):
     params, variables = slam.synthetic_params(n, W, H, c['fx'], c['fy'], c['cx'], c['cy'], num_frames=3, seed=seed, device="cuda",
                                               anisotropic=aniso, region=region)
     k = [[c['fx'], 0, c['cx']], [0, c['fy'], c['cy']], [0, 0, 1]]
-    w2c = torch.eye(4, device="cuda")
-    cam = slam.setup_camera(W, H, k, np.eye(4, dtype=np.float32), device="cuda")
+    cam_m, frame_m = _world_matrices(first_w2c, frame_w2c)
+    if first_w2c is not None:
+        c2w = torch.tensor(np.linalg.inv(cam_m.astype(np.float64))).float().cuda()
+        with torch.no_grad():
+            params['means3D'].copy_(params['means3D'] @ c2w[:3, :3].T + c2w[:3, 3])
+    w2c = torch.tensor(frame_m, device="cuda")
+    cam = slam.setup_camera(W, H, k, cam_m, device="cuda")
     im, depth = slam.synthetic_frame(params, cam, w2c, 1, rot_deg=0.4, trans_m=0.01)
     g = torch.Generator().manual_seed(seed + 1)
     im = (im + 0.03 * torch.randn(im.shape, generator=g).cuda()).clamp(0, 1).contiguous()
@@ -279,21 +299,24 @@ def _fused_case(cfg_name, aniso, tracking, monkeypatch, seed=0, region=None):
     torch.cuda.synchronize()
     assert not eng.check_overflow(grow=False)
     what = f"fused {cfg_name}{'-aniso' if aniso else ''}{'-clustered' if region else ''} {'tracking' if tracking else 'mapping'}"
-    g32, g64 = _fused_stages(eng, params, variables, frame, (W, H, k), c, cfg, tracking, what, monkeypatch)
+    if first_w2c is not None:
+        what += " at a general first-frame pose" + (" (another matrix for the depth channel)" if frame_w2c is not None else "")
+    g32, g64 = _fused_stages(eng, params, variables, frame, (W, H, k), c, cfg, tracking, what, monkeypatch, first_w2c=first_w2c, frame_w2c=frame_w2c)
+    eng.case = dict(params=params, variables=variables, frame=frame, cam_args=(W, H, k), c=c, cfg=cfg)
     return eng, g32, g64, what
 
 
-def _fused_stages(eng, params, variables, frame, cam_args, c, cfg, tracking, what, monkeypatch, time_idx=1):
+def _fused_stages(eng, params, variables, frame, cam_args, c, cfg, tracking, what, monkeypatch, time_idx=1, first_w2c=None, frame_w2c=None):
     """Stages (A)..(C) for an engine whose iteration on ``frame`` at pose ``time_idx`` has run; returns the oracle's float32 and
     float64 gradients of stage (D) for the same gradient planes."""
     from splatam_amd import slam
-    loss_ref, renders, plane_grads = _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch, time_idx)
+    loss_ref, renders, plane_grads = _oracle_get_loss(params, frame, variables, cam_args, cfg, tracking, monkeypatch, time_idx, first_w2c, frame_w2c)
     # (A) rendered planes
     imf, depthf, silf, dsqf = eng.rendered()
     nflip = 2e-4            # the fused glue rounds differently from torch's: a few more alpha >= 1/255 decisions flip than on the drop-in path
     got_im, got_ds = imf.cpu().numpy(), torch.cat([depthf, silf[None], dsqf]).cpu().numpy()
     # every pixel beyond 1e-4 explained by a decision the float64 oracle (float64 glue) finds within rounding of its threshold there
-    pc64, frame64 = _cpu_case(params, frame, cam_args, torch.float64, time_idx)
+    pc64, frame64 = _cpu_case(params, frame, cam_args, torch.float64, time_idx, first_w2c, frame_w2c)
     with torch.no_grad():
         tg64 = slam.transform_to_frame(pc64, time_idx, gaussians_grad=False, camera_grad=False)
         b_im, _, _, _, n_im = oracle_flip_bounds(slam.transformed_params2rendervar(pc64, tg64), frame64['cam'])
@@ -305,7 +328,7 @@ def _fused_stages(eng, params, variables, frame, cam_args, c, cfg, tracking, wha
     # whose camera-space depths agree to float32 rounding are ordered by that rounding, and the in-kernel glue (FMA chain) rounds
     # z = (R X + t).z differently from torch's matmul -- a legitimate swap of two list neighbours, verified per pixel
     big = (np.abs(got_im - renders[0].numpy()).max(axis=0) > 0.03) | (np.abs(got_ds - renders[1].numpy()).max(axis=0) > 0.3)
-    eng.depth_tie_pixels = _assert_depth_ties_explain(big, params, c, what, time_idx)
+    eng.depth_tie_pixels = _assert_depth_ties_explain(big, params, c, what, time_idx, first_w2c=first_w2c)
     # (B) loss
     loss_f = eng.loss()
     assert abs(loss_f - loss_ref) <= 1e-4 * abs(loss_ref), (what, loss_f, loss_ref)
@@ -319,8 +342,8 @@ def _fused_stages(eng, params, variables, frame, cam_args, c, cfg, tracking, wha
                           what=f"{what} dL/d(render) planes")
     assert float(planes[4:6].abs().max()) == 0.0 and float(plane_grads[1][1:3].abs().max()) == 0.0
     # (D) parameter / pose gradients for the SAME gradient planes, float32 and float64 oracle
-    g32 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float32, monkeypatch, time_idx)
-    g64 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float64, monkeypatch, time_idx)
+    g32 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float32, monkeypatch, time_idx, first_w2c, frame_w2c)
+    g64 = _oracle_backward_from_planes(params, frame, cam_args, planes, tracking, torch.float64, monkeypatch, time_idx, first_w2c, frame_w2c)
     return g32, g64
 
 
@@ -343,9 +366,12 @@ def _check_pose_gradient(eng, g32, g64, what, time_idx=1):
     gq32, gt32 = g32['cam_unnorm_rots'][0, :, time_idx], g32['cam_trans'][0, :, time_idx]
     gq64, gt64 = g64['cam_unnorm_rots'][0, :, time_idx], g64['cam_trans'][0, :, time_idx]
     print(what, "pose gradient", d[0:7], "oracle f32", gq32, gt32, "oracle f64", gq64, gt64)
+    tols = []
     for got, r32, r64 in ((d[0:4], gq32, gq64), (d[4:7], gt32, gt64)):
         tol = max(1e-4 * np.abs(r64).max(), 2.0 * np.abs(r32 - r64).max())
         assert np.abs(got - r64).max() <= tol, (what, got, r64, tol)
+        tols.append(tol)
+    return tols                         # (rotation, translation): the tolerances that were applied
 
 
 @pytest.mark.parametrize("cfg_name,aniso", [('B', False), ('B', True), ('D', False), ('D', True), ('E', False), ('E', True)])

@@ -13,7 +13,9 @@ from tests.util import assert_close_outliers, grad_scale, track_loop_loss_rtol
 pytestmark = pytest.mark.gpu
 
 
-def _scene(n, W, H, aniso=False, seed=0, num_frames=3):
+def _scene(n, W, H, aniso=False, seed=0, num_frames=3, first_w2c=None):
+    """``first_w2c`` (default: the identity): the camera's matrix and curr_data['w2c']; the map, made at the identity, is moved by its
+    inverse so that it fills the frame as before (tests/test_gpu_world_frame.py runs the variant comparisons below at a general one)."""
     from splatam_amd import slam
     f = 0.5 * W
     cx, cy = W / 2 - 0.5, H / 2 - 0.5
@@ -21,6 +23,11 @@ def _scene(n, W, H, aniso=False, seed=0, num_frames=3):
                                               anisotropic=aniso)
     k = [[f, 0, cx], [0, f, cy], [0, 0, 1]]
     w2c = torch.eye(4, device="cuda")
+    if first_w2c is not None:
+        w2c = torch.tensor(np.ascontiguousarray(np.asarray(first_w2c, dtype=np.float32)), device="cuda")
+        c2w = torch.tensor(np.linalg.inv(np.asarray(first_w2c, dtype=np.float64))).float().cuda()
+        with torch.no_grad():
+            params['means3D'].copy_(params['means3D'] @ c2w[:3, :3].T + c2w[:3, 3])
     cam = slam.setup_camera(W, H, k, w2c.cpu().numpy(), device="cuda")
     im, depth = slam.synthetic_frame(params, cam, w2c, 1, rot_deg=0.4, trans_m=0.01)
     g = torch.Generator().manual_seed(seed + 1)
@@ -192,12 +199,12 @@ def test_tracking_loop_matches_reference_loop():
 
 
 @pytest.mark.parametrize("tracking", [True, False])
-def test_bucketed_lists_match_exact_lists(tracking):
+def test_bucketed_lists_match_exact_lists(tracking, first_w2c=None):
     """check_overflow() teaches the engine the list statistics; from then on the per-tile lists are bucketed (no scan /
     scatter pass).  Same lists but for the entries that cannot blend, same results: only the order of float atomics differs."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
-    params, variables, frame, cam = _scene(20000, 320, 240, aniso=not tracking, seed=21)
+    params, variables, frame, cam = _scene(20000, 320, 240, aniso=not tracking, seed=21, first_w2c=first_w2c)
     cfg = slam.REPLICA_TRACKING if tracking else slam.REPLICA_MAPPING
     eng = FusedEngine(params, cam)
     eng.loss_backward(frame, 1, cfg, tracking=tracking)
@@ -454,13 +461,13 @@ def test_mapping_batch_equals_gradient_accumulation():
 
 
 @pytest.mark.parametrize("order", ["random", "scan"])
-def test_order_hint_changes_nothing_but_speed(order):
+def test_order_hint_changes_nothing_but_speed(order, first_w2c=None):
     """SplatState.order_hint (bucket slots taken per (workgroup, tile) through an LDS table instead of one returning atomic per
     instance): same lists after the in-kernel sort, hence bit-identical renders, for a map in random order (most instances
     fall back to their own atomic) and for one in pixel-scan order (the case it is for)."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
-    params, variables, frame, cam = _scene(30000, 320, 240, seed=31)
+    params, variables, frame, cam = _scene(30000, 320, 240, seed=31, first_w2c=first_w2c)
     if order == "scan":
         with torch.no_grad():
             z = params['means3D'][:, 2]
@@ -479,6 +486,8 @@ def test_order_hint_changes_nothing_but_speed(order):
         eng.loss_backward(frame, 1, cfg, tracking=False)                  # bucketed lists: the hinted path
         torch.cuda.synchronize()
         assert not eng.check_overflow(grow=False)
+        st = eng._workspace(False, with_ssim=False).st                    # the form of F1 the launch took: aggregated bucket slots or not
+        assert bool(st.order_hint) == hint and st.tile_stride > 0 and st.group_stride == 0
         outs.append((eng.buf['out6'].clone(), eng.grads['means3D'].clone(), eng.loss()))
     assert torch.equal(outs[0][0], outs[1][0])
     assert abs(outs[0][2] - outs[1][2]) <= 1e-6 * abs(outs[0][2])
@@ -641,7 +650,7 @@ def test_staged_records_handed_to_the_backward_composite_change_nothing_but_spee
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", ["random", "large", "odd_grid", "tracking"])
-def test_group_binning_changes_nothing_but_speed(case):
+def test_group_binning_changes_nothing_but_speed(case, first_w2c=None):
     """SplatState.group_count (one record per (Gaussian, 2 x 2-tile group), slots through an LDS histogram; the forward composite
     filters its group's records by tile rectangle): the per-tile lists after the composite's sort are those of the per-tile
     buckets WITHOUT the entries whose tile cannot hold a pixel with alpha >= 1/255 (splat_math.h live_tile_rect: 12-13 % of the
@@ -651,7 +660,7 @@ def test_group_binning_changes_nothing_but_speed(case):
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
     W, H = (328, 232) if case == "odd_grid" else (320, 240)
-    params, variables, frame, cam = _scene(30000 if case != "large" else 6000, W, H, seed=37)
+    params, variables, frame, cam = _scene(30000 if case != "large" else 6000, W, H, seed=37, first_w2c=first_w2c)
     if case == "large":
         with torch.no_grad():
             params['log_scales'] += 1.5
@@ -693,14 +702,14 @@ def test_group_binning_changes_nothing_but_speed(case):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("aniso", [False, True])
-def test_mapping_step_in_one_call_equals_loss_backward_plus_adam(aniso):
+def test_mapping_step_in_one_call_equals_loss_backward_plus_adam(aniso, first_w2c=None):
     """splat_iter_mapping_step (the Adam step of the map folded into the iteration's last kernel) against the two calls it replaces
     (splat_iter_loss_backward, splat_iter_adam_map), three iterations: same parameters and moments up to the summation order of
     the backward composite's float atomics (Adam with eps = 1e-15 turns a gradient that is rounding noise into a +-lr step, so
     elements are compared where the gradient is significant), and the loss / pose outputs of the folded F7."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine, PARAM_ORDER
-    params, variables, frame, cam = _scene(8000, 208, 160, aniso=aniso, seed=11)
+    params, variables, frame, cam = _scene(8000, 208, 160, aniso=aniso, seed=11, first_w2c=first_w2c)
     cfg = slam.REPLICA_MAPPING
     e1 = FusedEngine({k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}, cam)
     e2 = FusedEngine({k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}, cam)
@@ -770,14 +779,14 @@ def test_stale_hint_with_bucketed_lists_is_flagged_and_memory_safe(groups):
 @pytest.mark.gpu
 @pytest.mark.parametrize("lists", ["exact", "learnt"])
 @pytest.mark.parametrize("world", [2, 3])
-def test_tile_row_sharded_tracking_equals_whole_frame_tracking(lists, world):
+def test_tile_row_sharded_tracking_equals_whole_frame_tracking(lists, world, first_w2c=None):
     """Tracking sharded over tile rows (SplatState.tile_row_begin / _end, splat_iter_finish): ``world`` engines holding the same map and
     pose each composite their band of the frame; their partial sums, added (what the all-reduce does), give the whole frame's loss
     and pose gradient; every rank then takes the same Adam step.  Against the whole-frame tracking loop over four iterations, with the
     exact lists of a fresh engine and with learnt bucketed lists / group records."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
-    params, variables, frame, cam = _scene(20000, 328, 248, seed=53)        # 21 x 16 tiles: bands of 8 + 8 or 5 + 5 + 6 rows
+    params, variables, frame, cam = _scene(20000, 328, 248, seed=53, first_w2c=first_w2c)        # 21 x 16 tiles: bands of 8 + 8 or 5 + 5 + 6 rows
     cfg = slam.REPLICA_TRACKING
 
     def engine():
@@ -1005,14 +1014,14 @@ def test_every_view_keeps_its_own_launch_order():
 
 @pytest.mark.parametrize("n,W,H,label", [(20000, 328, 248, "one batch per tile"), (64000, 328, 248, "two to three batches per tile"),
                                          (4000, 200, 120, "sparse: empty tiles, pixels outside the image")])
-def test_tracking_composites_in_one_kernel_equal_the_two_kernels(n, W, H, label):
+def test_tracking_composites_in_one_kernel_equal_the_two_kernels(n, W, H, label, first_w2c=None):
     """SplatLossConfig.fused_composite: the tracking iteration's forward composite, loss and backward composite as ONE kernel (the
     backward pass walks the batch the forward pass left in LDS; planes in registers) against the two-kernel form: rendered planes,
     gradient planes, final_T / n_contrib bit for bit (the forward pass is the same code), loss and pose gradient to float-atomic
     summation order; and, without the planes, the same tracking LOOP."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
-    params, variables, frame, cam = _scene(n, W, H, seed=91)
+    params, variables, frame, cam = _scene(n, W, H, seed=91, first_w2c=first_w2c)
     cfg = slam.REPLICA_TRACKING
     out = {}
     for fused in (True, False):
@@ -1024,12 +1033,14 @@ def test_tracking_composites_in_one_kernel_equal_the_two_kernels(n, W, H, label)
         eng.loss_backward(frame, 1, cfg, tracking=True)                         # planes kept
         torch.cuda.synchronize()
         assert not eng.check_overflow(grow=False)
+        assert eng._lc_keep.fused_composite == (2 if fused else 0)              # the form the launch took
         out[fused] = dict(out6=eng.buf['out6'].clone(), dplanes=eng.buf['dL_dout6'].clone(), T=eng.buf['final_T'].clone(),
                           nc=eng.buf['n_contrib'].clone(), d=eng.buf['d_cam'].clone(), longest=eng.max_list_hint)
         for _ in range(4):                                                      # the loop's own iterations: no planes
             eng.tracking_iteration(frame, cfg)
         torch.cuda.synchronize()
         assert not eng.check_overflow(grow=False)
+        assert eng._lc_keep.fused_composite == (1 if fused else 0)
         out[fused].update(rot=eng.params['cam_unnorm_rots'].detach().clone(), trans=eng.params['cam_trans'].detach().clone(), loss=eng.loss())
     a, b = out[True], out[False]
     print(label, "longest list", a['longest'])

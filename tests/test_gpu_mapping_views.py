@@ -26,11 +26,13 @@ KEYS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_sca
 _SCENES = {}
 
 
-def _scene(size):
-    """The scene of one size, made once per session (every test works on clones of its parameters)."""
-    if size not in _SCENES:
-        _SCENES[size] = multiview_scene(size, seed=17)
-    return _SCENES[size]
+def _scene(size, first_w2c=None):
+    """The scene of one size, made once per session (every test works on clones of its parameters); ``first_w2c``: the map and all
+    eight keyframes under a first-frame matrix other than the identity."""
+    key = size if first_w2c is None else (size, np.asarray(first_w2c, dtype=np.float32).tobytes())
+    if key not in _SCENES:
+        _SCENES[key] = multiview_scene(size, seed=17, first_w2c=first_w2c)
+    return _SCENES[key]
 
 
 def _clone(params):
@@ -127,18 +129,18 @@ def test_view_at_a_real_pose_vs_oracle(view, tracking, monkeypatch):
 # 3. mapping_batch at BASELINE config 3
 # ------------------------------------------------------------------------------------------------------------------------------
 
-def test_mapping_batch_config3_vs_autograd_and_adam():
-    """8 keyframe views per mapping step on B's map: the averaged gradient, the moments on EVERY row (after one step
+def test_mapping_batch_config3_vs_autograd_and_adam(size='B', first_w2c=None):
+    """8 keyframe views per mapping step on B's map (tests/test_gpu_world_frame.py: the small map under a general first-frame matrix): the averaged gradient, the moments on EVERY row (after one step
     exp_avg = 0.1 g and exp_avg_sq = 0.001 g^2), the parameters where the gradient is significant; rows no view sees keep a zero
     gradient, zero moments and bit-identical parameters.  Then the same step over two emulated ranks (5 + 3 views)."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
-    params, variables, cam, k, views, c = _scene('B')
+    params, variables, cam, k, views, c = _scene(size, first_w2c)
     cfg = slam.REPLICA_MAPPING
     t0 = time.time()
     ref = _clone(params)
     per_view, radii = _reference_views(ref, variables, views, cfg)
-    groups, _ = view_partition(radii, params, FORWARD_VIEW, what="B")
+    groups, _ = view_partition(radii, params, FORWARD_VIEW, what=size, first_w2c=first_w2c)
     none = torch.as_tensor(groups['no view'], device="cuda")
     mean = {key: sum(g[key] for g in per_view) / len(views) for key in KEYS}
     opt = slam.initialize_optimizer(ref, cfg['lrs'], tracking=False)

@@ -60,9 +60,10 @@ def _variables(params):
     return {'max_2D_radius': z(), 'means2D_gradient_accum': z(), 'denom': z(), 'timestep': z(), 'scene_radius': torch.tensor(2.0, device="cuda")}
 
 
-def test_tracking_statements_run_fused_and_match_the_dropin_path():
+def test_tracking_statements_run_fused_and_match_the_dropin_path(first_w2c=None):
+    """(``first_w2c``: tests/test_gpu_world_frame.py runs these statements with curr_data['w2c'] and the camera at a general matrix)"""
     from splatam_amd import plugin, slam
-    params, _, frame, cam = _scene(12000, 256, 192, aniso=False, seed=11)
+    params, _, frame, cam = _scene(12000, 256, 192, aniso=False, seed=11, first_w2c=first_w2c)
     cfg = slam.REPLICA_TRACKING
     ref = {k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}
     mine = {k: torch.nn.Parameter(v.detach().clone()) for k, v in params.items()}
@@ -101,12 +102,12 @@ def _assert_adam_step_matches(name, p_mine, p_ref, p_before, m_mine, m_ref, lr):
     assert flipped <= 5e-3, (name, flipped)                                             # elements whose gradient is rounding noise
 
 
-def test_mapping_statements_with_the_references_pruning_run_fused():
+def test_mapping_statements_with_the_references_pruning_run_fused(first_w2c=None):
     """Mapping iterations in the reference's statements; the pruning schedule removes rows at iteration 0 (the reference's own
     remove_points slices the optimizer state and re-creates every parameter: that iteration takes no Adam step), iteration 1 steps
     the smaller map: parameters and moments after that ONE step element-wise against torch.optim.Adam on the drop-in path."""
     from splatam_amd import plugin, slam
-    params, _, frame, cam = _scene(8000, 208, 160, aniso=False, seed=7)
+    params, _, frame, cam = _scene(8000, 208, 160, aniso=False, seed=7, first_w2c=first_w2c)
     with torch.no_grad():
         params['logit_opacities'][::5] = -6.0                       # a fifth of the map is transparent: pruned at iteration 0
     cfg = slam.REPLICA_MAPPING

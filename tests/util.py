@@ -22,6 +22,42 @@ def tilted_w2c(th=0.3, t=(0.1, -0.05, 0.2)):
     return np.array([[c, 0, s, t[0]], [0, 1, 0, t[1]], [-s, 0, c, t[2]], [0, 0, 0, 1]], dtype=np.float32)
 
 
+def rigid_w2c(angle, axis, t):
+    """float32 world-to-camera 4x4: rotation by ``angle`` (rad) about ``axis`` (Rodrigues, formed in float64), translation ``t``."""
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    M = np.eye(4)
+    M[:3, :3] = np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * (K @ K)
+    M[:3, 3] = t
+    return M.astype(np.float32)
+
+
+def general_w2c():
+    """A GENERAL first-frame matrix (the M of tests/golden/make_golden_world_frame.py): 0.35 rad about (1, 2, 3) -- the off-diagonal
+    pairs of R differ by 0.55 / 0.37 / 0.18, so no row / column or transposition mix-up of any pair goes unseen (tilted_w2c turns
+    about y only: R_01 = R_10 = 0) -- and three distinct non-zero translation components."""
+    return rigid_w2c(0.35, (1.0, 2.0, 3.0), (0.1, -0.07, 0.2))
+
+
+def other_w2c():
+    """A second general matrix: curr_data['w2c'] of a caller whose depth channel disagrees with its camera
+    (/root/reference/scripts/post_splatam_opt.py:275,307)."""
+    return rigid_w2c(0.25, (-2.0, 1.0, 1.5), (-0.06, 0.12, 0.15))
+
+
+def loop_first_w2c():
+    """The matrix the reference's frame loop passes: first_frame_w2c = torch.linalg.inv(pose) (/root/reference/scripts/splatam.py) of
+    the first relative pose P0_rel = inv(P0) @ P0, formed in float32 as _preprocess_poses does
+    (/root/reference/datasets/gradslam_datasets/basedataset.py:194-195) for a non-trivial dataset pose P0: an identity up to float32
+    rounding only."""
+    P0 = torch.tensor(np.linalg.inv(rigid_w2c(0.9, (0.3, -1.0, 0.5), (1.7, -0.4, 2.3)).astype(np.float64)), dtype=torch.float32)
+    P0_rel = torch.linalg.inv(P0) @ P0
+    M = torch.linalg.inv(P0_rel).numpy()
+    assert not np.array_equal(M, np.eye(4, dtype=np.float32)) and np.abs(M - np.eye(4)).max() < 1e-5
+    return np.ascontiguousarray(M)
+
+
 def assert_close_outliers(got, ref, atol, rtol=0.0, max_outlier_frac=0.0, outlier_atol=None, what=""):
     """|got-ref| <= atol + rtol*|ref| everywhere except for a bounded fraction of
     elements (float32 threshold flips: alpha<1/255, T<1e-4, power>0 decisions taken
@@ -262,6 +298,22 @@ def pose_quat(rx_deg, ry_deg):
                      w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2, w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2])
 
 
+def conjugate_pose(q, t, first_w2c):
+    """The pose (q', t') that shows a map moved by M^-1 to a camera built from M exactly as (q, t) shows the unmoved map to a
+    camera at the identity: M pose' M^-1 = pose, i.e. R' = Rm^T R Rm, t' = Rm^T (R tm + t - tm)."""
+    w, x, y, z = np.asarray(q, dtype=np.float64) / np.linalg.norm(q)
+    Rq = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                   [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                   [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    M = np.asarray(first_w2c, dtype=np.float64)
+    Rm, tm = M[:3, :3], M[:3, 3]
+    R2 = Rm.T @ Rq @ Rm
+    t2 = Rm.T @ (Rq @ tm + np.asarray(t, dtype=np.float64) - tm)
+    w2 = 0.5 * np.sqrt(max(1.0 + np.trace(R2), 1e-12))          # (rotations far below 180 degrees: w is well away from zero)
+    q2 = np.array([w2, (R2[2, 1] - R2[1, 2]) / (4 * w2), (R2[0, 2] - R2[2, 0]) / (4 * w2), (R2[1, 0] - R2[0, 1]) / (4 * w2)])
+    return q2, t2
+
+
 def frame_at_pose(params, cam, w2c_first, q, t):
     """'Ground-truth' RGB-D frame: the map rendered (HIP drop-in rasterizer) from the world-to-camera pose (q, t) -- what
     splatam_amd.slam.synthetic_frame does for its fixed small perturbation of the identity."""
@@ -281,8 +333,9 @@ def frame_at_pose(params, cam, w2c_first, q, t):
     return im.contiguous(), depth.contiguous()
 
 
-def multiview_scene(size, seed=0, aniso=False):
-    """One seeded map (splatam_amd.slam.synthetic_params at the identity pose), the 8 keyframe poses of MULTIVIEW_POSES in
+def multiview_scene(size, seed=0, aniso=False, first_w2c=None):
+    """One seeded map (splatam_amd.slam.synthetic_params at the identity pose; with ``first_w2c`` = M the camera and curr_data['w2c']
+    are M and the map is moved by M^-1, so every keyframe sees what it saw at the identity), the 8 keyframe poses of MULTIVIEW_POSES in
     ``cam_unnorm_rots`` / ``cam_trans`` [..., 1..8], and per keyframe a frame rendered from a pose 0.4 deg / 1 cm off the keyframe's
     (so that the loss has a real gradient), with the noise and the invalid-depth patch of the single-view tests.
     Returns (params, variables, cam, k, views = [(frame, time_idx), ...], c)."""
@@ -292,16 +345,24 @@ def multiview_scene(size, seed=0, aniso=False):
     params, variables = slam.synthetic_params(n, W, H, c['fx'], c['fy'], c['cx'], c['cy'], num_frames=1 + len(MULTIVIEW_POSES), seed=seed,
                                               device="cuda", anisotropic=aniso)
     k = [[c['fx'], 0, c['cx']], [0, c['fy'], c['cy']], [0, 0, 1]]
-    w2c = torch.eye(4, device="cuda")
-    cam = slam.setup_camera(W, H, k, np.eye(4, dtype=np.float32), device="cuda")
+    first = np.eye(4, dtype=np.float32) if first_w2c is None else np.ascontiguousarray(np.asarray(first_w2c, dtype=np.float32))
+    if first_w2c is not None:
+        c2w = torch.tensor(np.linalg.inv(first.astype(np.float64))).float().cuda()
+        with torch.no_grad():
+            params['means3D'].copy_(params['means3D'] @ c2w[:3, :3].T + c2w[:3, 3])
+    w2c = torch.tensor(first, device="cuda")
+    cam = slam.setup_camera(W, H, k, first, device="cuda")
     g = torch.Generator().manual_seed(seed + 1)
     views = []
     for i, ((rx, ry), t) in enumerate(MULTIVIEW_POSES, start=1):
         q = pose_quat(rx, ry)
+        q_gt, t_gt = pose_quat(rx + 0.3, ry - 0.4), np.asarray(t) + np.array([0.01, -0.005, 0.005])
+        if first_w2c is not None:
+            (q, t), (q_gt, t_gt) = conjugate_pose(q, t, first), conjugate_pose(q_gt, t_gt, first)
         with torch.no_grad():
             params['cam_unnorm_rots'][0, :, i] = torch.as_tensor(q, dtype=torch.float32, device="cuda")
             params['cam_trans'][0, :, i] = torch.as_tensor(t, dtype=torch.float32, device="cuda")
-        im, depth = frame_at_pose(params, cam, w2c, pose_quat(rx + 0.3, ry - 0.4), np.asarray(t) + np.array([0.01, -0.005, 0.005]))
+        im, depth = frame_at_pose(params, cam, w2c, q_gt, t_gt)
         im = (im + 0.03 * torch.randn(im.shape, generator=g).cuda()).clamp(0, 1).contiguous()
         depth = (depth * (1 + 0.01 * torch.randn(depth.shape, generator=g).cuda())).contiguous()
         depth[:, : H // 8, : W // 8] = 0.0                  # a patch of invalid depth (mask path)
@@ -309,8 +370,18 @@ def multiview_scene(size, seed=0, aniso=False):
     return params, variables, cam, k, views, c
 
 
-def camera_depths(params, time_idx):
-    """float64 camera-space z of every Gaussian centre at pose ``time_idx``."""
+def camera_depths(params, time_idx, first_w2c=None):
+    """float64 camera-space z of every Gaussian centre at pose ``time_idx`` (seen through the first-frame matrix, when there is one)."""
+    if first_w2c is not None:
+        q = params['cam_unnorm_rots'][0, :, time_idx].detach().double().cpu().numpy()
+        t = params['cam_trans'][0, :, time_idx].detach().double().cpu().numpy()
+        w, x, y, z = q / np.linalg.norm(q)
+        Rq = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                       [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                       [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+        M = np.asarray(first_w2c, dtype=np.float64)
+        Xc = params['means3D'].detach().double().cpu().numpy() @ Rq.T + t
+        return Xc @ M[2, :3] + M[2, 3]
     q = params['cam_unnorm_rots'][0, :, time_idx].detach().double().cpu().numpy()
     t = params['cam_trans'][0, :, time_idx].detach().double().cpu().numpy()
     w, x, y, z = q / np.linalg.norm(q)
@@ -318,7 +389,7 @@ def camera_depths(params, time_idx):
     return params['means3D'].detach().double().cpu().numpy() @ row2 + t[2]
 
 
-def view_partition(radii_per_view, params, forward_view, min_frac=0.03, what=""):
+def view_partition(radii_per_view, params, forward_view, min_frac=0.03, what="", first_w2c=None):
     """Rows of the map by how many keyframe views see them (radii > 0 of the reference renders): every view, some only, none; and
     the rows the near plane (z <= 0.2) culls in ``forward_view``.  Each group must hold at least ``min_frac`` of the map, so that
     no comparison over a group passes on an empty set."""
@@ -326,7 +397,7 @@ def view_partition(radii_per_view, params, forward_view, min_frac=0.03, what="")
     count = seen.sum(axis=0)
     P = seen.shape[1]
     groups = {'every view': count == seen.shape[0], 'some views': (count > 0) & (count < seen.shape[0]), 'no view': count == 0,
-              'behind the near plane (forward view)': camera_depths(params, forward_view) <= 0.2}
+              'behind the near plane (forward view)': camera_depths(params, forward_view, first_w2c) <= 0.2}
     print(f"{what} partition of {P} rows: " + ", ".join(f"{k} {int(v.sum())} ({100 * v.mean():.1f} %)" for k, v in groups.items()))
     for k, v in groups.items():
         assert v.mean() >= min_frac, (what, k, int(v.sum()))
