@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 11       /* 11: SplatAdamMap.one_minus_beta1 / _beta2 (torch's 1 - beta, formed in double);
+#define SPLAT_ABI_VERSION 12       /* 12: evaluation metrics (SplatEvalConfig, SplatEvalWorkspace, splat_eval_workspace_layout / _bind, splat_eval_metrics, splat_iter_eval);
+                                      11: SplatAdamMap.one_minus_beta1 / _beta2 (torch's 1 - beta, formed in double);
                                       10: group binning behind the reference API (SplatState.group_* in splat_preprocess_forward / splat_render_forward,
                                       SPLAT_LAYOUT_GROUPS), SplatState.tile_recs (staged records handed from the forward to the backward composite), SplatCamera.bg == NULL = black, SplatGrads.flags (SPLAT_GRADS_UPSTREAM_SCALE), SplatState.status_host,
                                       SplatState.tile_order entries hold tile + 1 (a zeroed buffer is the natural order) and are laid out on request (SPLAT_LAYOUT_TILE_ORDER),
@@ -654,6 +655,64 @@ int splat_map_densify_select(SplatMapStore *store, const SplatDensifyArgs *args,
  * log_scales = log(exp(log_scales) / (0.8 n)).  Adam moments and max_2D_radius / means2D_gradient_accum / denom of the new rows
  * are zero.  The caller then sets map.P = counts[0]; the split originals are removed with splat_map_prune(to_remove = flags). */
 int splat_map_duplicate(SplatMapStore *store, const SplatDensifyArgs *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Evaluation of a finished run (the per-frame part of eval(), /root/reference/utils/eval_helpers.py:408-623): PSNR, depth
+ * "RMSE", depth L1 and MS-SSIM of one rendered frame against its RGB-D frame, as ONE ROW OF EIGHT DOUBLES in device memory.
+ * Nothing is read back: a caller evaluates frame after frame into a table and reads the table once.
+ *   valid = gt_depth > 0, presence = silhouette > sil_thres;
+ *   sil_mask = 1 (the reference's `mapping_iters == 0 and not add_new_gaussians` branch): images are weighted by presence * valid
+ *     and the depth difference by presence; sil_mask = 0: images by valid;
+ *   PSNR = mean over r, g, b of 20 log10(1 / sqrt(mean over ALL H * W pixels of (weighted_im - weighted_gt)^2)) (calc_psnr,
+ *     /root/reference/utils/slam_external.py:49-51: masked pixels count as zeros);
+ *   depth RMSE = sum(sqrt(d^2) * valid) / sum(valid) -- the reference takes the root per pixel, so its "RMSE" IS the L1 below; both
+ *     slots are kept, as both of its files are;
+ *   MS-SSIM = pytorch_msssim.ms_ssim(weighted_im, weighted_gt, data_range = 1): 11-tap sigma-1.5 window without padding, five
+ *     levels, 2 x 2 average pooling between them (an odd dimension is zero-padded in front), weights 0.0448 0.2856 0.3001 0.2363
+ *     0.1333 (restated in splatam_amd/slam.py `ms_ssim`; upstream asserts min(H, W) > 160, and so does this).
+ * A count of zero valid pixels or a NaN in a plane gives what the torch expressions give (inf / NaN); no special cases.
+ * LPIPS is not computed (it needs network weights this library does not carry).
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SPLAT_EVAL_ROW 8         /* doubles per output row */
+#define SPLAT_EVAL_PSNR 0
+#define SPLAT_EVAL_DEPTH_RMSE 1
+#define SPLAT_EVAL_DEPTH_L1 2
+#define SPLAT_EVAL_MS_SSIM 3     /* NaN when cfg->ms_ssim is 0 */
+#define SPLAT_EVAL_VALID 4       /* number of pixels with gt_depth > 0 */
+#define SPLAT_EVAL_FLAGGED 5     /* != 0: the render behind this row ran on truncated / unsorted lists (st.status OVERFLOW or STALE_HINT):
+                                    re-size the lists and evaluate the frame again (splat_iter_eval only; 0 from splat_eval_metrics) */
+#define SPLAT_EVAL_LEVELS 5
+#define SPLAT_EVAL_SUMS 40       /* doubles per copy of SplatEvalWorkspace.sums: [0..2] squared error per channel, [3] depth term, [4] valid count,
+                                    [8 + 6 level + 2 channel] sum of the contrast-structure term, [... + 1] sum of ssim over the level's window positions */
+
+typedef struct SplatEvalConfig {
+    float sil_thres;
+    int32_t sil_mask;            /* 1: presence * valid weighting (see above) */
+    int32_t ms_ssim;             /* 0: PSNR and depth only (one kernel less per level; any frame size) */
+} SplatEvalConfig;
+
+/* The evaluation's own scratch (it borrows nothing of SplatIterWorkspace: map edits and iterations own ssim_maps / sums). */
+typedef struct SplatEvalWorkspace {
+    float *pyramid;              /* pooled weighted_im and weighted_gt of levels 1..4, three channels each (NULL without MS-SSIM) */
+    double *sums;                /* [SPLAT_ITER_SUM_COPIES + 1][SPLAT_EVAL_SUMS]: the copies the workgroups add into -- zero before the first call,
+                                    left zeroed by every call --, then one row the finish kernel leaves the frame's TOTALS in (a report
+                                    for tests and tools: the level means are totals / window positions) */
+} SplatEvalWorkspace;
+#define SPLAT_EVAL_LAYOUT_MS_SSIM 1 /* splat_eval_workspace_layout: with the pyramid (needs min(width, height) > 160) */
+/* Arrays "pyramid" (with SPLAT_EVAL_LAYOUT_MS_SSIM) and "sums" in the SplatArrayInfo convention; returns their number or -SPLAT_E_INVALID. */
+int splat_eval_workspace_layout(int32_t width, int32_t height, int32_t flags, SplatArrayInfo *out, int32_t max_entries, size_t *total_bytes);
+int splat_eval_workspace_bind(SplatEvalWorkspace *ews, void *slab, const SplatArrayInfo *arrays, int32_t n);
+
+/* The metric kernels alone, on caller-supplied planes (a render of the drop-in rasterizer, or of anything else): rgb [3][H][W],
+ * depth [H][W], silhouette [H][W] (may be NULL with sil_mask 0), gt_im [3][H][W], gt_depth [H][W]; out_row: SPLAT_EVAL_ROW device doubles.
+ * At most six launches (five levels + finish), two without MS-SSIM.  SPLAT_E_INVALID with cfg->ms_ssim when min(width, height) <= 160. */
+int splat_eval_metrics(int32_t width, int32_t height, const float *rgb, const float *depth, const float *silhouette, const float *gt_im,
+                       const float *gt_depth, const SplatEvalConfig *cfg, const SplatEvalWorkspace *ews, double *out_row, void *stream);
+
+/* splat_iter_render of `map` at pose frame->time_idx followed by splat_eval_metrics of ws->out6 against frame->im / frame->depth;
+ * the render's capacity status goes into out_row[SPLAT_EVAL_FLAGGED].  Leaves the workspace as splat_iter_render leaves it. */
+int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame, const SplatEvalConfig *cfg,
+                    SplatIterWorkspace *ws, const SplatEvalWorkspace *ews, double *out_row, void *stream);
 
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup

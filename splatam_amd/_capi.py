@@ -18,7 +18,7 @@ SPLAT_MAX_CHANNELS = 8
 SPLAT_GRAD_STRIDE = 16
 SPLAT_COUNTER_STRIDE = 32
 SPLAT_GROUP_TILES = 2
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -116,8 +116,17 @@ class SplatArrayInfo(C.Structure):
     _fields_ = [("name", C.c_char_p), ("bytes", C.c_size_t), ("offset", C.c_size_t), ("zero_init", C.c_int32)]
 
 
+class SplatEvalConfig(C.Structure):
+    _fields_ = [("sil_thres", C.c_float), ("sil_mask", C.c_int32), ("ms_ssim", C.c_int32)]
+
+
+class SplatEvalWorkspace(C.Structure):
+    _fields_ = [("pyramid", _fp), ("sums", _fp)]
+
+
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatIterWorkspace,
-                    SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo)
+                    SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
+                    SplatEvalConfig, SplatEvalWorkspace)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -137,6 +146,8 @@ SPLAT_STATUS_INSTANCES, SPLAT_STATUS_OVERFLOW, SPLAT_STATUS_LONGEST, SPLAT_STATU
 SPLAT_REPORT_DROT, SPLAT_REPORT_DTRANS, SPLAT_REPORT_LOSS, SPLAT_REPORT_SUMS = 0, 4, 7, 8
 SPLAT_REPORT_FLAG, SPLAT_REPORT_MEDIAN, SPLAT_REPORT_DEPTH_TERM, SPLAT_REPORT_IM_TERM = 12, 13, 14, 15
 SPLAT_REPORT_STATUS, SPLAT_REPORT_FLAGGED, SPLAT_REPORT_SKIPPED = 16, 20, 21
+SPLAT_EVAL_ROW, SPLAT_EVAL_LEVELS, SPLAT_EVAL_SUMS, SPLAT_EVAL_LAYOUT_MS_SSIM = 8, 5, 40, 1
+SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED = 0, 1, 2, 3, 4, 5
 
 
 def lists_sorted_by_composite(max_list_hint: int) -> bool:
@@ -158,6 +169,7 @@ EXPORTS = (
     "splat_iter_means2d_accumulate", "splat_map_densify_select", "splat_map_duplicate",
     "splat_workspace_bytes", "splat_state_layout", "splat_state_bind", "splat_iter_workspace_layout", "splat_iter_workspace_bind",
     "splat_iter_workspace_bytes",
+    "splat_eval_workspace_layout", "splat_eval_workspace_bind", "splat_eval_metrics", "splat_iter_eval",
 )
 
 _lib = None
@@ -249,6 +261,15 @@ def lib():
     L.splat_iter_workspace_bind.argtypes = [C.POINTER(SplatIterWorkspace), _fp, info, C.c_int32, C.c_int64, C.c_int32]
     L.splat_iter_workspace_bytes.restype = C.c_size_t
     L.splat_iter_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32]
+    L.splat_eval_workspace_layout.restype = C.c_int
+    L.splat_eval_workspace_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, info, C.c_int32, C.POINTER(C.c_size_t)]
+    L.splat_eval_workspace_bind.restype = C.c_int
+    L.splat_eval_workspace_bind.argtypes = [C.POINTER(SplatEvalWorkspace), _fp, info, C.c_int32]
+    L.splat_eval_metrics.restype = C.c_int
+    L.splat_eval_metrics.argtypes = [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.POINTER(SplatEvalConfig), C.POINTER(SplatEvalWorkspace), _fp, _fp]
+    L.splat_iter_eval.restype = C.c_int
+    L.splat_iter_eval.argtypes = [cam, C.POINTER(SplatMap), C.POINTER(SplatFrameData), C.POINTER(SplatEvalConfig),
+                                  C.POINTER(SplatIterWorkspace), C.POINTER(SplatEvalWorkspace), _fp, _fp]
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int
@@ -309,6 +330,18 @@ def iter_workspace_layout(P, width, height, capacity, group_stride, flags):
     n = lib().splat_iter_workspace_layout(P, width, height, capacity, group_stride, flags, arrays, SPLAT_LAYOUT_MAX_ARRAYS, C.byref(total))
     if n < 0 or n > SPLAT_LAYOUT_MAX_ARRAYS:
         raise RuntimeError(f"splat_iter_workspace_layout({P}, {width}, {height}, {capacity}, {group_stride}, {flags}) failed: {n}")
+    return Layout(arrays, n, int(total.value))
+
+
+def eval_workspace_layout(width, height, ms_ssim=True):
+    """The evaluation's scratch (SplatEvalWorkspace): ``pyramid`` (with MS-SSIM) and ``sums``.  Raises for a frame MS-SSIM cannot
+    take (min(width, height) <= 160: four poolings must leave room for the 11-tap window)."""
+    arrays = (SplatArrayInfo * 4)()
+    total = C.c_size_t(0)
+    n = lib().splat_eval_workspace_layout(int(width), int(height), SPLAT_EVAL_LAYOUT_MS_SSIM if ms_ssim else 0, arrays, 4, C.byref(total))
+    if n < 0 or n > 4:
+        raise RuntimeError(f"splat_eval_workspace_layout({width}, {height}, ms_ssim={bool(ms_ssim)}) failed: "
+                           f"{lib().splat_error_string(-n).decode()} (MS-SSIM needs min(width, height) > 160)")
     return Layout(arrays, n, int(total.value))
 
 

@@ -59,6 +59,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatMap); SPLAT_SIZEOF_CASE(SplatFrameData); SPLAT_SIZEOF_CASE(SplatLossConfig); SPLAT_SIZEOF_CASE(SplatIterWorkspace);
     SPLAT_SIZEOF_CASE(SplatAdamMap); SPLAT_SIZEOF_CASE(SplatPoseAdam); SPLAT_SIZEOF_CASE(SplatMapStore); SPLAT_SIZEOF_CASE(SplatAddArgs);
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
+    SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -323,6 +324,30 @@ int splat_iter_render(const SplatCamera *cam, const SplatMap *map, const SplatFr
     return check(launch_iter_render(*cam, *map, *frame, *ws, (hipStream_t)stream));
 }
 
+static bool valid_eval(int32_t width, int32_t height, const SplatEvalConfig *cfg, const SplatEvalWorkspace *ews, const double *out_row) {
+    if (width <= 0 || height <= 0 || (long long)width * height > 0x3fffffffLL || !cfg || !ews || !ews->sums || !out_row) return false;
+    // (pytorch_msssim asserts the same: four poolings must leave room for the 11-tap window)
+    if (cfg->ms_ssim && ((width < height ? width : height) <= 160 || !ews->pyramid)) return false;
+    return true;
+}
+
+int splat_eval_metrics(int32_t width, int32_t height, const float *rgb, const float *depth, const float *silhouette, const float *gt_im,
+                       const float *gt_depth, const SplatEvalConfig *cfg, const SplatEvalWorkspace *ews, double *out_row, void *stream) {
+    if (!valid_eval(width, height, cfg, ews, out_row) || !rgb || !depth || !gt_im || !gt_depth || (cfg->sil_mask && !silhouette)) return SPLAT_E_INVALID;
+    return check(launch_eval_metrics(width, height, rgb, depth, silhouette, gt_im, gt_depth, *cfg, *ews, nullptr, out_row, (hipStream_t)stream));
+}
+
+int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame, const SplatEvalConfig *cfg,
+                    SplatIterWorkspace *ws, const SplatEvalWorkspace *ews, double *out_row, void *stream) {
+    if (!valid_iter_common(cam, map, frame, ws) || !frame->im || !frame->depth) return SPLAT_E_INVALID;
+    if (!valid_eval(cam->image_width, cam->image_height, cfg, ews, out_row)) return SPLAT_E_INVALID;
+    const hipError_t e = launch_iter_render(*cam, *map, *frame, *ws, (hipStream_t)stream);
+    if (e != hipSuccess) return SPLAT_E_LAUNCH;
+    const size_t HW = (size_t)cam->image_width * (size_t)cam->image_height;
+    return check(launch_eval_metrics(cam->image_width, cam->image_height, ws->out6, ws->out6 + 3 * HW, ws->out6 + 4 * HW, frame->im, frame->depth,
+                                     *cfg, *ews, ws->st.status, out_row, (hipStream_t)stream));
+}
+
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }
 
 static bool valid_store(const SplatMapStore *st) {
@@ -563,6 +588,27 @@ int splat_iter_workspace_bind(SplatIterWorkspace *ws, void *slab, const SplatArr
 #undef BIND
     }
     ws->st.group_stride = ws->st.group_recs ? group_stride : 0;
+    return SPLAT_OK;
+}
+
+int splat_eval_workspace_layout(int32_t width, int32_t height, int32_t flags, SplatArrayInfo *out, int32_t max_entries, size_t *total_bytes) {
+    if (width <= 0 || height <= 0 || (long long)width * height > 0x3fffffffLL) return -SPLAT_E_INVALID;
+    if ((flags & SPLAT_EVAL_LAYOUT_MS_SSIM) && (width < height ? width : height) <= 160) return -SPLAT_E_INVALID;
+    LayoutWriter w{out, max_entries};
+    if (flags & SPLAT_EVAL_LAYOUT_MS_SSIM) w.add("pyramid", eval_pyramid_bytes(width, height), 0);
+    w.add("sums", 8 * (size_t)(SPLAT_ITER_SUM_COPIES + 1) * SPLAT_EVAL_SUMS, 1);
+    if (total_bytes) *total_bytes = (w.offset + SPLAT_SLAB_ALIGN - 1) / SPLAT_SLAB_ALIGN * SPLAT_SLAB_ALIGN;
+    return w.n;
+}
+
+int splat_eval_workspace_bind(SplatEvalWorkspace *ews, void *slab, const SplatArrayInfo *arrays, int32_t n) {
+    if (!ews || !slab || !arrays || n < 0 || ((uintptr_t)slab % SPLAT_SLAB_ALIGN) != 0) return SPLAT_E_INVALID;
+    char *base = static_cast<char *>(slab);
+    for (int32_t i = 0; i < n; ++i) {
+        if (!arrays[i].name) return SPLAT_E_INVALID;
+        if (strcmp(arrays[i].name, "pyramid") == 0) ews->pyramid = reinterpret_cast<float *>(base + arrays[i].offset);
+        if (strcmp(arrays[i].name, "sums") == 0) ews->sums = reinterpret_cast<double *>(base + arrays[i].offset);
+    }
     return SPLAT_OK;
 }
 

@@ -83,6 +83,11 @@ hipError_t launch_iter_adam_pose(const SplatMap &map, int time_idx, const float 
                                  float eps, float bc2_sqrt, float ss_rot, float ss_trans, hipStream_t s);
 hipError_t launch_iter_render(const SplatCamera &cam, const SplatMap &map, const SplatFrameData &frame, SplatIterWorkspace &ws,
                               hipStream_t s);
+// evalmetrics.hip: the metric kernels on five planes; status: the SplatState.status words of the render behind them, or NULL
+hipError_t launch_eval_metrics(int W, int H, const float *rgb, const float *depth, const float *sil, const float *gt_im,
+                               const float *gt_depth, const SplatEvalConfig &cfg, const SplatEvalWorkspace &ews, const int32_t *status,
+                               double *out_row, hipStream_t s);
+size_t eval_pyramid_bytes(int W, int H);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

@@ -326,6 +326,39 @@ class FusedEngine:
                         "splat_iter_render")
         return self.rendered()
 
+    # ------------------------------------------------------------------ evaluation (csrc/evalmetrics.hip; nothing is read here)
+    def evaluate_frame(self, curr_data, time_idx, out_row, sil_thres, sil_mask=False, ms_ssim=True):
+        """Render the map from pose ``time_idx`` and write the frame's metrics against ``curr_data['im']`` / ``['depth']`` into
+        ``out_row`` (8 float64 on the device: psnr, depth_rmse, depth_l1, ms_ssim -- NaN when off --, valid count, != 0 when the
+        render ran on truncated lists, 2 spare; include/splat_hip.h SPLAT_EVAL_*).  Enqueues only: rows are read by the caller, as a
+        table, when it pleases.  The planes stay in ``rendered()``."""
+        self._check_cam(curr_data)
+        _check_eval_row(out_row, self.dev)
+        fr = _capi.SplatFrameData()
+        im, depth = curr_data['im'], curr_data['depth']
+        for name, t, c in (("im", im, 3), ("depth", depth, 1)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, self.H, self.W)):
+                raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {self.H}, {self.W}] on {self.dev}")
+        w2c = self._frame_w2c(curr_data)
+        if not (im.is_contiguous() and depth.is_contiguous()):
+            im, depth = im.contiguous(), depth.contiguous()
+        fr.im, fr.depth, fr.w2c, fr.time_idx = im.data_ptr(), depth.data_ptr(), w2c.data_ptr(), int(time_idx)
+        self._frame_keep = (im, depth, w2c)
+        self._tile_rows, self._stats_partial = None, False
+        self._select_order(int(time_idx))
+        ews, _ = eval_workspace(self.dev, self.W, self.H, ms_ssim)
+        cfg = _eval_config(sil_thres, sil_mask, ms_ssim)
+        ws = self._workspace(False, with_ssim=False)
+        ws.max_2D_radius = None
+        m = self._map_struct()
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_iter_eval(C.byref(self._cam), C.byref(m), C.byref(fr), C.byref(cfg), C.byref(ws), C.byref(ews),
+                                               out_row.data_ptr(), self._stream()), "splat_iter_eval")
+
+    def evaluate_metrics(self, rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True):
+        """``evaluate_metrics`` of this module (the metric kernels alone, on caller-supplied planes of any size)."""
+        return evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
+
     def lists_known(self):
         """The per-tile list statistics (bucket stride, longest list) are usable for the map as it is: an edit kept them (_set_rows)."""
         return self.tile_stride > 0 and self.max_list_hint > 0
@@ -1016,3 +1049,62 @@ class FusedEngine:
         """(im[3,H,W], depth[1,H,W], silhouette[H,W], depth_sq[1,H,W]) of the last iteration."""
         o = self.buf['out6']
         return o[0:3], o[3:4], o[4], o[5:6]
+
+
+# ---------------------------------------------------------------------- evaluation metrics on planes (csrc/evalmetrics.hip)
+_eval_bufs: dict = {}
+
+
+def eval_workspace(dev, width, height, ms_ssim):
+    """(SplatEvalWorkspace, its ``sums`` tensor) for a device and frame size, allocated on first use and kept (6.5 MB at 1200 x 680).
+    The evaluation owns its scratch: an engine's ``buf['sums']`` / ``buf['ssim_maps']`` belong to its iterations.  ``sums`` is
+    [SPLAT_ITER_SUM_COPIES + 1][SPLAT_EVAL_SUMS]: the copies (zero between calls) and, last, the totals of the latest frame."""
+    key = (str(dev), int(width), int(height), bool(ms_ssim))
+    if key not in _eval_bufs:
+        lay = _capi.eval_workspace_layout(width, height, ms_ssim)
+        pyramid = torch.empty(lay.bytes["pyramid"] // 4, dtype=torch.float32, device=dev) if ms_ssim else None
+        sums = torch.zeros(lay.bytes["sums"] // 8, dtype=torch.float64, device=dev).view(-1, _capi.SPLAT_EVAL_SUMS)
+        _eval_bufs[key] = (pyramid, sums)
+    pyramid, sums = _eval_bufs[key]
+    ews = _capi.SplatEvalWorkspace()
+    ews.pyramid, ews.sums = (pyramid.data_ptr() if pyramid is not None else None), sums.data_ptr()
+    return ews, sums
+
+
+def _eval_config(sil_thres, sil_mask, ms_ssim):
+    c = _capi.SplatEvalConfig()
+    c.sil_thres, c.sil_mask, c.ms_ssim = float(sil_thres), int(bool(sil_mask)), int(bool(ms_ssim))
+    return c
+
+
+def _check_eval_row(out_row, dev):
+    if not (isinstance(out_row, torch.Tensor) and out_row.dtype == torch.float64 and out_row.device == dev
+            and out_row.is_contiguous() and out_row.numel() >= _capi.SPLAT_EVAL_ROW):
+        raise RuntimeError(f"out_row must be a contiguous float64 tensor of {_capi.SPLAT_EVAL_ROW} elements on {dev}")
+
+
+def evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True):
+    """The metric kernels alone: ``rgb`` [3,H,W], ``depth`` [1,H,W] or [H,W], ``sil`` [H,W] (the two renders of the drop-in
+    rasterizer, say) against ``curr_data['im']`` / ``['depth']``, all float32 on one CUDA/HIP device; the row
+    (include/splat_hip.h SPLAT_EVAL_*; slot 5 is 0) goes to ``out_row`` (8 float64 on that device).  Enqueues on the current
+    stream and reads nothing.  Returns the evaluation's sums buffer, whose last row holds the frame's totals once the kernels have
+    run (level means = totals / window positions).  MS-SSIM needs min(H, W) > 160 (RuntimeError otherwise, before any launch)."""
+    if not isinstance(rgb, torch.Tensor) or rgb.device.type != "cuda":
+        raise RuntimeError("evaluate_metrics needs CUDA/HIP tensors; the HIP library has no CPU path")
+    dev = rgb.device
+    _check_eval_row(out_row, dev)
+    H, W = int(rgb.shape[-2]), int(rgb.shape[-1])
+    planes = []
+    for name, t, n in (("rgb", rgb, 3), ("depth", depth, 1), ("sil", sil, 1), ("curr_data['im']", curr_data['im'], 3),
+                       ("curr_data['depth']", curr_data['depth'], 1)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and t.numel() == n * H * W):
+            got = f"{t.dtype}, {tuple(t.shape)}, {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise RuntimeError(f"{name} must be a float32 tensor of {n} x {H} x {W} elements on {dev} (got {got})")
+        planes.append(t if t.is_contiguous() else t.contiguous())
+    ews, sums = eval_workspace(dev, W, H, ms_ssim)
+    cfg = _eval_config(sil_thres, sil_mask, ms_ssim)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_eval_metrics(W, H, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
+                                                   planes[3].data_ptr(), planes[4].data_ptr(), C.byref(cfg), C.byref(ews),
+                                                   out_row.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "splat_eval_metrics")
+    return sums

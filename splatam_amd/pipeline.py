@@ -263,7 +263,7 @@ class _PhaseTimer:
         return {k: round(v, 3) for k, v in done.items()}
 
 
-def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacity=None, verbose=False):
+def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacity=None, verbose=False, evaluate=None):
     """Runs the SplaTAM frame loop over ``dataset``; returns ``(params, variables, stats)`` with
     ``stats = {keyframe_time_indices, tracking_iters, mapping_iters, tracking_s, mapping_s, mapping_loop_s, num_gaussians,
     redone_iterations, phase_ms}`` (``mapping_loop_s``: the iterations alone, where the reference's own mapping timer runs,
@@ -290,7 +290,13 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
       * mapping: every iteration draws ``world`` keyframe views instead of one (the same random stream on every rank, the
         reference's one-random-keyframe-per-iteration rule /root/reference/scripts/splatam.py:831-845 applied ``world`` times),
         rank r renders the r-th, ONE gradient all-reduce (mean) follows, and every rank takes the identical Adam step;
-      * after every edit of the map (densification, pruning) the row counts of the replicas are compared (all-reduce of min / max)."""
+      * after every edit of the map (densification, pruning) the row counts of the replicas are compared (all-reduce of min / max).
+
+    ``evaluate``: ``None`` (default) -- the loop ends where it always did; a dict with any of ``eval_every`` (1), ``eval_dir`` (None),
+    ``ms_ssim`` (True) -- the run's last act is the reference's (scripts/splatam.py:961-971): ``evaluation.evaluate`` on the final
+    parameters with the mapping configuration's ``sil_thres`` / ``num_iters`` / ``add_new_gaussians``, returned as ``stats['eval']``
+    (PSNR, depth L1, MS-SSIM per evaluated frame, ATE; LPIPS is not computed).  The fused engine evaluates on its own map, the other
+    engines' parameters get a throw-away ``FusedEngine``; with several ranks rank 0 evaluates and the dict is broadcast."""
     from . import dist as sdist
     if engine not in ("fused", "dropin", "plugin", "plugin_map_edits"):
         raise ValueError(engine)
@@ -438,6 +444,21 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
             stats['plugin'] = plugin.session_stats()
             installed.uninstall()
     stats['keyframe_time_indices'] = keyframe_time_indices
+    if evaluate is not None:
+        from . import evaluation
+        opts = dict(evaluate)
+        unknown = set(opts) - {'eval_every', 'eval_dir', 'ms_ssim'}
+        if unknown:
+            raise ValueError(f"evaluate: unknown keys {sorted(unknown)} (eval_every, eval_dir, ms_ssim)")
+        box = [None]
+        if rank == 0:
+            with torch.no_grad():
+                box[0] = evaluation.evaluate(dataset, params, num_frames, mcfg['sil_thres'], mcfg['num_iters'], mcfg['add_new_gaussians'],
+                                             engine=eng if fused else None, **opts)
+        if world > 1:
+            import torch.distributed as tdist
+            tdist.broadcast_object_list(box, src=0)
+        stats['eval'] = box[0]
     return params, variables, stats
 
 

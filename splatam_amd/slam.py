@@ -26,6 +26,8 @@ here                                           reference
 ``remove_points`` / ``prune_gaussians``        utils/slam_external.py:139-188
 ``accumulate_mean2d_gradient`` / ``densify``   utils/slam_external.py:100-104 / 191-240 (gradient-based densification of the
                                                gaussian_splatting / post_splatam_opt configs; torch formulation only)
+``eval_frame_metrics`` / ``ms_ssim``           utils/eval_helpers.py:466-505 (per-frame part of ``eval``) / pytorch_msssim.ms_ssim
+``evaluate_ate``                               utils/eval_helpers.py:23-77 (``align`` + ``evaluate_ate``)
 =============================================  =============================================
 
 Differences are host-side only and do not change results: masked sums are
@@ -554,6 +556,105 @@ def _reset_opacities(params, optimizer):
 REPLICA_PRUNE = dict(start_after=0, remove_big_after=0, stop_after=20, prune_every=20, removal_opacity_threshold=0.005,
                      final_removal_opacity_threshold=0.005, reset_opacities=False, reset_opacities_every=500)
 """/root/reference/configs/replica/splatam.py:102-111."""
+
+
+# --------------------------------------------------------------------------
+# evaluation of a finished run (the parity target of csrc/evalmetrics.hip)
+# --------------------------------------------------------------------------
+
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def ms_ssim(X, Y):
+    """Multi-scale SSIM of two [1,3,H,W] images in [0, 1] as ``pytorch_msssim.ms_ssim(X, Y, data_range=1.0)`` computes it
+    (the package is not vendored; this restatement is the specification the kernels are held to): an 11-tap sigma-1.5 window
+    applied separably WITHOUT padding, five levels, between levels a 2x2 average pooling that zero-pads an odd dimension on both
+    sides (so its windows are shifted by one against the even case and n becomes n // 2 + 1), the contrast-structure mean of
+    levels 0..3 and the ssim mean of level 4, each clamped at 0, raised to the level weights, multiplied, averaged over channels.
+    Works in the dtype of ``X``.  Like the package it refuses min(H, W) <= 160."""
+    if X.shape != Y.shape or X.dim() != 4:
+        raise ValueError(f"ms_ssim takes two [N,C,H,W] images of one shape (got {tuple(X.shape)}, {tuple(Y.shape)})")
+    if min(X.shape[-2:]) <= (11 - 1) * 2 ** 4:
+        raise ValueError(f"ms_ssim needs min(H, W) > 160 (four poolings must leave room for the 11-tap window); got {tuple(X.shape[-2:])}")
+    C = X.shape[1]
+    c = torch.arange(11, dtype=X.dtype, device=X.device) - 5
+    g = torch.exp(-c ** 2 / (2 * 1.5 ** 2))
+    g = g / g.sum()
+
+    def blur(x):
+        x = F.conv2d(x, g.view(1, 1, -1, 1).repeat(C, 1, 1, 1), groups=C)
+        return F.conv2d(x, g.view(1, 1, 1, -1).repeat(C, 1, 1, 1), groups=C)
+
+    vals = []
+    for level in range(5):
+        mu1, mu2 = blur(X), blur(Y)
+        s1, s2, s12 = blur(X * X) - mu1 * mu1, blur(Y * Y) - mu2 * mu2, blur(X * Y) - mu1 * mu2
+        cs = (2 * s12 + 0.03 ** 2) / (s1 + s2 + 0.03 ** 2)
+        if level < 4:
+            vals.append(torch.relu(cs.flatten(2).mean(-1)))
+            pad = [d % 2 for d in X.shape[2:]]
+            X, Y = F.avg_pool2d(X, 2, padding=pad), F.avg_pool2d(Y, 2, padding=pad)
+        else:
+            ss = (2 * mu1 * mu2 + 0.01 ** 2) / (mu1 * mu1 + mu2 * mu2 + 0.01 ** 2) * cs
+            vals.append(torch.relu(ss.flatten(2).mean(-1)))
+    w = torch.tensor(MS_SSIM_WEIGHTS, dtype=X.dtype, device=X.device).view(-1, 1, 1)
+    return torch.prod(torch.stack(vals) ** w, 0).mean()
+
+
+def calc_psnr(img1, img2):
+    """Per channel: the mean runs over ALL pixels (masked ones count as zeros)."""
+    mse = ((img1 - img2) ** 2).view(img1.shape[0], -1).mean(1, keepdim=True)
+    return 20 * torch.log10(1.0 / torch.sqrt(mse))
+
+
+def eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=True):
+    """The numbers the reference's ``eval`` forms for one frame from its two renders: ``im`` [3,H,W] (colour render),
+    ``depth_sil`` [>=2,H,W] (depth, silhouette).  ``sil_mask``: the reference's ``mapping_iters == 0 and not add_new_gaussians``
+    branch -- images weighted by presence * valid, depth difference by presence; otherwise images by valid.
+    Returns a dict of 0-d tensors: psnr, depth_rmse, depth_l1, ms_ssim (None when not asked for), valid.
+
+    ``depth_rmse`` keeps the reference's quirk: it takes the square root PER PIXEL (sqrt(d^2) = |d|) before summing, so the
+    number it reports as depth RMSE equals ``depth_l1`` by construction."""
+    valid = curr_data['depth'] > 0
+    rastered_depth = depth_sil[0:1] * valid
+    presence = depth_sil[1] > sil_thres
+    if sil_mask:
+        weighted_im, weighted_gt = im * presence * valid, curr_data['im'] * presence * valid
+        diff = (rastered_depth - curr_data['depth']) * presence
+    else:
+        weighted_im, weighted_gt = im * valid, curr_data['im'] * valid
+        diff = rastered_depth - curr_data['depth']
+    out = {'psnr': calc_psnr(weighted_im, weighted_gt).mean(),
+           'depth_rmse': (torch.sqrt(diff ** 2) * valid).sum() / valid.sum(),
+           'depth_l1': (torch.abs(diff) * valid).sum() / valid.sum(),
+           'ms_ssim': ms_ssim(weighted_im.unsqueeze(0), weighted_gt.unsqueeze(0)) if with_ms_ssim else None,
+           'valid': valid.sum()}
+    return out
+
+
+def align_trajectories(model, data):
+    """Horn's closed-form rigid alignment of two 3xn point sets (numpy, float64): rotation [3,3], translation [3,1] taking
+    ``model`` onto ``data``, and the per-point distance after alignment [n]."""
+    import numpy as np
+    model, data = np.asarray(model, dtype=np.float64), np.asarray(data, dtype=np.float64)
+    mc, dc = model.mean(1, keepdims=True), data.mean(1, keepdims=True)
+    Wm = (model - mc) @ (data - dc).T
+    U, _, Vh = np.linalg.svd(Wm.T)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vh) < 0:
+        S[2, 2] = -1
+    rot = U @ S @ Vh
+    trans = dc - rot @ mc
+    err = rot @ model + trans - data
+    return rot, trans, np.sqrt((err * err).sum(0))
+
+
+def evaluate_ate(gt_w2c_list, est_w2c_list):
+    """The reference's trajectory error: the TRANSLATION COLUMNS of the 4x4 world-to-camera matrices (not camera centres) of the
+    two lists are aligned rigidly and the MEAN distance is returned -- under the name "ATE RMSE" upstream; both kept."""
+    gt = torch.stack([m[:3, 3] for m in gt_w2c_list]).detach().cpu().numpy().T
+    est = torch.stack([m[:3, 3] for m in est_w2c_list]).detach().cpu().numpy().T
+    return float(align_trajectories(gt, est)[2].mean())
 
 
 # --------------------------------------------------------------------------
