@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 12       /* 12: evaluation metrics (SplatEvalConfig, SplatEvalWorkspace, splat_eval_workspace_layout / _bind, splat_eval_metrics, splat_iter_eval);
+#define SPLAT_ABI_VERSION 13       /* 13: frame preparation (splat_frame_prepare);
+                                      12: evaluation metrics (SplatEvalConfig, SplatEvalWorkspace, splat_eval_workspace_layout / _bind, splat_eval_metrics, splat_iter_eval);
                                       11: SplatAdamMap.one_minus_beta1 / _beta2 (torch's 1 - beta, formed in double);
                                       10: group binning behind the reference API (SplatState.group_* in splat_preprocess_forward / splat_render_forward,
                                       SPLAT_LAYOUT_GROUPS), SplatState.tile_recs (staged records handed from the forward to the backward composite), SplatCamera.bg == NULL = black, SplatGrads.flags (SPLAT_GRADS_UPSTREAM_SCALE), SplatState.status_host,
@@ -713,6 +714,17 @@ int splat_eval_metrics(int32_t width, int32_t height, const float *rgb, const fl
  * the render's capacity status goes into out_row[SPLAT_EVAL_FLAGGED].  Leaves the workspace as splat_iter_render leaves it. */
 int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame, const SplatEvalConfig *cfg,
                     SplatIterWorkspace *ws, const SplatEvalWorkspace *ews, double *out_row, void *stream);
+
+/* Frame preparation: a frame as a dataset hands it over -- color_hwc [src_h][src_w][3] in 0..255, depth_hw [src_h][src_w] (the
+ * trailing 1 of [H][W][1] changes nothing) -- to the planes every other entry takes: im_out [3][dst_h][dst_w] in 0..1 (one float32
+ * division by 255), depth_out [dst_h][dst_w].  With dst == src this is the layout change alone.  Otherwise colour is resampled
+ * bilinearly on the 0..255 values with pixel centres at half-integers (per axis f = (d + 0.5) * src / dst - 0.5, taps floor(f) and the
+ * next, clamped to the row with weight 0) and depth takes the nearest source pixel min(floor(d * (1 / (dst / src))), src - 1), the index
+ * evaluated in double: the documented rules of cv2.resize INTER_LINEAR / INTER_NEAREST, which the reference's datasets apply on the host
+ * (csrc/frame_math.h; restated, not checked against OpenCV itself).  One launch on `stream`, no allocation, nothing read back; the
+ * outputs may be views into larger buffers (16-byte stores are used only where width and alignment allow). */
+int splat_frame_prepare(int32_t src_w, int32_t src_h, const float *color_hwc, const float *depth_hw, int32_t dst_w, int32_t dst_h,
+                        float *im_out, float *depth_out, void *stream);
 
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup

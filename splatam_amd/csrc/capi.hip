@@ -348,6 +348,13 @@ int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFram
                                      *cfg, *ews, ws->st.status, out_row, (hipStream_t)stream));
 }
 
+int splat_frame_prepare(int32_t src_w, int32_t src_h, const float *color_hwc, const float *depth_hw, int32_t dst_w, int32_t dst_h,
+                        float *im_out, float *depth_out, void *stream) {
+    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || (long long)src_w * src_h > 0x3fffffffLL || (long long)dst_w * dst_h > 0x3fffffffLL
+        || !color_hwc || !depth_hw || !im_out || !depth_out) return SPLAT_E_INVALID;
+    return check(launch_frame_prepare(src_w, src_h, color_hwc, depth_hw, dst_w, dst_h, im_out, depth_out, (hipStream_t)stream));
+}
+
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }
 
 static bool valid_store(const SplatMapStore *st) {

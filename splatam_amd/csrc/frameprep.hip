@@ -1,0 +1,62 @@
+// frameprep.hip -- a frame as a dataset hands it over (color[H][W][3] in 0..255, depth[H][W][1]) -> the planes the loop works on
+// (im[3][h][w] in 0..1, depth[1][h][w]) at the same or another size, in one streaming kernel: what the reference's datasets do on
+// the host with two cv2.resize calls and the loop with permute(2, 0, 1) / 255.  The arithmetic is frame_math.h's.
+//
+//   P1 frame_prepare_kernel<V>   one lane = V consecutive output x of one row (V = 4 when the width and the planes' alignment allow
+//                                16-byte stores, else 1): consecutive lanes take consecutive x, so the four plane stores coalesce;
+//                                the y taps and the nearest row are the same for a whole wave but for the row breaks.
+//                                No LDS, no atomics, plain stores.
+#include "splat_device.h"
+#include "frame_math.h"
+
+namespace splat {
+namespace {
+
+constexpr int kBlock = 256;
+
+template <int V>
+__global__ void __launch_bounds__(kBlock) frame_prepare_kernel(int sw, int sh, const float *__restrict__ color, const float *__restrict__ depth_in,
+                                                               int dw, int dh, float *__restrict__ im, float *__restrict__ depth_out) {
+    const int per_row = dw / V;                                     // (V divides dw: the launcher's choice)
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (long long)per_row * dh) return;
+    const int y = (int)(i / per_row), x0 = (int)(i % per_row) * V;
+    const FrameTap ty = frame_linear_tap(y, sh, dh);
+    const int ny = frame_nearest_index(y, sh, dh);
+    const float *row0 = color + (size_t)ty.s0 * sw * 3, *row1 = color + (size_t)ty.s1 * sw * 3;
+    const float *drow = depth_in + (size_t)ny * sw;
+    float out[4][V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const FrameTap tx = frame_linear_tap(x0 + v, sw, dw);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            out[c][v] = frame_colour(row0[3 * tx.s0 + c], row0[3 * tx.s1 + c], row1[3 * tx.s0 + c], row1[3 * tx.s1 + c], tx.w, ty.w);
+        out[3][v] = drow[frame_nearest_index(x0 + v, sw, dw)];
+    }
+    const size_t plane = (size_t)dw * dh, o = (size_t)y * dw + x0;
+    if (V == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *reinterpret_cast<float4 *>(im + c * plane + o) = make_float4(out[c][0], out[c][1], out[c][2], out[c][3]);
+        *reinterpret_cast<float4 *>(depth_out + o) = make_float4(out[3][0], out[3][1], out[3][2], out[3][3]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) im[c * plane + o] = out[c][0];
+        depth_out[o] = out[3][0];
+    }
+}
+
+}  // namespace
+
+hipError_t launch_frame_prepare(int sw, int sh, const float *color, const float *depth, int dw, int dh, float *im, float *depth_out,
+                                hipStream_t s) {
+    // 16-byte stores need every plane's every row start on 16 bytes: the width a multiple of 4 and both bases aligned
+    const bool vec = dw % 4 == 0 && (((uintptr_t)im | (uintptr_t)depth_out) & 15) == 0;
+    const long long items = (long long)(vec ? dw / 4 : dw) * dh;
+    const dim3 grid((unsigned)((items + kBlock - 1) / kBlock));
+    if (vec) hipLaunchKernelGGL(frame_prepare_kernel<4>, grid, dim3(kBlock), 0, s, sw, sh, color, depth, dw, dh, im, depth_out);
+    else hipLaunchKernelGGL(frame_prepare_kernel<1>, grid, dim3(kBlock), 0, s, sw, sh, color, depth, dw, dh, im, depth_out);
+    return hipGetLastError();
+}
+
+}  // namespace splat

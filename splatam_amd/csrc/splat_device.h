@@ -88,6 +88,9 @@ hipError_t launch_eval_metrics(int W, int H, const float *rgb, const float *dept
                                const float *gt_depth, const SplatEvalConfig &cfg, const SplatEvalWorkspace &ews, const int32_t *status,
                                double *out_row, hipStream_t s);
 size_t eval_pyramid_bytes(int W, int H);
+// frameprep.hip: a dataset frame (color[sh][sw][3] in 0..255, depth[sh][sw]) -> im[3][dh][dw] in 0..1, depth[dh][dw]
+hipError_t launch_frame_prepare(int sw, int sh, const float *color, const float *depth, int dw, int dh, float *im, float *depth_out,
+                                hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

@@ -46,7 +46,6 @@ class FusedEngine:
         self.L = _capi.lib()
         self.params = params
         self.variables = variables
-        self.cam_settings = cam
         dev = params['means3D'].device
         if dev.type != "cuda":
             raise RuntimeError("FusedEngine needs CUDA/HIP tensors; the HIP library has no CPU path")
@@ -67,19 +66,9 @@ class FusedEngine:
             track_max_radius = variables.get('max_2D_radius')
         P_alloc = self.Pcap
         self.num_frames = params['cam_unnorm_rots'].shape[-1]
-        H, W = int(cam.image_height), int(cam.image_width)
-        self.H, self.W = H, W
-        T = int(self.L.splat_num_tiles(W, H))
         f32, i32 = torch.float32, torch.int32
-        self.capacity = int(capacity) if capacity else 4 * P + 65536
         z = dict(device=dev)
         b = self.buf = {}
-        # every array of the iteration's workspace is sized by the LIBRARY (splat_iter_workspace_layout, include/splat_hip.h "Scratch
-        # layouts"); they are tensors of their own here because the per-Gaussian ones grow with the map (_grow_rows / rebind)
-        self._alloc_fixed(self._layout(P_alloc))
-        self._alloc_rows(self._layout(P_alloc))
-        GT = _capi.SPLAT_GROUP_TILES
-        self.num_groups = (((W + 15) // 16 + GT - 1) // GT) * (((H + 15) // 16 + GT - 1) // GT)
         # launch order of the composites' workgroups (SplatState.tile_work / tile_order): heaviest tiles of every XCD band first.  An entry
         # holds tile + 1; the zero-initialised buffer of the library's layout IS the natural order
         self.tile_order_on = os.environ.get("SPLAT_TILE_ORDER", "1") != "0"
@@ -87,7 +76,17 @@ class FusedEngine:
         # of its view.  Mapping draws a random keyframe per iteration (/root/reference/scripts/splatam.py:831-845): the order the
         # previous iteration left belongs to another view
         self.order_per_view = os.environ.get("SPLAT_TILE_ORDER_PER_VIEW", "1") != "0"
-        self._natural_order, self._orders = torch.zeros_like(b['tile_order']), {}
+        self.use_recs = {"0": 0, "1": 1}.get(os.environ.get("SPLAT_TILE_RECS", "auto"), 2)      # SplatState.tile_recs: 0 never, 1 always, 2 by list length
+        # what belongs to a CAMERA (size, launch struct, per-pixel and per-tile arrays, lists, list statistics, tile orders) lives in
+        # the attributes and ``buf`` entries named by _CAMERA_ATTRS / _camera_bufs(); the engine holds the current camera's there and
+        # the others' in ``_cams`` (add_camera / _activate).  Everything else -- the map, its Adam state, the per-Gaussian scratch, the
+        # pose state -- exists once
+        self._cams, self._cur, self._cam_ok = [None], 0, {}
+        self.auto_cameras = False       # True: a curr_data['cam'] the engine does not know is registered on first use (add_camera)
+        self._init_camera(cam, capacity)
+        # every array of the iteration's workspace is sized by the LIBRARY (splat_iter_workspace_layout, include/splat_hip.h "Scratch
+        # layouts"); they are tensors of their own here because the per-Gaussian ones grow with the map (_grow_rows / rebind)
+        self._alloc_rows(self._layout(P_alloc))
         b['pose_state'] = torch.zeros(_capi.SPLAT_POSE_STATE, dtype=f32, **z)
         self.max_2D_radius = self.store['max_2D_radius'] if self.managed else track_max_radius
         b['counts'] = torch.zeros(8, dtype=i32, **z)
@@ -100,9 +99,6 @@ class FusedEngine:
         self.map_step = 0
         self.pose_step = 0
         self.track_time_idx = None
-        self.max_list_hint = 0          # longest tile list seen at the last check_overflow(); 0 = unknown
-        self.tile_stride = 0            # > 0: bucketed lists (no scan / scatter pass), learnt by check_overflow()
-        self.num_tiles = T
         self.allow_buckets = True
         # group binning (SplatState.group_count): with bucketed lists short enough for the composite's own sort, the per-Gaussian
         # kernel files one record per 2 x 2-tile group (slots through an LDS histogram) and the composite filters its group's
@@ -113,23 +109,128 @@ class FusedEngine:
         # 500 k rows took the two-kernel form.  Since F6 requests all its moments in one round (round 3) the fused form is ahead at every
         # size measured (mapping at 816 k rows 1 491 -> 1 505 it/s, at 5 M 383 -> 386): no limit by default (SPLAT_FUSED_ADAM_MAX_ROWS)
         self.fused_adam_max_rows = int(os.environ.get("SPLAT_FUSED_ADAM_MAX_ROWS", 1 << 30))
-        self._tile_rows = None          # (begin, end): the band of tile rows the next iteration composites (tile-row-sharded tracking)
-        self._stats_partial = False     # the last iteration's list statistics cover a band only: check_overflow() does not learn from them
-        self.sub_bins = 1               # counters per tile on the exact-list path (16 once lists get very long: SplatState.sub_bins)
         # rows in creation (pixel-scan) order: true for a map this engine grew itself (add_valid_depth_points / add_new_gaussians
         # append per pixel in scan order); callers that hand over such a map may set it.  Only a speed hint (SplatState.order_hint)
         self.creation_order = bool(self.managed and P == 0)
         self.keep_map_grads = True      # mapping_iteration: store the gradients beside the fused Adam step (False: as the reference's loop, which discards them)
-        self.use_recs = {"0": 0, "1": 1}.get(os.environ.get("SPLAT_TILE_RECS", "auto"), 2)      # SplatState.tile_recs: 0 never, 1 always, 2 by list length
-        self._alloc_lists(self.capacity)
-        self._cam = self._make_cam(cam)
-        self._cam_ok = {}
         self._frame_keep = None
         self.track_fused = os.environ.get("SPLAT_TRACK_FUSED", "1") != "0"    # tracking: forward + loss + backward composite in one kernel
         self.track_fused_full = os.environ.get("SPLAT_TRACK_FUSED_FULL", "1") != "0"   # ... also when the map's gradients are wanted (the mapping form inside)
         self.fold_sums = os.environ.get("SPLAT_FOLD_SUMS", "1") != "0"     # tile-row-sharded tracking: exchange 256 B instead of 16 KB
         self.skipped_iterations = 0     # of the last check_overflow() / digest_report(): iterations whose Adam step the device skipped
+
+    # ------------------------------------------------------------------ cameras
+    _CAMERA_ATTRS = ("cam_settings", "H", "W", "num_tiles", "num_groups", "capacity", "_cam", "_cam_keep", "tile_stride", "max_list_hint",
+                     "sub_bins", "_learnt_P", "_stats_partial", "_orders", "_natural_order", "_tile_rows")
+    _LIST_BUFS = ("keys", "keys_alt", "point_list", "long_items", "tile_recs", "group_recs", "outlier_err", "outlier_scratch")
+
+    def _init_camera(self, cam, capacity=None):
+        """The current camera's state from scratch: size, fixed arrays, lists of ``capacity`` instances, unknown list statistics."""
+        self.cam_settings = cam
+        H, W = int(cam.image_height), int(cam.image_width)
+        self.H, self.W = H, W
+        self.num_tiles = int(self.L.splat_num_tiles(W, H))
+        GT = _capi.SPLAT_GROUP_TILES
+        self.num_groups = (((W + 15) // 16 + GT - 1) // GT) * (((H + 15) // 16 + GT - 1) // GT)
+        self._cam = self._make_cam(cam)             # (raises for a camera the fused path cannot render, before anything is allocated)
+        self._alloc_fixed(self._layout(self.Pcap))
+        self._natural_order, self._orders = torch.zeros_like(self.buf['tile_order']), {}
+        self.max_list_hint = 0          # longest tile list seen at the last check_overflow(); 0 = unknown
+        self.tile_stride = 0            # > 0: bucketed lists (no scan / scatter pass), learnt by check_overflow()
+        self._tile_rows = None          # (begin, end): the band of tile rows the next iteration composites (tile-row-sharded tracking)
+        self._stats_partial = False     # the last iteration's list statistics cover a band only: check_overflow() does not learn from them
+        self.sub_bins = 1               # counters per tile on the exact-list path (16 once lists get very long: SplatState.sub_bins)
         self._learnt_P = None           # rows of the map the list statistics were learnt on (rebind keeps them for a similar map)
+        self._alloc_lists(int(capacity) if capacity else 4 * self.P + 65536)
+
+    def _camera_bufs(self):
+        return tuple(key for _, key, _ in self._FIXED_ARRAYS) + self._LIST_BUFS
+
+    def _stash(self):
+        """The current camera's attributes and arrays, as they are now, into its entry of ``_cams``."""
+        st = {a: getattr(self, a) for a in self._CAMERA_ATTRS}
+        st['buf'] = {k: self.buf[k] for k in self._camera_bufs() if k in self.buf}
+        self._cams[self._cur] = st
+
+    def _activate(self, index):
+        """Make camera ``index`` the current one: attribute and dict moves only -- no allocation, no launch, nothing read."""
+        if index == self._cur:
+            return
+        self._stash()
+        st = self._cams[index]
+        for a in self._CAMERA_ATTRS:
+            setattr(self, a, st[a])
+        for k in self._camera_bufs():
+            self.buf.pop(k, None)
+        self.buf.update(st['buf'])
+        self._cams[index], self._cur = None, index      # (the current camera's state lives on the engine: no second reference to its arrays)
+
+    def _same_camera(self, cam, ref):
+        return (int(cam.image_height) == int(ref.image_height) and int(cam.image_width) == int(ref.image_width)
+                and float(cam.tanfovx) == float(ref.tanfovx) and float(cam.tanfovy) == float(ref.tanfovy)
+                and float(cam.scale_modifier) == float(ref.scale_modifier)
+                and all(torch.equal(getattr(cam, f).to(self.dev).float().reshape(-1), getattr(ref, f).to(self.dev).float().reshape(-1))
+                        for f in ("viewmatrix", "projmatrix", "bg")))
+
+    def _find_camera(self, cam):
+        """Index of the known camera ``cam`` equals (size, tan-fov, scale modifier, view, projection, background), or None.  The
+        comparison reads the matrices once per settings object; the object is remembered afterwards."""
+        hit = self._cam_ok.get(id(cam))
+        if hit is not None:
+            return hit[1]
+        for i in range(len(self._cams)):
+            ref = self.cam_settings if i == self._cur else self._cams[i]['cam_settings']
+            if cam is ref or self._same_camera(cam, ref):
+                self._cam_ok[id(cam)] = (cam, i)        # keeps the tuple alive, so the id stays unique
+                return i
+        return None
+
+    @property
+    def num_cameras(self):
+        return len(self._cams)
+
+    def add_camera(self, cam, capacity=None):
+        """Register another camera (a GaussianRasterizationSettings) on this engine's map and make it the current one; a camera the
+        engine already knows is selected.  The new camera gets per-pixel planes, tile arrays and lists of its own (``capacity``
+        instances, default as at construction) and learns its list statistics on its first use, like a new engine does.  The map,
+        its Adam state and the per-Gaussian scratch are shared.  Returns the camera's index.
+        The capacity flag is the camera's (``d_cam``) while the backward accumulator is the map's: call ``check_overflow()`` BEFORE leaving
+        a camera whose last iterations may have been flagged -- it clears the accumulator a flagged iteration left dirty, and the next
+        camera's own flag is down, so its iteration would step on it."""
+        i = self._find_camera(cam)
+        if i is None:
+            self._stash()
+            held = {k: self.buf.pop(k) for k in self._camera_bufs() if k in self.buf}
+            self._cams.append(None)
+            prev, self._cur = self._cur, len(self._cams) - 1
+            try:
+                self._init_camera(cam, capacity)
+            except Exception:
+                self._cams.pop()
+                self._cur = prev
+                for a in self._CAMERA_ATTRS:
+                    setattr(self, a, self._cams[prev][a])
+                for k in self._camera_bufs():
+                    self.buf.pop(k, None)
+                self.buf.update(held)
+                self._cams[prev] = None
+                raise
+            self._cam_ok[id(cam)] = (cam, self._cur)
+            return self._cur
+        self._activate(i)
+        return i
+
+    def select_camera(self, cam):
+        """Make the known camera ``cam`` equals the current one (``lists_known`` / ``check_overflow`` / ``rendered`` speak for it).
+        As with ``add_camera``: ``check_overflow()`` first when the camera being left may have been flagged."""
+        i = self._find_camera(cam)
+        if i is None:
+            raise RuntimeError("select_camera: this FusedEngine does not know that camera (add_camera registers it)")
+        self._activate(i)
+        return i
+
+    def _other_cameras(self):
+        return [st for i, st in enumerate(self._cams) if i != self._cur]
 
     # ------------------------------------------------------------------ capacity-managed map
     # workspace arrays by the library's field names: (key in self.buf, dtype, trailing shape); per-Gaussian ones grow with the map
@@ -245,6 +346,11 @@ class FusedEngine:
             if ref is None or abs(P - ref) > keep_lists_within * max(ref, 1):
                 self.tile_stride = 0
                 self.max_list_hint = 0
+            for st in self._other_cameras():
+                ref = st['_learnt_P']
+                if ref is None or abs(P - ref) > keep_lists_within * max(ref, 1):
+                    st['tile_stride'] = 0
+                    st['max_list_hint'] = 0
         return self
 
     def _grow_rows(self, new_cap):
@@ -307,6 +413,11 @@ class FusedEngine:
         if ref is None or self.tile_stride == 0 or abs(self.P - ref) > keep_lists_within * max(ref, 1):
             self.tile_stride = 0
             self.max_list_hint = 0
+        for st in self._other_cameras():        # the same decision for every other camera, on the rows ITS statistics were learnt on
+            ref = st['_learnt_P']
+            if ref is None or st['tile_stride'] == 0 or abs(self.P - ref) > keep_lists_within * max(ref, 1):
+                st['tile_stride'] = 0
+                st['max_list_hint'] = 0
 
     def render(self, curr_data, time_idx):
         """Forward-only 6-channel render of the map from pose ``time_idx`` (no loss, no gradients): returns
@@ -359,13 +470,18 @@ class FusedEngine:
         """``evaluate_metrics`` of this module (the metric kernels alone, on caller-supplied planes of any size)."""
         return evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
 
-    def lists_known(self):
-        """The per-tile list statistics (bucket stride, longest list) are usable for the map as it is: an edit kept them (_set_rows)."""
+    def lists_known(self, curr_data=None):
+        """The per-tile list statistics (bucket stride, longest list) are usable for the map as it is: an edit kept them (_set_rows).
+        They are a camera's own: of the camera of ``curr_data`` (which becomes the current one), or of the current camera."""
+        if curr_data is not None:
+            self._check_cam(curr_data)
         return self.tile_stride > 0 and self.max_list_hint > 0
 
     def relearn_lists(self, curr_data, time_idx):
         """One probe render with exact lists + ``check_overflow()``: sizes the list capacity and the per-tile buckets
-        for the map as it is now (call after an edit that did not keep them -- ``lists_known()``; one D2H read)."""
+        for the map as it is now (call after an edit that did not keep them -- ``lists_known()``; one D2H read).
+        Of the camera of ``curr_data``."""
+        self._check_cam(curr_data)
         self.tile_stride = 0
         self.max_list_hint = 0
         for _ in range(3):
@@ -377,6 +493,7 @@ class FusedEngine:
     def _append(self, mode, curr_data, time_idx, sil_thres, w2c=None):
         if not self.managed:
             raise RuntimeError("this FusedEngine was built without gaussian_capacity: the map cannot grow")
+        self._check_cam(curr_data)          # the frame's camera: its size, its render (out6), its scratch plane
         H, W = self.H, self.W
         im, depth = curr_data['im'].contiguous(), curr_data['depth'].contiguous()
         if tuple(im.shape) != (3, H, W) or tuple(depth.shape) != (1, H, W):
@@ -418,6 +535,7 @@ class FusedEngine:
             raise ValueError(f"Unknown mean_sq_dist_method {mean_sq_dist_method}")
         if gaussian_distribution is not None and (gaussian_distribution == "isotropic") != self.iso:
             raise ValueError("gaussian_distribution differs from the map's log_scales layout")
+        self._check_cam(curr_data)
         if depth_sil is None:
             # the densification render must come from complete, sorted lists: a spilled bucket / stale list-length hint would
             # permanently add wrong Gaussians (the status words are overwritten by the next relearn_lists)
@@ -432,10 +550,14 @@ class FusedEngine:
             self.buf['out6'][4] = depth_sil[1]
         return self._append(_capi.SPLAT_ADD_NON_PRESENCE, curr_data, time_idx, sil_thres)
 
-    def add_valid_depth_points(self, color, depth, intrinsics, w2c, time_idx=0):
+    def add_valid_depth_points(self, color, depth, intrinsics, w2c, time_idx=0, cam=None):
         """get_pointcloud(mask = depth > 0) + initialize_params' Gaussian rows (/root/reference/scripts/splatam.py:197-206):
-        one Gaussian per valid-depth pixel of the frame, appended to the map."""
-        return self._append(_capi.SPLAT_ADD_VALID_DEPTH, {'im': color, 'depth': depth, 'intrinsics': intrinsics}, time_idx, 0.0, w2c=w2c)
+        one Gaussian per valid-depth pixel of the frame, appended to the map.  ``cam``: the frame's camera when it is not the
+        current one (a densification frame of its own size: /root/reference/scripts/splatam.py:185-200)."""
+        data = {'im': color, 'depth': depth, 'intrinsics': intrinsics}
+        if cam is not None:
+            data['cam'] = cam
+        return self._append(_capi.SPLAT_ADD_VALID_DEPTH, data, time_idx, 0.0, w2c=w2c)
 
     def remove_points(self, to_remove=None, removal_opacity_threshold=0.0, big_scale=None):
         """remove_points (/root/reference/utils/slam_external.py:139-162): stable in-place compaction of parameters,
@@ -638,22 +760,19 @@ class FusedEngine:
         return cam
 
     def _check_cam(self, curr_data):
-        """The engine bakes the camera into its launch arguments at construction; the reference's get_loss reads
-        curr_data['cam'] on every call (/root/reference/scripts/splatam.py:249).  A different camera is an error here, not a
-        silently ignored argument."""
+        """The camera is the one of ``curr_data['cam']``, as the reference's get_loss reads it on every call
+        (/root/reference/scripts/splatam.py:249): a settings tuple that equals a camera of this engine selects it.  One the engine does
+        not know is registered on first use with ``auto_cameras``; otherwise it is an error, not a silently ignored argument."""
         cam = curr_data.get('cam') if hasattr(curr_data, 'get') else None
-        if cam is None or cam is self.cam_settings or id(cam) in self._cam_ok:
+        if cam is None or cam is self.cam_settings:
             return
-        ref = self.cam_settings
-        same = (int(cam.image_height) == int(ref.image_height) and int(cam.image_width) == int(ref.image_width)
-                and float(cam.tanfovx) == float(ref.tanfovx) and float(cam.tanfovy) == float(ref.tanfovy)
-                and float(cam.scale_modifier) == float(ref.scale_modifier)
-                and all(torch.equal(getattr(cam, f).to(self.dev).float().reshape(-1), getattr(ref, f).to(self.dev).float().reshape(-1))
-                        for f in ("viewmatrix", "projmatrix", "bg")))
-        if not same:
-            raise RuntimeError("curr_data['cam'] differs from the camera this FusedEngine was built for "
-                               "(build one engine per camera / resolution)")
-        self._cam_ok[id(cam)] = cam          # keeps the tuple alive, so the id stays unique
+        i = self._find_camera(cam)
+        if i is None:
+            if not self.auto_cameras:
+                raise RuntimeError("curr_data['cam'] differs from the camera(s) this FusedEngine was built for "
+                                   "(add_camera(cam) registers another one; auto_cameras = True does so on first use)")
+            i = self.add_camera(cam)
+        self._activate(i)
 
     def _frame_w2c(self, curr_data):
         """curr_data['w2c'] as the kernels read it: 16 contiguous floats on the engine's device (row 2 is the depth channel of
@@ -1049,6 +1168,40 @@ class FusedEngine:
         """(im[3,H,W], depth[1,H,W], silhouette[H,W], depth_sq[1,H,W]) of the last iteration."""
         o = self.buf['out6']
         return o[0:3], o[3:4], o[4], o[5:6]
+
+
+# ---------------------------------------------------------------------- frame preparation (csrc/frameprep.hip)
+def prepare_frame(color, depth, size=None, out=None):
+    """A frame as the datasets hand it over -- ``color`` [H, W, 3] in 0..255, ``depth`` [H, W, 1] (or [H, W]), float32 on one
+    CUDA/HIP device -- as every entry of this module takes it: ``(im [3, h, w] in 0..1, depth [1, h, w])`` at ``size = (h, w)``
+    (default: the frame's own size, i.e. the loop's ``permute(2, 0, 1) / 255``).  At another size colour is resampled bilinearly
+    and depth by nearest source pixel (include/splat_hip.h splat_frame_prepare; ``slam.prepare_frame`` is the same arithmetic in
+    torch).  One launch on the current stream, nothing read back.  ``out = (im, depth)``: contiguous float32 tensors of those
+    shapes to write into (views into larger buffers are fine); otherwise two new tensors."""
+    if not isinstance(color, torch.Tensor) or color.device.type != "cuda":
+        raise RuntimeError("prepare_frame needs CUDA/HIP tensors; the HIP library has no CPU path (slam.prepare_frame is the torch form)")
+    dev = color.device
+    if color.dim() != 3 or color.shape[2] != 3:
+        raise RuntimeError(f"color must be [H, W, 3] (got {tuple(color.shape)})")
+    H, W = int(color.shape[0]), int(color.shape[1])
+    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if h <= 0 or w <= 0:
+        raise RuntimeError(f"size must be positive (got {(h, w)})")
+    src = []
+    for name, t, n in (("color", color, 3 * H * W), ("depth", depth, H * W)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and t.numel() == n):
+            got = f"{t.dtype}, {tuple(t.shape)}, {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise RuntimeError(f"{name} must be a float32 tensor of {n} elements on {dev} (got {got})")
+        src.append(t if t.is_contiguous() else t.contiguous())
+    if out is None:
+        out = (torch.empty(3, h, w, dtype=torch.float32, device=dev), torch.empty(1, h, w, dtype=torch.float32, device=dev))
+    for name, t, shape in (("out[0]", out[0], (3, h, w)), ("out[1]", out[1], (1, h, w))):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == shape and t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_frame_prepare(W, H, src[0].data_ptr(), src[1].data_ptr(), w, h, out[0].data_ptr(), out[1].data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream), "splat_frame_prepare")
+    return out[0], out[1]
 
 
 # ---------------------------------------------------------------------- evaluation metrics on planes (csrc/evalmetrics.hip)

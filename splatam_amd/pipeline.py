@@ -5,7 +5,7 @@ storing a keyframe (/root/reference/scripts/splatam.py:654-905), without the ref
 here                                           reference
 =============================================  =============================================
 ``keyframe_selection_overlap``                 utils/keyframe_selection.py:44-103 (+ its get_pointcloud :10-41)
-``replica_config``                             configs/replica/splatam.py (the values the loop reads)
+``replica_config`` / ``splatam_s_config``      configs/replica/splatam.py / splatam_s.py (the values the loop reads)
 ``rgbd_slam``                                  scripts/splatam.py:455-905 (frame loop: pose initialisation, tracking with
                                                best-candidate bookkeeping and the depth-loss retry, densification,
                                                keyframe selection, mapping with pruning, keyframe list)
@@ -118,6 +118,18 @@ def replica_config(tracking_iters=40, mapping_iters=60, map_every=1, keyframe_ev
                      prune_gaussians=True, pruning_dict=dict(slam.REPLICA_PRUNE), use_gaussian_splatting_densification=False))
 
 
+def splatam_s_config(width=1200, height=680, **kw):
+    """The entries of /root/reference/configs/replica/splatam_s.py (SplaTAM-S) that the frame loop reads: 10 tracking and 15
+    mapping iterations, a mapping window of 32, tracking at the frame's own size and densification at half of it (600 x 340 under
+    the 1200 x 680 map), everything else as ``replica_config``.  ``width`` / ``height``: the dataset's frame size, i.e.
+    ``desired_image_width`` / ``_height``."""
+    cfg = replica_config(**dict(dict(tracking_iters=10, mapping_iters=15, mapping_window_size=32), **kw))
+    cfg['data'] = dict(desired_image_height=int(height), desired_image_width=int(width),
+                       tracking_image_height=int(height), tracking_image_width=int(width),
+                       densification_image_height=int(height) // 2, densification_image_width=int(width) // 2)
+    return cfg
+
+
 def save_params(output_params, output_dir, time_idx=None):
     """``params.npz`` (or ``params<time_idx>.npz``): one array per entry of the params dict."""
     os.makedirs(output_dir, exist_ok=True)
@@ -219,24 +231,84 @@ def _est_w2c(params, time_idx):
     return w2c
 
 
-def initialize_first_timestep(dataset, num_frames, scene_radius_depth_ratio, mean_sq_dist_method, gaussian_distribution, device="cuda"):
-    """Map, variables, intrinsics, first-frame world-to-camera and camera from frame 0."""
-    color, depth, intrinsics, pose = dataset[0]
+def initialize_first_timestep(dataset, num_frames, scene_radius_depth_ratio, mean_sq_dist_method, gaussian_distribution, device="cuda",
+                              densify_frame=None, first=None):
+    """Map, variables, intrinsics, first-frame world-to-camera and camera from frame 0.  ``densify_frame`` = (im, depth,
+    intrinsics[3, 3]) of the first densification frame when densification has a size of its own: the point cloud, its mean squared
+    distances and the scene radius then come from IT, camera and w2c from the full frame (scripts/splatam.py:185-206).  ``first``:
+    ``dataset[0]`` when the caller has read it already."""
+    color, depth, intrinsics, pose = dataset[0] if first is None else first
     color = color.permute(2, 0, 1) / 255
     depth = depth.permute(2, 0, 1)
     intrinsics = intrinsics[:3, :3]
     w2c = torch.linalg.inv(pose)
     cam = slam.setup_camera(color.shape[2], color.shape[1], intrinsics.cpu().numpy(), w2c.detach().cpu().numpy(), device=device)
+    cloud_intrinsics = intrinsics
+    if densify_frame is not None:
+        color, depth, cloud_intrinsics = densify_frame
     mask = (depth > 0).reshape(-1)
-    cloud, msd = slam.get_pointcloud(color, depth, intrinsics, w2c, mask=mask, compute_mean_sq_dist=True,
+    cloud, msd = slam.get_pointcloud(color, depth, cloud_intrinsics, w2c, mask=mask, compute_mean_sq_dist=True,
                                      mean_sq_dist_method=mean_sq_dist_method)
     params, variables = slam.initialize_params(cloud, num_frames, msd, gaussian_distribution)
     variables['scene_radius'] = torch.max(depth) / scene_radius_depth_ratio
     return params, variables, intrinsics, w2c, cam
 
 
+class _ReducedFrames:
+    """The frames of one of the loop's reduced resolutions (tracking, densification): from a dataset of that size, as the reference
+    keeps one (scripts/splatam.py:537-587), or derived from the full-size frame -- ``prepare_frame`` (the HIP kernel for frames on the
+    device, the torch mirror on the CPU) and ``scale_intrinsics``, i.e. what such a dataset does to every frame it loads."""
+
+    def __init__(self, dataset, size, full_size, full_k):
+        self.dataset, self.size = dataset, (int(size[0]), int(size[1]))
+        self._first, self._planes = None, None
+        if dataset is not None:
+            self._first = dataset[0]                    # (read once: size and intrinsics now, the frame itself at time index 0)
+            color, _, k, _ = self._first
+            self.size = (int(color.shape[0]), int(color.shape[1]))
+            self.intrinsics = k[:3, :3]
+        else:
+            self.intrinsics = slam.scale_intrinsics(full_k, self.size[0] / full_size[0], self.size[1] / full_size[1])[:3, :3]
+        self.cam = None
+
+    def frame(self, time_idx, full_color, full_depth):
+        """(im [3, h, w], depth [1, h, w]); ``full_*``: the full-size frame as the dataset hands it over.  Derived frames on the
+        device are written into ONE pair of planes kept for this resolution (a reduced frame is used within its own time index only:
+        the keyframe list keeps full-size frames)."""
+        if self.dataset is not None:
+            color, depth, _, _ = self._first if (time_idx == 0 and self._first is not None) else self.dataset[time_idx]
+            self._first = None
+            return (color.permute(2, 0, 1) / 255).contiguous(), depth.permute(2, 0, 1).contiguous()
+        if full_color.device.type == "cuda":
+            from . import fused
+            if self._planes is None:
+                h, w = self.size
+                self._planes = (torch.empty(3, h, w, dtype=torch.float32, device=full_color.device),
+                                torch.empty(1, h, w, dtype=torch.float32, device=full_color.device))
+            return fused.prepare_frame(full_color, full_depth, self.size, out=self._planes)
+        return slam.prepare_frame(full_color, full_depth, self.size)
+
+    def curr_data(self, time_idx, full_color, full_depth, w2c):
+        im, depth = self.frame(time_idx, full_color, full_depth)
+        return {'cam': self.cam, 'im': im, 'depth': depth, 'id': time_idx, 'intrinsics': self.intrinsics, 'w2c': w2c}
+
+
+def _reduced_frames(which, dataset, config, full_size, full_k):
+    """The tracking / densification frames of a run, or None when that step runs on the full frame: a dataset the caller passed, or
+    ``config['data'][<which>_image_height / _width]`` that differ from the dataset's size (equal sizes mean "not separate":
+    scripts/splatam.py:498-517)."""
+    if dataset is not None:
+        return _ReducedFrames(dataset, (0, 0), full_size, full_k)
+    data = config.get('data') or {}
+    if f"{which}_image_height" not in data:
+        return None
+    size = (int(data[f"{which}_image_height"]), int(data[f"{which}_image_width"]))
+    return None if size == tuple(full_size) else _ReducedFrames(None, size, full_size, full_k)
+
+
 class _PhaseTimer:
-    """Wall time per named phase of the frame being processed (a device synchronisation on either side: ~10 per frame)."""
+    """Wall time per named phase of the frame being processed (a device synchronisation on either side: ~10 per frame; ``sync=False``:
+    host time only, for a phase whose device work the next synchronised phase waits for anyway)."""
 
     def __init__(self, dev):
         self.dev, self.frame, self._open = dev, {}, []
@@ -245,17 +317,19 @@ class _PhaseTimer:
         if self.dev.type == "cuda":
             torch.cuda.synchronize(self.dev)
 
-    def __call__(self, name):
-        self._name = name
+    def __call__(self, name, sync=True):
+        self._name, self._sync_next = name, sync
         return self
 
     def __enter__(self):
-        self._sync()
-        self._open.append((self._name, time.perf_counter()))
+        if self._sync_next:
+            self._sync()
+        self._open.append((self._name, time.perf_counter(), self._sync_next))
 
     def __exit__(self, *exc):
-        self._sync()
-        name, t0 = self._open.pop()
+        name, t0, sync = self._open.pop()
+        if sync:
+            self._sync()
         self.frame[name] = self.frame.get(name, 0.0) + 1e3 * (time.perf_counter() - t0)
 
     def next_frame(self):
@@ -263,12 +337,22 @@ class _PhaseTimer:
         return {k: round(v, 3) for k, v in done.items()}
 
 
-def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacity=None, verbose=False, evaluate=None):
+def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacity=None, verbose=False, evaluate=None,
+              tracking_dataset=None, densify_dataset=None):
     """Runs the SplaTAM frame loop over ``dataset``; returns ``(params, variables, stats)`` with
     ``stats = {keyframe_time_indices, tracking_iters, mapping_iters, tracking_s, mapping_s, mapping_loop_s, num_gaussians,
     redone_iterations, phase_ms}`` (``mapping_loop_s``: the iterations alone, where the reference's own mapping timer runs,
     scripts/splatam.py:825-891; ``mapping_s`` also holds densification, keyframe selection and list re-learning; ``phase_ms``: one
-    dict per frame -- tracking, add_new_gaussians, keyframe_selection, relearn_lists, mapping_iterations, prune, keyframe_store).
+    dict per frame -- prepare_frames, tracking, add_new_gaussians, keyframe_selection, relearn_lists, mapping_iterations, prune,
+    keyframe_store).
+
+    Resolutions of their own (SplaTAM-S, the iPhone configurations: scripts/splatam.py:498-517, 537-587): tracking runs on
+    ``tracking_dataset``'s frames and camera, ``add_new_gaussians`` and the first frame's point cloud on ``densify_dataset``'s;
+    keyframe selection, mapping, the keyframe list and the evaluation stay on ``dataset``'s full-size frames.  Without such a dataset
+    the sizes are read from ``config['data']`` (``tracking_image_height / _width``, ``densification_image_height / _width``; sizes
+    equal to the dataset's mean "not separate") and the reduced frames are derived from the full frame by ``prepare_frame`` +
+    ``slam.scale_intrinsics`` -- on the device for a dataset on the device.  The fused engine holds ONE map and one camera per
+    resolution (FusedEngine.add_camera).  Not with several ranks.
 
     ``engine``: "fused" (FusedEngine: every iteration one C call, the map edited in place on the device), "dropin" (the
     reference-shaped PyTorch loop of splatam_amd.slam on the drop-in rasterizer), or "plugin": the SAME reference-shaped loop -- its
@@ -314,11 +398,20 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
         raise NotImplementedError("gradient-based densification inside the frame loop needs engine='fused'")
     dist_kind = config.get('gaussian_distribution', 'isotropic')
     eng = None
+    first = dataset[0]
+    color0, depth0, intr0, pose0 = first
+    full_size = (int(color0.shape[0]), int(color0.shape[1]))
+    tracking_frames = _reduced_frames("tracking", tracking_dataset, config, full_size, intr0)
+    densify_frames = _reduced_frames("densification", densify_dataset, config, full_size, intr0)
+    if world > 1 and (tracking_frames is not None or densify_frames is not None):
+        raise NotImplementedError("tracking / densification at resolutions of their own is not supported in the multi-rank frame loop")
+    densify0 = None
+    if densify_frames is not None:
+        densify0 = densify_frames.frame(0, color0, depth0) + (densify_frames.intrinsics,)
     if fused:
         # first frame on the device: an empty capacity-managed map + one append of every valid-depth pixel
         # (splat_map_add_new_gaussians, SPLAT_ADD_VALID_DEPTH) = get_pointcloud + initialize_params of the reference
         from .fused import FusedEngine
-        color0, depth0, intr0, pose0 = dataset[0]
         color0 = (color0.permute(2, 0, 1) / 255).contiguous()
         depth0 = depth0.permute(2, 0, 1).contiguous()
         dev = depth0.device
@@ -335,20 +428,32 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
         params = {'means3D': z(0, 3), 'rgb_colors': z(0, 3), 'unnorm_rotations': z(0, 4), 'logit_opacities': z(0, 1),
                   'log_scales': z(0, cols), 'cam_unnorm_rots': torch.nn.Parameter(rots), 'cam_trans': z(1, 3, num_frames)}
         variables = {k: torch.zeros(0, device=dev) for k in ('max_2D_radius', 'means2D_gradient_accum', 'denom', 'timestep')}
-        variables['scene_radius'] = torch.max(depth0) / config['scene_radius_depth_ratio']
+        variables['scene_radius'] = torch.max(depth0 if densify0 is None else densify0[1]) / config['scene_radius_depth_ratio']
         cap = gaussian_capacity or int(H * W * 2.5) + 65536
         eng = FusedEngine(params, cam, gaussian_capacity=cap, variables=variables)
         eng.keep_map_grads = False      # (a mapping iteration's gradients are discarded after its step: /root/reference/scripts/splatam.py:860-861)
         if config['mean_sq_dist_method'] != "projective":
             raise ValueError(f"Unknown mean_sq_dist_method {config['mean_sq_dist_method']}")
-        eng.add_valid_depth_points(color0, depth0, intrinsics, first_frame_w2c)
-        scene_radius = variables['scene_radius']
     else:
         params, variables, intrinsics, first_frame_w2c, cam = initialize_first_timestep(
             dataset, num_frames, config['scene_radius_depth_ratio'], config['mean_sq_dist_method'], dist_kind,
-            device=dataset[0][1].device)
+            device=depth0.device, densify_frame=densify0, first=first)
         dev = params['means3D'].device
         first_frame_w2c = first_frame_w2c.to(dev).float().contiguous()
+    # the cameras of the reduced resolutions: their own size and intrinsics at the FIRST frame's pose (scripts/splatam.py:191, 586)
+    for frames in (tracking_frames, densify_frames):
+        if frames is not None:
+            frames.cam = slam.setup_camera(frames.size[1], frames.size[0], frames.intrinsics.cpu().numpy(),
+                                           first_frame_w2c.detach().cpu().numpy(), device=dev)
+            if fused:
+                eng.add_camera(frames.cam)           # one map, a camera per resolution
+    if fused:
+        if densify0 is None:
+            eng.select_camera(cam)
+            eng.add_valid_depth_points(color0, depth0, intrinsics, first_frame_w2c)
+        else:
+            eng.add_valid_depth_points(densify0[0], densify0[1], densify0[2], first_frame_w2c, cam=densify_frames.cam)
+        scene_radius = variables['scene_radius']
     keyframe_list, keyframe_time_indices = [], []
     stats = dict(tracking_iters=0, mapping_iters=0, tracking_s=0.0, mapping_s=0.0, mapping_loop_s=0.0, redone_iterations=0,
                  num_gaussians=[], phase_ms=[], frame_s=[], decisions=[])
@@ -360,10 +465,18 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     try:
         for time_idx in range(num_frames):
             t_frame = time.perf_counter()
-            color, depth, _, gt_pose = dataset[time_idx]
-            color = (color.permute(2, 0, 1) / 255).contiguous()
-            depth = depth.permute(2, 0, 1).contiguous()
-            curr_data = {'cam': cam, 'im': color, 'depth': depth, 'id': time_idx, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
+            will_add = time_idx > 0 and (time_idx + 1) % config['map_every'] == 0 and mcfg['add_new_gaussians']
+            # (with one resolution the phase is the permute / 255 the loop always did: timed on the host, no synchronisation added)
+            with phase("prepare_frames", sync=tracking_frames is not None or densify_frames is not None):
+                raw_color, raw_depth, _, gt_pose = dataset[time_idx]
+                color = (raw_color.permute(2, 0, 1) / 255).contiguous()
+                depth = raw_depth.permute(2, 0, 1).contiguous()
+                curr_data = {'cam': cam, 'im': color, 'depth': depth, 'id': time_idx, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
+                # tracking runs on the tracking frame, add_new_gaussians on the densification frame (scripts/splatam.py:660-667, 781-789)
+                tracking_curr_data = curr_data if tracking_frames is None else \
+                    tracking_frames.curr_data(time_idx, raw_color, raw_depth, first_frame_w2c)
+                densify_curr_data = curr_data if (densify_frames is None or not will_add) else \
+                    densify_frames.curr_data(time_idx, raw_color, raw_depth, first_frame_w2c)
             # what the loop DECIDED on this frame, engine independent (host integers only; tests/loop_trace.py derives the same table
             # from a recording of the reference's own rgbd_slam)
             decided = dict(time_idx=time_idx, tracking_iters=0, rows_after_add=None, selected=None, views=[], prunes=[], rows_end=None,
@@ -373,13 +486,18 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
                 slam.initialize_camera_pose(params, time_idx, forward_prop=tcfg['forward_prop'])
 
             # ---------------- tracking (scripts/splatam.py:676-744)
+            if fused and tracking_frames is not None and time_idx > 0 and not tcfg['use_gt_poses'] and not eng.lists_known(tracking_curr_data):
+                # a tracking camera of its own whose list statistics are unknown (its first frame, or an edit dropped them): one probe
+                # render sizes its lists, instead of a flagged first iteration and a phase run again
+                with phase("relearn_lists"):
+                    eng.relearn_lists(tracking_curr_data, time_idx)
             with phase("tracking"):
                 t0 = time.perf_counter()
                 if time_idx > 0 and not tcfg['use_gt_poses']:
                     if plugged:
-                        n_track, variables = _track_frame_statements(params, variables, curr_data, time_idx, tcfg)
+                        n_track, variables = _track_frame_statements(params, variables, tracking_curr_data, time_idx, tcfg)
                     else:
-                        n_track = _track_frame(params, variables, curr_data, time_idx, tcfg, eng, stats)
+                        n_track = _track_frame(params, variables, tracking_curr_data, time_idx, tcfg, eng, stats)
                     stats['tracking_iters'] += n_track
                     decided['tracking_iters'] = n_track
                     sdist.broadcast_pose(params, time_idx)              # replicas: one pose for the map edits that follow
@@ -396,9 +514,9 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
                 if mcfg['add_new_gaussians'] and time_idx > 0:
                     with phase("add_new_gaussians"):
                         if fused:
-                            eng.add_new_gaussians(curr_data, mcfg['sil_thres'], time_idx, config['mean_sq_dist_method'], dist_kind)
+                            eng.add_new_gaussians(densify_curr_data, mcfg['sil_thres'], time_idx, config['mean_sq_dist_method'], dist_kind)
                         else:
-                            params, variables = slam.add_new_gaussians(params, variables, curr_data, mcfg['sil_thres'], time_idx,
+                            params, variables = slam.add_new_gaussians(params, variables, densify_curr_data, mcfg['sil_thres'], time_idx,
                                                                        config['mean_sq_dist_method'], dist_kind)
                     decided['rows_after_add'] = int(params['means3D'].shape[0])
                     sdist.assert_replicated_count(int(params['means3D'].shape[0]), f"add_new_gaussians (frame {time_idx})", dev)
@@ -410,7 +528,7 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
                         selected.append(len(keyframe_list) - 1)
                     selected.append(-1)
                     decided['selected'] = [int(x) for x in selected[:-1 - (1 if len(keyframe_list) > 0 else 0)]]
-                if fused and not eng.lists_known():
+                if fused and not eng.lists_known(curr_data):
                     with phase("relearn_lists"):
                         eng.relearn_lists(curr_data, time_idx)
                 if dev.type == "cuda":
@@ -453,6 +571,8 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
         box = [None]
         if rank == 0:
             with torch.no_grad():
+                if fused:
+                    eng.select_camera(cam)          # the evaluation renders the full-size frames
                 box[0] = evaluation.evaluate(dataset, params, num_frames, mcfg['sil_thres'], mcfg['num_iters'], mcfg['add_new_gaussians'],
                                              engine=eng if fused else None, **opts)
         if world > 1:

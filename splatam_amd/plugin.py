@@ -176,7 +176,8 @@ def _scalar(rep, slot):
 
 
 class _Session:
-    """Engines for the caller's current tensors (one per camera resolution), the phase the next iterations belong to."""
+    """Engines for the caller's current tensors (one per camera resolution; map_edits: ONE, with a camera per resolution), the phase
+    the next iterations belong to."""
 
     def __init__(self):
         self.engines = {}           # (H, W) -> FusedEngine
@@ -198,9 +199,10 @@ class _Session:
         where the reference replaces them.  A tensor replaced behind the engine's back (an un-adapted edit) is an error, not a re-bind."""
         hw = (int(cam.image_height), int(cam.image_width))
         eng = self.engines.get(hw)
+        if eng is None and self.engines:
+            # another resolution (a tracking / densification camera of its own): a camera more on the ONE engine that owns the map
+            eng = self.engines[hw] = next(iter(self.engines.values()))
         if eng is None:
-            if self.engines:
-                raise NotImplementedError("plugin.install(map_edits=True): one camera resolution per run (the engine owns the map)")
             if variables is None:
                 raise RuntimeError("plugin.install(map_edits=True) needs the caller's `variables` dict (the per-Gaussian variables move with the rows)")
             P = int(params['means3D'].shape[0])
@@ -215,6 +217,10 @@ class _Session:
         elif eng.params is not params or any(params[k].data_ptr() != eng.store[k].data_ptr() or params[k].shape[0] != eng.P for k in PARAM_ORDER):
             raise RuntimeError("plugin.install(map_edits=True): the Gaussian tensors were replaced outside add_new_gaussians / prune_gaussians; "
                                "the engine owns the map in this mode")
+        if cam is not eng.cam_settings and eng._find_camera(cam) != eng._cur:
+            # the reports in flight speak of the camera that produced them: look at all of them before another one becomes current
+            self.drain(eng)
+            eng.add_camera(cam)
         now = tuple(params[k] for k in _ALL_KEYS) + (variables.get('max_2D_radius') if variables is not None else None,)
         self.bound[hw] = now
         return eng, now
@@ -311,7 +317,7 @@ class _Session:
         if opt is None or rep.args is None or rep.args[-1] or skipped <= 0:
             return                                              # (tracking: repeat_tracking re-runs the iteration instead)
         if self.map_edits:
-            for eng in self.engines.values():
+            for eng in {id(e): e for e in self.engines.values()}.values():      # (one engine, filed under every camera size)
                 eng.map_step = max(eng.map_step - int(skipped), 0)
         for g in opt.param_groups:             # (the pose groups carry state only when bundle adjustment steps them)
             st = opt.state.get(g['params'][0])
@@ -439,7 +445,7 @@ class FusedOptimizer(torch.optim.Adam):
                 raise NotImplementedError("plugin.install(map_edits=True): Gaussian learning rates in the TRACKING optimizer are not supported")
             if not tracking:
                 if s.engines:
-                    for eng in s.engines.values():
+                    for eng in {id(e): e for e in s.engines.values()}.values():      # (one engine, filed under every camera size)
                         eng.reset_map_optimizer()           # a new optimizer: fresh moments, step count 0 (:821)
                 else:
                     s.pending_map_reset = True
