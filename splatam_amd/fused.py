@@ -18,6 +18,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 import math
+from collections import ChainMap
+from types import MappingProxyType
 
 import torch
 
@@ -31,6 +33,132 @@ _FLAG_SLOTS = 16        # floats ahead of the flat gradient bucket (one 64-byte 
 _REPORT_FLAG, _REPORT_STATUS, _REPORT_SKIPPED = _capi.SPLAT_REPORT_FLAG, _capi.SPLAT_REPORT_STATUS, _capi.SPLAT_REPORT_SKIPPED
 _STATUS_INSTANCES, _STATUS_OVERFLOW = _capi.SPLAT_STATUS_INSTANCES, _capi.SPLAT_STATUS_OVERFLOW
 _STATUS_LONGEST, _STATUS_STALE_HINT = _capi.SPLAT_STATUS_LONGEST, _capi.SPLAT_STATUS_STALE_HINT
+
+
+def _layout(W, H, rows=0, capacity=0, group_stride=0, outlier=False):
+    """Every array of the iteration's workspace is sized by the LIBRARY (splat_iter_workspace_layout, include/splat_hip.h "Scratch
+    layouts"); they are tensors of their own here because the per-Gaussian ones grow with the map, the lists with a camera's needs."""
+    flags = _capi.SPLAT_LAYOUT_SSIM | _capi.SPLAT_LAYOUT_TILE_ORDER | _capi.SPLAT_LAYOUT_RECS | (_capi.SPLAT_LAYOUT_OUTLIER if outlier else 0)
+    return _capi.iter_workspace_layout(int(rows), W, H, int(capacity), int(group_stride), flags)
+
+
+def _new(dev, lay, name, dtype, tail=()):
+    n = lay.bytes[name] // torch.empty((), dtype=dtype).element_size()
+    t = (torch.zeros if lay.zero_init[name] else torch.empty)(n, dtype=dtype, device=dev)
+    return t.view((-1,) + tuple(tail)) if tail else t
+
+
+class _Camera:
+    """What ONE camera of a ``FusedEngine`` owns: its size and launch struct, the per-pixel and per-tile arrays, the lists and what has
+    been learnt about them, the tile orders.  Arrays live in ``buf`` under the names the engine's ``buf`` shows them by.  Complete when
+    the constructor returns; the map, its Adam state and the per-Gaussian scratch are the engine's."""
+    # workspace arrays by the library's field names: (name in the layout, key in ``buf``, dtype)
+    _FIXED_ARRAYS = (("st.tile_count", "tile_count", torch.int32), ("st.tile_base", "tile_base", torch.int32),
+                     ("st.tile_cursor", "tile_cursor", torch.int32), ("st.long_base", "long_base", torch.int32),
+                     ("st.group_count", "group_count", torch.int32), ("st.status", "status", torch.int32),
+                     ("st.tile_work", "tile_work", torch.int32), ("st.tile_order", "tile_order", torch.int32),
+                     ("st.final_T", "final_T", torch.float32), ("st.n_contrib", "n_contrib", torch.int32),
+                     ("out6", "out6", torch.float32), ("dL_dout6", "dL_dout6", torch.float32),
+                     ("ssim_maps", "ssim_maps", torch.float32), ("sums", "sums", torch.float64), ("d_cam", "d_cam", torch.float32))
+
+    def __init__(self, dev, settings, rows, capacity, use_recs):
+        """settings: a GaussianRasterizationSettings; rows: the map's row capacity; capacity: (Gaussian, tile) instances the lists
+        hold.  List statistics start unknown: the camera learns them on its first use (``FusedEngine.check_overflow``)."""
+        self.dev, self.settings = dev, settings
+        self.H, self.W = H, W = int(settings.image_height), int(settings.image_width)
+        self.num_tiles = int(_capi.lib().splat_num_tiles(W, H))
+        GT = _capi.SPLAT_GROUP_TILES
+        self.num_groups = (((W + 15) // 16 + GT - 1) // GT) * (((H + 15) // 16 + GT - 1) // GT)
+        self.struct = self._make_struct(settings)   # (raises for a camera the fused path cannot render, before anything is allocated)
+        self.buf = {}
+        self._alloc_fixed(_layout(W, H, rows))
+        # launch order of the composites' workgroups (SplatState.tile_work / tile_order): heaviest tiles of every XCD band first.  An entry
+        # holds tile + 1; the zero-initialised buffer of the library's layout IS the natural order.  One order PER VIEW (keyed by the
+        # frame's time index, the last 64 views): an iteration leaves the order for the NEXT visit of its view.  Mapping draws a random
+        # keyframe per iteration (/root/reference/scripts/splatam.py:831-845): the order the previous iteration left belongs to another view
+        self._natural_order, self._orders = torch.zeros_like(self.buf['tile_order']), {}
+        self.max_list_hint = 0          # longest tile list seen at the last check_overflow(); 0 = unknown
+        self.tile_stride = 0            # > 0: bucketed lists (no scan / scatter pass), learnt by check_overflow()
+        self._tile_rows = None          # (begin, end): the band of tile rows the next iteration composites (tile-row-sharded tracking)
+        self._stats_partial = False     # the last iteration's list statistics cover a band only: check_overflow() does not learn from them
+        self.sub_bins = 1               # counters per tile on the exact-list path (16 once lists get very long: SplatState.sub_bins)
+        self.learnt_P = None            # rows of the map the list statistics were learnt on (keep_lists)
+        self.alloc_lists(capacity, use_recs)
+
+    def _make_struct(self, settings):
+        if float(settings.bg.abs().max()) != 0.0:
+            raise RuntimeError("the fused iteration renders with a zero background (as setup_camera builds it)")
+        view = _cached_contiguous(settings.viewmatrix)
+        proj = _cached_contiguous(settings.projmatrix)
+        campos = _cached_contiguous(settings.campos)
+        bg6 = torch.zeros(8, dtype=torch.float32, device=self.dev)
+        cam = _capi.SplatCamera()
+        cam.image_height, cam.image_width = self.H, self.W
+        cam.tanfovx, cam.tanfovy = float(settings.tanfovx), float(settings.tanfovy)
+        cam.bg, cam.scale_modifier = bg6.data_ptr(), float(settings.scale_modifier)
+        cam.viewmatrix, cam.projmatrix = view.data_ptr(), proj.data_ptr()
+        cam.sh_degree, cam.campos, cam.prefiltered = 0, campos.data_ptr(), 0
+        self._struct_keep = (bg6, view, proj, campos)
+        return cam
+
+    def _alloc_fixed(self, lay):
+        for name, key, dtype in self._FIXED_ARRAYS:
+            self.buf[key] = _new(self.dev, lay, name, dtype)
+        for key, lead in (('final_T', ()), ('n_contrib', ()), ('out6', (6,)), ('dL_dout6', (6,)), ('ssim_maps', (9,))):
+            self.buf[key] = self.buf[key].view(lead + (self.H, self.W))
+
+    def alloc_lists(self, capacity, use_recs):
+        self.capacity = int(capacity)
+        lay = _layout(self.W, self.H, capacity=self.capacity)
+        for name, key, dtype in (("st.keys", "keys", torch.int64), ("st.keys_alt", "keys_alt", torch.int64),        # keys_alt: merge passes of lists beyond LDS
+                                 ("st.point_list", "point_list", torch.int32),
+                                 # work-item table of the multi-workgroup sort (SplatState.long_items): one word per 1024 keys of a long list
+                                 ("st.long_items", "long_items", torch.int32)):
+            self.buf[key] = _new(self.dev, lay, name, dtype)
+        # the staged record of every list entry, handed from the forward to the backward composite (SplatState.tile_recs: 48 bytes per
+        # slot; left out beyond 16 GB -- the clustered stress scenes' hundreds of millions of slots -- where the backward composite
+        # gathers as before)
+        self.buf['tile_recs'] = None
+        if use_recs and lay.bytes["st.tile_recs"] <= 16 << 30:
+            self.buf['tile_recs'] = _new(self.dev, lay, "st.tile_recs", torch.float32)
+
+    def alloc_group_recs(self, group_stride):   # the records of group binning, when first needed or outgrown (FusedEngine._workspace)
+        recs = self.buf['group_recs'] = _new(self.dev, _layout(self.W, self.H, group_stride=group_stride), "st.group_recs", torch.int32)
+        assert recs.numel() == self.num_groups * group_stride * 4
+        return recs
+
+    def alloc_outlier_scratch(self):            # of the median selection (ignore_outlier_depth_loss), on first use
+        lay = _layout(self.W, self.H, outlier=True)
+        self.buf['outlier_err'] = _new(self.dev, lay, "outlier_err", torch.float32)
+        self.buf['outlier_scratch'] = _new(self.dev, lay, "outlier_scratch", torch.int32)
+
+    def set_sub_bins(self, S):
+        """Very long per-tile lists stay on the exact-list path (their buckets would not fit); their count / scatter atomics
+        are then spread over S counters per tile (same-address serialisation otherwise: 0.9 ms per pass at 11 M instances)."""
+        if S == self.sub_bins:
+            return
+        CS = _capi.SPLAT_COUNTER_STRIDE
+        self.sub_bins = S
+        self.buf['tile_count'] = torch.zeros(self.num_tiles * CS * S, dtype=torch.int32, device=self.dev)
+        self.buf['tile_cursor'] = torch.zeros(self.num_tiles * CS * S, dtype=torch.int32, device=self.dev)
+
+    def select_order(self, view):
+        """Point ``buf['tile_order']`` at the launch order view ``view`` left at its last visit (the natural order at its first)."""
+        o = self._orders.pop(view, None)
+        if o is None:
+            if len(self._orders) >= 64:
+                self._orders.pop(next(iter(self._orders)))          # the view visited longest ago
+            o = self._natural_order.clone()
+        self._orders[view] = o                                      # (most recently visited last)
+        self.buf['tile_order'] = o
+
+    def keep_lists(self, P, within, only_bucketed):
+        """Keep or forget the list statistics for a map of ``P`` rows: kept when the rows moved by less than ``within`` of the rows the
+        statistics were learnt on.  ``only_bucketed``: a camera without buckets (``tile_stride == 0``) forgets in any case, which
+        resets a ``max_list_hint`` it still holds."""
+        ref = self.learnt_P
+        if ref is None or (only_bucketed and self.tile_stride == 0) or abs(P - ref) > within * max(ref, 1):
+            self.tile_stride, self.max_list_hint = 0, 0     # exact lists until check_overflow() / relearn_lists() learns them again
 
 
 class FusedEngine:
@@ -50,10 +178,8 @@ class FusedEngine:
         if dev.type != "cuda":
             raise RuntimeError("FusedEngine needs CUDA/HIP tensors; the HIP library has no CPU path")
         self.dev = dev
-        for k in PARAM_ORDER + ("cam_unnorm_rots", "cam_trans"):
-            t = params[k]
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise RuntimeError(f"params['{k}'] must be a contiguous float32 tensor on {dev}")
+        self._check_params(params)
+        # ---- the map, once: parameters / ``store``, per-Gaussian scratch rows, pose state, gradients and Adam moments; its arrays are in ``map_buf``
         P = params['means3D'].shape[0]
         self.P = P
         self.iso = params['log_scales'].shape[1] == 1
@@ -64,37 +190,14 @@ class FusedEngine:
             self._adopt(params, variables)
         elif variables is not None and track_max_radius is None:
             track_max_radius = variables.get('max_2D_radius')
-        P_alloc = self.Pcap
         self.num_frames = params['cam_unnorm_rots'].shape[-1]
-        f32, i32 = torch.float32, torch.int32
-        z = dict(device=dev)
-        b = self.buf = {}
-        # launch order of the composites' workgroups (SplatState.tile_work / tile_order): heaviest tiles of every XCD band first.  An entry
-        # holds tile + 1; the zero-initialised buffer of the library's layout IS the natural order
-        self.tile_order_on = os.environ.get("SPLAT_TILE_ORDER", "1") != "0"
-        # ... one order PER VIEW (keyed by the frame's time index, the last 64 views): an iteration leaves the order for the NEXT visit
-        # of its view.  Mapping draws a random keyframe per iteration (/root/reference/scripts/splatam.py:831-845): the order the
-        # previous iteration left belongs to another view
-        self.order_per_view = os.environ.get("SPLAT_TILE_ORDER_PER_VIEW", "1") != "0"
-        self.use_recs = {"0": 0, "1": 1}.get(os.environ.get("SPLAT_TILE_RECS", "auto"), 2)      # SplatState.tile_recs: 0 never, 1 always, 2 by list length
-        # what belongs to a CAMERA (size, launch struct, per-pixel and per-tile arrays, lists, list statistics, tile orders) lives in
-        # the attributes and ``buf`` entries named by _CAMERA_ATTRS / _camera_bufs(); the engine holds the current camera's there and
-        # the others' in ``_cams`` (add_camera / _activate).  Everything else -- the map, its Adam state, the per-Gaussian scratch, the
-        # pose state -- exists once
-        self._cams, self._cur, self._cam_ok = [None], 0, {}
-        self.auto_cameras = False       # True: a curr_data['cam'] the engine does not know is registered on first use (add_camera)
-        self._init_camera(cam, capacity)
-        # every array of the iteration's workspace is sized by the LIBRARY (splat_iter_workspace_layout, include/splat_hip.h "Scratch
-        # layouts"); they are tensors of their own here because the per-Gaussian ones grow with the map (_grow_rows / rebind)
-        self._alloc_rows(self._layout(P_alloc))
-        b['pose_state'] = torch.zeros(_capi.SPLAT_POSE_STATE, dtype=f32, **z)
+        self.map_buf = {}
+        self._alloc_rows(_layout(int(cam.image_width), int(cam.image_height), self.Pcap))
+        self.map_buf['pose_state'] = torch.zeros(_capi.SPLAT_POSE_STATE, dtype=torch.float32, device=dev)
         self.max_2D_radius = self.store['max_2D_radius'] if self.managed else track_max_radius
-        b['counts'] = torch.zeros(8, dtype=i32, **z)
-        # map gradients: ONE flat buffer (the all-reduce bucket of the view-sharded mapping step), viewed per parameter
+        self.map_buf['counts'] = torch.zeros(8, dtype=torch.int32, device=dev)
         self._widths = [3, 3, 4, 1, 1 if self.iso else 3]
-        self._grad_store = torch.zeros(_FLAG_SLOTS + sum(self._widths) * P_alloc, dtype=f32, **z)
-        self._m_store = {k: torch.zeros(P_alloc, w, dtype=f32, **z) for k, w in zip(PARAM_ORDER, self._widths)}
-        self._v_store = {k: torch.zeros(P_alloc, w, dtype=f32, **z) for k, w in zip(PARAM_ORDER, self._widths)}
+        self._alloc_map_state(self.Pcap)
         self._layout_rows()
         self.map_step = 0
         self.pose_step = 0
@@ -118,52 +221,27 @@ class FusedEngine:
         self.track_fused_full = os.environ.get("SPLAT_TRACK_FUSED_FULL", "1") != "0"   # ... also when the map's gradients are wanted (the mapping form inside)
         self.fold_sums = os.environ.get("SPLAT_FOLD_SUMS", "1") != "0"     # tile-row-sharded tracking: exchange 256 B instead of 16 KB
         self.skipped_iterations = 0     # of the last check_overflow() / digest_report(): iterations whose Adam step the device skipped
+        # ---- the cameras: each a _Camera that owns what belongs to it; ``_camera`` names the current one, whose arrays ``buf`` shows beside
+        # the map's.  The engine's: whether the composites launch in a learnt order, one per view, and whether records are staged
+        self.tile_order_on = os.environ.get("SPLAT_TILE_ORDER", "1") != "0"
+        self.order_per_view = os.environ.get("SPLAT_TILE_ORDER_PER_VIEW", "1") != "0"
+        self.use_recs = {"0": 0, "1": 1}.get(os.environ.get("SPLAT_TILE_RECS", "auto"), 2)      # SplatState.tile_recs: 0 never, 1 always, 2 by list length
+        self._cams, self._cam_ok, self._camera = [], {}, None
+        self.auto_cameras = False       # True: a curr_data['cam'] the engine does not know is registered on first use (add_camera)
+        self.add_camera(cam, capacity)
+
+    def _check_params(self, params):
+        for k in PARAM_ORDER + ("cam_unnorm_rots", "cam_trans"):
+            t = params[k]
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.dev:
+                raise RuntimeError(f"params['{k}'] must be a contiguous float32 tensor on {self.dev}")
 
     # ------------------------------------------------------------------ cameras
-    _CAMERA_ATTRS = ("cam_settings", "H", "W", "num_tiles", "num_groups", "capacity", "_cam", "_cam_keep", "tile_stride", "max_list_hint",
-                     "sub_bins", "_learnt_P", "_stats_partial", "_orders", "_natural_order", "_tile_rows")
-    _LIST_BUFS = ("keys", "keys_alt", "point_list", "long_items", "tile_recs", "group_recs", "outlier_err", "outlier_scratch")
-
-    def _init_camera(self, cam, capacity=None):
-        """The current camera's state from scratch: size, fixed arrays, lists of ``capacity`` instances, unknown list statistics."""
-        self.cam_settings = cam
-        H, W = int(cam.image_height), int(cam.image_width)
-        self.H, self.W = H, W
-        self.num_tiles = int(self.L.splat_num_tiles(W, H))
-        GT = _capi.SPLAT_GROUP_TILES
-        self.num_groups = (((W + 15) // 16 + GT - 1) // GT) * (((H + 15) // 16 + GT - 1) // GT)
-        self._cam = self._make_cam(cam)             # (raises for a camera the fused path cannot render, before anything is allocated)
-        self._alloc_fixed(self._layout(self.Pcap))
-        self._natural_order, self._orders = torch.zeros_like(self.buf['tile_order']), {}
-        self.max_list_hint = 0          # longest tile list seen at the last check_overflow(); 0 = unknown
-        self.tile_stride = 0            # > 0: bucketed lists (no scan / scatter pass), learnt by check_overflow()
-        self._tile_rows = None          # (begin, end): the band of tile rows the next iteration composites (tile-row-sharded tracking)
-        self._stats_partial = False     # the last iteration's list statistics cover a band only: check_overflow() does not learn from them
-        self.sub_bins = 1               # counters per tile on the exact-list path (16 once lists get very long: SplatState.sub_bins)
-        self._learnt_P = None           # rows of the map the list statistics were learnt on (rebind keeps them for a similar map)
-        self._alloc_lists(int(capacity) if capacity else 4 * self.P + 65536)
-
-    def _camera_bufs(self):
-        return tuple(key for _, key, _ in self._FIXED_ARRAYS) + self._LIST_BUFS
-
-    def _stash(self):
-        """The current camera's attributes and arrays, as they are now, into its entry of ``_cams``."""
-        st = {a: getattr(self, a) for a in self._CAMERA_ATTRS}
-        st['buf'] = {k: self.buf[k] for k in self._camera_bufs() if k in self.buf}
-        self._cams[self._cur] = st
-
-    def _activate(self, index):
-        """Make camera ``index`` the current one: attribute and dict moves only -- no allocation, no launch, nothing read."""
-        if index == self._cur:
-            return
-        self._stash()
-        st = self._cams[index]
-        for a in self._CAMERA_ATTRS:
-            setattr(self, a, st[a])
-        for k in self._camera_bufs():
-            self.buf.pop(k, None)
-        self.buf.update(st['buf'])
-        self._cams[index], self._cur = None, index      # (the current camera's state lives on the engine: no second reference to its arrays)
+    def _use(self, camera):
+        """Make ``camera`` the current one: two references -- no allocation, no launch, nothing read."""
+        if camera is not self._camera:
+            self._camera = camera   # (``buf``: what callers read.  Read-only: the engine's own writes name the owner's dict)
+            self.buf = MappingProxyType(ChainMap(camera.buf, self.map_buf))
 
     def _same_camera(self, cam, ref):
         return (int(cam.image_height) == int(ref.image_height) and int(cam.image_width) == int(ref.image_width)
@@ -178,9 +256,8 @@ class FusedEngine:
         hit = self._cam_ok.get(id(cam))
         if hit is not None:
             return hit[1]
-        for i in range(len(self._cams)):
-            ref = self.cam_settings if i == self._cur else self._cams[i]['cam_settings']
-            if cam is ref or self._same_camera(cam, ref):
+        for i, known in enumerate(self._cams):
+            if cam is known.settings or self._same_camera(cam, known.settings):
                 self._cam_ok[id(cam)] = (cam, i)        # keeps the tuple alive, so the id stays unique
                 return i
         return None
@@ -188,6 +265,11 @@ class FusedEngine:
     @property
     def num_cameras(self):
         return len(self._cams)
+
+    def is_current(self, cam):
+        """The settings ``cam`` are, or equal, the current camera's: selecting them would change nothing."""
+        i = self._find_camera(cam)
+        return i is not None and self._cams[i] is self._camera
 
     def add_camera(self, cam, capacity=None):
         """Register another camera (a GaussianRasterizationSettings) on this engine's map and make it the current one; a camera the
@@ -199,25 +281,12 @@ class FusedEngine:
         camera's own flag is down, so its iteration would step on it."""
         i = self._find_camera(cam)
         if i is None:
-            self._stash()
-            held = {k: self.buf.pop(k) for k in self._camera_bufs() if k in self.buf}
-            self._cams.append(None)
-            prev, self._cur = self._cur, len(self._cams) - 1
-            try:
-                self._init_camera(cam, capacity)
-            except Exception:
-                self._cams.pop()
-                self._cur = prev
-                for a in self._CAMERA_ATTRS:
-                    setattr(self, a, self._cams[prev][a])
-                for k in self._camera_bufs():
-                    self.buf.pop(k, None)
-                self.buf.update(held)
-                self._cams[prev] = None
-                raise
-            self._cam_ok[id(cam)] = (cam, self._cur)
-            return self._cur
-        self._activate(i)
+            # built completely before the engine learns of it: a camera the fused path refuses leaves the engine as it was
+            new = _Camera(self.dev, cam, self.Pcap, int(capacity) if capacity else 4 * self.P + 65536, self.use_recs)
+            i = len(self._cams)
+            self._cams.append(new)
+            self._cam_ok[id(cam)] = (cam, i)
+        self._use(self._cams[i])
         return i
 
     def select_camera(self, cam):
@@ -226,44 +295,31 @@ class FusedEngine:
         i = self._find_camera(cam)
         if i is None:
             raise RuntimeError("select_camera: this FusedEngine does not know that camera (add_camera registers it)")
-        self._activate(i)
+        self._use(self._cams[i])
         return i
 
-    def _other_cameras(self):
-        return [st for i, st in enumerate(self._cams) if i != self._cur]
+    def _keep_lists(self, within, only_bucketed):
+        """Every camera keeps or forgets its list statistics for the map as it is now, on the rows ITS statistics were learnt on."""
+        for camera in self._cams:
+            camera.keep_lists(self.P, within, only_bucketed)
 
     # ------------------------------------------------------------------ capacity-managed map
-    # workspace arrays by the library's field names: (key in self.buf, dtype, trailing shape); per-Gaussian ones grow with the map
+    # the per-Gaussian workspace arrays by the library's field names: (name in the layout, key in ``map_buf``, dtype, trailing shape)
     _ROW_ARRAYS = (("st.conic_opacity", "conic", torch.float32, (4,)), ("st.xy", "xy", torch.float32, (2,)), ("st.rect", "rect", torch.int32, (2,)),
                    ("st.depth", "depth", torch.float32, ()), ("st.radii", "radii", torch.int32, ()), ("feat8", "feat8", torch.float32, (8,)),
                    ("accum", "accum", torch.float32, (_capi.SPLAT_GRAD_STRIDE,)))
-    _FIXED_ARRAYS = (("st.tile_count", "tile_count", torch.int32), ("st.tile_base", "tile_base", torch.int32),
-                     ("st.tile_cursor", "tile_cursor", torch.int32), ("st.long_base", "long_base", torch.int32),
-                     ("st.group_count", "group_count", torch.int32), ("st.status", "status", torch.int32),
-                     ("st.tile_work", "tile_work", torch.int32), ("st.tile_order", "tile_order", torch.int32),
-                     ("st.final_T", "final_T", torch.float32),
-                     ("st.n_contrib", "n_contrib", torch.int32), ("out6", "out6", torch.float32), ("dL_dout6", "dL_dout6", torch.float32),
-                     ("ssim_maps", "ssim_maps", torch.float32), ("sums", "sums", torch.float64), ("d_cam", "d_cam", torch.float32))
-
-    def _layout(self, rows, capacity=0, group_stride=0, outlier=False):
-        flags = _capi.SPLAT_LAYOUT_SSIM | _capi.SPLAT_LAYOUT_TILE_ORDER | _capi.SPLAT_LAYOUT_RECS | (_capi.SPLAT_LAYOUT_OUTLIER if outlier else 0)
-        return _capi.iter_workspace_layout(int(rows), self.W, self.H, int(capacity), int(group_stride), flags)
-
-    def _new(self, lay, name, dtype, tail=()):
-        n = lay.bytes[name] // torch.empty((), dtype=dtype).element_size()
-        t = (torch.zeros if lay.zero_init[name] else torch.empty)(n, dtype=dtype, device=self.dev)
-        return t.view((-1,) + tuple(tail)) if tail else t
-
-    def _alloc_fixed(self, lay):
-        for name, key, dtype in self._FIXED_ARRAYS:
-            self.buf[key] = self._new(lay, name, dtype)
-        H, W = self.H, self.W
-        for key, lead in (('final_T', ()), ('n_contrib', ()), ('out6', (6,)), ('dL_dout6', (6,)), ('ssim_maps', (9,))):
-            self.buf[key] = self.buf[key].view(lead + (H, W))
 
     def _alloc_rows(self, lay):
         for name, key, dtype, tail in self._ROW_ARRAYS:
-            self.buf[key] = self._new(lay, name, dtype, tail)
+            self.map_buf[key] = _new(self.dev, lay, name, dtype, tail)
+
+    def _alloc_map_state(self, rows):
+        """Gradients and Adam moments of a map of up to ``rows`` rows, zeroed.  The gradients are ONE flat buffer (the all-reduce bucket
+        of the view-sharded mapping step), viewed per parameter (_layout_rows)."""
+        z = dict(dtype=torch.float32, device=self.dev)
+        self._grad_store = torch.zeros(_FLAG_SLOTS + sum(self._widths) * rows, **z)
+        self._m_store = {k: torch.zeros(rows, w, **z) for k, w in zip(PARAM_ORDER, self._widths)}
+        self._v_store = {k: torch.zeros(rows, w, **z) for k, w in zip(PARAM_ORDER, self._widths)}
 
     def _adopt(self, params, variables):
         """Move the caller's Gaussian tensors into backing arrays of ``self.Pcap`` rows."""
@@ -318,11 +374,7 @@ class FusedEngine:
         (gaussian_capacity) are edited through add_new_gaussians / remove_points instead."""
         if self.managed:
             raise RuntimeError("rebind is for engines on caller-owned tensors")
-        dev = self.dev
-        for k in PARAM_ORDER + ("cam_unnorm_rots", "cam_trans"):
-            t = params[k]
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
-                raise RuntimeError(f"params['{k}'] must be a contiguous float32 tensor on {dev}")
+        self._check_params(params)
         if (params['log_scales'].shape[1] == 1) != self.iso or params['cam_unnorm_rots'].shape[-1] != self.num_frames:
             raise RuntimeError("rebind: the map's layout (isotropy, number of frames) differs from the engine's")
         P = int(params['means3D'].shape[0])
@@ -332,49 +384,34 @@ class FusedEngine:
             # per-Gaussian scratch for the grown map (+12.5 %: the next few edits fit); accum must be zero, the others are written
             # by the per-Gaussian kernel before they are read
             cap = P + P // 8 + 1024
-            f32, i32, b = torch.float32, torch.int32, self.buf
-            self._alloc_rows(self._layout(cap))
-            self._grad_store = torch.zeros(_FLAG_SLOTS + sum(self._widths) * cap, dtype=f32, device=dev)
-            self._m_store = {k: torch.zeros(cap, w, dtype=f32, device=dev) for k, w in zip(PARAM_ORDER, self._widths)}
-            self._v_store = {k: torch.zeros(cap, w, dtype=f32, device=dev) for k, w in zip(PARAM_ORDER, self._widths)}
+            self._alloc_rows(_layout(self._camera.W, self._camera.H, cap))
+            self._alloc_map_state(cap)
             self.Pcap = cap
         changed = P != self.P
         self.P = P
         self._layout_rows()
         if changed:
-            ref = self._learnt_P
-            if ref is None or abs(P - ref) > keep_lists_within * max(ref, 1):
-                self.tile_stride = 0
-                self.max_list_hint = 0
-            for st in self._other_cameras():
-                ref = st['_learnt_P']
-                if ref is None or abs(P - ref) > keep_lists_within * max(ref, 1):
-                    st['tile_stride'] = 0
-                    st['max_list_hint'] = 0
+            # (a camera that holds a list length but no buckets keeps it here; a map edit, _set_rows, drops it)
+            self._keep_lists(keep_lists_within, only_bucketed=False)
         return self
 
     def _grow_rows(self, new_cap):
         """Re-allocate every per-Gaussian array for ``new_cap`` rows (contents of the first P rows kept)."""
         if not self.managed:
             raise RuntimeError("this FusedEngine was built without gaussian_capacity: the map cannot grow")
-        dev, P, b = self.dev, self.P, self.buf
-        f32, i32 = torch.float32, torch.int32
-
-        def grown(t, rows):
-            n = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-            n[:P] = t[:P]
-            return n
+        dev, P = self.dev, self.P
         self.Pcap = int(new_cap)
-        for k in list(self.store):
-            self.store[k] = grown(self.store[k], self.Pcap)
+        for k, t in self.store.items():
+            self.store[k] = torch.zeros((self.Pcap,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
+            self.store[k][:P] = t[:P]
+        m, v = self._m_store, self._v_store
+        self._alloc_map_state(self.Pcap)
         for k in PARAM_ORDER:
-            self._m_store[k] = grown(self._m_store[k], self.Pcap)
-            self._v_store[k] = grown(self._v_store[k], self.Pcap)
-        self._grad_store = torch.zeros(_FLAG_SLOTS + sum(self._widths) * self.Pcap, dtype=f32, device=dev)
-        self._alloc_rows(self._layout(self.Pcap))
-        b.pop('flags', None)
-        b.pop('stage', None)
-        b.pop('map_scratch', None)
+            self._m_store[k][:P] = m[k][:P]
+            self._v_store[k][:P] = v[k][:P]
+        self._alloc_rows(_layout(self._camera.W, self._camera.H, self.Pcap))
+        for key in ('flags', 'stage', 'map_scratch'):          # (sized by the rows: allocated again when next needed)
+            self.map_buf.pop(key, None)
         self._publish()
         self._layout_rows()
 
@@ -390,15 +427,21 @@ class FusedEngine:
             st.means2D_gradient_accum = self.store['means2D_gradient_accum'].data_ptr()
             st.denom = self.store['denom'].data_ptr()
             st.timestep = self.store['timestep'].data_ptr()
-        st.counts = self.buf['counts'].data_ptr()
+        st.counts = self.map_buf['counts'].data_ptr()
         return st
 
     def _map_scratch(self, n):
         words = int(self.L.splat_map_scratch_words(int(n)))
-        sc = self.buf.get('map_scratch')
+        sc = self.map_buf.get('map_scratch')
         if sc is None or sc.numel() < words:
-            sc = self.buf['map_scratch'] = torch.zeros(words, dtype=torch.int32, device=self.dev)
+            sc = self.map_buf['map_scratch'] = torch.zeros(words, dtype=torch.int32, device=self.dev)
         return sc
+
+    def _flags(self):               # one byte per row of the map: the selection of a pruning / densification step
+        f = self.map_buf.get('flags')
+        if f is None or f.numel() < self.Pcap:
+            f = self.map_buf['flags'] = torch.empty(self.Pcap, dtype=torch.uint8, device=self.dev)
+        return f
 
     def _set_rows(self, P, keep_lists_within=0.10):
         self.P = int(P)
@@ -409,31 +452,51 @@ class FusedEngine:
         # loop's edits: +0.7 % per add_new_gaussians, a handful of rows per pruning): the buckets are 1.5x the longest list seen, the
         # statistics are refreshed at the end of every phase, and a list that does outgrow its bucket raises the flag (the skipped
         # iterations are run again), so stale statistics can cost time, never a wrong step
-        ref = self._learnt_P
-        if ref is None or self.tile_stride == 0 or abs(self.P - ref) > keep_lists_within * max(ref, 1):
-            self.tile_stride = 0
-            self.max_list_hint = 0
-        for st in self._other_cameras():        # the same decision for every other camera, on the rows ITS statistics were learnt on
-            ref = st['_learnt_P']
-            if ref is None or st['tile_stride'] == 0 or abs(self.P - ref) > keep_lists_within * max(ref, 1):
-                st['tile_stride'] = 0
-                st['max_list_hint'] = 0
+        # (only_bucketed: a camera that holds a list length but no buckets drops it as well; rebind keeps it)
+        self._keep_lists(keep_lists_within, only_bucketed=True)
+
+    def _frame(self, curr_data, time_idx, images=True):
+        """The SplatFrameData of ``curr_data`` at pose ``time_idx`` (``images``: with its planes); ``_frame_keep`` keeps what it names alive.
+        curr_data['w2c'] as the kernels read it: 16 contiguous floats on the engine's device (row 2 is the depth channel of
+        the depth / silhouette render).  Anything else -- float64 from an inverse taken in double, a CPU tensor, a batch of
+        matrices -- would be read as 16 floats of something else; the reference's own matmul raises a RuntimeError for a dtype or
+        device mismatch (/root/reference/utils/slam_helpers.py:196-213), and so does this, before anything is launched.
+        Attribute reads only; a non-contiguous view is made contiguous."""
+        w2c = curr_data['w2c']
+        if not (isinstance(w2c, torch.Tensor) and w2c.dtype == torch.float32 and w2c.device == self.dev and tuple(w2c.shape) == (4, 4)):
+            got = f"{w2c.dtype}, {tuple(w2c.shape)}, {w2c.device}" if isinstance(w2c, torch.Tensor) else type(w2c).__name__
+            raise RuntimeError(f"curr_data['w2c'] must be a float32 tensor of shape [4, 4] on {self.dev} (got {got})")
+        if not w2c.is_contiguous():
+            w2c = w2c.contiguous()
+        fr = _capi.SplatFrameData()
+        fr.w2c, fr.time_idx = w2c.data_ptr(), int(time_idx)
+        if images:
+            im, depth = curr_data['im'], curr_data['depth']
+            if not (im.is_contiguous() and depth.is_contiguous()):
+                im, depth = im.contiguous(), depth.contiguous()
+            fr.im, fr.depth = im.data_ptr(), depth.data_ptr()
+            self._frame_keep = (im, depth, w2c)
+        else:
+            self._frame_keep = (w2c,)
+        return fr
+
+    def _whole_frame_workspace(self, time_idx):
+        """The workspace of a forward-only render of the whole frame (its list statistics are the frame's) in view ``time_idx``'s order."""
+        self._camera._tile_rows, self._camera._stats_partial = None, False
+        self._select_order(int(time_idx))
+        ws = self._workspace(False, with_ssim=False)
+        ws.max_2D_radius = None
+        return ws
 
     def render(self, curr_data, time_idx):
         """Forward-only 6-channel render of the map from pose ``time_idx`` (no loss, no gradients): returns
         ``rendered()``.  The render of add_new_gaussians (/root/reference/scripts/splatam.py:381-385)."""
         self._check_cam(curr_data)
-        fr = _capi.SplatFrameData()
-        w2c = self._frame_w2c(curr_data)
-        fr.im, fr.depth, fr.w2c, fr.time_idx = None, None, w2c.data_ptr(), int(time_idx)
-        self._frame_keep = (w2c,)
-        self._tile_rows, self._stats_partial = None, False         # a whole-frame render: its list statistics are the frame's
-        self._select_order(int(time_idx))
-        ws = self._workspace(False, with_ssim=False)
-        ws.max_2D_radius = None
+        fr = self._frame(curr_data, time_idx, images=False)
+        ws = self._whole_frame_workspace(time_idx)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_iter_render(C.byref(self._cam), C.byref(m), C.byref(fr), C.byref(ws), self._stream()),
+            _capi.check(self.L.splat_iter_render(C.byref(self._camera.struct), C.byref(m), C.byref(fr), C.byref(ws), self._stream()),
                         "splat_iter_render")
         return self.rendered()
 
@@ -445,25 +508,17 @@ class FusedEngine:
         table, when it pleases.  The planes stay in ``rendered()``."""
         self._check_cam(curr_data)
         _check_eval_row(out_row, self.dev)
-        fr = _capi.SplatFrameData()
-        im, depth = curr_data['im'], curr_data['depth']
-        for name, t, c in (("im", im, 3), ("depth", depth, 1)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, self.H, self.W)):
-                raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {self.H}, {self.W}] on {self.dev}")
-        w2c = self._frame_w2c(curr_data)
-        if not (im.is_contiguous() and depth.is_contiguous()):
-            im, depth = im.contiguous(), depth.contiguous()
-        fr.im, fr.depth, fr.w2c, fr.time_idx = im.data_ptr(), depth.data_ptr(), w2c.data_ptr(), int(time_idx)
-        self._frame_keep = (im, depth, w2c)
-        self._tile_rows, self._stats_partial = None, False
-        self._select_order(int(time_idx))
-        ews, _ = eval_workspace(self.dev, self.W, self.H, ms_ssim)
+        cam = self._camera
+        for name, t, c in (("im", curr_data['im'], 3), ("depth", curr_data['depth'], 1)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, cam.H, cam.W)):
+                raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {cam.H}, {cam.W}] on {self.dev}")
+        fr = self._frame(curr_data, time_idx)
+        ews, _ = eval_workspace(self.dev, cam.W, cam.H, ms_ssim)
         cfg = _eval_config(sil_thres, sil_mask, ms_ssim)
-        ws = self._workspace(False, with_ssim=False)
-        ws.max_2D_radius = None
+        ws = self._whole_frame_workspace(time_idx)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_iter_eval(C.byref(self._cam), C.byref(m), C.byref(fr), C.byref(cfg), C.byref(ws), C.byref(ews),
+            _capi.check(self.L.splat_iter_eval(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(cfg), C.byref(ws), C.byref(ews),
                                                out_row.data_ptr(), self._stream()), "splat_iter_eval")
 
     def evaluate_metrics(self, rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True):
@@ -475,15 +530,14 @@ class FusedEngine:
         They are a camera's own: of the camera of ``curr_data`` (which becomes the current one), or of the current camera."""
         if curr_data is not None:
             self._check_cam(curr_data)
-        return self.tile_stride > 0 and self.max_list_hint > 0
+        return self._camera.tile_stride > 0 and self._camera.max_list_hint > 0
 
     def relearn_lists(self, curr_data, time_idx):
         """One probe render with exact lists + ``check_overflow()``: sizes the list capacity and the per-tile buckets
         for the map as it is now (call after an edit that did not keep them -- ``lists_known()``; one D2H read).
         Of the camera of ``curr_data``."""
         self._check_cam(curr_data)
-        self.tile_stride = 0
-        self.max_list_hint = 0
+        self._camera.tile_stride, self._camera.max_list_hint = 0, 0
         for _ in range(3):
             self.render(curr_data, time_idx)
             if not self.check_overflow():
@@ -494,7 +548,8 @@ class FusedEngine:
         if not self.managed:
             raise RuntimeError("this FusedEngine was built without gaussian_capacity: the map cannot grow")
         self._check_cam(curr_data)          # the frame's camera: its size, its render (out6), its scratch plane
-        H, W = self.H, self.W
+        cam = self._camera
+        H, W = cam.H, cam.W
         im, depth = curr_data['im'].contiguous(), curr_data['depth'].contiguous()
         if tuple(im.shape) != (3, H, W) or tuple(depth.shape) != (1, H, W):
             raise RuntimeError("frame size differs from the engine's camera")
@@ -503,20 +558,20 @@ class FusedEngine:
         a = _capi.SplatAddArgs()
         a.mode, a.width, a.height = mode, W, H
         a.im, a.depth = im.data_ptr(), depth.data_ptr()
-        a.out6 = self.buf['out6'].data_ptr() if mode == _capi.SPLAT_ADD_NON_PRESENCE else None
+        a.out6 = cam.buf['out6'].data_ptr() if mode == _capi.SPLAT_ADD_NON_PRESENCE else None
         a.fx, a.fy, a.cx, a.cy, a.sil_thres, a.time_idx = fx, fy, cx, cy, float(sil_thres), int(time_idx)
         keep = (im, depth)
         if w2c is not None:
             w2c = w2c.to(device=self.dev, dtype=torch.float32).contiguous()
             a.w2c = w2c.data_ptr()
             keep += (w2c,)
-        a.err = self.buf['ssim_maps'].data_ptr()
+        a.err = cam.buf['ssim_maps'].data_ptr()
         a.scratch = self._map_scratch(max(H * W, self.Pcap)).data_ptr()
         while True:
             st = self._store_struct(with_moments=True)
             with torch.cuda.device(self.dev):
                 _capi.check(self.L.splat_map_add_new_gaussians(C.byref(st), C.byref(a), self._stream()), "splat_map_add_new_gaussians")
-            counts = self.buf['counts'].tolist()            # the one host sync of the edit
+            counts = self.map_buf['counts'].tolist()        # the one host sync of the edit
             if not counts[2]:
                 break
             self._grow_rows(int((self.P + counts[1]) * 1.5) + 1024)
@@ -546,8 +601,8 @@ class FusedEngine:
             else:
                 raise RuntimeError("add_new_gaussians: the per-tile lists could not be sized for the densification render")
         else:
-            self.buf['out6'][3] = depth_sil[0]
-            self.buf['out6'][4] = depth_sil[1]
+            out6 = self._camera.buf['out6']
+            out6[3], out6[4] = depth_sil[0], depth_sil[1]
         return self._append(_capi.SPLAT_ADD_NON_PRESENCE, curr_data, time_idx, sil_thres)
 
     def add_valid_depth_points(self, color, depth, intrinsics, w2c, time_idx=0, cam=None):
@@ -574,18 +629,16 @@ class FusedEngine:
         if to_remove is not None:
             keep = to_remove.to(device=self.dev, dtype=torch.uint8).contiguous()
             a.to_remove = keep.data_ptr()
-        b = self.buf
-        if 'flags' not in b:
-            b['flags'] = torch.empty(self.Pcap, dtype=torch.uint8, device=self.dev)
         st = self._store_struct(with_moments=True)
         need = ((self.Pcap + 3) // 4 * 4) * int(self.L.splat_map_row_floats(C.byref(st)))
-        if 'stage' not in b or b['stage'].numel() < need:
-            b['stage'] = torch.empty(need, dtype=torch.float32, device=self.dev)
-        a.flags, a.stage = b['flags'].data_ptr(), b['stage'].data_ptr()
+        stage = self.map_buf.get('stage')
+        if stage is None or stage.numel() < need:
+            stage = self.map_buf['stage'] = torch.empty(need, dtype=torch.float32, device=self.dev)
+        a.flags, a.stage = self._flags().data_ptr(), stage.data_ptr()
         a.scratch = self._map_scratch(max(self.H * self.W, self.Pcap)).data_ptr()
         with torch.cuda.device(self.dev):
             _capi.check(self.L.splat_map_prune(C.byref(st), C.byref(a), self._stream()), "splat_map_prune")
-        counts = b['counts'].tolist()
+        counts = self.map_buf['counts'].tolist()
         if counts[1]:
             self._set_rows(counts[0])
         return counts[1]
@@ -628,7 +681,7 @@ class FusedEngine:
         ws = self._workspace(False, with_ssim=False)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_iter_means2d_accumulate(C.byref(self._cam), C.byref(m), C.byref(ws),
+            _capi.check(self.L.splat_iter_means2d_accumulate(C.byref(self._camera.struct), C.byref(m), C.byref(ws),
                                                              self.store['means2D_gradient_accum'].data_ptr(), self.store['denom'].data_ptr(),
                                                              out.data_ptr() if out is not None and self.P else None, self._stream()),
                         "splat_iter_means2d_accumulate")
@@ -645,19 +698,16 @@ class FusedEngine:
         ws = self._workspace(False, with_ssim=False)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_iter_means2d_accumulate(C.byref(self._cam), C.byref(m), C.byref(ws), None, None, out.data_ptr(),
+            _capi.check(self.L.splat_iter_means2d_accumulate(C.byref(self._camera.struct), C.byref(m), C.byref(ws), None, None, out.data_ptr(),
                                                              self._stream()), "splat_iter_means2d_accumulate")
         return out
 
     def _densify_args(self, mode, thr, small, rows_with_grad, n=1, samples=None):
-        b = self.buf
-        if 'flags' not in b or b['flags'].numel() < self.Pcap:
-            b['flags'] = torch.empty(self.Pcap, dtype=torch.uint8, device=self.dev)
         a = _capi.SplatDensifyArgs()
         a.mode, a.grad_thresh, a.small_scale = mode, float(thr), float(small)
         a.rows_with_grad, a.num_to_split_into = int(rows_with_grad), int(n)
         a.samples = samples.data_ptr() if samples is not None and samples.numel() else None
-        a.flags = b['flags'].data_ptr()
+        a.flags = self._flags().data_ptr()
         a.scratch = self._map_scratch(max(self.H * self.W, self.Pcap)).data_ptr()
         return a
 
@@ -669,7 +719,7 @@ class FusedEngine:
             st = self._store_struct(with_moments=True)
             with torch.cuda.device(self.dev):
                 _capi.check(self.L.splat_map_densify_select(C.byref(st), C.byref(a), self._stream()), "splat_map_densify_select")
-            counts = self.buf['counts'].tolist()            # host sync (the reference synchronises on its boolean indexing here)
+            counts = self.map_buf['counts'].tolist()        # host sync (the reference synchronises on its boolean indexing here)
             if not counts[2]:
                 break
             self._grow_rows(int((self.P + counts[1] * n) * 1.5) + 1024)
@@ -678,7 +728,7 @@ class FusedEngine:
             return 0
         samples = None
         if mode == _capi.SPLAT_DENSIFY_SPLIT:
-            sel = self.buf['flags'][:self.P].bool()
+            sel = self.map_buf['flags'][:self.P].bool()
             ls = self.store['log_scales'][:self.P]
             stds = torch.exp(ls)[sel].repeat(n, 3) if self.iso else torch.exp(ls)[sel].repeat(n, 1)
             # (the reference's repeat(n, 3) of an [S, 3] anisotropic scale would be [S n, 9]: its densify only works for isotropic maps)
@@ -714,7 +764,7 @@ class FusedEngine:
                 self.store[k][:self.P].zero_()
             if S:
                 to_remove = torch.zeros(self.P, dtype=torch.uint8, device=self.dev)
-                to_remove[:P1] = self.buf['flags'][:P1]
+                to_remove[:P1] = self.map_buf['flags'][:P1]
                 self.remove_points(to_remove)
             op_thr = densify_dict['final_removal_opacity_threshold'] if iter == densify_dict['stop_after'] \
                 else densify_dict['removal_opacity_threshold']
@@ -728,63 +778,19 @@ class FusedEngine:
 
     # ------------------------------------------------------------------ plumbing
     def _alloc_lists(self, capacity):
-        self.capacity = int(capacity)
-        lay = self._layout(0, capacity=self.capacity)
-        for name, key, dtype in (("st.keys", "keys", torch.int64), ("st.keys_alt", "keys_alt", torch.int64),        # keys_alt: merge passes of lists beyond LDS
-                                 ("st.point_list", "point_list", torch.int32),
-                                 # work-item table of the multi-workgroup sort (SplatState.long_items): one word per 1024 keys of a long list
-                                 ("st.long_items", "long_items", torch.int32)):
-            self.buf[key] = self._new(lay, name, dtype)
-        # the staged record of every list entry, handed from the forward to the backward composite (SplatState.tile_recs: 48 bytes per
-        # slot; left out beyond 16 GB -- the clustered stress scenes' hundreds of millions of slots -- where the backward composite
-        # gathers as before)
-        self.buf['tile_recs'] = None
-        if self.use_recs and lay.bytes["st.tile_recs"] <= 16 << 30:
-            self.buf['tile_recs'] = self._new(lay, "st.tile_recs", torch.float32)
-
-    def _make_cam(self, settings):
-        bg = _cached_contiguous(settings.bg)
-        view = _cached_contiguous(settings.viewmatrix)
-        proj = _cached_contiguous(settings.projmatrix)
-        campos = _cached_contiguous(settings.campos)
-        if float(bg.abs().max()) != 0.0:
-            raise RuntimeError("the fused iteration renders with a zero background (as setup_camera builds it)")
-        bg6 = torch.zeros(8, dtype=torch.float32, device=self.dev)
-        cam = _capi.SplatCamera()
-        cam.image_height, cam.image_width = self.H, self.W
-        cam.tanfovx, cam.tanfovy = float(settings.tanfovx), float(settings.tanfovy)
-        cam.bg, cam.scale_modifier = bg6.data_ptr(), float(settings.scale_modifier)
-        cam.viewmatrix, cam.projmatrix = view.data_ptr(), proj.data_ptr()
-        cam.sh_degree, cam.campos, cam.prefiltered = 0, campos.data_ptr(), 0
-        self._cam_keep = (bg6, view, proj, campos)
-        return cam
+        self._camera.alloc_lists(capacity, self.use_recs)
 
     def _check_cam(self, curr_data):
         """The camera is the one of ``curr_data['cam']``, as the reference's get_loss reads it on every call
         (/root/reference/scripts/splatam.py:249): a settings tuple that equals a camera of this engine selects it.  One the engine does
         not know is registered on first use with ``auto_cameras``; otherwise it is an error, not a silently ignored argument."""
         cam = curr_data.get('cam') if hasattr(curr_data, 'get') else None
-        if cam is None or cam is self.cam_settings:
+        if cam is None or cam is self._camera.settings:
             return
-        i = self._find_camera(cam)
-        if i is None:
-            if not self.auto_cameras:
-                raise RuntimeError("curr_data['cam'] differs from the camera(s) this FusedEngine was built for "
-                                   "(add_camera(cam) registers another one; auto_cameras = True does so on first use)")
-            i = self.add_camera(cam)
-        self._activate(i)
-
-    def _frame_w2c(self, curr_data):
-        """curr_data['w2c'] as the kernels read it: 16 contiguous floats on the engine's device (row 2 is the depth channel of
-        the depth / silhouette render).  Anything else -- float64 from an inverse taken in double, a CPU tensor, a batch of
-        matrices -- would be read as 16 floats of something else; the reference's own matmul raises a RuntimeError for a dtype or
-        device mismatch (/root/reference/utils/slam_helpers.py:196-213), and so does this, before anything is launched.
-        Attribute reads only; a non-contiguous view is made contiguous."""
-        w2c = curr_data['w2c']
-        if not (isinstance(w2c, torch.Tensor) and w2c.dtype == torch.float32 and w2c.device == self.dev and tuple(w2c.shape) == (4, 4)):
-            got = f"{w2c.dtype}, {tuple(w2c.shape)}, {w2c.device}" if isinstance(w2c, torch.Tensor) else type(w2c).__name__
-            raise RuntimeError(f"curr_data['w2c'] must be a float32 tensor of shape [4, 4] on {self.dev} (got {got})")
-        return w2c if w2c.is_contiguous() else w2c.contiguous()
+        if self._find_camera(cam) is None and not self.auto_cameras:
+            raise RuntimeError("curr_data['cam'] differs from the camera(s) this FusedEngine was built for "
+                               "(add_camera(cam) registers another one; auto_cameras = True does so on first use)")
+        self.add_camera(cam)
 
     def _map_struct(self):
         p = self.params
@@ -800,37 +806,37 @@ class FusedEngine:
         return m
 
     def _workspace(self, with_map_grads, with_ssim):
-        b = self.buf
+        cam = self._camera
+        b, rows, hint, stride = cam.buf, self.map_buf, cam.max_list_hint, cam.tile_stride
         ws = _capi.SplatIterWorkspace()
         st = ws.st
-        st.depth, st.xy, st.conic_opacity, st.rect = b['depth'].data_ptr(), b['xy'].data_ptr(), b['conic'].data_ptr(), b['rect'].data_ptr()
-        st.radii = b['radii'].data_ptr()
+        st.depth, st.xy, st.conic_opacity, st.rect = rows['depth'].data_ptr(), rows['xy'].data_ptr(), rows['conic'].data_ptr(), rows['rect'].data_ptr()
+        st.radii = rows['radii'].data_ptr()
         st.tile_count, st.tile_base, st.tile_cursor = b['tile_count'].data_ptr(), b['tile_base'].data_ptr(), b['tile_cursor'].data_ptr()
-        st.keys, st.point_list, st.capacity = b['keys'].data_ptr(), b['point_list'].data_ptr(), self.capacity
+        st.keys, st.point_list, st.capacity = b['keys'].data_ptr(), b['point_list'].data_ptr(), cam.capacity
         st.keys_alt, st.long_base = b['keys_alt'].data_ptr(), b['long_base'].data_ptr()
         # staged records handed from the forward to the backward composite (B-loop, mapping +1.4 %; B: the forward composite's 34 MB of
         # extra stores, mapping -1.4 %).  SPLAT_TILE_RECS=1 / 0 forces them on / off
-        recs_on = self.use_recs == 1 or (self.use_recs == 2 and self.max_list_hint > _capi.RECS_MIN_LIST)
-        st.tile_recs = b['tile_recs'].data_ptr() if (recs_on and b.get('tile_recs') is not None) else None
+        recs_on = self.use_recs == 1 or (self.use_recs == 2 and hint > _capi.RECS_MIN_LIST)
+        st.tile_recs = b['tile_recs'].data_ptr() if (recs_on and b['tile_recs'] is not None) else None
         st.long_items = b['long_items'].data_ptr()
-        st.max_list_hint = self.max_list_hint
-        st.tile_stride = self.tile_stride
-        st.tile_row_begin, st.tile_row_end = self._tile_rows if self._tile_rows else (0, 0)
+        st.max_list_hint, st.tile_stride = hint, stride
+        st.tile_row_begin, st.tile_row_end = cam._tile_rows or (0, 0)
         st.group_count, st.group_recs, st.group_stride = b['group_count'].data_ptr(), None, 0
-        if self.group_bins and self.tile_stride > 0 and _capi.lists_sorted_by_composite(self.max_list_hint):
-            gs = _capi.SPLAT_GROUP_TILES ** 2 * self.tile_stride
-            need = self.num_groups * gs * 4
+        if self.group_bins and stride > 0 and _capi.lists_sorted_by_composite(hint):
+            gs = _capi.SPLAT_GROUP_TILES ** 2 * stride
+            need = cam.num_groups * gs * 4
             if need <= 1 << 30:                       # (int32 words; 4 GiB of records)
-                if b.get('group_recs') is None or b['group_recs'].numel() < need:
-                    b['group_recs'] = self._new(self._layout(0, group_stride=gs), "st.group_recs", torch.int32)
-                    assert b['group_recs'].numel() == need
-                st.group_recs, st.group_stride = b['group_recs'].data_ptr(), gs
+                recs = b.get('group_recs')
+                if recs is None or recs.numel() < need:
+                    recs = cam.alloc_group_recs(gs)
+                st.group_recs, st.group_stride = recs.data_ptr(), gs
         st.order_hint = int(self.creation_order)
         if self.tile_order_on:
             st.tile_work, st.tile_order = b['tile_work'].data_ptr(), b['tile_order'].data_ptr()
-        st.sub_bins = self.sub_bins if self.tile_stride == 0 else 1
+        st.sub_bins = cam.sub_bins if stride == 0 else 1
         st.final_T, st.n_contrib, st.status = b['final_T'].data_ptr(), b['n_contrib'].data_ptr(), b['status'].data_ptr()
-        ws.feat8, ws.out6, ws.dL_dout6, ws.accum = b['feat8'].data_ptr(), b['out6'].data_ptr(), b['dL_dout6'].data_ptr(), b['accum'].data_ptr()
+        ws.feat8, ws.out6, ws.dL_dout6, ws.accum = rows['feat8'].data_ptr(), b['out6'].data_ptr(), b['dL_dout6'].data_ptr(), rows['accum'].data_ptr()
         ws.ssim_maps = b['ssim_maps'].data_ptr() if with_ssim else None
         ws.sums = b['sums'].data_ptr()
         ws.max_2D_radius = self.max_2D_radius.data_ptr() if self.max_2D_radius is not None else None
@@ -845,16 +851,9 @@ class FusedEngine:
         return ws
 
     def _select_order(self, view):
-        """Point ``buf['tile_order']`` at the launch order view ``view`` left at its last visit (the natural order at its first)."""
-        if not (self.tile_order_on and self.order_per_view):
-            return
-        o = self._orders.pop(view, None)
-        if o is None:
-            if len(self._orders) >= 64:
-                self._orders.pop(next(iter(self._orders)))          # the view visited longest ago
-            o = self._natural_order.clone()
-        self._orders[view] = o                                      # (most recently visited last)
-        self.buf['tile_order'] = o
+        """The current camera composites in the launch order view ``view`` left (_Camera.select_order)."""
+        if self.tile_order_on and self.order_per_view:
+            self._camera.select_order(view)
 
     def _stream(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -884,41 +883,35 @@ class FusedEngine:
         if map_grads is None:
             map_grads = not tracking
         self._check_cam(curr_data)
-        fr = _capi.SplatFrameData()
-        im, depth = curr_data['im'], curr_data['depth']
-        w2c = self._frame_w2c(curr_data)
-        if not (im.is_contiguous() and depth.is_contiguous()):
-            im, depth = im.contiguous(), depth.contiguous()
-        fr.im, fr.depth, fr.w2c, fr.time_idx = im.data_ptr(), depth.data_ptr(), w2c.data_ptr(), int(time_idx)
-        self._frame_keep = (im, depth, w2c)
+        cam = self._camera
+        fr = self._frame(curr_data, time_idx)
         if keep_planes is None:
             keep_planes = pose_adam is None
         # (with the map's gradients the one-kernel form carries the backward composite's mapping form at four workgroups per CU: ahead
         #  where a tile's list is one or two batches -- B: +6.4 % --, behind where it is three -- B-loop: -1.2 %; profiles/r06_experiments.md 4)
-        full_ok = self.track_fused_full and 0 < self.max_list_hint <= 400
+        full_ok = self.track_fused_full and 0 < cam.max_list_hint <= 400
         one_kernel = (2 if keep_planes else 1) if (tracking and self.track_fused and (not map_grads or full_ok)) else 0
         lc = self.loss_config(cfg, tracking, do_ba, defer_finish=tile_rows is not None, fused_composite=one_kernel)
-        self._tile_rows = tile_rows         # a band: the iteration stops before its last kernel (finish_iteration completes it)
-        self._stats_partial = tile_rows is not None
+        cam._tile_rows = tile_rows          # a band: the iteration stops before its last kernel (finish_iteration completes it)
+        cam._stats_partial = tile_rows is not None
         self._lc_keep = lc
-        if lc.ignore_outlier_depth_loss and 'outlier_err' not in self.buf:       # scratch of the median selection, on first use
-            lay = self._layout(0, outlier=True)
-            self.buf['outlier_err'] = self._new(lay, "outlier_err", torch.float32)
-            self.buf['outlier_scratch'] = self._new(lay, "outlier_scratch", torch.int32)
-        self._select_order(int(time_idx))
+        if lc.ignore_outlier_depth_loss and 'outlier_err' not in cam.buf:
+            cam.alloc_outlier_scratch()
+        if self.tile_order_on and self.order_per_view:
+            cam.select_order(int(time_idx))
         ws = self._workspace(map_grads, with_ssim=not tracking)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
             if pose_adam is not None:
-                _capi.check(self.L.splat_iter_tracking_step(C.byref(self._cam), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
+                _capi.check(self.L.splat_iter_tracking_step(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
                                                             C.byref(pose_adam), self._stream()), "splat_iter_tracking_step")
             elif map_adam is not None:
-                _capi.check(self.L.splat_iter_mapping_step(C.byref(self._cam), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
+                _capi.check(self.L.splat_iter_mapping_step(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
                                                            C.byref(map_adam), self._stream()), "splat_iter_mapping_step")
             else:
-                _capi.check(self.L.splat_iter_loss_backward(C.byref(self._cam), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
+                _capi.check(self.L.splat_iter_loss_backward(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
                                                             self._stream()), "splat_iter_loss_backward")
-        self._tile_rows = None
+        cam._tile_rows = None
         self._fr_keep = fr
 
     def finish_iteration(self, pose_adam=None):
@@ -928,7 +921,7 @@ class FusedEngine:
         ws = self._workspace(False, with_ssim=False)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_iter_finish(C.byref(self._cam), C.byref(m), C.byref(self._fr_keep), C.byref(self._lc_keep), C.byref(ws),
+            _capi.check(self.L.splat_iter_finish(C.byref(self._camera.struct), C.byref(m), C.byref(self._fr_keep), C.byref(self._lc_keep), C.byref(ws),
                                                  C.byref(pose_adam) if pose_adam is not None else None, self._stream()), "splat_iter_finish")
 
     def tile_row_band(self, rank, world):
@@ -954,7 +947,7 @@ class FusedEngine:
             o.grad[k] = self.grads[name].data_ptr()
             o.exp_avg[k] = self.exp_avg[name].data_ptr()
             o.exp_avg_sq[k] = self.exp_avg_sq[name].data_ptr()
-        o.gate = self.buf['d_cam'].data_ptr()
+        o.gate = self._camera.buf['d_cam'].data_ptr()
         return o
 
     def adam_map(self, lrs, beta1=0.9, beta2=0.999, eps=1e-15):
@@ -973,7 +966,7 @@ class FusedEngine:
 
     def begin_tracking(self, time_idx):
         """Fresh Adam state and best-candidate bookkeeping for one frame (:680-684)."""
-        st = self.buf['pose_state']
+        st = self.map_buf['pose_state']
         st.zero_()
         st[14] = 1e20
         st[15:19] = self.params['cam_unnorm_rots'].detach()[0, :, time_idx]
@@ -987,13 +980,13 @@ class FusedEngine:
         bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_iter_adam_pose(C.byref(m), self.track_time_idx, self.buf['d_cam'].data_ptr(),
-                                                    self.buf['pose_state'].data_ptr(), beta1, beta2, eps, math.sqrt(bc2),
+            _capi.check(self.L.splat_iter_adam_pose(C.byref(m), self.track_time_idx, self._camera.buf['d_cam'].data_ptr(),
+                                                    self.map_buf['pose_state'].data_ptr(), beta1, beta2, eps, math.sqrt(bc2),
                                                     lr_rot / bc1, lr_trans / bc1, self._stream()), "splat_iter_adam_pose")
 
     def end_tracking(self):
         """Copy the best candidate back (:741-744)."""
-        st, t = self.buf['pose_state'], self.track_time_idx
+        st, t = self.map_buf['pose_state'], self.track_time_idx
         with torch.no_grad():
             self.params['cam_unnorm_rots'][0, :, t] = st[15:19]
             self.params['cam_trans'][0, :, t] = st[19:22]
@@ -1004,7 +997,7 @@ class FusedEngine:
         t, beta1, beta2 = self.pose_step, 0.9, 0.999
         bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
         pa = _capi.SplatPoseAdam()
-        pa.state, pa.beta1, pa.beta2, pa.eps, pa.bc2_sqrt = self.buf['pose_state'].data_ptr(), beta1, beta2, 1e-8, math.sqrt(bc2)
+        pa.state, pa.beta1, pa.beta2, pa.eps, pa.bc2_sqrt = self.map_buf['pose_state'].data_ptr(), beta1, beta2, 1e-8, math.sqrt(bc2)
         pa.step_size_rot, pa.step_size_trans = cfg['lrs']['cam_unnorm_rots'] / bc1, cfg['lrs']['cam_trans'] / bc1
         return pa
 
@@ -1022,13 +1015,14 @@ class FusedEngine:
         if cfg['ignore_outlier_depth_loss']:
             raise RuntimeError("tile-row-sharded tracking needs a pixel-local loss: not with ignore_outlier_depth_loss")
         self.loss_backward(curr_data, self.track_time_idx, cfg, tracking=True, tile_rows=self.tile_row_band(*shard), keep_planes=False)
+        sums = self._camera.buf['sums']
         if self.fold_sums:
             # the 64 copies of the partial sums folded into the first (one tiny launch): the exchange carries 256 bytes, not 16 KB
             with torch.cuda.device(self.dev):
-                _capi.check(self.L.splat_iter_fold_sums(self.buf['sums'].data_ptr(), self._stream()), "splat_iter_fold_sums")
-            allreduce_sums(self.buf['sums'][:_capi.SPLAT_ITER_SUMS])
+                _capi.check(self.L.splat_iter_fold_sums(sums.data_ptr(), self._stream()), "splat_iter_fold_sums")
+            allreduce_sums(sums[:_capi.SPLAT_ITER_SUMS])
         else:
-            allreduce_sums(self.buf['sums'])
+            allreduce_sums(sums)
         self.finish_iteration(pa)
 
     def mapping_iteration(self, iter_data, iter_time_idx, cfg, bucket_allreduce=None, keep_grads=None):
@@ -1076,7 +1070,7 @@ class FusedEngine:
         truncated-list contribution: nobody may step on it).  ``flat``: another buffer laid out like ``_exchange_flat`` (mapping_batch's
         accumulator)."""
         flat = self._exchange_flat if flat is None else flat
-        flag = self.buf['d_cam'][_REPORT_FLAG:_REPORT_FLAG + 1]
+        flag = self._camera.buf['d_cam'][_REPORT_FLAG:_REPORT_FLAG + 1]
         flat[0:1].copy_(flag)
         all_reduce(flat)
         torch.maximum(flag, (flat[0:1] != 0.0).to(flag.dtype), out=flag)
@@ -1089,7 +1083,7 @@ class FusedEngine:
 
     # ------------------------------------------------------------------ read-backs (host sync)
     def loss(self):
-        return float(self.buf['d_cam'][_capi.SPLAT_REPORT_LOSS])
+        return float(self._camera.buf['d_cam'][_capi.SPLAT_REPORT_LOSS])
 
     def check_overflow(self, grow=True):
         """Lists are fixed-size; an iteration whose instances did not fit rendered truncated / empty lists and flagged
@@ -1098,8 +1092,8 @@ class FusedEngine:
         took no step.  Also learns the list statistics: from then on the per-tile lists are BUCKETED at 1.5x the longest
         list seen (the per-Gaussian kernel writes instances straight into their tile's bucket: no scan kernel, no
         scatter pass) and the long-list sort launch is skipped while lists stay short."""
-        stat = self.buf['status'].tolist()
-        rep = self.buf['d_cam'].cpu()
+        stat = self._camera.buf['status'].tolist()
+        rep = self._camera.buf['d_cam'].cpu()
         return self._digest(stat, float(rep[_REPORT_FLAG]) != 0.0, int(rep.view(torch.int32)[_REPORT_SKIPPED]), grow)
 
     def digest_report(self, report, grow=True):
@@ -1111,63 +1105,65 @@ class FusedEngine:
                             hysteresis=True)
 
     def _digest(self, stat, sticky, skipped, grow, hysteresis=False):
-        bad = sticky or stat[_STATUS_OVERFLOW] != 0 or stat[_STATUS_STALE_HINT] != 0 or (self.tile_stride == 0 and stat[_STATUS_INSTANCES] > self.capacity)
+        cam, b = self._camera, self._camera.buf
+        bad = sticky or stat[_STATUS_OVERFLOW] != 0 or stat[_STATUS_STALE_HINT] != 0 or (cam.tile_stride == 0 and stat[_STATUS_INSTANCES] > cam.capacity)
         self.skipped_iterations = 0
         if bad:
             self.skipped_iterations = max(int(skipped), 1)
-            self.buf['d_cam'][_REPORT_FLAG] = 0.0
-            self.buf['d_cam'][_REPORT_SKIPPED] = 0.0    # (an int32 counter: the bit pattern of 0.0 is 0)
-            self.buf['status'].zero_()
-            self.buf['tile_count'].zero_()
-            self.buf['group_count'].zero_()
-            self.buf['accum'].zero_()
-            self.buf['sums'].zero_()
-            self.max_list_hint = 0
+            b['d_cam'][_REPORT_FLAG] = 0.0
+            b['d_cam'][_REPORT_SKIPPED] = 0.0    # (an int32 counter: the bit pattern of 0.0 is 0)
+            b['status'].zero_()
+            b['tile_count'].zero_()
+            b['group_count'].zero_()
+            self.map_buf['accum'].zero_()
+            b['sums'].zero_()
+            cam.max_list_hint = 0
             if grow:
-                if self.tile_stride > 0:            # a bucket overflowed: back to exact lists, re-learn
-                    self.tile_stride = 0
-                if stat[_STATUS_INSTANCES] > self.capacity:
+                cam.tile_stride = 0                 # (a bucket overflowed: back to exact lists, re-learn)
+                if stat[_STATUS_INSTANCES] > cam.capacity:
                     self._alloc_lists(int(stat[_STATUS_INSTANCES] * 1.5) + 65536)
             return True
-        if self._stats_partial:                 # the last iteration composited a band of tile rows: its statistics are not the frame's
+        if cam._stats_partial:                  # the last iteration composited a band of tile rows: its statistics are not the frame's
             return False
         longest = int(stat[_STATUS_LONGEST])
-        self.max_list_hint = longest            # short lists: sorted inside the composite, no sort launch
-        self._learnt_P = self.P
-        self._set_sub_bins(16 if longest > 2048 else 1)
+        cam.max_list_hint = longest             # short lists: sorted inside the composite, no sort launch
+        cam.learnt_P = self.P
+        cam.set_sub_bins(16 if longest > 2048 else 1)
         if grow and self.allow_buckets and longest > 0:
             stride = max(256, (int(longest * 1.5) + 63) // 64 * 64)
             # buckets cost 20 bytes per slot (keys, their merge partner, sorted ids): up to ~15 GB of the 288 GB for the clustered
             # stress scenes (337 M slots at 5 M Gaussians) -- one returning atomic per instance instead of count + scan + scatter
             # (reports digested every iteration: the stride only moves when the margin has become thin or the buckets far too wide --
             #  a stride that follows every fluctuation of the longest list would re-lay the buckets iteration by iteration)
-            if hysteresis and self.tile_stride > 0 and longest * 5 // 4 <= self.tile_stride <= 2 * stride:
-                stride = self.tile_stride
-            if stride != self.tile_stride and stride * self.num_tiles <= 768 * 1024 * 1024:
-                if stride * self.num_tiles > self.capacity:
-                    self._alloc_lists(stride * self.num_tiles)
-                self.tile_stride = stride
+            if hysteresis and cam.tile_stride > 0 and longest * 5 // 4 <= cam.tile_stride <= 2 * stride:
+                stride = cam.tile_stride
+            if stride != cam.tile_stride and stride * cam.num_tiles <= 768 * 1024 * 1024:
+                if stride * cam.num_tiles > cam.capacity:
+                    self._alloc_lists(stride * cam.num_tiles)
+                cam.tile_stride = stride
         return False
-
-    def _set_sub_bins(self, S):
-        """Very long per-tile lists stay on the exact-list path (their buckets would not fit); their count / scatter atomics
-        are then spread over S counters per tile (same-address serialisation otherwise: 0.9 ms per pass at 11 M instances)."""
-        if S == self.sub_bins:
-            return
-        CS = _capi.SPLAT_COUNTER_STRIDE
-        self.sub_bins = S
-        self.buf['tile_count'] = torch.zeros(self.num_tiles * CS * S, dtype=torch.int32, device=self.dev)
-        self.buf['tile_cursor'] = torch.zeros(self.num_tiles * CS * S, dtype=torch.int32, device=self.dev)
 
     @property
     def seen(self):
         """variables['seen'] of the last iteration ([P], /root/reference/scripts/splatam.py:343)."""
-        return self.buf['radii'][:self.P] > 0
+        return self.map_buf['radii'][:self.P] > 0
 
     def rendered(self):
         """(im[3,H,W], depth[1,H,W], silhouette[H,W], depth_sq[1,H,W]) of the last iteration."""
-        o = self.buf['out6']
+        o = self._camera.buf['out6']
         return o[0:3], o[3:4], o[4], o[5:6]
+
+
+def _of_current_camera(field, assignable=False):
+    put = (lambda self, value: setattr(self._camera, field, value)) if assignable else None
+    return property(lambda self: getattr(self._camera, field), put, doc=f"``{field}`` of the current camera")
+
+
+# what callers read on the engine with "the current camera's" meaning (the engine's own hot paths read the _Camera itself); the list
+# statistics can also be set: tests force stale ones
+for _name in ("H", "W", "num_tiles", "num_groups", "capacity", "sub_bins", "_orders", "_natural_order", "_stats_partial", "tile_stride", "max_list_hint"):
+    setattr(FusedEngine, _name, _of_current_camera(_name, assignable=_name in ("tile_stride", "max_list_hint")))
+FusedEngine.cam_settings, FusedEngine._cam = _of_current_camera("settings"), _of_current_camera("struct")
 
 
 # ---------------------------------------------------------------------- frame preparation (csrc/frameprep.hip)

@@ -217,7 +217,7 @@ class _Session:
         elif eng.params is not params or any(params[k].data_ptr() != eng.store[k].data_ptr() or params[k].shape[0] != eng.P for k in PARAM_ORDER):
             raise RuntimeError("plugin.install(map_edits=True): the Gaussian tensors were replaced outside add_new_gaussians / prune_gaussians; "
                                "the engine owns the map in this mode")
-        if cam is not eng.cam_settings and eng._find_camera(cam) != eng._cur:
+        if not eng.is_current(cam):
             # the reports in flight speak of the camera that produced them: look at all of them before another one becomes current
             self.drain(eng)
             eng.add_camera(cam)

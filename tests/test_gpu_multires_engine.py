@@ -54,9 +54,10 @@ def planes(eng, frame, t=1):
     return [x.clone() for x in eng.render(frame, t)]
 
 
-def assert_renders_like_single_camera_engines(eng, frames, what):
+def assert_renders_like_single_camera_engines(eng, frames, what, build=None):
+    """``build(cam)``: the fresh single-camera engine (default: a managed one on a copy of ``eng``'s map)."""
     for size, frame in frames.items():
-        single = managed(eng.params, eng.variables, frame['cam'])
+        single = build(frame['cam']) if build else managed(eng.params, eng.variables, frame['cam'])
         a, b = planes(single, frame), planes(single, frame)
         got = planes(eng, frame)
         assert (eng.H, eng.W) == size and tuple(got[0].shape) == (3,) + size
@@ -217,6 +218,105 @@ def test_overflow_protocol_is_per_camera():
     torch.cuda.synchronize()
     assert not eng.check_overflow()
     assert not torch.equal(before['means3D'], eng.params['means3D'].detach())              # the repeat took its step
+
+
+def learn_lists(eng, frames):
+    """First use of every camera of ``frames``: a render on exact lists, then check_overflow() learns the camera's statistics."""
+    for frame in frames.values():
+        eng.render(frame, 1)
+        assert not eng.check_overflow()
+        assert eng.lists_known(frame)
+
+
+def list_statistics(eng, cams):
+    out = {}
+    for size, cam in cams.items():
+        eng.select_camera(cam)
+        out[size] = (eng.tile_stride, eng.max_list_hint)
+    return out
+
+
+def test_a_refused_camera_changes_nothing():
+    """A camera the fused path cannot render (non-zero background) raises from add_camera; the engine, its two cameras, the current
+    camera and the bytes allocated are what they were."""
+    params, variables, w2c, cams, frames = make_scene()
+    eng = managed(params, variables, cams[SIZES[0]])
+    eng.add_camera(cams[SIZES[1]])
+    two = {size: frames[size] for size in SIZES[:2]}
+    learn_lists(eng, two)
+    refused = cams[SIZES[2]]._replace(bg=torch.ones(3, device="cuda"))
+
+    def current():
+        return (eng.H, eng.W, eng.tile_stride, eng.max_list_hint, eng.capacity, eng.buf['keys'].data_ptr(), eng.buf['out6'].data_ptr())
+    gc.collect()
+    torch.cuda.synchronize()
+    before, allocated = current(), torch.cuda.memory_allocated()
+    assert before[:2] == SIZES[1] and before[2] > 0 and before[3] > 0
+    with pytest.raises(RuntimeError, match="zero background"):
+        eng.add_camera(refused)
+    assert eng.num_cameras == 2
+    assert current() == before
+    gc.collect()
+    torch.cuda.synchronize()
+    print(f"allocated before the refused camera {allocated} B, after {torch.cuda.memory_allocated()} B")
+    assert torch.cuda.memory_allocated() == allocated
+    assert_renders_like_single_camera_engines(eng, two, "after a refused camera")
+
+
+def test_a_small_edit_keeps_every_cameras_list_statistics():
+    """Five rows removed of 8 000 (the rule keeps statistics within 10 % of the rows they were learnt on): all three cameras keep
+    theirs, and a fourth that has never rendered has none to keep.  (The large edit that drops them all:
+    test_growth_and_list_statistics_per_camera.)"""
+    from splatam_amd import slam
+    params, variables, w2c, cams, frames = make_scene()
+    eng = managed(params, variables, cams[SIZES[0]])
+    for size in SIZES[1:]:
+        eng.add_camera(cams[size])
+    learn_lists(eng, frames)
+    learnt = list_statistics(eng, cams)
+    assert all(stride > 0 and longest > 0 for stride, longest in learnt.values()), learnt
+    k = frames[SIZES[0]]['intrinsics'].cpu().clone()
+    k[0] *= 40 / W
+    k[1] *= 24 / H
+    fourth = slam.setup_camera(40, 24, k.numpy(), np.eye(4, dtype=np.float32), device="cuda")
+    assert eng.add_camera(fourth) == 3 and (eng.H, eng.W) == (24, 40)
+    to_remove = torch.zeros(eng.P, dtype=torch.bool, device="cuda")
+    to_remove[[3, 1000, 2500, 4000, N - 1]] = True
+    assert eng.remove_points(to_remove) == 5 and eng.P == N - 5
+    assert list_statistics(eng, cams) == learnt
+    for size in SIZES:
+        assert eng.lists_known(frames[size]), size
+    eng.select_camera(fourth)
+    assert (eng.tile_stride, eng.max_list_hint) == (0, 0) and not eng.lists_known()
+
+
+def test_rebind_applies_its_rule_to_every_camera():
+    """An engine on caller-owned tensors with two cameras: ``rebind`` to a map of 5 % more rows keeps both cameras' statistics (and fits
+    the row headroom), to one of 50 % more rows drops both; each camera then learns again and renders what a fresh engine renders."""
+    from splatam_amd.fused import FusedEngine
+    params, variables, w2c, cams, frames = make_scene()
+    two = {size: frames[size] for size in SIZES[:2]}
+    two_cams = {size: cams[size] for size in SIZES[:2]}
+    eng = FusedEngine(copy_map(params, variables)[0], cams[SIZES[0]], row_headroom=0.125)
+    eng.add_camera(cams[SIZES[1]])
+    learn_lists(eng, two)
+    learnt = list_statistics(eng, two_cams)
+    assert all(stride > 0 and longest > 0 for stride, longest in learnt.values()), learnt
+
+    def with_more_rows(extra):
+        return {k: (torch.cat([v.detach(), v.detach()[:extra]]) if k in PARAM_KEYS else v.detach().clone()).contiguous()
+                for k, v in params.items()}
+    eng.rebind(with_more_rows(N // 20))
+    assert eng.P == N + N // 20 and eng.Pcap == int(N * 1.125)
+    assert list_statistics(eng, two_cams) == learnt
+    eng.rebind(with_more_rows(N // 2))
+    assert eng.P == N + N // 2 and eng.Pcap >= eng.P
+    assert list_statistics(eng, two_cams) == {size: (0, 0) for size in two}
+    learn_lists(eng, two)
+
+    def fresh(cam):
+        return FusedEngine({k: v.detach().clone() for k, v in eng.params.items()}, cam)
+    assert_renders_like_single_camera_engines(eng, two, "after rebind", build=fresh)
 
 
 def single_camera_footprint():
