@@ -17,8 +17,6 @@ namespace splat {
 
 constexpr int kEvalLevels = 5;
 constexpr int kEvalTaps = 11;
-constexpr float kEvalC1 = 0.01f * 0.01f;
-constexpr float kEvalC2 = 0.03f * 0.03f;
 
 // slots of one copy of SplatEvalWorkspace.sums (SPLAT_EVAL_SUMS doubles)
 constexpr int kEvalSumSq = 0;        // [0..2] sum over ALL pixels of (weighted_im - weighted_gt)^2, per channel
@@ -84,9 +82,9 @@ SPLAT_HD float eval_depth_term(float rendered, float gt_depth, const EvalPixel &
 SPLAT_HD float eval_ssim_pixel(float mu1, float mu2, float e11, float e22, float e12, float *cs) {
     const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
     const float s1 = e11 - mu1_sq, s2 = e22 - mu2_sq, s12 = e12 - mu12;
-    const float c = (2.f * s12 + kEvalC2) / (s1 + s2 + kEvalC2);
+    const float c = (2.f * s12 + kSsimC2) / (s1 + s2 + kSsimC2);
     *cs = c;
-    return (2.f * mu12 + kEvalC1) / (mu1_sq + mu2_sq + kEvalC1) * c;
+    return (2.f * mu12 + kSsimC1) / (mu1_sq + mu2_sq + kSsimC1) * c;
 }
 
 // The frame's numbers from the totals of the sums (tot: kEvalSums doubles), in double, in three steps so that a kernel can spread

@@ -6,27 +6,19 @@
 //                              rendered planes, the frame and the two masks, and takes the PSNR and depth sums
 //   Q2 eval_finish_kernel      totals the copies of the sums, forms the row in double (eval_math.h: eval_finish), zeroes the sums
 //
-// The level kernel follows the mapping loss' SSIM kernel (fused.hip F4: vertical pass first, in registers, one thread per window
-// column; only vertical sums through LDS; four output pixels per thread of the horizontal pass; XCD-ordered tiles; double partial
-// sums spread over copies).  It is not that kernel: the window is unpadded (a tile's 32 x 24 outputs read the 42 x 34 pixels BELOW
-// AND RIGHT of its origin), there are no derivative maps, and a tile OWNS the 32 x 24 input pixels at its origin: it alone adds
-// their PSNR / depth terms and writes the 16 x 12 pooled pixels that start at half its origin.
+// The level kernel runs the window pass of window_sums.h on an UNPADDED window that starts at the tile's origin (a tile's 32 x 24 outputs
+// read the 42 x 34 pixels below and right of it); a tile OWNS the 32 x 24 input pixels at its origin: it alone adds their PSNR / depth
+// terms, in the load loop, and writes the 16 x 12 pooled pixels that start at half its origin.
 #include "splat_device.h"
 #include "eval_math.h"
+#include "window_sums.h"
 
 namespace splat {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kTW = 32, kTR = 4, kTG = 6;   // tile width; output rows per thread of the vertical pass; row groups per workgroup
-constexpr int kTH = kTR * kTG;              // tile height 24
-constexpr int kCols = kTW + kEvalTaps - 1;  // 42 window columns
-constexpr int kRows = kTR + kEvalTaps - 1;  // 14 input rows per thread
-constexpr int kStride = 45;                 // LDS row stride in elements (1 mod 4: the 64-bit reads of the horizontal pass fall on distinct banks)
-constexpr int kItems = kTH * (kTW / 4);     // horizontal work items: (row, group of 4 columns)
-constexpr int kPooled = (kTW / 2) * (kTH / 2);
-static_assert(kCols * kTG <= kBlock && kItems <= kBlock && kPooled <= kBlock, "one trip per pass");
-typedef float f2 __attribute__((ext_vector_type(2)));
+constexpr int kBlock = kWinBlock;
+constexpr int kPooled = (kWinTW / 2) * (kWinTH / 2);
+static_assert(kEvalTaps == kWinTaps && kPooled <= kBlock, "the window pass' taps; one trip over the pooled pixels");
 
 struct LevelArgs {
     // level 0: the planes of the frame and of the render; levels 1..4: x, y = [3][H][W] of the pyramid
@@ -40,19 +32,6 @@ struct LevelArgs {
     float win[kEvalTaps];
 };
 
-// blockIdx -> (tile column, tile row, channel): XCD x (workgroups are dealt to the 8 XCDs round robin) owns a contiguous run of the
-// (channel, row, column) order, so a tile's halo was read through the same L2 by the workgroup before it or one tile row earlier
-__device__ __forceinline__ bool level_tile(int W, int H, int &bx, int &by, int &ch) {
-    const int ntx = (W + kTW - 1) / kTW, nty = (H + kTH - 1) / kTH, total = 3 * ntx * nty, per = (total + 7) / 8;
-    const int b = blockIdx.x, slot = b >> 3, t = (b & 7) * per + slot;
-    if (slot >= per || t >= total) return false;
-    ch = t / (ntx * nty);
-    const int r = t - ch * ntx * nty;
-    by = r / ntx;
-    bx = r - by * ntx;
-    return true;
-}
-
 // (x, y) of channel `ch` at pixel offset `off` of the level; level 0 weighs the planes (eval_math.h) and returns the masks
 template <bool L0>
 __device__ __forceinline__ f2 level_pixel(const LevelArgs &a, const float *X, const float *Y, int off, EvalPixel &m) {
@@ -65,62 +44,41 @@ __device__ __forceinline__ f2 level_pixel(const LevelArgs &a, const float *X, co
     return p;
 }
 
-// per-thread partial sums -> one atomicAdd each into this workgroup's copy; the wave reduction already runs in double (the PSNR /
-// depth sums are compared at 1e-6).  FRAME: v = squared error, depth term, valid count, cs, ssim; otherwise v = cs, ssim
-template <bool FRAME, int N>
-__device__ __forceinline__ void block_sums(double *sums, int ch, int level, const float (&v)[N], double *s_part /* [N][waves] */) {
-    static_assert(N == (FRAME ? 5 : 2), "the slots below");
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, k = threadIdx.x;
-    constexpr int nw = kBlock / 64;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double x = (double)v[i];
-        for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-        if (lane == 0) s_part[i * nw + wave] = x;
-    }
-    __syncthreads();
-    if (k < N) {
-        double t = 0.0;
-        for (int w = 0; w < nw; ++w) t += s_part[k * nw + w];
-        const int base = eval_level_slot(level, ch);
-        const int slot = !FRAME ? base + k : k == 0 ? kEvalSumSq + ch : k == 1 ? kEvalSumDepth : k == 2 ? kEvalSumValid : base + k - 3;
-        if (t != 0.0) atomicAdd(sums + (size_t)(blockIdx.x % SPLAT_ITER_SUM_COPIES) * SPLAT_EVAL_SUMS + slot, t);
-    }
-}
-
 // SSIM false: PSNR and depth sums alone (ms_ssim off; level 0 only)
 template <bool L0, bool SSIM>
 __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
-    __shared__ f2 svA[kTH][kStride], svB[kTH][kStride];        // vertical sums of (x, y) and (x x, y y)
-    __shared__ float svC[kTH][kStride];                        // ... of x y
+    __shared__ WindowLds<2> S;                      // vertical sums of (x, y), (x x, y y) and x y
     __shared__ double s_part[5 * (kBlock / 64)];
+    float g[kWinTaps];
+#pragma unroll
+    for (int k = 0; k < kWinTaps; ++k) g[k] = a.win[k];
     int bx, by, ch;
-    if (!level_tile(a.W, a.H, bx, by, ch)) return;
+    if (!xcd_tile(a.W, a.H, bx, by, ch)) return;
     const int W = a.W, H = a.H, tid = threadIdx.x;
-    const int x0 = bx * kTW, y0 = by * kTH;
+    const int x0 = bx * kWinTW, y0 = by * kWinTH;
     const size_t HW = (size_t)H * W;
     const float *X = a.x + ch * HW, *Y = a.y + ch * HW;
     const bool sil_mask = a.sil_mask != 0;
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};       // squared error, depth term, valid count (owned pixels); cs, ssim (owned window positions)
-    {   // vertical pass: thread = (window column, group of kTR output rows); the thread's first kTR rows of the tile's first kTW
+    {   // vertical pass: thread = (window column, group of kWinTR output rows); the thread's first kWinTR rows of the tile's first kWinTW
         // columns are pixels the tile owns
-        const int grp = tid / kCols, col = tid - grp * kCols;
-        constexpr int rows = SSIM ? kRows : kTR;
-        if (grp < kTG && (SSIM || col < kTW)) {
+        const int grp = tid / kWinCols, col = tid - grp * kWinCols;
+        constexpr int rows = SSIM ? kWinRows : kWinTR;
+        if (grp < kWinTG && (SSIM || col < kWinTW)) {
             const int xx = x0 + col;
             const bool cin = xx < W;
             const int xc = min(xx, W - 1);
             float vx[rows], vy[rows];
 #pragma unroll
             for (int t = 0; t < rows; ++t) {
-                const int yy = y0 + grp * kTR + t;
+                const int yy = y0 + grp * kWinTR + t;
                 const bool in = cin && yy < H;
                 const int off = min(yy, H - 1) * W + xc;    // (a row or column outside the image: any address inside the plane, value discarded)
                 EvalPixel m{};
                 const f2 p = level_pixel<L0>(a, X, Y, off, m);
                 vx[t] = in ? p.x : 0.f;
                 vy[t] = in ? p.y : 0.f;
-                if (L0 && t < kTR && col < kTW) {
+                if (L0 && t < kWinTR && col < kWinTW) {
                     const float d = p.x - p.y;
                     acc[0] += in ? d * d : 0.f;
                     if (ch == 0) {
@@ -130,67 +88,33 @@ __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
                     }
                 }
             }
-            if constexpr (SSIM) {
-                f2 vA[kTR], vB[kTR];
-                float vC[kTR];
-#pragma unroll
-                for (int j = 0; j < kTR; ++j) { vA[j] = (f2)(0.f); vB[j] = (f2)(0.f); vC[j] = 0.f; }
-#pragma unroll
-                for (int t = 0; t < kRows; ++t) {
-                    const f2 p = {vx[t], vy[t]};
-                    const f2 q = p * p;
-                    const float xy = p.x * p.y;
-#pragma unroll
-                    for (int j = 0; j < kTR; ++j) {
-                        const int tap = t - j;
-                        if (tap >= 0 && tap < kEvalTaps) {
-                            const f2 w = (f2)(a.win[tap]);
-                            vA[j] = __builtin_elementwise_fma(w, p, vA[j]);
-                            vB[j] = __builtin_elementwise_fma(w, q, vB[j]);
-                            vC[j] = fmaf(a.win[tap], xy, vC[j]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < kTR; ++j) { svA[grp * kTR + j][col] = vA[j]; svB[grp * kTR + j][col] = vB[j]; svC[grp * kTR + j][col] = vC[j]; }
-            }
+            if constexpr (SSIM)
+                window_vertical<2>(g, [&](int t, f2 (&p)[2], float &c) {
+                    p[0] = f2{vx[t], vy[t]};
+                    p[1] = p[0] * p[0];
+                    c = p[0].x * p[0].y;
+                }, S, grp, col);
         }
     }
     if constexpr (SSIM) {
         __syncthreads();
-        if (tid < kItems) {                         // horizontal pass: 14 columns of sums feed 4 window positions
-            const int hr = tid / (kTW / 4), hc = (tid & (kTW / 4 - 1)) * 4;
-            f2 oA[4], oB[4];
-            float oC[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { oA[j] = (f2)(0.f); oB[j] = (f2)(0.f); oC[j] = 0.f; }
-#pragma unroll
-            for (int t = 0; t < 14; ++t) {
-                const f2 pa = svA[hr][hc + t], pb = svB[hr][hc + t];
-                const float pc = svC[hr][hc + t];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int tap = t - j;
-                    if (tap >= 0 && tap < kEvalTaps) {
-                        const f2 w = (f2)(a.win[tap]);
-                        oA[j] = __builtin_elementwise_fma(w, pa, oA[j]);
-                        oB[j] = __builtin_elementwise_fma(w, pb, oB[j]);
-                        oC[j] = fmaf(a.win[tap], pc, oC[j]);
-                    }
-                }
-            }
+        if (tid < kWinItems) {                      // horizontal pass: 4 window positions
+            const int hr = tid / (kWinTW / 4), hc = (tid & (kWinTW / 4 - 1)) * 4;
+            f2 o[2][4];                             // (mu1, mu2), (E11, E22)
+            float oC[4];                            // E12
+            window_horizontal<2>(g, S, hr, hc, o, oC);
             const int yy = y0 + hr;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float cs;
-                const float ss = eval_ssim_pixel(oA[j].x, oA[j].y, oB[j].x, oB[j].y, oC[j], &cs);
+                const float ss = eval_ssim_pixel(o[0][j].x, o[0][j].y, o[1][j].x, o[1][j].y, oC[j], &cs);
                 const bool ok = yy + kEvalTaps - 1 < H && x0 + hc + j + kEvalTaps - 1 < W;      // the whole window lies inside the level
                 acc[3] += ok ? cs : 0.f;
                 acc[4] += ok ? ss : 0.f;
             }
         }
         if (a.px && tid < kPooled) {                // the next level's pixels that start at half this tile's origin
-            const int px = x0 / 2 + (tid & (kTW / 2 - 1)), py = y0 / 2 + tid / (kTW / 2);
+            const int px = x0 / 2 + (tid & (kWinTW / 2 - 1)), py = y0 / 2 + tid / (kWinTW / 2);
             if (px < a.PW && py < a.PH) {
                 const int ix = eval_pool_first(px, W), iy = eval_pool_first(py, H);
                 f2 s = (f2)(0.f);
@@ -209,11 +133,14 @@ __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
             }
         }
     }
+    // the wave reduction runs in double: the PSNR / depth sums are compared at 1e-6
+    double *const copy = sum_copy(a.sums, SPLAT_EVAL_SUMS);
+    const int base = eval_level_slot(a.level, ch);
     if constexpr (L0) {
-        block_sums<true>(a.sums, ch, a.level, acc, s_part);
+        block_sums_to<5, double>(copy, acc, s_part, [&](int k) { return k == 0 ? kEvalSumSq + ch : k == 1 ? kEvalSumDepth : k == 2 ? kEvalSumValid : base + k - 3; });
     } else {
         const float v[2] = {acc[3], acc[4]};
-        block_sums<false>(a.sums, ch, a.level, v, s_part);
+        block_sums_to<2, double>(copy, v, s_part, [&](int k) { return base + k; });
     }
 }
 
@@ -271,12 +198,8 @@ hipError_t launch_eval_metrics(int W, int H, const float *rgb, const float *dept
     a.sil_thres = cfg.sil_thres;
     a.sil_mask = cfg.sil_mask;
     a.W = W; a.H = H;
-    auto grid = [](int w, int h) {
-        const int tiles = 3 * ((w + kTW - 1) / kTW) * ((h + kTH - 1) / kTH);
-        return dim3(8 * ((tiles + 7) / 8));         // (level_tile: XCD x owns a contiguous run of tiles)
-    };
     if (!cfg.ms_ssim) {
-        hipLaunchKernelGGL((eval_level_kernel<true, false>), grid(W, H), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((eval_level_kernel<true, false>), xcd_tile_grid(W, H), dim3(kBlock), 0, s, a);
     } else {
         float *next = ews.pyramid;
         for (int l = 0; l < kEvalLevels; ++l) {
@@ -286,8 +209,8 @@ hipError_t launch_eval_metrics(int W, int H, const float *rgb, const float *dept
             const size_t plane3 = 3 * (size_t)a.PW * a.PH;
             a.px = last ? nullptr : next;
             a.py = last ? nullptr : next + plane3;
-            if (l == 0) hipLaunchKernelGGL((eval_level_kernel<true, true>), grid(a.W, a.H), dim3(kBlock), 0, s, a);
-            else hipLaunchKernelGGL((eval_level_kernel<false, true>), grid(a.W, a.H), dim3(kBlock), 0, s, a);
+            if (l == 0) hipLaunchKernelGGL((eval_level_kernel<true, true>), xcd_tile_grid(a.W, a.H), dim3(kBlock), 0, s, a);
+            else hipLaunchKernelGGL((eval_level_kernel<false, true>), xcd_tile_grid(a.W, a.H), dim3(kBlock), 0, s, a);
             a.x = a.px; a.y = a.py;
             a.W = a.PW; a.H = a.PH;
             next += 2 * plane3;

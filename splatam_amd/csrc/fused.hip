@@ -24,6 +24,7 @@
 #include "splat_device.h"
 
 #include "fused_math.h"
+#include "window_sums.h"
 
 namespace splat {
 
@@ -296,35 +297,6 @@ __global__ __launch_bounds__(kDenseBlock) void fused_preprocess_dense_kernel(Fus
     if (spilled) st.status[SPLAT_STATUS_OVERFLOW] = 1;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// block-level sums -> double atomics
-// ---------------------------------------------------------------------------------------------------------
-// ws.sums holds SPLAT_ITER_SUM_COPIES copies of the SPLAT_ITER_SUMS partial sums (one 256-byte pair of lines each):
-// a workgroup adds to copy (its linear id % copies), so that the few thousand workgroups of a launch do not queue
-// their atomics on ONE line (measured: ~12 ns per same-line atomic, i.e. 60 us for 4 900 workgroups).
-__device__ __forceinline__ double *sum_copy(double *sums) {
-    const unsigned b = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    return sums + (size_t)(b % SPLAT_ITER_SUM_COPIES) * SPLAT_ITER_SUMS;
-}
-
-template <int N>
-__device__ __forceinline__ void block_sum_to(double *dst, const float (&v)[N], double *s_part /* [N][waves] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        float x = v[k];
-        for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-        if (lane == 0) s_part[k * nw + wave] = (double)x;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < N) {
-        double t = 0.0;
-        for (int w = 0; w < nw; ++w) t += s_part[threadIdx.x * nw + w];
-        if (t != 0.0) atomicAdd(dst + threadIdx.x, t);
-    }
-    __syncthreads();
-}
-
 // total of one partial sum over the copies: call with a full wave; every lane returns the total
 __device__ __forceinline__ double sum_total(const double *sums, int k) {
     static_assert(SPLAT_ITER_SUM_COPIES == 64, "one copy per lane");
@@ -333,28 +305,9 @@ __device__ __forceinline__ double sum_total(const double *sums, int k) {
     return v;
 }
 
-struct Pixel {
-    bool mask;          // the depth (and, for tracking with the silhouette, colour) loss mask
-    float d_err;        // |gt_depth - depth| (finite when mask)
-    float d_sign;       // d|gt - d| / dd = sign(d - gt)
-};
-
-__device__ __forceinline__ float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
-
-// median: of |gt - d| * (gt > 0) over the frame, only read with ignore_outlier_depth_loss
-// (/root/reference/scripts/splatam.py:264-272: mask = (depth_error < 10 * median) & (gt > 0) & nan_mask [& silhouette])
+// the depth loss mask and terms of one pixel under the iteration's configuration (fused_math.h)
 __device__ __forceinline__ Pixel depth_pixel(const SplatLossConfig &cfg, float depth, float sil, float depth_sq, float gt, float median) {
-    Pixel r;
-    const float unc = depth_sq - depth * depth;
-    const bool nan_ok = !(depth != depth) && !(unc != unc);
-    bool m = gt > 0.f && nan_ok;
-    if (cfg.ignore_outlier_depth_loss) m = m && (fabsf(gt - depth) < 10.f * median);
-    if (cfg.tracking && cfg.use_sil_for_loss) m = m && (sil > cfg.sil_thres);
-    r.mask = m;
-    const float diff = gt - depth;
-    r.d_err = m ? fabsf(diff) : 0.f;
-    r.d_sign = m ? -sgn(diff) : 0.f;
-    return r;
+    return splat::depth_pixel(cfg.ignore_outlier_depth_loss != 0, cfg.tracking && cfg.use_sil_for_loss, cfg.sil_thres, depth, sil, depth_sq, gt, median);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -367,7 +320,6 @@ __global__ __launch_bounds__(kBlock) void track_loss_kernel(FusedArgs a, int HW)
     __shared__ double s_part[2 * (kBlock / 64)];
     const float *o = a.ws.out6;
     float *g = a.ws.dL_dout6;
-    const bool masked_im = a.cfg.use_sil_for_loss || a.cfg.ignore_outlier_depth_loss;
     const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     float acc[2] = {0.f, 0.f};
     const int nvec = HW / V;
@@ -388,16 +340,13 @@ __global__ __launch_bounds__(kBlock) void track_loss_kernel(FusedArgs a, int HW)
         ld(a.frame.depth, in[9]);
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-            const Pixel px = depth_pixel(a.cfg, in[3][v], in[4][v], in[5][v], in[9][v], median);
+            const float o6[6] = {in[0][v], in[1][v], in[2][v], in[3][v], in[4][v], in[5][v]}, im3[3] = {in[6][v], in[7][v], in[8][v]};
+            const TrackPixel px = track_pixel(a.cfg.ignore_outlier_depth_loss != 0, a.cfg.use_sil_for_loss != 0, a.cfg.sil_thres, a.cfg.use_l1 != 0,
+                                              a.cfg.w_im, a.cfg.w_depth, o6, im3, in[9][v], median);
             acc[0] += px.d_err;
-            out[3][v] = a.cfg.use_l1 ? a.cfg.w_depth * px.d_sign : 0.f;
-            const bool cm = masked_im ? px.mask : true;
+            acc[1] += px.im_err;
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float diff = in[6 + ch][v] - in[ch][v];
-                acc[1] += cm ? fabsf(diff) : 0.f;
-                out[ch][v] = cm ? -a.cfg.w_im * sgn(diff) : 0.f;
-            }
+            for (int ch = 0; ch < 4; ++ch) out[ch][v] = px.g[ch];
         }
 #pragma unroll
         for (int ch = 0; ch < 4; ++ch) {
@@ -405,31 +354,12 @@ __global__ __launch_bounds__(kBlock) void track_loss_kernel(FusedArgs a, int HW)
             else g[ch * (size_t)HW + i] = out[ch][0];
         }
     }
-    block_sum_to<2>(sum_copy(a.ws.sums), acc, s_part);
+    block_sums_to<2>(sum_copy(a.ws.sums, SPLAT_ITER_SUMS), acc, s_part);
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // F4 / F5: SSIM (11x11, sigma 1.5, zero padding; /root/reference/utils/slam_external.py:54-97)
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kSsimR = 5;                   // window radius
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// blockIdx -> (tile column, tile row, channel) of F4 / F5.  Workgroups are dealt to the 8 XCDs round robin and each XCD has its own
-// L2: with a plain 3-d grid the eight neighbours of a tile run on eight OTHER XCDs, and every halo pixel (the window is 1.9x the tile) comes from
-// memory again (F5: 167 MB of traffic for 75 MB of planes).  Here XCD x owns a contiguous run of the (channel, row, column) order, so a
-// tile's halo was read by the workgroup before it or one tile row earlier, through the SAME L2.
-template <int TW, int TH>
-__device__ __forceinline__ bool ssim_tile(int W, int H, int &bx, int &by, int &ch) {
-    const int ntx = (W + TW - 1) / TW, nty = (H + TH - 1) / TH, total = 3 * ntx * nty, per = (total + 7) / 8;
-    const int b = blockIdx.x, slot = b >> 3, t = (b & 7) * per + slot;
-    if (slot >= per || t >= total) return false;
-    ch = t / (ntx * nty);
-    const int r = t - ch * ntx * nty;
-    by = r / ntx;
-    bx = r - by * ntx;
-    return true;
-}
-
 // exp(-(x-5)^2 / (2 * 1.5^2)) normalised in float32, as create_window builds it (/root/reference/utils/slam_external.py:54-56)
 void ssim_window_host(float *g) {
     float s = 0.f;
@@ -452,20 +382,9 @@ __device__ __forceinline__ float ssim_pixel_dev(float mu1, float mu2, float e11,
     return map;
 }
 
-// F4 / F5 are separable 11-tap passes, VERTICAL pass first and without LDS: a thread owns one column of the window (lanes =
-// consecutive columns: the loads coalesce), holds kCR + 10 input rows in registers and forms kCR output rows of vertical sums; only
-// those go through LDS (24 rows x 42 columns, no halo rows), and the horizontal pass reads 14 columns for 4 output pixels, which it
-// finishes and stores as one float4 per plane: 10.5 LDS reads and 76 multiply-adds per pixel, 21 KB (F4) / 13 KB (F5) of LDS, one
-// barrier.  (Rounds 2-4 ran the passes the other way round -- window staged in LDS, horizontal pass over 26 halo rows for 16 output
-// rows, 12 rows of five sums read back per two output pixels: 29 LDS reads and 87 multiply-adds per pixel, 26 KB, two barriers:
-// F4 31.2 -> 25.0 us, F5 22.2 -> 21.0 us at 1200x680, profiles/r04_experiments.md 10.)  The five window statistics travel as two
-// float pairs + one float, so that the 11-tap sums are v_pk_fma_f32 (two statistics per instruction).
-constexpr int kCW = 32, kCR = 4, kCG = 6;   // tile width; output rows per thread of the vertical pass; row groups per workgroup
-constexpr int kCH = kCR * kCG;              // tile height 24
-constexpr int kCCols = kCW + 2 * kSsimR;    // 42 columns with halo
-constexpr int kCStride = 45;                // LDS row stride in elements: 1 mod 4, the 64-bit reads of the horizontal pass fall on distinct banks
-constexpr int kCItems = kCH * (kCW / 4);    // horizontal work items: (row, group of 4 columns)
-static_assert(kCCols * kCG <= kBlock && kCItems <= kBlock, "one trip per pass");
+// F4 / F5 run the separable 11-tap window pass of window_sums.h over the ZERO-PADDED window that starts kWinRadius pixels above and left
+// of the tile: F4 on two pairs + one single statistic (21 KB of LDS), F5 on one pair + one single (13 KB); a thread of the horizontal
+// pass finishes its four pixels and stores them as one float4 per plane.
 
 // four consecutive pixels of a plane row (clamped addresses; the caller discards what lies outside the image)
 template <bool VEC>
@@ -500,99 +419,74 @@ __device__ __forceinline__ float ld_off(const float *plane, unsigned byte_off) {
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// a window column's kWinRows values of up to three planes at one offset (zero outside the image); every load in flight before the first use
+template <int NPL>
+__device__ __forceinline__ void load_window_column(const float *const (&plane)[NPL], int W, int H, int x0, int y0, int grp, int col, float (&v)[NPL][kWinRows]) {
+    const int xx = x0 - kWinRadius + col;
+    const bool cin = xx >= 0 && xx < W;
+    const int xc = min(max(xx, 0), W - 1);
+#pragma unroll
+    for (int t = 0; t < kWinRows; ++t) {
+        const int yy = y0 + grp * kWinTR - kWinRadius + t;
+        const bool in = cin && yy >= 0 && yy < H;
+        // (any address inside the plane will do for a row outside the image: its value is discarded)
+        const unsigned off = (unsigned)min(max(yy * (4 * W) + 4 * xc, 0), 4 * (H * W - 1));
+        float tmp[NPL];
+#pragma unroll
+        for (int n = 0; n < NPL; ++n) tmp[n] = ld_off(plane[n], off);
+#pragma unroll
+        for (int n = 0; n < NPL; ++n) v[n][t] = in ? tmp[n] : 0.f;
+    }
+}
+
 // VEC: W % 4 == 0 and every plane 16-byte aligned (the launcher checks): whole float4 loads / stores of a thread's four pixels
 template <bool VEC>
 __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W, int H) {
-    __shared__ f2 svA[kCH][kCStride], svB[kCH][kCStride];      // vertical sums of (x, y) and (x x, y y)
-    __shared__ float svC[kCH][kCStride];                       // ... of x y
+    __shared__ WindowLds<2> S;                  // vertical sums of (x, y), (x x, y y) and x y
     __shared__ double s_part[4 * (kBlock / 64)];
-    float g[11];
+    float g[kWinTaps];
 #pragma unroll
-    for (int k = 0; k < 11; ++k) g[k] = a.win[k];
+    for (int k = 0; k < kWinTaps; ++k) g[k] = a.win[k];
     int bx, by, ch;
-    if (!ssim_tile<kCW, kCH>(W, H, bx, by, ch)) return;
+    if (!xcd_tile(W, H, bx, by, ch)) return;
     const int tid = threadIdx.x;
-    const int x0 = bx * kCW, y0 = by * kCH;
+    const int x0 = bx * kWinTW, y0 = by * kWinTH;
     const size_t HW = (size_t)H * W;
     const float *X = a.ws.out6 + ch * HW, *Y = a.frame.im + ch * HW;
     float *M = a.ws.ssim_maps + (size_t)(3 * ch) * HW;
     // the horizontal pass' work item and its own pixels (image L1 term; z == 0 slice: the depth-loss inputs)
-    const int hr = tid / (kCW / 4), hc = (tid & (kCW / 4 - 1)) * 4;
+    const int hr = tid / (kWinTW / 4), hc = (tid & (kWinTW / 4 - 1)) * 4;
     float own_x[4], own_y[4];
-    {   // vertical pass: thread = (column of the window, group of kCR output rows); every load in flight before the first sum
-        const int grp = tid / kCCols, col = tid - grp * kCCols;
-        if (grp < kCG) {
-            const int xx = x0 - kSsimR + col;
-            const bool cin = xx >= 0 && xx < W;
-            const int xc = min(max(xx, 0), W - 1);
-            float vx[kCR + 10], vy[kCR + 10];
-#pragma unroll
-            for (int t = 0; t < kCR + 10; ++t) {
-                const int yy = y0 + grp * kCR - kSsimR + t;
-                const bool in = cin && yy >= 0 && yy < H;
-                // (any address inside the plane will do for a row outside the image: its value is discarded)
-                const unsigned off = (unsigned)min(max(yy * (4 * W) + 4 * xc, 0), 4 * (H * W - 1));
-                const float tx = ld_off(X, off), ty = ld_off(Y, off);
-                vx[t] = in ? tx : 0.f;
-                vy[t] = in ? ty : 0.f;
-            }
-            f2 vA[kCR], vB[kCR];
-            float vC[kCR];
-#pragma unroll
-            for (int j = 0; j < kCR; ++j) { vA[j] = (f2)(0.f); vB[j] = (f2)(0.f); vC[j] = 0.f; }
-#pragma unroll
-            for (int t = 0; t < kCR + 10; ++t) {
-                const f2 p = {vx[t], vy[t]};
-                const f2 q = p * p;
-                const float xy = p.x * p.y;
-#pragma unroll
-                for (int j = 0; j < kCR; ++j) {
-                    const int tap = t - j;
-                    if (tap >= 0 && tap < 11) {
-                        const f2 w = (f2)(g[tap]);
-                        vA[j] = __builtin_elementwise_fma(w, p, vA[j]);
-                        vB[j] = __builtin_elementwise_fma(w, q, vB[j]);
-                        vC[j] = fmaf(g[tap], xy, vC[j]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kCR; ++j) { svA[grp * kCR + j][col] = vA[j]; svB[grp * kCR + j][col] = vB[j]; svC[grp * kCR + j][col] = vC[j]; }
+    {   // vertical pass: thread = (column of the window, group of kWinTR output rows)
+        const int grp = tid / kWinCols, col = tid - grp * kWinCols;
+        if (grp < kWinTG) {
+            const float *const planes[2] = {X, Y};
+            float v[2][kWinRows];
+            load_window_column(planes, W, H, x0, y0, grp, col, v);
+            window_vertical<2>(g, [&](int t, f2 (&p)[2], float &c) {
+                p[0] = f2{v[0][t], v[1][t]};
+                p[1] = p[0] * p[0];
+                c = p[0].x * p[0].y;
+            }, S, grp, col);
         }
     }
     // (requested here, when the window's registers are free again; they are used at the very end of the horizontal pass)
-    if (tid < kCItems) {
+    if (tid < kWinItems) {
         load_px4<VEC>(X, y0 + hr, x0 + hc, W, H, own_x);
         load_px4<VEC>(Y, y0 + hr, x0 + hc, W, H, own_y);
     }
     __syncthreads();
     const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};        // depth L1 (masked), image L1, mask count, SSIM map sum
-    if (tid < kCItems) {                        // horizontal pass: 14 columns of sums feed 4 output pixels
-        f2 oA[4], oB[4];
-        float oC[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { oA[j] = (f2)(0.f); oB[j] = (f2)(0.f); oC[j] = 0.f; }
-#pragma unroll
-        for (int t = 0; t < 14; ++t) {
-            const f2 pa = svA[hr][hc + t], pb = svB[hr][hc + t];
-            const float pc = svC[hr][hc + t];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int tap = t - j;
-                if (tap >= 0 && tap < 11) {
-                    const f2 w = (f2)(g[tap]);
-                    oA[j] = __builtin_elementwise_fma(w, pa, oA[j]);
-                    oB[j] = __builtin_elementwise_fma(w, pb, oB[j]);
-                    oC[j] = fmaf(g[tap], pc, oC[j]);
-                }
-            }
-        }
+    if (tid < kWinItems) {
+        f2 o[2][4];                             // (mu1, mu2), (E11, E22)
+        float oC[4];                            // E12
+        window_horizontal<2>(g, S, hr, hc, o, oC);
         const int yy = y0 + hr;
         float d0[4], d1[4], d2[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float map = ssim_pixel_dev(oA[j].x, oA[j].y, oB[j].x, oB[j].y, oC[j], &d0[j], &d1[j], &d2[j]);
+            const float map = ssim_pixel_dev(o[0][j].x, o[0][j].y, o[1][j].x, o[1][j].y, oC[j], &d0[j], &d1[j], &d2[j]);
             // (selects, not branches: the compiler sinks a pixel's sums into its conditional block and keeps all 70 inputs alive)
             const bool ok = yy < H && x0 + hc + j < W;
             acc[3] += ok ? map : 0.f;
@@ -602,7 +496,7 @@ __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W
         store_px4<VEC>(M + HW, yy, x0 + hc, W, H, d1);
         store_px4<VEC>(M + 2 * HW, yy, x0 + hc, W, H, d2);
     }
-    if (ch == 0 && tid < kCItems) {
+    if (ch == 0 && tid < kWinItems) {
         // the depth loss of the z == 0 slice (a third of the workgroups), behind everything else: its sixteen input registers held
         // through the passes would cost the kernel a wave per SIMD; the planes come through L2 (the forward composite wrote them)
         const int yy = y0 + hr;
@@ -619,97 +513,57 @@ __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W
             acc[2] += ok && px.mask ? 1.f : 0.f;
         }
     }
-    block_sum_to<4>(sum_copy(a.ws.sums), acc, s_part);
+    block_sums_to<4>(sum_copy(a.ws.sums, SPLAT_ITER_SUMS), acc, s_part);
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(kBlock) void map_loss_backward_kernel(FusedArgs a, int W, int H) {
-    __shared__ f2 svA[kCH][kCStride];           // vertical sums of (d/dmu1, d/dE11)
-    __shared__ float svC[kCH][kCStride];        // ... of d/dE12
+    __shared__ WindowLds<1> S;                  // vertical sums of (d/dmu1, d/dE11) and d/dE12
     __shared__ float s_count;
-    float g[11];
+    float g[kWinTaps];
 #pragma unroll
-    for (int k = 0; k < 11; ++k) g[k] = a.win[k];
+    for (int k = 0; k < kWinTaps; ++k) g[k] = a.win[k];
     int bx, by, ch;
-    if (!ssim_tile<kCW, kCH>(W, H, bx, by, ch)) return;
+    if (!xcd_tile(W, H, bx, by, ch)) return;
     const int tid = threadIdx.x;
-    const int x0 = bx * kCW, y0 = by * kCH;
+    const int x0 = bx * kWinTW, y0 = by * kWinTH;
     const size_t HW = (size_t)H * W;
     const float *M = a.ws.ssim_maps + (size_t)(3 * ch) * HW;
     if (tid < 64) {
         const double c = sum_total(a.ws.sums, 2);
         if (tid == 0) s_count = (float)c;
     }
-    const int hr = tid / (kCW / 4), hc = (tid & (kCW / 4 - 1)) * 4;
+    const int hr = tid / (kWinTW / 4), hc = (tid & (kWinTW / 4 - 1)) * 4;
     float own_x[4], own_y[4];
     {   // vertical pass (see ssim_forward_kernel)
-        const int grp = tid / kCCols, col = tid - grp * kCCols;
-        if (grp < kCG) {
-            const int xx = x0 - kSsimR + col;
-            const bool cin = xx >= 0 && xx < W;
-            const int xc = min(max(xx, 0), W - 1);
-            float v0[kCR + 10], v1[kCR + 10], v2[kCR + 10];
-#pragma unroll
-            for (int t = 0; t < kCR + 10; ++t) {
-                const int yy = y0 + grp * kCR - kSsimR + t;
-                const bool in = cin && yy >= 0 && yy < H;
-                const unsigned off = (unsigned)min(max(yy * (4 * W) + 4 * xc, 0), 4 * (H * W - 1));
-                const float t0 = ld_off(M, off), t1 = ld_off(M + HW, off), t2 = ld_off(M + 2 * HW, off);
-                v0[t] = in ? t0 : 0.f;
-                v1[t] = in ? t1 : 0.f;
-                v2[t] = in ? t2 : 0.f;
-            }
-            f2 vA[kCR];
-            float vC[kCR];
-#pragma unroll
-            for (int j = 0; j < kCR; ++j) { vA[j] = (f2)(0.f); vC[j] = 0.f; }
-#pragma unroll
-            for (int t = 0; t < kCR + 10; ++t) {
-                const f2 p = {v0[t], v1[t]};
-#pragma unroll
-                for (int j = 0; j < kCR; ++j) {
-                    const int tap = t - j;
-                    if (tap >= 0 && tap < 11) {
-                        vA[j] = __builtin_elementwise_fma((f2)(g[tap]), p, vA[j]);
-                        vC[j] = fmaf(g[tap], v2[t], vC[j]);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < kCR; ++j) { svA[grp * kCR + j][col] = vA[j]; svC[grp * kCR + j][col] = vC[j]; }
+        const int grp = tid / kWinCols, col = tid - grp * kWinCols;
+        if (grp < kWinTG) {
+            const float *const planes[3] = {M, M + HW, M + 2 * HW};
+            float v[3][kWinRows];
+            load_window_column(planes, W, H, x0, y0, grp, col, v);
+            window_vertical<1>(g, [&](int t, f2 (&p)[1], float &c) {
+                p[0] = f2{v[0][t], v[1][t]};
+                c = v[2][t];
+            }, S, grp, col);
         }
     }
-    if (tid < kCItems) {
+    if (tid < kWinItems) {
         load_px4<VEC>(a.ws.out6 + ch * HW, y0 + hr, x0 + hc, W, H, own_x);
         load_px4<VEC>(a.frame.im + ch * HW, y0 + hr, x0 + hc, W, H, own_y);
     }
     __syncthreads();
-    if (tid >= kCItems) return;
+    if (tid >= kWinItems) return;
     const float inv_n = 1.0f / (3.0f * (float)HW);
     const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     const float count = s_count;
-    f2 oA[4];
+    f2 o[1][4];
     float oC[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { oA[j] = (f2)(0.f); oC[j] = 0.f; }
-#pragma unroll
-    for (int t = 0; t < 14; ++t) {
-        const f2 pa = svA[hr][hc + t];
-        const float pc = svC[hr][hc + t];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int tap = t - j;
-            if (tap >= 0 && tap < 11) {
-                oA[j] = __builtin_elementwise_fma((f2)(g[tap]), pa, oA[j]);
-                oC[j] = fmaf(g[tap], pc, oC[j]);
-            }
-        }
-    }
+    window_horizontal<1>(g, S, hr, hc, o, oC);
     float out[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const float xv = own_x[j], yv = own_y[j];
-        const float dssim = oA[j].x + 2.f * xv * oA[j].y + yv * oC[j];
+        const float dssim = o[0][j].x + 2.f * xv * o[0][j].y + yv * oC[j];
         out[j] = a.cfg.w_im * (0.8f * sgn(xv - yv) * inv_n - 0.2f * inv_n * dssim);
     }
     store_px4<VEC>(a.ws.dL_dout6 + ch * HW, y0 + hr, x0 + hc, W, H, out);
@@ -1023,7 +877,7 @@ __global__ __launch_bounds__(kBlock, ISO ? 5 : 4) void fused_backward_kernel(Fus
     }
     // a band of tile rows (the other ranks hold the other bands): this rank's capacity flags travel with the partial sums
     if (a.cfg.defer_finish && i == 0 && (ws.st.status[SPLAT_STATUS_OVERFLOW] | ws.st.status[SPLAT_STATUS_STALE_HINT]) != 0) atomicAdd(ws.sums + kFlagSum, 1.0);
-    if (a.cfg.camera_grad) block_sum_to<kPoseSums>(sum_copy(ws.sums) + 8, pose, s_part);
+    if (a.cfg.camera_grad) block_sums_to<kPoseSums>(sum_copy(ws.sums, SPLAT_ITER_SUMS) + 8, pose, s_part);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1193,8 +1047,7 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
                 hipLaunchKernelGGL(track_loss_kernel<1>, dim3(blocks), dim3(kBlock), 0, s, a, HW);
             }
         } else {
-            const int tiles = 3 * ((W + kCW - 1) / kCW) * ((H + kCH - 1) / kCH);
-            const dim3 grid(8 * ((tiles + 7) / 8));                 // (ssim_tile: XCD x owns a contiguous run of tiles)
+            const dim3 grid = xcd_tile_grid(W, H);
             if ((W & 3) == 0 && aligned16(ws.out6) && aligned16(frame.im) && aligned16(frame.depth) && aligned16(ws.ssim_maps) && aligned16(ws.dL_dout6)) {
                 hipLaunchKernelGGL(ssim_forward_kernel<true>, grid, dim3(kBlock), 0, s, a, W, H);
                 hipLaunchKernelGGL(map_loss_backward_kernel<true>, grid, dim3(kBlock), 0, s, a, W, H);

@@ -10,6 +10,7 @@
 //   build_rotation                           /root/reference/utils/slam_external.py:25-42
 //   quat_mult                                /root/reference/utils/slam_helpers.py:21-29
 //   _ssim (per-pixel part)                   /root/reference/utils/slam_external.py:75-97
+//   get_loss (the masked L1 terms, per pixel) /root/reference/scripts/splatam.py:256-288
 // and their hand-derived adjoints (what torch.autograd computes for the reference).
 #pragma once
 
@@ -18,8 +19,6 @@
 namespace splat {
 
 constexpr float kNormEps = 1e-12f;       // torch.nn.functional.normalize: v / max(|v|, eps)
-constexpr float kSsimC1 = 0.01f * 0.01f;
-constexpr float kSsimC2 = 0.03f * 0.03f;
 
 // y = v / max(|v|, eps); returns 1 / max(|v|, eps)
 SPLAT_HD float normalize4(const float *v, float *y) {
@@ -167,6 +166,55 @@ SPLAT_HD float ssim_pixel(float mu1, float mu2, float e11, float e22, float e12,
     *de11 = -map / Dd;
     *de12 = 2.f * A * iCD;
     return map;
+}
+
+// ---- the masked L1 losses, per pixel (/root/reference/scripts/splatam.py:256-288) ----------------------------
+SPLAT_HD float sgn(float x) { return (x > 0.f) ? 1.f : ((x < 0.f) ? -1.f : 0.f); }
+
+struct Pixel {
+    bool mask;          // the depth (and, for tracking with the silhouette, colour) loss mask
+    float d_err;        // |gt_depth - depth| (finite when mask)
+    float d_sign;       // d|gt - d| / dd = sign(d - gt); +0 where gt == d
+};
+
+// mask = (gt > 0) & ~isnan(depth) & ~isnan(uncertainty) [& |gt - depth| < 10 median] [& sil > sil_thres]
+// median: of |gt - d| * (gt > 0) over the frame, only read with outlier rejection (ignore_outlier_depth_loss);
+// use_sil: tracking with use_sil_for_loss
+SPLAT_HD Pixel depth_pixel(bool reject_outliers, bool use_sil, float sil_thres, float depth, float sil, float depth_sq, float gt, float median) {
+    Pixel r;
+    const float unc = depth_sq - depth * depth;
+    bool m = gt > 0.f && !(depth != depth) && !(unc != unc);
+    const float diff = gt - depth;
+    if (reject_outliers) m = m && (fabsf(diff) < 10.f * median);
+    if (use_sil) m = m && (sil > sil_thres);
+    r.mask = m;
+    r.d_err = m ? fabsf(diff) : 0.f;
+    r.d_sign = m ? ((diff > 0.f) ? -1.f : ((diff < 0.f) ? 1.f : 0.f)) : 0.f;
+    return r;
+}
+
+// The tracking loss of one pixel (get_loss with tracking=True): o = the six rendered channels r, g, b, depth, silhouette, depth^2.
+// The colour terms take the depth mask when the silhouette or outlier rejection is in use, every pixel otherwise.  The silhouette
+// and depth^2 channels carry no gradient (the silhouette only masks, the uncertainty is detached).
+struct TrackPixel {
+    float d_err, im_err;    // masked |gt - depth|; (masked) sum over r, g, b of |im - colour|
+    float g[4];             // dL/d(r, g, b, depth) of  w_im * im_err + (use_l1 ? w_depth * d_err : 0)
+};
+
+SPLAT_HD TrackPixel track_pixel(bool reject_outliers, bool use_sil, float sil_thres, bool use_l1, float w_im, float w_depth,
+                                const float *o, const float *im3, float gt, float median) {
+    TrackPixel r;
+    const Pixel px = depth_pixel(reject_outliers, use_sil, sil_thres, o[3], o[4], o[5], gt, median);
+    r.d_err = px.d_err;
+    r.g[3] = use_l1 ? w_depth * px.d_sign : 0.f;
+    const bool cm = (use_sil || reject_outliers) ? px.mask : true;
+    r.im_err = 0.f;
+    for (int ch = 0; ch < 3; ++ch) {
+        const float di = im3[ch] - o[ch];
+        r.im_err += cm ? fabsf(di) : 0.f;
+        r.g[ch] = cm ? -w_im * sgn(di) : 0.f;
+    }
+    return r;
 }
 
 // Adam, one element (torch.optim.Adam, amsgrad=False, weight_decay=0): step_size = lr / (1 - beta1^t),

@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "splat_device.h"
+#include "fused_math.h"
 
 #ifndef SPLAT_BLOCK_RADIAL
 #define SPLAT_BLOCK_RADIAL 1       // the forward composite's 4x4-block lists: radial test per block on top of the box test (r06_experiments.md 9)
@@ -767,7 +768,7 @@ __global__ __launch_bounds__(256, ((forward_compact6<C, CS, WITH_DEPTH>() || (SP
         __syncthreads();
         if (tid == 0) st.tile_work[tile] = s_work;
     }
-    float acc_depth = 0.f, acc_im = 0.f;
+    float acc[2] = {0.f, 0.f};                  // TRACK: masked depth L1, (masked) image L1
     if (inside) {
         const size_t HW = (size_t)H * W;
         const size_t pix = (size_t)py * W + px;
@@ -781,38 +782,20 @@ __global__ __launch_bounds__(256, ((forward_compact6<C, CS, WITH_DEPTH>() || (SP
         }
         if constexpr (WITH_DEPTH) out_depth[pix] = D;
         if constexpr (TRACK) {
-            // channels: r, g, b, depth, silhouette, depth^2; mask = (gt > 0) & ~isnan(depth) & ~isnan(uncertainty) [& sil > thres]
             // (the four inputs of the loss requested together, ahead of the gradient stores: the compiler cannot move a load over a store
             //  it cannot prove disjoint, and the epilogue is a tail nothing hides)
             const float gt = ep.depth[pix];
             const float im3[3] = {ep.im[pix], ep.im[HW + pix], ep.im[2 * HW + pix]};
-            const float unc = o[5] - o[3] * o[3];
-            bool m = gt > 0.f && !(o[3] != o[3]) && !(unc != unc);
-            if (ep.use_sil_for_loss) m = m && (o[4] > ep.sil_thres);
-            const float dd = gt - o[3];
-            acc_depth = m ? fabsf(dd) : 0.f;
-            const float dsign = m ? ((dd > 0.f) ? -1.f : ((dd < 0.f) ? 1.f : 0.f)) : 0.f;
-            ep.dL_dout6[3 * HW + pix] = ep.use_l1 ? ep.w_depth * dsign : 0.f;
-            const bool cm = ep.use_sil_for_loss ? m : true;
+            const TrackPixel t = track_pixel(false, ep.use_sil_for_loss != 0, ep.sil_thres, ep.use_l1 != 0, ep.w_im, ep.w_depth, o, im3, gt, 0.f);
+            acc[0] = t.d_err;
+            acc[1] = t.im_err;
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                const float di = im3[ch] - o[ch];
-                acc_im += cm ? fabsf(di) : 0.f;
-                ep.dL_dout6[ch * HW + pix] = cm ? -ep.w_im * ((di > 0.f) ? 1.f : ((di < 0.f) ? -1.f : 0.f)) : 0.f;
-            }
+            for (int ch = 0; ch < 4; ++ch) ep.dL_dout6[ch * HW + pix] = t.g[ch];
         }
     }
     if constexpr (TRACK) {
-        // workgroup sums -> one of the SPLAT_ITER_SUM_COPIES copies of the partial sums (double atomics)
-        __shared__ double s_loss[2][4];
-        float a0 = acc_depth, a1 = acc_im;
-        for (int msk = 32; msk >= 1; msk >>= 1) { a0 += __shfl_xor(a0, msk, 64); a1 += __shfl_xor(a1, msk, 64); }
-        if (lane == 0) { s_loss[0][wave] = (double)a0; s_loss[1][wave] = (double)a1; }
-        __syncthreads();
-        if (tid < 2) {
-            const double t = s_loss[tid][0] + s_loss[tid][1] + s_loss[tid][2] + s_loss[tid][3];
-            if (t != 0.0) atomicAdd(ep.sums + (size_t)(blockIdx.x % SPLAT_ITER_SUM_COPIES) * SPLAT_ITER_SUMS + tid, t);
-        }
+        __shared__ double s_loss[2 * 4];
+        block_sums_to<2>(sum_copy(ep.sums, SPLAT_ITER_SUMS), acc, s_loss);
     }
 }
 
@@ -1307,7 +1290,7 @@ __device__ __forceinline__ void track_fused_body(const TrackFusedArgs &args) {
     constexpr size_t kBwd = (kHead + 15) / 16 * 16 + sizeof(PairBuf);
     __shared__ __attribute__((aligned(16))) unsigned char s_raw[kFwd > kBwd ? kFwd : kBwd];
     __shared__ unsigned s_wmax[4];
-    __shared__ double s_loss[2][4];
+    __shared__ double s_loss[2 * 4];
     BatchT &B = *reinterpret_cast<BatchT *>(s_raw);
     uint64_t *const s_keys = reinterpret_cast<uint64_t *>(s_raw + kKeysAt);
     PairBuf &PB = *reinterpret_cast<PairBuf *>(s_raw + (kHead + 15) / 16 * 16);
@@ -1336,8 +1319,8 @@ __device__ __forceinline__ void track_fused_body(const TrackFusedArgs &args) {
     for (int ch = 0; ch < C; ++ch) Cc[ch] = 0.f;
     const int staged = forward_tile<C, CS, false, true, false>(feat8, st, B, s_keys, tile, tx, ty, gx, tid, (float)fx_, (float)fy_, finside, Tr, D, Cc, flast);
     (void)D;
-    // ---- the loss of this pixel and its gradient planes, in registers (the arithmetic of render_forward_kernel's TRACK epilogue)
-    float acc_depth = 0.f, acc_im = 0.f, g[4] = {0.f, 0.f, 0.f, 0.f};
+    // ---- the loss of this pixel and its gradient planes, in registers (fused_math.h: track_pixel, as render_forward_kernel's TRACK epilogue)
+    float acc[2] = {0.f, 0.f}, g[4] = {0.f, 0.f, 0.f, 0.f};
     if (finside) {
         const size_t pix = (size_t)fy_ * W + fx_;
         const float gt = ep.depth[pix];
@@ -1345,20 +1328,11 @@ __device__ __forceinline__ void track_fused_body(const TrackFusedArgs &args) {
         float o[C];
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) o[ch] = Cc[ch] + Tr * bg_of(cam, ch);
-        const float unc = o[5] - o[3] * o[3];
-        bool m = gt > 0.f && !(o[3] != o[3]) && !(unc != unc);
-        if (ep.use_sil_for_loss) m = m && (o[4] > ep.sil_thres);
-        const float dd = gt - o[3];
-        acc_depth = m ? fabsf(dd) : 0.f;
-        const float dsign = m ? ((dd > 0.f) ? -1.f : ((dd < 0.f) ? 1.f : 0.f)) : 0.f;
-        g[3] = ep.use_l1 ? ep.w_depth * dsign : 0.f;
-        const bool cm = ep.use_sil_for_loss ? m : true;
+        const TrackPixel t = track_pixel(false, ep.use_sil_for_loss != 0, ep.sil_thres, ep.use_l1 != 0, ep.w_im, ep.w_depth, o, im3, gt, 0.f);
+        acc[0] = t.d_err;
+        acc[1] = t.im_err;
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const float di = im3[ch] - o[ch];
-            acc_im += cm ? fabsf(di) : 0.f;
-            g[ch] = cm ? -ep.w_im * ((di > 0.f) ? 1.f : ((di < 0.f) ? -1.f : 0.f)) : 0.f;
-        }
+        for (int ch = 0; ch < 4; ++ch) g[ch] = t.g[ch];
         if constexpr (KEEP) {
             st.final_T[pix] = Tr;
             st.n_contrib[pix] = (int)flast;
@@ -1368,16 +1342,8 @@ __device__ __forceinline__ void track_fused_body(const TrackFusedArgs &args) {
             for (int ch = 0; ch < 4; ++ch) ep.dL_dout6[ch * HW + pix] = g[ch];
         }
     }
-    {
-        float a0 = acc_depth, a1 = acc_im;
-        for (int msk = 32; msk >= 1; msk >>= 1) { a0 += __shfl_xor(a0, msk, 64); a1 += __shfl_xor(a1, msk, 64); }
-        if (lane == 0) { s_loss[0][wave] = (double)a0; s_loss[1][wave] = (double)a1; }
-        __syncthreads();                    // (also: every wave has left the forward pass -- the key array may become the pair buffer)
-        if (tid < 2) {
-            const double t = s_loss[tid][0] + s_loss[tid][1] + s_loss[tid][2] + s_loss[tid][3];
-            if (t != 0.0) atomicAdd(ep.sums + (size_t)(blockIdx.x % SPLAT_ITER_SUM_COPIES) * SPLAT_ITER_SUMS + tid, t);
-        }
-    }
+    // (exactly ONE barrier in here, and it is also: every wave has left the forward pass -- the key array may become the pair buffer)
+    block_sums_to<2>(sum_copy(ep.sums, SPLAT_ITER_SUMS), acc, s_loss);
     // ---- to the backward pass' layout: lane = pixel (lane & 7, lane >> 3) of the quadrant; its values sit in lane `src` of the forward layout
     const int qx = lane & 7, qy = lane >> 3;
     const int src = 16 * ((qx >> 2) + 2 * (qy >> 2)) + 4 * (qy & 3) + (qx & 3);

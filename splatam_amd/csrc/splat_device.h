@@ -117,6 +117,44 @@ __device__ __forceinline__ void load_cam(CamConst &c, const SplatCamera &cam) {
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
+// ---------------------------------------------------------------------------
+// workgroup sums -> double atomics
+// ---------------------------------------------------------------------------
+// Partial sums are kept in SPLAT_ITER_SUM_COPIES copies of `stride` doubles (SplatIterWorkspace.sums: SPLAT_ITER_SUMS, one 256-byte pair
+// of lines each; SplatEvalWorkspace.sums: SPLAT_EVAL_SUMS): a workgroup of a 1-d grid adds to copy (its id % copies), so that the few
+// thousand workgroups of a launch do not queue their atomics on ONE line (measured: ~12 ns per same-line atomic, i.e. 60 us for 4 900
+// workgroups).
+__device__ __forceinline__ double *sum_copy(double *sums, int stride) { return sums + (size_t)(blockIdx.x % SPLAT_ITER_SUM_COPIES) * stride; }
+
+// N per-thread partial sums of a 256-thread workgroup -> one atomicAdd each, of sum k into copy[slot(k)].  T: the type the wave
+// reduction runs in (the waves' results are added in double).  One barrier inside and none behind: call it once, by every thread.
+template <int N, typename T = float, typename Slot>
+__device__ __forceinline__ void block_sums_to(double *copy, const float (&v)[N], double *s_part /* [N][4] */, Slot slot) {
+    constexpr int nw = 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T x[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) x[k] = (T)v[k];
+    for (int m = 32; m >= 1; m >>= 1) {         // (the N butterflies side by side: six shuffle latencies, not 6 N)
+#pragma unroll
+        for (int k = 0; k < N; ++k) x[k] += __shfl_xor(x[k], m, 64);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s_part[k * nw + wave] = (double)x[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < N) {
+        const double *p = s_part + threadIdx.x * nw;
+        const double t = p[0] + p[1] + p[2] + p[3];
+        if (t != 0.0) atomicAdd(copy + slot((int)threadIdx.x), t);
+    }
+}
+template <int N, typename T = float>
+__device__ __forceinline__ void block_sums_to(double *copy, const float (&v)[N], double *s_part) {
+    block_sums_to<N, T>(copy, v, s_part, [](int k) { return k; });
+}
+
 // status word k (1: a bucket overflowed, 3: a list beyond the composite's sort) is raised, and with it the caller's pinned host word
 __device__ __forceinline__ void raise_status(const SplatState &st, int k) {
     st.status[k] = 1;

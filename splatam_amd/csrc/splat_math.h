@@ -29,6 +29,8 @@ constexpr float kAlphaMax = 0.99f;
 constexpr float kTStop = 0.0001f;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kTile = 16;
+constexpr float kSsimC1 = 0.01f * 0.01f;      // SSIM's two stabilisers at data range 1 (the mapping loss and the evaluation's MS-SSIM)
+constexpr float kSsimC2 = 0.03f * 0.03f;
 
 // Camera constants shared by every Gaussian of a launch.  m(r,c) = flat[c*4+r].
 struct CamConst {

@@ -120,6 +120,22 @@ void hm_ssim_pixel(int n, const float *mu1, const float *mu2, const float *e11, 
     for (int i = 0; i < n; ++i) map[i] = ssim_pixel(mu1[i], mu2[i], e11[i], e22[i], e12[i], dmu1 + i, de11 + i, de12 + i);
 }
 
+// the tracking loss per pixel: out6[6][n] rendered channels, im[3][n], gt[n] -> grad[4][n] = dL/d(r, g, b, depth), sums[2] = the two error
+// terms over the pixels (in double, like the kernels' workgroup sums)
+void hm_track_pixel(int n, int reject_outliers, int use_sil, float sil_thres, int use_l1, float w_im, float w_depth, float median,
+                    const float *out6, const float *im, const float *gt, float *grad, double *sums) {
+    sums[0] = sums[1] = 0.0;
+    for (int i = 0; i < n; ++i) {
+        float o[6], im3[3];
+        for (int ch = 0; ch < 6; ++ch) o[ch] = out6[(size_t)ch * n + i];
+        for (int ch = 0; ch < 3; ++ch) im3[ch] = im[(size_t)ch * n + i];
+        const TrackPixel t = track_pixel(reject_outliers != 0, use_sil != 0, sil_thres, use_l1 != 0, w_im, w_depth, o, im3, gt[i], median);
+        sums[0] += t.d_err;
+        sums[1] += t.im_err;
+        for (int ch = 0; ch < 4; ++ch) grad[(size_t)ch * n + i] = t.g[ch];
+    }
+}
+
 void hm_adam(int n, float *param, const float *grad, float *m, float *v, float beta1, float beta2, float step_size,
              float bc2_sqrt, float eps) {
     for (int i = 0; i < n; ++i) param[i] = adam_update(param[i], grad[i], m[i], v[i], beta1, beta2, step_size, bc2_sqrt, eps);

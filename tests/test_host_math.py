@@ -182,6 +182,101 @@ def test_fused_ssim_pixel_against_autograd(shim):
     assert (grad - ref).abs().max() <= 2e-4 * ref.abs().max()
 
 
+class _PlanesRenderer:
+    """Stands in for the rasterizer inside slam.get_loss: the colour pass returns ``im``, the depth-silhouette pass ``depth_sil``."""
+    planes = None
+
+    def __init__(self, raster_settings):
+        pass
+
+    def __call__(self, **rendervar):
+        n = rendervar['means3D'].shape[0]
+        return _PlanesRenderer.planes.pop(0), torch.ones(n, dtype=torch.int32), None
+
+
+def _track_pixel_planes(nan_depth):
+    """512 random pixels (most of them valid and present) with the special ones placed by hand; returns the planes and the indices.
+    nan_depth: one rendered depth is NaN (not together with outlier rejection: torch.median of the frame's errors would be NaN)."""
+    g = torch.Generator().manual_seed(11)
+    H, W = 16, 32
+    n = H * W
+    gt = 1.0 + 3.0 * torch.rand(n, generator=g)
+    depth = gt + 0.05 * torch.randn(n, generator=g)
+    sil = torch.where(torch.rand(n, generator=g) < 0.85, torch.ones(n), torch.rand(n, generator=g))
+    depth_sq = depth * depth + 0.01 * torch.rand(n, generator=g)
+    gt_im = torch.rand(3, n, generator=g)
+    im = (gt_im + 0.1 * torch.randn(3, n, generator=g)).clamp(0, 1)
+    gt[torch.rand(n, generator=g) < 0.1] = 0.0                      # holes of the depth sensor
+    at = dict(gt_zero=3, nan_depth=40, nan_unc=41, sil_at=70, sil_below=71, sil_above=72, depth_equal=100, colour_equal=130,
+              outlier_in=200, outlier_out=201)
+    for k in at.values():
+        gt[k], sil[k] = 2.0, 1.0
+        depth[k] = 2.03125
+        depth_sq[k] = depth[k] * depth[k] + 0.001
+    gt[at['gt_zero']] = 0.0
+    if nan_depth:
+        depth[at['nan_depth']] = float('nan')
+    depth_sq[at['nan_unc']] = float('nan')                          # depth^2 channel not a number: the uncertainty is NaN, the depth is not
+    sil[at['sil_at']] = 0.99
+    sil[at['sil_below']] = float(np.nextafter(np.float32(0.99), np.float32(0)))
+    sil[at['sil_above']] = float(np.nextafter(np.float32(0.99), np.float32(1)))
+    depth[at['depth_equal']] = gt[at['depth_equal']]
+    im[1, at['colour_equal']] = gt_im[1, at['colour_equal']]
+    # either side of 10 * median: both errors lie far above the median itself, so placing them does not move it
+    err = ((gt - depth).abs() * (gt > 0)).nan_to_num(0.0)
+    med = float(err.median())
+    depth[at['outlier_in']] = 2.0 + 9.9 * med
+    depth[at['outlier_out']] = 2.0 + 10.1 * med
+    err = ((gt - depth).abs() * (gt > 0)).nan_to_num(0.0)
+    assert float(err.median()) == med and err[at['outlier_in']] < 10 * err.median() < err[at['outlier_out']]
+    out6 = torch.cat([im, depth[None], sil[None], depth_sq[None]])
+    return H, W, out6, gt_im, gt, err.median(), at
+
+
+def test_track_pixel_against_autograd_of_get_loss(shim, monkeypatch):
+    """track_pixel (fused_math.h; the tracking loss of the loss kernel and of both composites) against torch autograd of get_loss
+    with the two renders replaced by given planes.  Sums: relative 1e-6.  Gradient values: exact -- they are +-weight or 0 -- wherever
+    the argument of abs is non-zero, and 0 of either sign at the kinks (torch: sign(0) = 0; -0.0 == 0.0 holds)."""
+    from splatam_amd import slam
+    H, W, n = 16, 32, 512
+    params, variables = slam.synthetic_params(4, W, H, 30.0, 30.0, W / 2, H / 2, num_frames=2, seed=0, device="cpu")
+    cam = slam.setup_camera(W, H, [[30.0, 0, W / 2], [0, 30.0, H / 2], [0, 0, 1]], np.eye(4), device="cpu")
+    monkeypatch.setattr(slam, 'Renderer', _PlanesRenderer)
+    w_im, w_depth, sil_thres = 0.5, 1.0, 0.99
+    shim.hm_track_pixel.argtypes = [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_float] * 3 + [C.POINTER(C.c_float)] * 4 + [C.POINTER(C.c_double)]
+    for use_sil, outliers, use_l1 in ((True, False, True), (False, False, True), (True, False, False), (False, True, True), (True, True, True)):
+        _, _, out6, gt_im, gt, median, at = _track_pixel_planes(nan_depth=not outliers)
+        frame = {'cam': cam, 'im': gt_im.reshape(3, H, W), 'depth': gt.reshape(1, H, W), 'id': 1, 'w2c': torch.eye(4)}
+        planes = _np(out6)
+        im = out6[:3].reshape(3, H, W).clone().requires_grad_(True)
+        depth_sil = out6[3:].reshape(3, H, W).clone().requires_grad_(True)
+        _PlanesRenderer.planes = [im, depth_sil]
+        loss, _, wl = slam.get_loss(params, frame, dict(variables), 1, dict(im=w_im, depth=w_depth), use_sil, sil_thres, use_l1, outliers,
+                                    tracking=True)
+        loss.backward()
+        d_grad = depth_sil.grad[0:1] if use_l1 else torch.zeros(1, H, W)      # (without the depth term the depth render takes no part)
+        ref = np.concatenate([_np(im.grad).reshape(3, n), _np(d_grad).reshape(1, n)])
+        got, sums = np.full((4, n), 7.0, np.float32), np.zeros(2, np.float64)
+        shim.hm_track_pixel(n, int(outliers), int(use_sil), sil_thres, int(use_l1), w_im, w_depth, float(median), _p(planes), _p(_np(gt_im)),
+                            _p(_np(gt)), _p(got), _p(sums, C.c_double))
+        cfg = (use_sil, outliers, use_l1)
+        assert abs(w_im * sums[1] - float(wl['im'].detach())) <= 1e-6 * float(wl['im'].detach()), cfg
+        if use_l1:
+            assert abs(w_depth * sums[0] - float(wl['depth'].detach())) <= 1e-6 * float(wl['depth'].detach()), cfg
+        assert not np.isnan(ref).any() and (got == ref).all(), (cfg, np.argwhere(got != ref))
+        # ... and the hand-placed pixels did what they are there for
+        k = at['depth_equal']
+        assert got[3, k] == 0 and got[1, at['colour_equal']] == 0 and abs(got[0, at['colour_equal']]) == w_im
+        for name in ('gt_zero', 'nan_unc'):
+            assert got[3, at[name]] == 0 and (got[:3, at[name]] == 0).all() == (use_sil or outliers), (cfg, name)
+        if use_l1:
+            assert abs(got[3, at['sil_above']]) == w_depth
+            assert (got[3, at['sil_at']] == 0) == use_sil and (got[3, at['sil_below']] == 0) == use_sil, cfg
+            assert abs(got[3, at['outlier_in']]) == w_depth and (got[3, at['outlier_out']] == 0) == outliers, cfg
+        else:
+            assert (got[3] == 0).all()
+
+
 def test_fused_adam_matches_torch(shim):
     g = torch.Generator().manual_seed(1)
     p0 = torch.randn(1000, generator=g)
