@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 13       /* 13: frame preparation (splat_frame_prepare);
+#define SPLAT_ABI_VERSION 14       /* 14: frame ingest (splat_frame_ingest);
+                                      13: frame preparation (splat_frame_prepare);
                                       12: evaluation metrics (SplatEvalConfig, SplatEvalWorkspace, splat_eval_workspace_layout / _bind, splat_eval_metrics, splat_iter_eval);
                                       11: SplatAdamMap.one_minus_beta1 / _beta2 (torch's 1 - beta, formed in double);
                                       10: group binning behind the reference API (SplatState.group_* in splat_preprocess_forward / splat_render_forward,
@@ -725,6 +726,18 @@ int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFram
  * outputs may be views into larger buffers (16-byte stores are used only where width and alignment allow). */
 int splat_frame_prepare(int32_t src_w, int32_t src_h, const float *color_hwc, const float *depth_hw, int32_t dst_w, int32_t dst_h,
                         float *im_out, float *depth_out, void *stream);
+
+/* Frame ingest, the step before: what an image decoder leaves -- rgb_hwc [color_h][color_w][3] bytes and depth_raw [depth_h][depth_w],
+ * the integers of a 16-bit depth PNG, whose size may differ from the colour image's (ScanNet) -- to the frame a dataset hands over:
+ * color_out_hwc [dst_h][dst_w][3] float32 in 0..255 and depth_out [dst_h][dst_w] float32 in metres.  Colour is resampled with the
+ * rules of splat_frame_prepare on the byte values (no division: at dst == colour size every output is the byte itself, exactly);
+ * depth takes the nearest source pixel by the same index rule and is float32(double(raw) / png_depth_scale): one division in double,
+ * one narrowing, which is what the reference's datasets compute on the host (bit-equal for every uint16 and every scale > 0).  The
+ * loop's planes follow by splat_frame_prepare or by permute / 255.  One launch on `stream`, no allocation, nothing read back; the
+ * outputs may be views into larger buffers (16-byte stores are used only where dst_w is a multiple of 4 and both outputs start on
+ * 16 bytes).  SPLAT_E_INVALID for a non-positive size or scale and for NULL pointers. */
+int splat_frame_ingest(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const uint16_t *depth_raw,
+                       double png_depth_scale, int32_t dst_w, int32_t dst_h, float *color_out_hwc, float *depth_out, void *stream);
 
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup

@@ -18,7 +18,7 @@ SPLAT_MAX_CHANNELS = 8
 SPLAT_GRAD_STRIDE = 16
 SPLAT_COUNTER_STRIDE = 32
 SPLAT_GROUP_TILES = 2
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -170,7 +170,7 @@ EXPORTS = (
     "splat_workspace_bytes", "splat_state_layout", "splat_state_bind", "splat_iter_workspace_layout", "splat_iter_workspace_bind",
     "splat_iter_workspace_bytes",
     "splat_eval_workspace_layout", "splat_eval_workspace_bind", "splat_eval_metrics", "splat_iter_eval",
-    "splat_frame_prepare",
+    "splat_frame_prepare", "splat_frame_ingest",
 )
 
 _lib = None
@@ -273,6 +273,8 @@ def lib():
                                   C.POINTER(SplatIterWorkspace), C.POINTER(SplatEvalWorkspace), _fp, _fp]
     L.splat_frame_prepare.restype = C.c_int
     L.splat_frame_prepare.argtypes = [C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp]
+    L.splat_frame_ingest.restype = C.c_int
+    L.splat_frame_ingest.argtypes = [C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_double, C.c_int32, C.c_int32, _fp, _fp, _fp]
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int

@@ -1,7 +1,9 @@
 // frame_math.h -- index and blend arithmetic of frame preparation (a dataset frame color[H][W][3] in 0..255, depth[H][W][1] -> the
-// loop's im[3][h][w] in 0..1, depth[1][h][w], at the same or at another size), written once as host/device inline functions:
-// frameprep.hip calls them per lane, tests/test_frame_math_cpu.py compiles the very same header with g++ (tests/frame_math_shim.cpp)
-// and checks it against the float64 numpy form of the same definitions (tests/frame_ref.py).
+// loop's im[3][h][w] in 0..1, depth[1][h][w], at the same or at another size) and of frame ingest (a decoded image's bytes and a depth
+// PNG's integers -> such a dataset frame), written once as host/device inline functions:
+// frameprep.hip calls them per lane, tests/test_frame_math_cpu.py and tests/test_ingest_math_cpu.py compile the very same header with
+// g++ (tests/frame_math_shim.cpp, tests/ingest_math_shim.cpp) and check it against the float64 numpy form of the same definitions
+// (tests/frame_ref.py).
 //
 // Restates (in this project's words; nothing is copied) what the reference's datasets do to a frame on the host
 // (/root/reference/datasets/gradslam_datasets/basedataset.py:210-257): colour through cv2.resize(INTER_LINEAR) on the 0..255 values,
@@ -11,6 +13,7 @@
 #pragma once
 
 #include <math.h>
+#include <stdint.h>
 
 #include "splat_math.h"
 
@@ -46,10 +49,22 @@ SPLAT_HD int frame_nearest_index(int d, int src, int dst) {
 
 SPLAT_HD float frame_lerp(float a, float b, float w) { return a + w * (b - a); }
 
-// one channel of one destination pixel from its four source values (0..255): along x on both rows, then along y, then ONE division
-SPLAT_HD float frame_colour(float v00, float v01, float v10, float v11, float wx, float wy) {
+// one channel of one destination pixel from its four source values (0..255), still in 0..255: along x on both rows, then along y.
+// With both weights 0 (equal sizes) this is v00 itself.
+SPLAT_HD float frame_blend(float v00, float v01, float v10, float v11, float wx, float wy) {
     const float top = frame_lerp(v00, v01, wx), bottom = frame_lerp(v10, v11, wx);
-    return frame_lerp(top, bottom, wy) / 255.0f;
+    return frame_lerp(top, bottom, wy);
 }
+
+// ... and as the loop's image in 0..1: the blend, then ONE division
+SPLAT_HD float frame_colour(float v00, float v01, float v10, float v11, float wx, float wy) {
+    return frame_blend(v00, v01, v10, v11, wx, wy) / 255.0f;
+}
+
+// Frame ingest (splat_frame_ingest): a depth PNG's integer as metres.  The reference's datasets divide the float64 image by
+// png_depth_scale and narrow the quotient to float32 afterwards (basedataset.py:249-257, :336), so the division here is ONE division in
+// double and ONE narrowing: bit-equal to that for every uint16 and every scale.  (A float32 division rounds once where this rounds
+// twice; the two agree for many scales, 6553.5 / 5000 / 1000 among them, but not provably for all.)
+SPLAT_HD float frame_depth_metres(uint16_t raw, double png_depth_scale) { return (float)((double)raw / png_depth_scale); }
 
 }  // namespace splat

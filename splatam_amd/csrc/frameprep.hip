@@ -6,6 +6,13 @@
 //                                16-byte stores, else 1): consecutive lanes take consecutive x, so the four plane stores coalesce;
 //                                the y taps and the nearest row are the same for a whole wave but for the row breaks.
 //                                No LDS, no atomics, plain stores.
+//   P2 frame_ingest_kernel<V>    the step before P1: a decoded image's bytes rgb[H][W][3] and a depth PNG's integers depth[H'][W'] ->
+//                                the dataset frame color[h][w][3] in 0..255, depth[h][w] in metres (splat_frame_ingest).  The same lane
+//                                ownership; a lane's V pixels are 3V consecutive floats of the interleaved colour row, so with V = 4
+//                                a lane stores 48 contiguous bytes as three 16-byte stores and a wave 3 KiB without a gap.  The source
+//                                bytes are read one by one through __restrict__ const pointers: neighbouring lanes read neighbouring
+//                                or overlapping bytes of at most two rows, which the vector cache serves from the lines the first
+//                                lane brought in (the 2.4 MB image is read from memory once; nothing is staged).
 #include "splat_device.h"
 #include "frame_math.h"
 
@@ -46,7 +53,53 @@ __global__ void __launch_bounds__(kBlock) frame_prepare_kernel(int sw, int sh, c
     }
 }
 
+template <int V>
+__global__ void __launch_bounds__(kBlock) frame_ingest_kernel(int cw, int ch, const uint8_t *__restrict__ rgb, int zw, int zh,
+                                                              const uint16_t *__restrict__ depth_raw, double png_depth_scale,
+                                                              int dw, int dh, float *__restrict__ color_out, float *__restrict__ depth_out) {
+    const int per_row = dw / V;                                     // (V divides dw: the launcher's choice)
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= (long long)per_row * dh) return;
+    const int y = (int)(i / per_row), x0 = (int)(i % per_row) * V;
+    const FrameTap ty = frame_linear_tap(y, ch, dh);
+    const uint8_t *row0 = rgb + (size_t)ty.s0 * cw * 3, *row1 = rgb + (size_t)ty.s1 * cw * 3;
+    const uint16_t *drow = depth_raw + (size_t)frame_nearest_index(y, zh, dh) * zw;
+    float c[3 * V], d[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const FrameTap tx = frame_linear_tap(x0 + v, cw, dw);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            c[3 * v + k] = frame_blend((float)row0[3 * tx.s0 + k], (float)row0[3 * tx.s1 + k], (float)row1[3 * tx.s0 + k],
+                                       (float)row1[3 * tx.s1 + k], tx.w, ty.w);
+        d[v] = frame_depth_metres(drow[frame_nearest_index(x0 + v, zw, dw)], png_depth_scale);
+    }
+    const size_t o = (size_t)y * dw + x0;
+    if (V == 4) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+            *reinterpret_cast<float4 *>(color_out + 3 * o + 4 * q) = make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);
+        *reinterpret_cast<float4 *>(depth_out + o) = make_float4(d[0], d[1], d[2], d[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) color_out[3 * o + k] = c[k];
+        depth_out[o] = d[0];
+    }
+}
+
 }  // namespace
+
+hipError_t launch_frame_ingest(int cw, int ch, const uint8_t *rgb, int zw, int zh, const uint16_t *depth_raw, double png_depth_scale,
+                               int dw, int dh, float *color_out, float *depth_out, hipStream_t s) {
+    // 16-byte stores: a lane's 4 pixels start at float 12 * (...) of the colour and 4 * (...) of the depth, so, as in
+    // launch_frame_prepare, the width a multiple of 4 and both bases aligned put every store on 16 bytes
+    const bool vec = dw % 4 == 0 && (((uintptr_t)color_out | (uintptr_t)depth_out) & 15) == 0;
+    const long long items = (long long)(vec ? dw / 4 : dw) * dh;
+    const dim3 grid((unsigned)((items + kBlock - 1) / kBlock));
+    if (vec) hipLaunchKernelGGL(frame_ingest_kernel<4>, grid, dim3(kBlock), 0, s, cw, ch, rgb, zw, zh, depth_raw, png_depth_scale, dw, dh, color_out, depth_out);
+    else hipLaunchKernelGGL(frame_ingest_kernel<1>, grid, dim3(kBlock), 0, s, cw, ch, rgb, zw, zh, depth_raw, png_depth_scale, dw, dh, color_out, depth_out);
+    return hipGetLastError();
+}
 
 hipError_t launch_frame_prepare(int sw, int sh, const float *color, const float *depth, int dw, int dh, float *im, float *depth_out,
                                 hipStream_t s) {

@@ -91,6 +91,10 @@ size_t eval_pyramid_bytes(int W, int H);
 // frameprep.hip: a dataset frame (color[sh][sw][3] in 0..255, depth[sh][sw]) -> im[3][dh][dw] in 0..1, depth[dh][dw]
 hipError_t launch_frame_prepare(int sw, int sh, const float *color, const float *depth, int dw, int dh, float *im, float *depth_out,
                                 hipStream_t s);
+// ... and the step before it: a decoded image's bytes rgb[ch][cw][3], a depth PNG's integers depth_raw[zh][zw] -> color[dh][dw][3] in
+// 0..255, depth[dh][dw] = raw / png_depth_scale
+hipError_t launch_frame_ingest(int cw, int ch, const uint8_t *rgb, int zw, int zh, const uint16_t *depth_raw, double png_depth_scale,
+                               int dw, int dh, float *color_out, float *depth_out, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

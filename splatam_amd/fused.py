@@ -1200,6 +1200,45 @@ def prepare_frame(color, depth, size=None, out=None):
     return out[0], out[1]
 
 
+# ---------------------------------------------------------------------- frame ingest (csrc/frameprep.hip)
+def ingest_frame(rgb_u8, depth_u16, png_depth_scale, size=None, out=None):
+    """What an image decoder leaves -- ``rgb_u8`` [H, W, 3] uint8 and ``depth_u16`` [H', W'] (or [H', W', 1]) uint16, the integers
+    of a depth PNG, on one CUDA/HIP device; the two sizes may differ -- as the frame a dataset hands over: ``(color [h, w, 3] float32
+    in 0..255, depth [h, w, 1] float32 in metres)`` at ``size = (h, w)`` (default: the colour image's size).  Colour is resampled
+    bilinearly on the byte values (exactly the bytes at equal size), depth is the nearest source pixel as
+    ``float32(float64(raw) / png_depth_scale)`` (include/splat_hip.h splat_frame_ingest).  One launch on the current stream,
+    nothing read back.  ``out = (color, depth)``: contiguous float32 tensors of those shapes to write into (views into larger buffers
+    are fine); otherwise two new tensors."""
+    if not isinstance(rgb_u8, torch.Tensor) or rgb_u8.device.type != "cuda":
+        raise RuntimeError("ingest_frame needs CUDA/HIP tensors; the HIP library has no CPU path (datasets.ingest_frame_cpu is the torch form on the host)")
+    dev = rgb_u8.device
+    if rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.numel() == 0:
+        raise RuntimeError(f"rgb_u8 must be a uint8 tensor [H, W, 3] (got {rgb_u8.dtype}, {tuple(rgb_u8.shape)})")
+    H, W = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
+    if not (isinstance(depth_u16, torch.Tensor) and depth_u16.dtype == torch.uint16 and depth_u16.device == dev and depth_u16.numel() > 0
+            and (depth_u16.dim() == 2 or (depth_u16.dim() == 3 and depth_u16.shape[2] == 1))):
+        got = f"{depth_u16.dtype}, {tuple(depth_u16.shape)}, {depth_u16.device}" if isinstance(depth_u16, torch.Tensor) else type(depth_u16).__name__
+        raise RuntimeError(f"depth_u16 must be a uint16 tensor [H, W] or [H, W, 1] on {dev} (got {got})")
+    zH, zW = int(depth_u16.shape[0]), int(depth_u16.shape[1])
+    scale = float(png_depth_scale)
+    if not scale > 0.0:
+        raise RuntimeError(f"png_depth_scale must be positive (got {png_depth_scale})")
+    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if h <= 0 or w <= 0:
+        raise RuntimeError(f"size must be positive (got {(h, w)})")
+    rgb = rgb_u8 if rgb_u8.is_contiguous() else rgb_u8.contiguous()
+    raw = depth_u16 if depth_u16.is_contiguous() else depth_u16.contiguous()
+    if out is None:
+        out = (torch.empty(h, w, 3, dtype=torch.float32, device=dev), torch.empty(h, w, 1, dtype=torch.float32, device=dev))
+    for name, t, shape in (("out[0]", out[0], (h, w, 3)), ("out[1]", out[1], (h, w, 1))):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == shape and t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_frame_ingest(W, H, rgb.data_ptr(), zW, zH, raw.data_ptr(), scale, w, h, out[0].data_ptr(),
+                                                   out[1].data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "splat_frame_ingest")
+    return out[0], out[1]
+
+
 # ---------------------------------------------------------------------- evaluation metrics on planes (csrc/evalmetrics.hip)
 _eval_bufs: dict = {}
 

@@ -1,0 +1,152 @@
+"""``python -m splatam_amd.run CONFIG.py``: runs a SplaTAM experiment file over a sequence on disk.
+
+The file is one of the reference's own (configs/<dataset>/*.py: a Python module whose ``config`` dict the reference's
+``scripts/splatam.py`` loads with ``SourceFileLoader``, :992-1001); this package ships none of them.  What happens here is what that
+script does around its frame loop, restated: the defaults of :458-464 and :494-517, the seeding of utils/common_utils.py:8-22, the
+datasets (``datasets.get_dataset`` at the full size, ``at_size`` siblings where tracking or densification have a size of their own),
+``pipeline.rgbd_slam``, the evaluation as the run's last act, and ``params.npz`` under ``workdir/run_name`` with the reference's extra
+entries (:973-986).  Keys the loop cannot honour stop the run with a message that names them.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+import sys
+import time
+from importlib.machinery import SourceFileLoader
+
+import numpy as np
+import torch
+
+EXTRA_PARAMS = ("timestep", "intrinsics", "w2c", "org_width", "org_height", "gt_w2c_all_frames", "keyframe_time_indices")
+
+
+def load_experiment(path):
+    """The ``config`` dict of an experiment file."""
+    import importlib.util
+    loader = SourceFileLoader(os.path.basename(path), path)
+    spec = importlib.util.spec_from_loader(loader.name, loader)
+    module = importlib.util.module_from_spec(spec)
+    loader.exec_module(module)
+    if not isinstance(getattr(module, "config", None), dict):
+        raise ValueError(f"{path} defines no `config` dict")
+    return module.config
+
+
+def seed_everything(seed=42):
+    random.seed(seed)
+    os.environ["PYTHONHASHSEED"] = str(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    torch.backends.cudnn.deterministic = True
+    torch.backends.cudnn.benchmark = False
+
+
+def apply_defaults(config):
+    """The entries the reference fills in before its loop; returns (separate densification size?, separate tracking size?)."""
+    tracking = config['tracking']
+    if "use_depth_loss_thres" not in tracking:
+        tracking['use_depth_loss_thres'] = False
+        tracking['depth_loss_thres'] = 100000
+    tracking.setdefault('visualize_tracking_loss', False)
+    config.setdefault('gaussian_distribution', "isotropic")
+    data = config['data']
+    data.setdefault('ignore_bad', False)
+    data.setdefault('use_train_split', True)
+    separate = {}
+    for which in ("densification", "tracking"):
+        if f"{which}_image_height" not in data:
+            data[f"{which}_image_height"] = data["desired_image_height"]
+            data[f"{which}_image_width"] = data["desired_image_width"]
+        separate[which] = (data[f"{which}_image_height"], data[f"{which}_image_width"]) != \
+            (data["desired_image_height"], data["desired_image_width"])
+    return separate["densification"], separate["tracking"]
+
+
+def check_supported(config):
+    """Stops with the name of a key this loop cannot honour."""
+    if config.get('use_wandb'):
+        raise SystemExit("config['use_wandb'] = True: wandb logging is not supported; set it to False")
+    if config.get('load_checkpoint'):
+        raise SystemExit("config['load_checkpoint'] = True: resuming from a checkpoint is not supported; set it to False")
+    if config['tracking'].get('visualize_tracking_loss'):
+        raise SystemExit("config['tracking']['visualize_tracking_loss']: the tracking-loss viewer is not supported; set it to False")
+    if config.get('mean_sq_dist_method') != "projective":
+        raise SystemExit(f"config['mean_sq_dist_method'] = {config.get('mean_sq_dist_method')!r}: only \"projective\" is supported")
+
+
+def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4):
+    """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``."""
+    from . import datasets, pipeline
+    separate_densification, separate_tracking = apply_defaults(config)
+    check_supported(config)
+    data = config['data']
+    device = torch.device(config.get("primary_device", "cuda:0"))
+    if "gradslam_data_cfg" not in data:
+        data_cfg = {"dataset_name": data["dataset_name"]}
+    else:
+        data_cfg = datasets.load_dataset_config(data["gradslam_data_cfg"])
+    dataset = datasets.get_dataset(
+        config_dict=data_cfg, basedir=data["basedir"], sequence=os.path.basename(data["sequence"]), start=data["start"], end=data["end"],
+        stride=data["stride"], desired_height=data["desired_image_height"], desired_width=data["desired_image_width"], device=device,
+        relative_pose=True, ignore_bad=data["ignore_bad"], use_train_split=data["use_train_split"], prefetch=prefetch)
+    try:
+        n = data["num_frames"] if num_frames is None else num_frames
+        n = len(dataset) if n == -1 else min(int(n), len(dataset))
+        densify = dataset.at_size(data["densification_image_height"], data["densification_image_width"]) if separate_densification else None
+        tracking = dataset.at_size(data["tracking_image_height"], data["tracking_image_width"]) if separate_tracking else None
+        opts = None
+        if evaluate:
+            ms_ssim = min(data["desired_image_height"], data["desired_image_width"]) > 160
+            if not ms_ssim:
+                print("frames with min(H, W) <= 160: MS-SSIM is not computed")
+            opts = dict(eval_every=config['eval_every'], ms_ssim=ms_ssim)
+        t0 = time.perf_counter()
+        params, variables, stats = pipeline.rgbd_slam(dataset, config, engine=engine, num_frames=n, evaluate=opts,
+                                                      tracking_dataset=tracking, densify_dataset=densify)
+        if device.type == "cuda":
+            torch.cuda.synchronize(device)
+        stats['run_s'] = time.perf_counter() - t0
+        stats['frames'] = n
+        stats['dataset'] = dict(dataset.stats)
+        intrinsics, pose0 = dataset.intrinsics, dataset.transformed_poses[0]
+        out = {k: v for k, v in params.items()}
+        out['timestep'] = variables['timestep']
+        out['intrinsics'] = intrinsics[:3, :3].detach().cpu().numpy()
+        out['w2c'] = torch.linalg.inv(pose0).detach().cpu().numpy()
+        out['org_width'] = data["desired_image_width"]
+        out['org_height'] = data["desired_image_height"]
+        out['gt_w2c_all_frames'] = np.stack([torch.linalg.inv(dataset.transformed_poses[t]).cpu().numpy() for t in range(n)], axis=0)
+        out['keyframe_time_indices'] = np.array(stats['keyframe_time_indices'])
+        path = pipeline.save_params(out, os.path.join(config["workdir"], config["run_name"]))
+    finally:
+        dataset.close()
+    return params, variables, stats, path
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(prog="python -m splatam_amd.run", description=__doc__.split("\n\n")[0])
+    parser.add_argument("experiment", help="path to a SplaTAM experiment file (a Python file that defines `config`)")
+    parser.add_argument("--engine", default="fused", choices=("fused", "dropin", "plugin", "plugin_map_edits"))
+    parser.add_argument("--num-frames", type=int, default=None, help="overrides config['data']['num_frames'] (-1 = all)")
+    parser.add_argument("--no-eval", action="store_true", help="skip the evaluation of the final map")
+    args = parser.parse_args(argv)
+    config = load_experiment(args.experiment)
+    seed_everything(config['seed'])
+    print(f"Seed set to: {config['seed']}")
+    _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval)
+    ev = stats.get('eval')
+    if ev is not None:
+        print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"
+              f"Average Depth L1: {100 * ev['avg_depth_l1']:.2f} cm\nAverage MS-SSIM: {ev['avg_ms_ssim']:.3f}\n"
+              f"Final Average ATE RMSE: {100 * ev['ate_rmse']:.2f} cm")
+    loop_s = sum(stats['frame_s'])
+    print(f"{stats['frames']} frames, {stats['num_gaussians'][-1]} Gaussians, keyframes {stats['keyframe_time_indices']}: "
+          f"{stats['frames'] / loop_s:.2f} frames/s in the loop")
+    print(f"saved {path}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
