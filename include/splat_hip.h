@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 14       /* 14: frame ingest (splat_frame_ingest);
+#define SPLAT_ABI_VERSION 15       /* 15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
+                                      14: frame ingest (splat_frame_ingest);
                                       13: frame preparation (splat_frame_prepare);
                                       12: evaluation metrics (SplatEvalConfig, SplatEvalWorkspace, splat_eval_workspace_layout / _bind, splat_eval_metrics, splat_iter_eval);
                                       11: SplatAdamMap.one_minus_beta1 / _beta2 (torch's 1 - beta, formed in double);
@@ -738,6 +739,21 @@ int splat_frame_prepare(int32_t src_w, int32_t src_h, const float *color_hwc, co
  * 16 bytes).  SPLAT_E_INVALID for a non-positive size or scale and for NULL pointers. */
 int splat_frame_ingest(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const uint16_t *depth_raw,
                        double png_depth_scale, int32_t dst_w, int32_t dst_h, float *color_out_hwc, float *depth_out, void *stream);
+
+/* Both steps in one launch, for frames that arrive one at a time from a sensor or a decoder: rgb_hwc [color_h][color_w][3] bytes and
+ * depth_raw [depth_h][depth_w] at a size of its own (smaller than the destination too: a 256 x 192 LiDAR image under 960 x 720) -> the
+ * loop's planes im_out [3][dst_h][dst_w] in 0..1 and depth_out [dst_h][dst_w] in metres.  Colour: the blend of splat_frame_ingest on the
+ * byte values, then ONE float32 division by 255 -- the operations of splat_frame_ingest followed by splat_frame_prepare at equal size
+ * in their order, so the planes are bit-equal to that pair's (float32(byte) / 255 at dst == colour size).  Depth: the nearest source
+ * pixel; SPLAT_DEPTH_U16: float32(double(raw) / depth_scale) as splat_frame_ingest; SPLAT_DEPTH_F32: the source float's 32 bits, copied
+ * (zeros, negatives, inf and NaN payloads unchanged: the loop's masks decide), depth_scale must be 1.0.  One launch on `stream`, no
+ * allocation, nothing read back; the outputs may be views into larger buffers (16-byte stores only where dst_w is a multiple of 4 and
+ * both outputs start on 16 bytes).  SPLAT_E_INVALID for a non-positive size or scale, an unknown depth_type, a scale other than 1.0
+ * with SPLAT_DEPTH_F32 and for NULL pointers. */
+#define SPLAT_DEPTH_U16 0
+#define SPLAT_DEPTH_F32 1
+int splat_frame_ingest_planes(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const void *depth_raw,
+                              int32_t depth_type, double depth_scale, int32_t dst_w, int32_t dst_h, float *im_out, float *depth_out, void *stream);
 
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup

@@ -18,7 +18,8 @@ SPLAT_MAX_CHANNELS = 8
 SPLAT_GRAD_STRIDE = 16
 SPLAT_COUNTER_STRIDE = 32
 SPLAT_GROUP_TILES = 2
-ABI_VERSION = 14
+ABI_VERSION = 15
+SPLAT_DEPTH_U16, SPLAT_DEPTH_F32 = 0, 1
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -170,7 +171,7 @@ EXPORTS = (
     "splat_workspace_bytes", "splat_state_layout", "splat_state_bind", "splat_iter_workspace_layout", "splat_iter_workspace_bind",
     "splat_iter_workspace_bytes",
     "splat_eval_workspace_layout", "splat_eval_workspace_bind", "splat_eval_metrics", "splat_iter_eval",
-    "splat_frame_prepare", "splat_frame_ingest",
+    "splat_frame_prepare", "splat_frame_ingest", "splat_frame_ingest_planes",
 )
 
 _lib = None
@@ -275,6 +276,9 @@ def lib():
     L.splat_frame_prepare.argtypes = [C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp]
     L.splat_frame_ingest.restype = C.c_int
     L.splat_frame_ingest.argtypes = [C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_double, C.c_int32, C.c_int32, _fp, _fp, _fp]
+    L.splat_frame_ingest_planes.restype = C.c_int
+    L.splat_frame_ingest_planes.argtypes = [C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                            _fp, _fp, _fp]
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int

@@ -364,6 +364,16 @@ int splat_frame_ingest(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc,
                                      depth_out, (hipStream_t)stream));
 }
 
+int splat_frame_ingest_planes(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const void *depth_raw,
+                              int32_t depth_type, double depth_scale, int32_t dst_w, int32_t dst_h, float *im_out, float *depth_out, void *stream) {
+    if (color_w <= 0 || color_h <= 0 || depth_w <= 0 || depth_h <= 0 || dst_w <= 0 || dst_h <= 0 || (long long)color_w * color_h > 0x3fffffffLL
+        || (long long)depth_w * depth_h > 0x3fffffffLL || (long long)dst_w * dst_h > 0x3fffffffLL || !(depth_scale > 0.0)
+        || (depth_type != SPLAT_DEPTH_U16 && depth_type != SPLAT_DEPTH_F32) || (depth_type == SPLAT_DEPTH_F32 && depth_scale != 1.0)
+        || !rgb_hwc || !depth_raw || !im_out || !depth_out) return SPLAT_E_INVALID;
+    return check(launch_frame_ingest_planes(color_w, color_h, rgb_hwc, depth_w, depth_h, depth_raw, depth_type == SPLAT_DEPTH_F32, depth_scale,
+                                            dst_w, dst_h, im_out, depth_out, (hipStream_t)stream));
+}
+
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }
 
 static bool valid_store(const SplatMapStore *st) {

@@ -95,6 +95,9 @@ hipError_t launch_frame_prepare(int sw, int sh, const float *color, const float 
 // 0..255, depth[dh][dw] = raw / png_depth_scale
 hipError_t launch_frame_ingest(int cw, int ch, const uint8_t *rgb, int zw, int zh, const uint16_t *depth_raw, double png_depth_scale,
                                int dw, int dh, float *color_out, float *depth_out, hipStream_t s);
+// ... and both in one: the bytes and the raw depth (uint16 integers or float32 metres) -> im[3][dh][dw] in 0..1, depth[dh][dw]
+hipError_t launch_frame_ingest_planes(int cw, int ch, const uint8_t *rgb, int zw, int zh, const void *depth_raw, bool depth_is_float,
+                                      double depth_scale, int dw, int dh, float *im, float *depth_out, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

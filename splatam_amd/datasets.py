@@ -4,11 +4,14 @@
 here                                           reference (restated; nothing is copied)
 =============================================  =============================================
 ``load_dataset_config``                        datasets/gradslam_datasets/dataconfig.py:5-54 (YAML with recursive ``inherit_from``)
-``get_dataset``                                scripts/splatam.py:40-64 (replica, replicav2, tum, scannet)
+``get_dataset``                                scripts/splatam.py:40-64 (replica, replicav2, tum, scannet, nerfcapture)
 ``RGBDDataset``                                datasets/gradslam_datasets/basedataset.py:105-341
 ``ReplicaDataset`` / ``ReplicaV2Dataset``      datasets/gradslam_datasets/replica.py
 ``TUMDataset``                                 datasets/gradslam_datasets/tum.py (nearest-timestamp association, 1/32 s thinning)
 ``ScannetDataset``                             datasets/gradslam_datasets/scannet.py
+``NeRFCaptureDataset``                         datasets/gradslam_datasets/nerfcapture.py (``transforms.json``, ``rgb/*``, ``depth/*``)
+``ingest_planes_cpu``                          scripts/iphone_demo.py:218-243 (a live frame's bytes and depth at the loop's sizes; the
+                                               host form of ``fused.ingest_planes``, which ``session.SlamSession.add_raw_frame`` runs)
 =============================================  =============================================
 
 ``dataset[i]`` is ``(color [H, W, 3] float32 in 0..255, depth [H, W, 1] float32 in metres, intrinsics [4, 4], pose [4, 4])`` on
@@ -37,7 +40,7 @@ import torch
 
 from . import slam
 
-SUPPORTED = ("replica", "replicav2", "tum", "scannet")
+SUPPORTED = ("replica", "replicav2", "tum", "scannet", "nerfcapture")
 MAX_WORKERS = 4             # decode threads (PIL releases the GIL while it inflates); never sized by the host's core count
 MAX_DEPTH = 4               # frames decoded ahead
 
@@ -79,6 +82,20 @@ def natural_sorted(names):
 # the torch form of splat_frame_ingest
 # --------------------------------------------------------------------------
 
+def _blend_cpu(rgb, size):
+    """The colour half of ``ingest_frame_cpu``: uint8 [H, W, 3] -> float32 [h, w, 3] in 0..255, blended along x on both rows, then along y."""
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    h, w = size
+    c = rgb.to(torch.float32)
+    y0, y1, wy = slam._linear_taps(h, H, "cpu")
+    x0, x1, wx = slam._linear_taps(w, W, "cpu")
+    wx, wy = wx.view(1, w, 1), wy.view(h, 1, 1)
+    r0, r1 = c[y0], c[y1]
+    top = r0[:, x0] + wx * (r0[:, x1] - r0[:, x0])
+    bottom = r1[:, x0] + wx * (r1[:, x1] - r1[:, x0])
+    return (top + wy * (bottom - top)).contiguous()
+
+
 def ingest_frame_cpu(rgb_u8, depth_u16, png_depth_scale, size=None):
     """``fused.ingest_frame`` in torch on the host, the kernel's operations in the kernel's order (the taps are
     ``slam.prepare_frame``'s): colour blended in float32 along x on both rows and then along y, depth the nearest source pixel as
@@ -88,17 +105,38 @@ def ingest_frame_cpu(rgb_u8, depth_u16, png_depth_scale, size=None):
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     zH, zW = int(raw.shape[0]), int(raw.shape[1])
     h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    c = rgb.to(torch.float32)
-    y0, y1, wy = slam._linear_taps(h, H, "cpu")
-    x0, x1, wx = slam._linear_taps(w, W, "cpu")
-    wx, wy = wx.view(1, w, 1), wy.view(h, 1, 1)
-    r0, r1 = c[y0], c[y1]
-    top = r0[:, x0] + wx * (r0[:, x1] - r0[:, x0])
-    bottom = r1[:, x0] + wx * (r1[:, x1] - r1[:, x0])
-    color = top + wy * (bottom - top)
     near = raw.reshape(zH, zW).to(torch.int32)[slam._nearest_index(h, zH, "cpu")][:, slam._nearest_index(w, zW, "cpu")]
     depth = (near.to(torch.float64) / float(png_depth_scale)).to(torch.float32)
-    return color.contiguous(), depth.reshape(h, w, 1)
+    return _blend_cpu(rgb, (h, w)), depth.reshape(h, w, 1)
+
+
+def ingest_planes_cpu(rgb_u8, depth_raw, depth_scale=None, size=None):
+    """``fused.ingest_planes`` in torch on the host, the kernel's operations in the kernel's order: the blend of ``ingest_frame_cpu``
+    on the bytes, one float32 division by 255, planar; depth the nearest source pixel -- a uint16 as
+    ``float32(float64(raw) / depth_scale)``, a float32 copied bit for bit (it is gathered as int32, so NaN payloads survive;
+    ``depth_scale`` must then be None or 1).  Arrays or CPU tensors in (uint8 [H, W, 3]; uint16 or float32 [H', W'] or [H', W', 1]),
+    tensors out: ``(im [3, h, w] float32 in 0..1, depth [1, h, w] float32)``."""
+    rgb, raw = torch.as_tensor(rgb_u8), torch.as_tensor(depth_raw)
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise RuntimeError(f"rgb_u8 must be uint8 [H, W, 3] (got {rgb.dtype}, {tuple(rgb.shape)})")
+    if raw.dtype not in (torch.uint16, torch.float32) or not (raw.dim() == 2 or (raw.dim() == 3 and raw.shape[2] == 1)):
+        raise RuntimeError(f"depth_raw must be uint16 or float32 [H, W] or [H, W, 1] (got {raw.dtype}, {tuple(raw.shape)})")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    zH, zW = int(raw.shape[0]), int(raw.shape[1])
+    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
+    if h <= 0 or w <= 0:
+        raise RuntimeError(f"size must be positive (got {(h, w)})")
+    ys, xs = slam._nearest_index(h, zH, "cpu"), slam._nearest_index(w, zW, "cpu")
+    if raw.dtype == torch.float32:
+        if depth_scale is not None and float(depth_scale) != 1.0:
+            raise RuntimeError(f"float32 depth is in metres already: depth_scale must be None or 1 (got {depth_scale})")
+        depth = raw.contiguous().view(torch.int32).reshape(zH, zW)[ys][:, xs].contiguous().view(torch.float32)
+        color = _blend_cpu(rgb, (h, w))
+    else:
+        if depth_scale is None or not float(depth_scale) > 0.0:
+            raise RuntimeError(f"uint16 depth needs a positive depth_scale (got {depth_scale})")
+        color, depth = ingest_frame_cpu(rgb, raw, depth_scale, size=(h, w))
+    return (color / 255.0).permute(2, 0, 1).contiguous(), depth.reshape(1, h, w)
 
 
 # --------------------------------------------------------------------------
@@ -464,7 +502,48 @@ class TUMDataset(RGBDDataset):
         return out
 
 
-_DATASETS = {"replica": ReplicaDataset, "replicav2": ReplicaV2Dataset, "tum": TUMDataset, "scannet": ScannetDataset}
+class NeRFCaptureDataset(RGBDDataset):
+    """A capture of the NeRFCapture app as the reference's demo writes it: ``<basedir>/<sequence>/transforms.json`` (``w``, ``h``,
+    ``fl_x``, ``fl_y``, ``cx``, ``cy`` and ``frames[]`` with ``file_path`` = ``rgb/<name>`` and a camera-to-world ``transform_matrix``
+    in OpenGL axes), the images ``rgb/*`` in natural order, depth as 16-bit PNGs at a size of their own with 6553.5 units per metre.
+    The depth path is the colour path below the capture with EVERY occurrence of ``rgb`` replaced by ``depth`` (the reference's
+    ``str.replace``: ``rgb/rgb_3.png`` would read ``depth/depth_3.png``).  Poses are ``P @ c2w @ P.T`` with P = diag(1, -1, -1, 1).
+    The camera comes from the capture itself: ``config_dict`` is accepted for ``get_dataset`` and not read."""
+
+    def __init__(self, config_dict=None, basedir=None, sequence=None, stride=None, start=0, end=-1, desired_height=1440,
+                 desired_width=1920, **kwargs):
+        import json
+        self.input_folder = os.path.join(basedir, sequence)
+        with open(os.path.join(self.input_folder, "transforms.json"), "r") as f:
+            self.cams_metadata = json.load(f)
+        meta = self.cams_metadata
+        own = {"dataset_name": "nerfcapture",
+               "camera_params": {"png_depth_scale": 6553.5, "image_height": meta["h"], "image_width": meta["w"],
+                                 "fx": meta["fl_x"], "fy": meta["fl_y"], "cx": meta["cx"], "cy": meta["cy"]}}
+        super().__init__(own, stride=1 if stride is None else stride, start=start, end=end, desired_height=desired_height,
+                         desired_width=desired_width, **kwargs)
+
+    def _filepaths(self):
+        by_path = {frame["file_path"]: frame for frame in self.cams_metadata["frames"]}
+        flip = np.diag([1.0, -1.0, -1.0, 1.0])
+        color_paths, depth_paths, self._poses = [], [], []
+        for name in natural_sorted(os.listdir(os.path.join(self.input_folder, "rgb"))):
+            name = f"rgb/{name}"
+            if name not in by_path:
+                raise ValueError(f"{os.path.join(self.input_folder, name)}: no entry with file_path {name!r} in transforms.json "
+                                 f"({len(by_path)} frames listed)")
+            color_paths.append(os.path.join(self.input_folder, name))
+            depth_paths.append(os.path.join(self.input_folder, name.replace("rgb", "depth")))
+            c2w = np.asarray(by_path[name]["transform_matrix"], dtype=np.float32).astype(np.float64).reshape(4, 4)
+            self._poses.append((flip @ c2w @ flip.T).astype(np.float32))
+        return color_paths, depth_paths
+
+    def _load_poses(self, num_imgs):
+        return self._poses
+
+
+_DATASETS = {"replica": ReplicaDataset, "replicav2": ReplicaV2Dataset, "tum": TUMDataset, "scannet": ScannetDataset,
+             "nerfcapture": NeRFCaptureDataset}
 
 
 def get_dataset(config_dict, basedir, sequence, **kwargs):

@@ -6,7 +6,7 @@ here                                           reference
 =============================================  =============================================
 ``keyframe_selection_overlap``                 utils/keyframe_selection.py:44-103 (+ its get_pointcloud :10-41)
 ``replica_config`` / ``splatam_s_config``      configs/replica/splatam.py / splatam_s.py (the values the loop reads)
-``rgbd_slam``                                  scripts/splatam.py:455-905 (frame loop: pose initialisation, tracking with
+``rgbd_slam`` (over ``session.SlamSession``)   scripts/splatam.py:455-905 (frame loop: pose initialisation, tracking with
                                                best-candidate bookkeeping and the depth-loss retry, densification,
                                                keyframe selection, mapping with pruning, keyframe list)
 ``save_params`` / ``load_params``              utils/common_utils.py:25-52 (``params.npz``)
@@ -232,14 +232,18 @@ def _est_w2c(params, time_idx):
 
 
 def initialize_first_timestep(dataset, num_frames, scene_radius_depth_ratio, mean_sq_dist_method, gaussian_distribution, device="cuda",
-                              densify_frame=None, first=None):
+                              densify_frame=None, first=None, planes=None):
     """Map, variables, intrinsics, first-frame world-to-camera and camera from frame 0.  ``densify_frame`` = (im, depth,
     intrinsics[3, 3]) of the first densification frame when densification has a size of its own: the point cloud, its mean squared
     distances and the scene radius then come from IT, camera and w2c from the full frame (scripts/splatam.py:185-206).  ``first``:
-    ``dataset[0]`` when the caller has read it already."""
+    ``dataset[0]`` when the caller has read it already; ``planes`` = (im [3, H, W] in 0..1, depth [1, H, W]) when it has the frame
+    in the loop's layout already (the item's colour and depth are then not read)."""
     color, depth, intrinsics, pose = dataset[0] if first is None else first
-    color = color.permute(2, 0, 1) / 255
-    depth = depth.permute(2, 0, 1)
+    if planes is not None:
+        color, depth = planes
+    else:
+        color = color.permute(2, 0, 1) / 255
+        depth = depth.permute(2, 0, 1)
     intrinsics = intrinsics[:3, :3]
     w2c = torch.linalg.inv(pose)
     cam = slam.setup_camera(color.shape[2], color.shape[1], intrinsics.cpu().numpy(), w2c.detach().cpu().numpy(), device=device)
@@ -255,29 +259,33 @@ def initialize_first_timestep(dataset, num_frames, scene_radius_depth_ratio, mea
 
 
 class _ReducedFrames:
-    """The frames of one of the loop's reduced resolutions (tracking, densification): from a dataset of that size, as the reference
-    keeps one (scripts/splatam.py:537-587), or derived from the full-size frame -- ``prepare_frame`` (the HIP kernel for frames on the
-    device, the torch mirror on the CPU) and ``scale_intrinsics``, i.e. what such a dataset does to every frame it loads."""
+    """The frames of one of the loop's reduced resolutions (tracking, densification): items of a dataset of that size, as the
+    reference keeps one (scripts/splatam.py:537-587; ``first_item``: its first, which fixes size and intrinsics), or derived from the
+    full-size frame -- ``prepare_frame`` (the HIP kernel for frames on the device, the torch mirror on the CPU) and
+    ``scale_intrinsics``, i.e. what such a dataset does to every frame it loads.  ``intrinsics``: the caller's own for the derived
+    frames (a live session scales those of the raw image)."""
 
-    def __init__(self, dataset, size, full_size, full_k):
-        self.dataset, self.size = dataset, (int(size[0]), int(size[1]))
-        self._first, self._planes = None, None
-        if dataset is not None:
-            self._first = dataset[0]                    # (read once: size and intrinsics now, the frame itself at time index 0)
-            color, _, k, _ = self._first
+    def __init__(self, first_item, size, full_size, full_k, intrinsics=None):
+        self.from_items, self.size = first_item is not None, (int(size[0]), int(size[1]))
+        self._planes = None
+        if first_item is not None:
+            color, _, k, _ = first_item
             self.size = (int(color.shape[0]), int(color.shape[1]))
             self.intrinsics = k[:3, :3]
+        elif intrinsics is not None:
+            self.intrinsics = intrinsics[:3, :3]
         else:
             self.intrinsics = slam.scale_intrinsics(full_k, self.size[0] / full_size[0], self.size[1] / full_size[1])[:3, :3]
         self.cam = None
 
-    def frame(self, time_idx, full_color, full_depth):
-        """(im [3, h, w], depth [1, h, w]); ``full_*``: the full-size frame as the dataset hands it over.  Derived frames on the
-        device are written into ONE pair of planes kept for this resolution (a reduced frame is used within its own time index only:
-        the keyframe list keeps full-size frames)."""
-        if self.dataset is not None:
-            color, depth, _, _ = self._first if (time_idx == 0 and self._first is not None) else self.dataset[time_idx]
-            self._first = None
+    def frame(self, time_idx, full_color, full_depth, item=None):
+        """(im [3, h, w], depth [1, h, w]); ``full_*``: the full-size frame as the dataset hands it over; ``item``: this time
+        index's item of the dataset of this size.  Derived frames on the device are written into ONE pair of planes kept for this
+        resolution (a reduced frame is used within its own time index only: the keyframe list keeps full-size frames)."""
+        if self.from_items:
+            if item is None:
+                raise ValueError(f"frame {time_idx}: this resolution takes its frames from a dataset of its own, and no item of it was passed")
+            color, depth = item[0], item[1]
             return (color.permute(2, 0, 1) / 255).contiguous(), depth.permute(2, 0, 1).contiguous()
         if full_color.device.type == "cuda":
             from . import fused
@@ -288,17 +296,17 @@ class _ReducedFrames:
             return fused.prepare_frame(full_color, full_depth, self.size, out=self._planes)
         return slam.prepare_frame(full_color, full_depth, self.size)
 
-    def curr_data(self, time_idx, full_color, full_depth, w2c):
-        im, depth = self.frame(time_idx, full_color, full_depth)
+    def curr_data(self, time_idx, full_color, full_depth, w2c, item=None):
+        im, depth = self.frame(time_idx, full_color, full_depth, item)
         return {'cam': self.cam, 'im': im, 'depth': depth, 'id': time_idx, 'intrinsics': self.intrinsics, 'w2c': w2c}
 
 
-def _reduced_frames(which, dataset, config, full_size, full_k):
-    """The tracking / densification frames of a run, or None when that step runs on the full frame: a dataset the caller passed, or
-    ``config['data'][<which>_image_height / _width]`` that differ from the dataset's size (equal sizes mean "not separate":
-    scripts/splatam.py:498-517)."""
-    if dataset is not None:
-        return _ReducedFrames(dataset, (0, 0), full_size, full_k)
+def _reduced_frames(which, first_item, config, full_size, full_k):
+    """The tracking / densification frames of a run, or None when that step runs on the full frame: the first item of a dataset the
+    caller passed, or ``config['data'][<which>_image_height / _width]`` that differ from the dataset's size (equal sizes mean "not
+    separate": scripts/splatam.py:498-517)."""
+    if first_item is not None:
+        return _ReducedFrames(first_item, (0, 0), full_size, full_k)
     data = config.get('data') or {}
     if f"{which}_image_height" not in data:
         return None
@@ -339,7 +347,8 @@ class _PhaseTimer:
 
 def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacity=None, verbose=False, evaluate=None,
               tracking_dataset=None, densify_dataset=None):
-    """Runs the SplaTAM frame loop over ``dataset``; returns ``(params, variables, stats)`` with
+    """Runs the SplaTAM frame loop over ``dataset`` -- the driver over ``session.SlamSession``, which holds the loop's set-up and its
+    per-frame body: every frame is one ``add_frame(*dataset[i])`` -- and returns ``(params, variables, stats)`` with
     ``stats = {keyframe_time_indices, tracking_iters, mapping_iters, tracking_s, mapping_s, mapping_loop_s, num_gaussians,
     redone_iterations, phase_ms}`` (``mapping_loop_s``: the iterations alone, where the reference's own mapping timer runs,
     scripts/splatam.py:825-891; ``mapping_s`` also holds densification, keyframe selection and list re-learning; ``phase_ms``: one
@@ -382,186 +391,25 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     (PSNR, depth L1, MS-SSIM per evaluated frame, ATE; LPIPS is not computed).  The fused engine evaluates on its own map, the other
     engines' parameters get a throw-away ``FusedEngine``; with several ranks rank 0 evaluates and the dict is broadcast."""
     from . import dist as sdist
-    if engine not in ("fused", "dropin", "plugin", "plugin_map_edits"):
-        raise ValueError(engine)
-    fused = engine == "fused"
-    plugged = engine in ("plugin", "plugin_map_edits")
+    from .session import SlamSession
     world, rank = sdist.world_size(), sdist.get_rank()
-    if plugged and world > 1:
-        raise NotImplementedError(f"engine='{engine}' runs the reference's single-process loop")
     num_frames = len(dataset) if num_frames is None else min(num_frames, len(dataset))
-    tcfg, mcfg = config['tracking'], config['mapping']
-    if mcfg.get('use_gaussian_splatting_densification') and not fused:
-        # the reference's own densify cannot run inside its SLAM loop either: it never extends variables['timestep'], and the
-        # remove_points that follows indexes it with the longer mask (utils/slam_external.py:206-227, 139-162).  The fused engine
-        # carries `timestep` along with the duplicated rows (FusedEngine.densify).
-        raise NotImplementedError("gradient-based densification inside the frame loop needs engine='fused'")
-    dist_kind = config.get('gaussian_distribution', 'isotropic')
-    eng = None
-    first = dataset[0]
-    color0, depth0, intr0, pose0 = first
-    full_size = (int(color0.shape[0]), int(color0.shape[1]))
-    tracking_frames = _reduced_frames("tracking", tracking_dataset, config, full_size, intr0)
-    densify_frames = _reduced_frames("densification", densify_dataset, config, full_size, intr0)
-    if world > 1 and (tracking_frames is not None or densify_frames is not None):
-        raise NotImplementedError("tracking / densification at resolutions of their own is not supported in the multi-rank frame loop")
-    densify0 = None
-    if densify_frames is not None:
-        densify0 = densify_frames.frame(0, color0, depth0) + (densify_frames.intrinsics,)
-    if fused:
-        # first frame on the device: an empty capacity-managed map + one append of every valid-depth pixel
-        # (splat_map_add_new_gaussians, SPLAT_ADD_VALID_DEPTH) = get_pointcloud + initialize_params of the reference
-        from .fused import FusedEngine
-        color0 = (color0.permute(2, 0, 1) / 255).contiguous()
-        depth0 = depth0.permute(2, 0, 1).contiguous()
-        dev = depth0.device
-        intrinsics = intr0[:3, :3]
-        first_frame_w2c = torch.linalg.inv(pose0).to(dev).float().contiguous()
-        H, W = color0.shape[1], color0.shape[2]
-        cam = slam.setup_camera(W, H, intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
-        cols = 1 if dist_kind == "isotropic" else 3
-        if dist_kind not in ("isotropic", "anisotropic"):
-            raise ValueError(f"Unknown gaussian_distribution {dist_kind}")
-        rots = torch.zeros(1, 4, num_frames, device=dev)
-        rots[:, 0, :] = 1.0
-        z = lambda *shape: torch.nn.Parameter(torch.zeros(*shape, device=dev))      # noqa: E731
-        params = {'means3D': z(0, 3), 'rgb_colors': z(0, 3), 'unnorm_rotations': z(0, 4), 'logit_opacities': z(0, 1),
-                  'log_scales': z(0, cols), 'cam_unnorm_rots': torch.nn.Parameter(rots), 'cam_trans': z(1, 3, num_frames)}
-        variables = {k: torch.zeros(0, device=dev) for k in ('max_2D_radius', 'means2D_gradient_accum', 'denom', 'timestep')}
-        variables['scene_radius'] = torch.max(depth0 if densify0 is None else densify0[1]) / config['scene_radius_depth_ratio']
-        cap = gaussian_capacity or int(H * W * 2.5) + 65536
-        eng = FusedEngine(params, cam, gaussian_capacity=cap, variables=variables)
-        eng.keep_map_grads = False      # (a mapping iteration's gradients are discarded after its step: /root/reference/scripts/splatam.py:860-861)
-        if config['mean_sq_dist_method'] != "projective":
-            raise ValueError(f"Unknown mean_sq_dist_method {config['mean_sq_dist_method']}")
-    else:
-        params, variables, intrinsics, first_frame_w2c, cam = initialize_first_timestep(
-            dataset, num_frames, config['scene_radius_depth_ratio'], config['mean_sq_dist_method'], dist_kind,
-            device=depth0.device, densify_frame=densify0, first=first)
-        dev = params['means3D'].device
-        first_frame_w2c = first_frame_w2c.to(dev).float().contiguous()
-    # the cameras of the reduced resolutions: their own size and intrinsics at the FIRST frame's pose (scripts/splatam.py:191, 586)
-    for frames in (tracking_frames, densify_frames):
-        if frames is not None:
-            frames.cam = slam.setup_camera(frames.size[1], frames.size[0], frames.intrinsics.cpu().numpy(),
-                                           first_frame_w2c.detach().cpu().numpy(), device=dev)
-            if fused:
-                eng.add_camera(frames.cam)           # one map, a camera per resolution
-    if fused:
-        if densify0 is None:
-            eng.select_camera(cam)
-            eng.add_valid_depth_points(color0, depth0, intrinsics, first_frame_w2c)
-        else:
-            eng.add_valid_depth_points(densify0[0], densify0[1], densify0[2], first_frame_w2c, cam=densify_frames.cam)
-        scene_radius = variables['scene_radius']
-    keyframe_list, keyframe_time_indices = [], []
-    stats = dict(tracking_iters=0, mapping_iters=0, tracking_s=0.0, mapping_s=0.0, mapping_loop_s=0.0, redone_iterations=0,
-                 num_gaussians=[], phase_ms=[], frame_s=[], decisions=[])
-    phase = _PhaseTimer(dev)
-    installed = None
-    if plugged:
-        from . import plugin
-        installed = plugin.install(slam, map_edits=engine == "plugin_map_edits")
-    try:
+    # the loop body and its set-up live in session.SlamSession: this is the driver over a finished sequence
+    with SlamSession(config, num_frames, engine=engine, gaussian_capacity=gaussian_capacity, verbose=verbose, return_pose=False,
+                     reference_division=True) as session:
+        # (the keyframe rule asks whether a pose is finite: answered once, from the dataset's host copy of the poses where it keeps one)
+        host_poses = getattr(dataset, 'poses', None)
+        finite = torch.isfinite(host_poses[:num_frames]).flatten(1).all(dim=1).tolist() \
+            if isinstance(host_poses, torch.Tensor) and host_poses.device.type == "cpu" and host_poses.shape[0] >= num_frames else None
         for time_idx in range(num_frames):
-            t_frame = time.perf_counter()
-            will_add = time_idx > 0 and (time_idx + 1) % config['map_every'] == 0 and mcfg['add_new_gaussians']
-            # (with one resolution the phase is the permute / 255 the loop always did: timed on the host, no synchronisation added)
-            with phase("prepare_frames", sync=tracking_frames is not None or densify_frames is not None):
-                raw_color, raw_depth, _, gt_pose = dataset[time_idx]
-                color = (raw_color.permute(2, 0, 1) / 255).contiguous()
-                depth = raw_depth.permute(2, 0, 1).contiguous()
-                curr_data = {'cam': cam, 'im': color, 'depth': depth, 'id': time_idx, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
-                # tracking runs on the tracking frame, add_new_gaussians on the densification frame (scripts/splatam.py:660-667, 781-789)
-                tracking_curr_data = curr_data if tracking_frames is None else \
-                    tracking_frames.curr_data(time_idx, raw_color, raw_depth, first_frame_w2c)
-                densify_curr_data = curr_data if (densify_frames is None or not will_add) else \
-                    densify_frames.curr_data(time_idx, raw_color, raw_depth, first_frame_w2c)
-            # what the loop DECIDED on this frame, engine independent (host integers only; tests/loop_trace.py derives the same table
-            # from a recording of the reference's own rgbd_slam)
-            decided = dict(time_idx=time_idx, tracking_iters=0, rows_after_add=None, selected=None, views=[], prunes=[], rows_end=None,
-                           keyframe=False)
-            stats['decisions'].append(decided)
-            if time_idx > 0:
-                slam.initialize_camera_pose(params, time_idx, forward_prop=tcfg['forward_prop'])
-
-            # ---------------- tracking (scripts/splatam.py:676-744)
-            if fused and tracking_frames is not None and time_idx > 0 and not tcfg['use_gt_poses'] and not eng.lists_known(tracking_curr_data):
-                # a tracking camera of its own whose list statistics are unknown (its first frame, or an edit dropped them): one probe
-                # render sizes its lists, instead of a flagged first iteration and a phase run again
-                with phase("relearn_lists"):
-                    eng.relearn_lists(tracking_curr_data, time_idx)
-            with phase("tracking"):
-                t0 = time.perf_counter()
-                if time_idx > 0 and not tcfg['use_gt_poses']:
-                    if plugged:
-                        n_track, variables = _track_frame_statements(params, variables, tracking_curr_data, time_idx, tcfg)
-                    else:
-                        n_track = _track_frame(params, variables, tracking_curr_data, time_idx, tcfg, eng, stats)
-                    stats['tracking_iters'] += n_track
-                    decided['tracking_iters'] = n_track
-                    sdist.broadcast_pose(params, time_idx)              # replicas: one pose for the map edits that follow
-                elif time_idx > 0:
-                    with torch.no_grad():
-                        rel = torch.linalg.inv(gt_pose).to(dev)
-                        params['cam_unnorm_rots'][..., time_idx] = _matrix_to_quaternion(rel[:3, :3])
-                        params['cam_trans'][..., time_idx] = rel[:3, 3]
-            stats['tracking_s'] += time.perf_counter() - t0
-
-            # ---------------- densification + keyframe mapping (scripts/splatam.py:768-891)
-            if time_idx == 0 or (time_idx + 1) % config['map_every'] == 0:
-                t0 = time.perf_counter()
-                if mcfg['add_new_gaussians'] and time_idx > 0:
-                    with phase("add_new_gaussians"):
-                        if fused:
-                            eng.add_new_gaussians(densify_curr_data, mcfg['sil_thres'], time_idx, config['mean_sq_dist_method'], dist_kind)
-                        else:
-                            params, variables = slam.add_new_gaussians(params, variables, densify_curr_data, mcfg['sil_thres'], time_idx,
-                                                                       config['mean_sq_dist_method'], dist_kind)
-                    decided['rows_after_add'] = int(params['means3D'].shape[0])
-                    sdist.assert_replicated_count(int(params['means3D'].shape[0]), f"add_new_gaussians (frame {time_idx})", dev)
-                with phase("keyframe_selection"), torch.no_grad():
-                    curr_w2c = _est_w2c(params, time_idx)
-                    selected = keyframe_selection_overlap(depth, curr_w2c, intrinsics.to(dev), keyframe_list[:-1],
-                                                          config['mapping_window_size'] - 2)
-                    if len(keyframe_list) > 0:
-                        selected.append(len(keyframe_list) - 1)
-                    selected.append(-1)
-                    decided['selected'] = [int(x) for x in selected[:-1 - (1 if len(keyframe_list) > 0 else 0)]]
-                if fused and not eng.lists_known(curr_data):
-                    with phase("relearn_lists"):
-                        eng.relearn_lists(curr_data, time_idx)
-                if dev.type == "cuda":
-                    torch.cuda.synchronize(dev)
-                t_loop = time.perf_counter()                        # the reference's mapping timer starts here (scripts/splatam.py:825)
-                t_prune0 = phase.frame.get("prune", 0.0)
-                with phase("mapping_iterations"):
-                    _map_frame(params, variables, curr_data, time_idx, selected, keyframe_list, mcfg, eng,
-                               scene_radius if fused else None, stats, phase, decided)
-                # (the prune phase is timed inside the loop: report the iterations without it)
-                phase.frame["mapping_iterations"] -= phase.frame.get("prune", 0.0) - t_prune0
-                stats['mapping_iters'] += mcfg['num_iters']
-                stats['mapping_s'] += time.perf_counter() - t0
-                stats['mapping_loop_s'] += time.perf_counter() - t_loop
-
-            # ---------------- keyframe list (scripts/splatam.py:893-905)
-            if time_idx == 0 or (time_idx + 1) % config['keyframe_every'] == 0 or time_idx == num_frames - 2:
-                with phase("keyframe_store"), torch.no_grad():
-                    keyframe_list.append({'id': time_idx, 'est_w2c': _est_w2c(params, time_idx), 'color': color, 'depth': depth})
-                    keyframe_time_indices.append(time_idx)
-                    decided['keyframe'] = True
-            decided['rows_end'] = int(params['means3D'].shape[0])
-            stats['num_gaussians'].append(int(params['means3D'].shape[0]))
-            stats['phase_ms'].append(phase.next_frame())
-            stats['frame_s'].append(time.perf_counter() - t_frame)
-            if verbose:
-                print(f"frame {time_idx}: {stats['num_gaussians'][-1]} Gaussians, keyframes {keyframe_time_indices}", flush=True)
-    finally:
-        if installed is not None:
-            from . import plugin
-            stats['plugin'] = plugin.session_stats()
-            installed.uninstall()
-    stats['keyframe_time_indices'] = keyframe_time_indices
+            session._begin_frame()               # (reading the frame counts towards its prepare_frames phase and its frame_s)
+            item = dataset[time_idx]
+            tracking_item = tracking_dataset[time_idx] if tracking_dataset is not None else None
+            densify_item = densify_dataset[time_idx] if densify_dataset is not None and session._densifies(time_idx) else None
+            session.add_frame(*item, tracking_item=tracking_item, densify_item=densify_item,
+                              _pose_finite=None if finite is None else bool(finite[time_idx]))
+        params, variables, stats = session.finish()
+    fused, eng, cam, mcfg = engine == "fused", session.engine, session.cam, config['mapping']
     if evaluate is not None:
         from . import evaluation
         opts = dict(evaluate)
