@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 15       /* 15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
+#define SPLAT_ABI_VERSION 16       /* 16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
+                                      15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
                                       14: frame ingest (splat_frame_ingest);
                                       13: frame preparation (splat_frame_prepare);
                                       12: evaluation metrics (SplatEvalConfig, SplatEvalWorkspace, splat_eval_workspace_layout / _bind, splat_eval_metrics, splat_iter_eval);
@@ -754,6 +755,53 @@ int splat_frame_ingest(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc,
 #define SPLAT_DEPTH_F32 1
 int splat_frame_ingest_planes(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const void *depth_raw,
                               int32_t depth_type, double depth_scale, int32_t dst_w, int32_t dst_h, float *im_out, float *depth_out, void *stream);
+
+/* The view layer (csrc/view.hip, arithmetic in csrc/view_math.h): any view of the map as display bytes and a point cloud, on the
+ * device.  One struct for both entry points; each reads the fields under its name and `width`, `height`, the intrinsics.
+ *
+ * splat_view_camera: one small launch that writes what a camera of the fused iteration reads -- w2c (16 floats row-major: what
+ * SplatFrameData.w2c points to), viewmatrix (its transpose), projmatrix ((P w2c)^T with the OpenGL-style P of the reference's
+ * setup_camera, /root/reference/utils/recon_helpers.py:8-13) and campos (-R^T t, 3 floats) -- into buffers the caller owns, so that ONE
+ * SplatCamera renders from any pose without a host read.  The pose is either `w2c_in` (16 device floats, row-major, rigid) or, with
+ * w2c_in == NULL, the map's pose of frame `time_idx`: first_w2c . rel_w2c[time_idx] with rel_w2c from cam_unnorm_rots / cam_trans
+ * ([1][4][num_frames] / [1][3][num_frames]) as transform_to_frame forms it.  `offset` (HOST pointer to 16 doubles, row-major, or NULL)
+ * is multiplied from the left (the follow camera of the reference's online viewer).  Evaluated in double, each output rounded once.
+ *
+ * splat_view_finish: one streaming pass over out6 ([6][height][width]: r, g, b, depth, silhouette, depth^2); every output is optional
+ * (NULL = not asked for).
+ *   rgb8   [height][width][3] bytes.  SPLAT_VIEW_COLOR: c = rgb + (1 - silhouette) bg (the composite ran on a zero background and the
+ *          weights sum to the silhouette), clamped to 0..1 (NaN -> 0), times 255, rounded to nearest.  SPLAT_VIEW_DEPTH: row
+ *          trunc(clip((depth - vmin) / (vmax - vmin), 0, 1) * 255) of `lut` ([256][3] device bytes; vmin == vmax: row 255 above vmin, else
+ *          row 0).  SPLAT_VIEW_SILHOUETTE: grey 1 - silhouette.
+ *   points [height * width][3] floats: pixel (u, v) at depth z as c2w ((u - cx) / fx z, (v - cy) / fy z, z), c2w the rigid inverse of
+ *          `w2c` (device, as splat_view_camera wrote it; read only when points are asked for).
+ *   colors [height * width][3] floats: what SPLAT_VIEW_COLOR shows, in 0..1.
+ * 16-byte loads and stores where width is a multiple of 4, out6 / points / colors start on 16 bytes and rgb8 on 4; a scalar path
+ * otherwise.  No allocation, nothing read back.  SPLAT_E_INVALID for a non-positive size, NULL inputs an asked-for output needs, an
+ * unknown mode, a time_idx outside the map. */
+#define SPLAT_VIEW_COLOR 0
+#define SPLAT_VIEW_DEPTH 1
+#define SPLAT_VIEW_SILHOUETTE 2
+typedef struct SplatViewArgs {
+    int32_t width, height;
+    double fx, fy, cx, cy, near_z, far_z;
+    /* splat_view_camera */
+    const float *w2c_in;
+    const float *cam_unnorm_rots, *cam_trans, *first_w2c;
+    int32_t num_frames, time_idx;
+    const double *offset;        /* HOST, or NULL */
+    float *w2c, *viewmatrix, *projmatrix, *campos;     /* outputs of splat_view_camera; w2c is an input of splat_view_finish (points) */
+    /* splat_view_finish */
+    const float *out6;
+    int32_t mode;
+    float bg[3];
+    float vmin, vmax;
+    const uint8_t *lut;
+    uint8_t *rgb8;
+    float *points, *colors;
+} SplatViewArgs;
+int splat_view_camera(const SplatViewArgs *view, void *stream);
+int splat_view_finish(const SplatViewArgs *view, void *stream);
 
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup

@@ -18,8 +18,9 @@ SPLAT_MAX_CHANNELS = 8
 SPLAT_GRAD_STRIDE = 16
 SPLAT_COUNTER_STRIDE = 32
 SPLAT_GROUP_TILES = 2
-ABI_VERSION = 15
+ABI_VERSION = 16
 SPLAT_DEPTH_U16, SPLAT_DEPTH_F32 = 0, 1
+SPLAT_VIEW_COLOR, SPLAT_VIEW_DEPTH, SPLAT_VIEW_SILHOUETTE = 0, 1, 2
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -125,9 +126,19 @@ class SplatEvalWorkspace(C.Structure):
     _fields_ = [("pyramid", _fp), ("sums", _fp)]
 
 
+class SplatViewArgs(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("near_z", C.c_double), ("far_z", C.c_double),
+                ("w2c_in", _fp), ("cam_unnorm_rots", _fp), ("cam_trans", _fp), ("first_w2c", _fp),
+                ("num_frames", C.c_int32), ("time_idx", C.c_int32), ("offset", C.POINTER(C.c_double)),
+                ("w2c", _fp), ("viewmatrix", _fp), ("projmatrix", _fp), ("campos", _fp),
+                ("out6", _fp), ("mode", C.c_int32), ("bg", C.c_float * 3), ("vmin", C.c_float), ("vmax", C.c_float),
+                ("lut", _fp), ("rgb8", _fp), ("points", _fp), ("colors", _fp)]
+
+
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatIterWorkspace,
                     SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
-                    SplatEvalConfig, SplatEvalWorkspace)
+                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -172,6 +183,7 @@ EXPORTS = (
     "splat_iter_workspace_bytes",
     "splat_eval_workspace_layout", "splat_eval_workspace_bind", "splat_eval_metrics", "splat_iter_eval",
     "splat_frame_prepare", "splat_frame_ingest", "splat_frame_ingest_planes",
+    "splat_view_camera", "splat_view_finish",
 )
 
 _lib = None
@@ -279,6 +291,10 @@ def lib():
     L.splat_frame_ingest_planes.restype = C.c_int
     L.splat_frame_ingest_planes.argtypes = [C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                             _fp, _fp, _fp]
+    for name in ("splat_view_camera", "splat_view_finish"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(SplatViewArgs), _fp]
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int

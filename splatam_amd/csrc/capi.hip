@@ -59,7 +59,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatMap); SPLAT_SIZEOF_CASE(SplatFrameData); SPLAT_SIZEOF_CASE(SplatLossConfig); SPLAT_SIZEOF_CASE(SplatIterWorkspace);
     SPLAT_SIZEOF_CASE(SplatAdamMap); SPLAT_SIZEOF_CASE(SplatPoseAdam); SPLAT_SIZEOF_CASE(SplatMapStore); SPLAT_SIZEOF_CASE(SplatAddArgs);
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
-    SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace);
+    SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -372,6 +372,23 @@ int splat_frame_ingest_planes(int32_t color_w, int32_t color_h, const uint8_t *r
         || !rgb_hwc || !depth_raw || !im_out || !depth_out) return SPLAT_E_INVALID;
     return check(launch_frame_ingest_planes(color_w, color_h, rgb_hwc, depth_w, depth_h, depth_raw, depth_type == SPLAT_DEPTH_F32, depth_scale,
                                             dst_w, dst_h, im_out, depth_out, (hipStream_t)stream));
+}
+
+int splat_view_camera(const SplatViewArgs *v, void *stream) {
+    if (!v || v->width <= 0 || v->height <= 0 || !v->w2c || !v->viewmatrix || !v->projmatrix || !v->campos) return SPLAT_E_INVALID;
+    if (!(v->fx > 0.0) || !(v->fy > 0.0) || !(v->far_z > v->near_z)) return SPLAT_E_INVALID;
+    if (!v->w2c_in && (!v->cam_unnorm_rots || !v->cam_trans || !v->first_w2c || v->num_frames <= 0 || v->time_idx < 0 || v->time_idx >= v->num_frames))
+        return SPLAT_E_INVALID;
+    return check(launch_view_camera(*v, (hipStream_t)stream));
+}
+
+int splat_view_finish(const SplatViewArgs *v, void *stream) {
+    if (!v || v->width <= 0 || v->height <= 0 || (long long)v->width * v->height > 0x3fffffffLL || !v->out6) return SPLAT_E_INVALID;
+    if (v->mode != SPLAT_VIEW_COLOR && v->mode != SPLAT_VIEW_DEPTH && v->mode != SPLAT_VIEW_SILHOUETTE) return SPLAT_E_INVALID;
+    if (v->rgb8 && v->mode == SPLAT_VIEW_DEPTH && !v->lut) return SPLAT_E_INVALID;
+    if (v->points && (!v->w2c || !(v->fx > 0.0) || !(v->fy > 0.0))) return SPLAT_E_INVALID;
+    if (!v->rgb8 && !v->points && !v->colors) return SPLAT_OK;
+    return check(launch_view_finish(*v, (hipStream_t)stream));
 }
 
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }

@@ -98,6 +98,10 @@ hipError_t launch_frame_ingest(int cw, int ch, const uint8_t *rgb, int zw, int z
 // ... and both in one: the bytes and the raw depth (uint16 integers or float32 metres) -> im[3][dh][dw] in 0..1, depth[dh][dw]
 hipError_t launch_frame_ingest_planes(int cw, int ch, const uint8_t *rgb, int zw, int zh, const void *depth_raw, bool depth_is_float,
                                       double depth_scale, int dw, int dh, float *im, float *depth_out, hipStream_t s);
+// view.hip: a camera that moves in place (w2c / viewmatrix / projmatrix / campos from a pose on the device), and out6 as display bytes
+// and a point cloud
+hipError_t launch_view_camera(const SplatViewArgs &v, hipStream_t s);
+hipError_t launch_view_finish(const SplatViewArgs &v, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

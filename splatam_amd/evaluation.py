@@ -10,11 +10,15 @@ Kept from the reference, quirks included (each is pinned by tests/golden/eval_re
   * "depth RMSE" takes its square root per pixel and therefore equals depth L1;
   * the trajectory error aligns the translation columns of the world-to-camera matrices, skips frames whose ground-truth pose
     holds a NaN, and is a MEAN distance reported as "ATE RMSE" (``slam.evaluate_ate``).
-Not kept: plots and saved images, and LPIPS -- it needs AlexNet weights that this package does not carry; the result says
+``save_frames=True`` writes the reference's four picture directories (``rendered_rgb/gs_%04d.png``, ``rendered_depth/gs_%04d.png``,
+``rgb/gt_%04d.png``, ``depth/gt_%04d.png``: eval_helpers.py:418-426, 509-528) from the planes the evaluation render left, through
+splat_view_finish (csrc/view.hip); the depth pictures carry matplotlib's jet, not ``cv2.COLORMAP_JET`` (``splatam_amd.view``).
+Not kept: the plots, and LPIPS -- it needs AlexNet weights that this package does not carry; the result says
 ``lpips: None`` instead of a made-up number.  A failure in the trajectory error is raised, not replaced by 100.0.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import time
 
@@ -81,14 +85,79 @@ def _mirror_row(params, curr_data, t, sil_thres, sil_mask, ms_ssim):
     return torch.stack([v.detach().double().cpu() for v in vals] + [torch.zeros((), dtype=torch.float64)] * 3)
 
 
+class _FrameSaver:
+    """``save_frames``: per evaluated frame four pictures [H, W, 3] uint8 -- rendered colour and depth from the planes the evaluation
+    render left, the ground-truth frame's colour and depth (its image, its depth, a silhouette of ones) -- formed on the device by
+    splat_view_finish, copied into one of ``SLOTS`` pinned slots on the current stream (an event after the copy) and encoded to PNG
+    by a small thread pool, which waits for the slot's event, not the evaluation.  A slot is reused once its PNGs are written."""
+    SLOTS, WORKERS = 4, 4
+    NAMES = (("rendered_rgb", "gs"), ("rendered_depth", "gs"), ("rgb", "gt"), ("depth", "gt"))
+
+    def __init__(self, eval_dir, dev, H, W):
+        from concurrent.futures import ThreadPoolExecutor
+        from .view import jet_lut
+        self.dirs = [os.path.join(eval_dir, d) for d, _ in self.NAMES]
+        for d in self.dirs:
+            os.makedirs(d, exist_ok=True)
+        self.dev = dev
+        self.lut = torch.from_numpy(jet_lut()).to(dev)
+        self.bytes = torch.zeros(4, H, W, 3, dtype=torch.uint8, device=dev)
+        self.gt6 = torch.ones(5, H, W, dtype=torch.float32, device=dev)        # plane 4, the silhouette, stays 1
+        self.slots = [dict(host=torch.empty(4, H, W, 3, dtype=torch.uint8, pin_memory=True), event=torch.cuda.Event(), jobs=[]) for _ in range(self.SLOTS)]
+        self.turn = 0
+        self.by_frame = {}              # frame -> its PNG jobs: a frame saved again (evaluated again on re-learnt lists) waits for them
+        self.pool = ThreadPoolExecutor(max_workers=self.WORKERS)
+
+    def save(self, t, out6, im, depth):
+        """Enqueue frame ``t``: ``out6`` the render's planes, ``im`` [3, H, W] / ``depth`` [1, H, W] the ground truth."""
+        from .fused import view_finish
+        from PIL import Image
+        view_finish(out6, "color", rgb8=self.bytes[0])
+        view_finish(out6, "depth", lut=self.lut, rgb8=self.bytes[1])           # (vmin 0, vmax 6: eval_helpers.py:513-514)
+        self.gt6[0:3], self.gt6[3] = im, depth[0]
+        view_finish(self.gt6, "color", rgb8=self.bytes[2])
+        view_finish(self.gt6, "depth", lut=self.lut, rgb8=self.bytes[3])
+        slot = self.slots[self.turn]
+        self.turn = (self.turn + 1) % self.SLOTS
+        for job in slot['jobs'] + self.by_frame.pop(t, []):
+            job.result()                                                       # (the PNGs of the slot's previous frame, and any earlier ones of THIS frame, are written)
+        slot['host'].copy_(self.bytes, non_blocking=True)
+        slot['event'].record(torch.cuda.current_stream(self.dev))
+        host, event = slot['host'].numpy(), slot['event']
+
+        def write(i):
+            event.synchronize()
+            Image.fromarray(host[i]).save(os.path.join(self.dirs[i], f"{self.NAMES[i][1]}_{t:04d}.png"))
+        slot['jobs'] = self.by_frame[t] = [self.pool.submit(write, i) for i in range(4)]
+
+    def close(self):
+        """Every PNG is on disk (a failed write raises here) and the pool is gone."""
+        try:
+            for slot in self.slots:
+                for job in slot['jobs']:
+                    job.result()
+        finally:
+            self.pool.shutdown(wait=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.close()
+        else:
+            self.pool.shutdown(wait=True)                                      # (the evaluation failed: its own error is the one to raise)
+
+
 def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every=1, engine=None, eval_dir=None,
-             ms_ssim=True):
+             ms_ssim=True, save_frames=False):
     """Evaluates ``params`` (the final map and trajectory of a run over ``dataset``) on frames ``eval_frame_indices(num_frames,
     eval_every)``.  Returns a dict: per-frame float64 arrays ``psnr``, ``depth_rmse``, ``depth_l1``, ``ms_ssim`` (NaN when
     ``ms_ssim=False``), their means ``avg_psnr`` ..., ``ate_rmse``, ``frames`` (the evaluated indices), ``lpips`` (None: not computed),
     ``repeated`` (frames evaluated twice because their render outgrew the learnt list buckets), ``eval_s`` / ``eval_ms_per_frame`` (wall
     time from the call to the table read, dataset access and list learning included).  With ``eval_dir`` the reference's text
-    files psnr.txt, rmse.txt, l1.txt, ssim.txt are written there.
+    files psnr.txt, rmse.txt, l1.txt, ssim.txt are written there; ``save_frames`` (needs ``eval_dir`` and an engine) also writes the
+    evaluated frames as PNGs (``_FrameSaver``) -- the metrics and their single table read are the same with and without it.
 
     ``engine``: a ``FusedEngine`` that holds ``params`` (it evaluates on its own map), ``None`` (a throw-away engine is built
     around ``params``), or the string ``"mirror"``: the torch mirror (``slam.eval_frame_metrics`` on two ``slam.Renderer`` calls per
@@ -124,39 +193,49 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
 
     repeated = []
     poses = []
-    if mirror:
-        rows = []
-        for t in range(num_frames):
-            color, depth, _, pose = _frame(dataset, t)
-            poses.append(pose)
-            if t in frames:
-                rows.append(_mirror_row(params, curr(t, color, depth), t, sil_thres, sil_mask, ms_ssim))
-        host = torch.stack(rows).numpy()
-    else:
-        engine.relearn_lists(curr(0, color0, depth0), 0)                      # (one read: sizes the list buckets for the map as it is)
-        table = torch.zeros(len(frames), _capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
-        row_of = {t: i for i, t in enumerate(frames)}
-        for t in range(num_frames):
-            color, depth, _, pose = _frame(dataset, t)
-            poses.append(pose)                                               # (every frame's pose feeds the trajectory error)
-            if t in row_of:
-                engine.evaluate_frame(curr(t, color, depth), t, table[row_of[t]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
-        host = _read_table(table)
-        for i, t in enumerate(frames):
-            if host[i, _capi.SPLAT_EVAL_FLAGGED] == 0:
-                continue
-            # this view's lists outgrew the buckets learnt on frame 0: its row was formed on truncated lists.  Re-learn on this view
-            # (exact lists, capacity grown as needed) and evaluate it again
-            repeated.append(t)
-            color, depth, _, _ = _frame(dataset, t)
-            for k in ('status', 'tile_count', 'group_count'):
-                engine.buf[k].zero_()
-            engine.relearn_lists(curr(t, color, depth), t)
-            again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
-            engine.evaluate_frame(curr(t, color, depth), t, again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
-            host[i] = _read_table(again)
-            if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
-                raise RuntimeError(f"frame {t}: the per-tile lists could not be sized for its evaluation render")
+    saver = None
+    if save_frames:
+        if eval_dir is None or mirror:
+            raise ValueError("save_frames needs eval_dir and an engine (the pictures are formed on the device)")
+        saver = _FrameSaver(eval_dir, dev, int(color0.shape[1]), int(color0.shape[2]))
+    with saver if saver is not None else contextlib.nullcontext():       # (leaving it: every PNG is on disk, the pool shut down)
+        if mirror:
+            rows = []
+            for t in range(num_frames):
+                color, depth, _, pose = _frame(dataset, t)
+                poses.append(pose)
+                if t in frames:
+                    rows.append(_mirror_row(params, curr(t, color, depth), t, sil_thres, sil_mask, ms_ssim))
+            host = torch.stack(rows).numpy()
+        else:
+            engine.relearn_lists(curr(0, color0, depth0), 0)                      # (one read: sizes the list buckets for the map as it is)
+            table = torch.zeros(len(frames), _capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
+            row_of = {t: i for i, t in enumerate(frames)}
+            for t in range(num_frames):
+                color, depth, _, pose = _frame(dataset, t)
+                poses.append(pose)                                               # (every frame's pose feeds the trajectory error)
+                if t in row_of:
+                    engine.evaluate_frame(curr(t, color, depth), t, table[row_of[t]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
+                    if saver is not None:
+                        saver.save(t, engine.buf['out6'], color, depth)
+            host = _read_table(table)
+            for i, t in enumerate(frames):
+                if host[i, _capi.SPLAT_EVAL_FLAGGED] == 0:
+                    continue
+                # this view's lists outgrew the buckets learnt on frame 0: its row was formed on truncated lists.  Re-learn on this view
+                # (exact lists, capacity grown as needed) and evaluate it again
+                repeated.append(t)
+                color, depth, _, _ = _frame(dataset, t)
+                for k in ('status', 'tile_count', 'group_count'):
+                    engine.buf[k].zero_()
+                engine.relearn_lists(curr(t, color, depth), t)
+                again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
+                engine.evaluate_frame(curr(t, color, depth), t, again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
+                host[i] = _read_table(again)
+                if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
+                    raise RuntimeError(f"frame {t}: the per-tile lists could not be sized for its evaluation render")
+                if saver is not None:
+                    saver.save(t, engine.buf['out6'], color, depth)          # (its pictures again, from the complete lists)
     t_metrics = time.perf_counter() - t_start          # (the table read above waited for the device)
     out = {'frames': list(frames), 'eval_s': t_metrics, 'eval_ms_per_frame': 1e3 * t_metrics / max(len(frames), 1), 'psnr': host[:, _capi.SPLAT_EVAL_PSNR].copy(), 'depth_rmse': host[:, _capi.SPLAT_EVAL_DEPTH_RMSE].copy(),
            'depth_l1': host[:, _capi.SPLAT_EVAL_DEPTH_L1].copy(), 'ms_ssim': host[:, _capi.SPLAT_EVAL_MS_SSIM].copy(),

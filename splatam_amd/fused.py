@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import math
-from collections import ChainMap
+from collections import ChainMap, namedtuple
 from types import MappingProxyType
 
 import torch
@@ -202,6 +202,7 @@ class FusedEngine:
         self.map_step = 0
         self.pose_step = 0
         self.track_time_idx = None
+        self.map_version = 0            # counts the edits of the map's rows (_set_rows, rebind): what render_view's replay caches are keyed by
         self.allow_buckets = True
         # group binning (SplatState.group_count): with bucketed lists short enough for the composite's own sort, the per-Gaussian
         # kernel files one record per 2 x 2-tile group (slots through an LDS histogram) and the composite filters its group's
@@ -389,6 +390,7 @@ class FusedEngine:
             self.Pcap = cap
         changed = P != self.P
         self.P = P
+        self.map_version += 1
         self._layout_rows()
         if changed:
             # (a camera that holds a list length but no buckets keeps it here; a map edit, _set_rows, drops it)
@@ -445,6 +447,7 @@ class FusedEngine:
 
     def _set_rows(self, P, keep_lists_within=0.10):
         self.P = int(P)
+        self.map_version += 1
         self._publish()
         self._layout_rows()
         # the per-tile list statistics were learnt for another map: back to exact lists until check_overflow() / relearn_lists()
@@ -775,6 +778,137 @@ class FusedEngine:
             with torch.no_grad():
                 self._reset_opacities()
         return changed
+
+    # ------------------------------------------------------------------ views (csrc/view.hip; nothing of the map or the loop is written)
+    def view_camera(self, width, height, capacity=None):
+        """A camera for LOOKING at the map: created once, moved in place by every ``render_view`` (``ViewCamera``).  It owns planes, lists
+        and list statistics of its own, like a camera of ``add_camera``, but the engine does not count it (``num_cameras``) and never
+        makes it the current one.  ``capacity``: (Gaussian, tile) instances its lists hold (default as at construction)."""
+        return ViewCamera(self, int(width), int(height), capacity)
+
+    def _rows_at(self, view, t):
+        """Rows of the map with ``timestep <= t``: a PREFIX of the rows, because rows are appended in time order and compacted stably.
+        Checked once per map version (one host read), and refused otherwise: gradient-based densification clones rows, and such a map
+        would be rendered wrongly from a prefix.  One more small host read per distinct ``t`` and version."""
+        ts = None if self.variables is None else self.variables.get('timestep')
+        if ts is None:
+            raise RuntimeError("render_view(max_timestep=...): this FusedEngine was built without variables['timestep']")
+        ts = ts[:self.P]
+        key = (self.map_version, self.P, ts.data_ptr() if self.P else 0)
+        if view._replay_key != key:
+            if self.P > 1 and not bool((ts[1:] >= ts[:-1]).all()):
+                raise RuntimeError("render_view(max_timestep=...): variables['timestep'] is not non-decreasing along the rows (gradient-based "
+                                   "densification clones rows): the Gaussians up to a time step are not a prefix of the map")
+            view._replay_key, view._replay_rows = key, {}
+        t = float(t)
+        rows = view._replay_rows.get(t)
+        if rows is None:
+            rows = int(torch.searchsorted(ts.contiguous(), torch.tensor([t], dtype=ts.dtype, device=ts.device), right=True)) if self.P else 0
+            view._replay_rows[t] = rows
+        return rows
+
+    def render_view(self, view, w2c=None, time_idx=None, intrinsics=None, mode="color", background=(0.0, 0.0, 0.0), depth_range=(0.0, 6.0),
+                    lut=None, max_timestep=None, points=False, offset=None, near=0.01, far=100, first_w2c=None, rgb8=True):
+        """The map from any pose, as display bytes (and a point cloud): three launches on the current stream -- splat_view_camera moves
+        ``view`` to the pose, splat_iter_render composites the map's own Gaussian arrays at it, splat_view_finish turns the six planes
+        into ``rgb8`` [H, W, 3] uint8 (``mode`` "color" on ``background``, "depth" through ``lut`` over ``depth_range``, "sil": grey
+        1 - silhouette) and, with ``points``, ``points`` / ``colors`` [H W, 3] float32 (the reference's rgbd2pcd).  Nothing is read on the
+        host.  Returns a ``ViewImage`` of tensors the VIEW keeps: the next call on it overwrites them.
+
+        The pose: ``w2c`` (float32 [4, 4] on the device, rigid), or ``time_idx``: the map's pose of that frame,
+        ``first_w2c . rel_w2c[time_idx]`` (``first_w2c``: float32 [4, 4] on the device, default the identity); ``offset`` (a 4 x 4 on
+        the host) is multiplied from the left.  ``intrinsics``: a 3 x 3 (or 4 x 4) matrix or ``(fx, fy, cx, cy)`` on the host, for the
+        view's size; a zoom is another matrix, not another view.  ``lut``: [256, 3] uint8 on the device (default: ``view.jet_lut``).
+        ``max_timestep = t``: only the Gaussians with ``timestep <= t`` (the reference's online replay), see ``_rows_at``.
+
+        Nothing is allocated after the view's first call, whatever the pose, mode or zoom, with two exceptions a caller chooses:
+        ``points`` asked for the first time allocates the two cloud arrays then, and the first render after a
+        ``view.check_overflow()`` that learnt or changed the bucket stride lays out the view's group records (and the digest itself may
+        grow the lists).  ``w2c`` / ``first_w2c`` must be contiguous (nothing is copied per call).  The current camera, its
+        ``rendered()``, list statistics and tile orders are left as they were; the render writes nothing into the map, its Adam moments
+        or ``variables`` (not ``max_2D_radius`` either).  The per-Gaussian scratch (``radii``, ``xy``, ...) IS shared with the loop:
+        a view render belongs BETWEEN iterations, not between an iteration and the read of its ``seen`` or its
+        ``accumulate_mean2d_gradient``.  The DIGEST of a flagged view (``view.check_overflow()``) does touch one array of the map's:
+        like every digest it zeroes the backward accumulator (``accum``), which is zero between iterations anyway -- so it, too,
+        belongs between iterations, never between ``loss_backward`` and the step that reads the accumulator.
+
+        Lists that did not fit do not stop the call: the picture is then incomplete and ``truncated`` (a device int32, != 0) says so,
+        from the view camera's status.  ``view.check_overflow()`` is the digest for that camera (grows the lists, learns the buckets):
+        call it where the image is read anyway, then render again."""
+        if (w2c is None) == (time_idx is None):
+            raise ValueError("render_view takes a w2c or a time_idx")
+        if view.engine is not self:
+            raise RuntimeError("this view camera belongs to another FusedEngine")
+        if intrinsics is None:
+            raise ValueError("render_view needs the view's intrinsics")
+        try:
+            view_mode = {"color": _capi.SPLAT_VIEW_COLOR, "depth": _capi.SPLAT_VIEW_DEPTH, "sil": _capi.SPLAT_VIEW_SILHOUETTE,
+                         "silhouette": _capi.SPLAT_VIEW_SILHOUETTE}[mode]
+        except KeyError:
+            raise ValueError(f"mode must be 'color', 'depth' or 'sil' (got {mode!r})") from None
+        fx, fy, cx, cy = _intrinsics4(intrinsics)
+        a = view.args
+        a.fx, a.fy, a.cx, a.cy, a.near_z, a.far_z = fx, fy, cx, cy, float(near), float(far)
+        keep = []
+        if w2c is not None:
+            a.w2c_in = _device_mat4(w2c, "w2c", self.dev, keep).data_ptr()
+        else:
+            time_idx = int(time_idx)
+            if not 0 <= time_idx < self.num_frames:
+                raise ValueError(f"time_idx {time_idx} is outside the map's {self.num_frames} frames")
+            rots, trans = self.params['cam_unnorm_rots'], self.params['cam_trans']
+            a.w2c_in = None
+            a.cam_unnorm_rots, a.cam_trans, a.num_frames, a.time_idx = rots.data_ptr(), trans.data_ptr(), self.num_frames, time_idx
+            a.first_w2c = (view.identity if first_w2c is None else _device_mat4(first_w2c, "first_w2c", self.dev, keep)).data_ptr()
+        if offset is None:
+            a.offset = None
+        else:
+            flat = [float(x) for row in (offset.tolist() if hasattr(offset, "tolist") else offset) for x in row]
+            if len(flat) != 16:
+                raise ValueError("offset must be a 4 x 4 matrix on the host")
+            view._offset[:] = flat
+            a.offset = view._offset
+        P = self.P if max_timestep is None else self._rows_at(view, max_timestep)          # (may raise: before anything is launched)
+        a.mode = view_mode
+        a.bg[:] = [float(c) for c in background]
+        a.vmin, a.vmax = float(depth_range[0]), float(depth_range[1])
+        if view_mode == _capi.SPLAT_VIEW_DEPTH and rgb8:
+            if lut is None:
+                lut = view.default_lut()
+            elif not (isinstance(lut, torch.Tensor) and lut.dtype == torch.uint8 and lut.device == self.dev and tuple(lut.shape) == (256, 3)
+                      and lut.is_contiguous()):
+                raise RuntimeError(f"lut must be a contiguous uint8 tensor of shape [256, 3] on {self.dev}")
+            a.lut = lut.data_ptr()
+            keep.append(lut)
+        cam = view.camera
+        a.out6 = cam.buf['out6'].data_ptr()
+        a.rgb8 = view.rgb8.data_ptr() if rgb8 else None
+        if points:
+            view.alloc_cloud()
+        a.points, a.colors = (view.points.data_ptr(), view.colors.data_ptr()) if points else (None, None)
+        cam.struct.tanfovx, cam.struct.tanfovy = view.W / (2.0 * fx), view.H / (2.0 * fy)
+        cam.keep_lists(P, 0.10, only_bucketed=True)         # (statistics learnt on another map: exact lists again)
+        current = self._camera
+        self._use(cam)
+        try:
+            ws = self._whole_frame_workspace(0)             # (forward only, max_2D_radius = None: FusedEngine.render's)
+            m = self._map_struct()
+            m.P = P
+            m.cam_unnorm_rots, m.cam_trans, m.num_frames = view.pose_rot.data_ptr(), view.pose_trans.data_ptr(), 1
+            fr = _capi.SplatFrameData()
+            fr.w2c, fr.time_idx = view.w2c.data_ptr(), 0
+            with torch.cuda.device(self.dev):
+                stream = self._stream()
+                _capi.check(self.L.splat_view_camera(C.byref(a), stream), "splat_view_camera")
+                _capi.check(self.L.splat_iter_render(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(ws), stream), "splat_iter_render")
+                _capi.check(self.L.splat_view_finish(C.byref(a), stream), "splat_view_finish")
+                status = cam.buf['status']
+                torch.bitwise_or(status[_STATUS_OVERFLOW:_STATUS_OVERFLOW + 1], status[_STATUS_STALE_HINT:_STATUS_STALE_HINT + 1], out=view.truncated)
+        finally:
+            self._use(current)
+        view._keep, view._rendered_P = keep, P
+        o = cam.buf['out6']
+        return ViewImage(view.rgb8 if rgb8 else None, view.points if points else None, view.colors if points else None, view.truncated, o)
 
     # ------------------------------------------------------------------ plumbing
     def _alloc_lists(self, capacity):
@@ -1164,6 +1298,132 @@ def _of_current_camera(field, assignable=False):
 for _name in ("H", "W", "num_tiles", "num_groups", "capacity", "sub_bins", "_orders", "_natural_order", "_stats_partial", "tile_stride", "max_list_hint"):
     setattr(FusedEngine, _name, _of_current_camera(_name, assignable=_name in ("tile_stride", "max_list_hint")))
 FusedEngine.cam_settings, FusedEngine._cam = _of_current_camera("settings"), _of_current_camera("struct")
+
+
+# ---------------------------------------------------------------------- views (csrc/view.hip)
+ViewImage = namedtuple("ViewImage", "rgb8 points colors truncated out6")
+ViewImage.__doc__ = """What ``FusedEngine.render_view`` returns, all on the device and all the VIEW's (overwritten by its next call): ``rgb8``
+[H, W, 3] uint8, ``points`` / ``colors`` [H W, 3] float32 (None unless asked for), ``truncated`` (int32 [1], != 0: the lists did not fit, the
+picture is incomplete), ``out6`` [6, H, W] (r, g, b, depth, silhouette, depth^2 on a zero background)."""
+
+
+def _intrinsics4(k):
+    """(fx, fy, cx, cy) as host floats from a 3 x 3 / 4 x 4 matrix or a 4-tuple (a tensor on the device is read back: keep it on the host)."""
+    if isinstance(k, (tuple, list)) and len(k) == 4 and not hasattr(k[0], "__len__"):
+        return tuple(float(x) for x in k)
+    if isinstance(k, torch.Tensor):
+        k = k.detach().cpu()
+    return float(k[0][0]), float(k[1][1]), float(k[0][2]), float(k[1][2])
+
+
+def _device_mat4(t, name, dev, keep):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == (4, 4)):
+        got = f"{t.dtype}, {tuple(t.shape)}, {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name} must be a float32 tensor of shape [4, 4] on {dev} (got {got})")
+    if not t.is_contiguous():           # (a copy per call would be an allocation per call: the caller makes it once)
+        raise RuntimeError(f"{name} must be contiguous (row-major 4 x 4): call .contiguous() once, not per view")
+    keep.append(t)
+    return t
+
+
+class ViewCamera:
+    """One camera that moves in place (``FusedEngine.view_camera``): a ``_Camera`` whose viewmatrix / projmatrix / campos are device
+    buffers of its own that splat_view_camera rewrites, the ``w2c`` its frames point at, a one-frame identity pose (so that the
+    composite's ``time_idx = 0`` applies no relative transform and the view matrix is the whole pose) and the outputs of
+    splat_view_finish.  The Gaussian arrays it renders are the map's own."""
+
+    def __init__(self, engine, width, height, capacity=None):
+        from .rasterizer import GaussianRasterizationSettings
+        if width <= 0 or height <= 0:
+            raise ValueError(f"a view needs a positive size (got {width} x {height})")
+        dev = engine.dev
+        self.engine, self.W, self.H = engine, width, height
+        z = dict(dtype=torch.float32, device=dev)
+        self.identity = torch.eye(4, **z)
+        self.mats = torch.eye(4, **z).repeat(3, 1, 1)              # w2c, viewmatrix, projmatrix: what splat_view_camera writes
+        self.w2c, self.viewmatrix, self.projmatrix = self.mats[0], self.mats[1:2], self.mats[2:3]
+        self.campos = torch.zeros(4, **z)[:3]
+        self.pose_rot = torch.tensor([1.0, 0.0, 0.0, 0.0], **z).view(1, 4, 1)
+        self.pose_trans = torch.zeros(1, 3, 1, **z)
+        settings = GaussianRasterizationSettings(image_height=height, image_width=width, tanfovx=1.0, tanfovy=1.0,
+                                                 bg=torch.zeros(3, **z), scale_modifier=1.0, viewmatrix=self.viewmatrix,
+                                                 projmatrix=self.projmatrix, sh_degree=0, campos=self.campos, prefiltered=False)
+        self.camera = _Camera(dev, settings, engine.Pcap, int(capacity) if capacity else 4 * engine.P + 65536, 0)
+        assert self.camera.struct.viewmatrix == self.viewmatrix.data_ptr() and self.camera.struct.projmatrix == self.projmatrix.data_ptr()
+        self.rgb8 = torch.zeros(height, width, 3, dtype=torch.uint8, device=dev)
+        self.points = self.colors = None
+        self.truncated = torch.zeros(1, dtype=torch.int32, device=dev)
+        from .view import jet_lut
+        self._lut = torch.from_numpy(jet_lut()).to(dev).contiguous()     # depth mode's default table (768 bytes: made here, so that a later mode allocates nothing)
+        self._offset = (C.c_double * 16)()
+        self._replay_key, self._replay_rows, self._keep, self._rendered_P = None, {}, None, engine.P
+        a = self.args = _capi.SplatViewArgs()
+        a.width, a.height = width, height
+        a.w2c, a.viewmatrix, a.projmatrix, a.campos = self.w2c.data_ptr(), self.viewmatrix.data_ptr(), self.projmatrix.data_ptr(), self.campos.data_ptr()
+
+    def alloc_cloud(self):
+        if self.points is None:
+            self.points = torch.zeros(self.H * self.W, 3, dtype=torch.float32, device=self.engine.dev)
+            self.colors = torch.zeros(self.H * self.W, 3, dtype=torch.float32, device=self.engine.dev)
+
+    def default_lut(self):
+        return self._lut
+
+    def check_overflow(self, grow=True):
+        """``FusedEngine.check_overflow`` for THIS camera (two small host reads): True when its renders since the last call ran on lists
+        that did not fit -- the lists are grown, the statistics learnt, and the caller renders again.  Between iterations, like the
+        render itself."""
+        eng, current = self.engine, self.engine._camera
+        eng._use(self.camera)
+        try:
+            skipped = eng.skipped_iterations
+            flagged = eng.check_overflow(grow)
+            if not flagged:
+                self.camera.learnt_P = self._rendered_P   # (a replay renders a prefix of the rows: the statistics are that prefix's)
+            eng.skipped_iterations = skipped            # (the loop's count of gated iterations is not the view's to change)
+            return flagged
+        finally:
+            eng._use(current)
+
+
+def view_finish(out6, mode="color", background=(0.0, 0.0, 0.0), depth_range=(0.0, 6.0), lut=None, rgb8=None, points=None, colors=None,
+                intrinsics=None, w2c=None):
+    """splat_view_finish on planes of the caller's (include/splat_hip.h): ``out6`` [>= 5, H, W] float32 on a CUDA/HIP device (r, g, b,
+    depth, silhouette; a ground-truth frame is its image, its depth and a silhouette of ones) -> ``rgb8`` [H, W, 3] uint8 in ``mode``
+    ("color" on ``background``, "depth": ``lut`` [256, 3] uint8 on the device over ``depth_range``, "sil"), ``points`` / ``colors`` [H W, 3]
+    float32 (``points`` needs ``intrinsics`` on the host and ``w2c`` float32 [4, 4] on the device).  Outputs are contiguous tensors of
+    the caller's with those element counts (views into larger buffers are fine); an output left None is not computed.  One launch on the
+    current stream, nothing read back.  Returns ``(rgb8, points, colors)``."""
+    if not (isinstance(out6, torch.Tensor) and out6.device.type == "cuda" and out6.dtype == torch.float32 and out6.dim() == 3
+            and out6.shape[0] >= 5 and out6.is_contiguous()):
+        raise RuntimeError("out6 must be a contiguous float32 tensor [>= 5, H, W] on a CUDA/HIP device; the HIP library has no CPU path")
+    dev, H, W = out6.device, int(out6.shape[1]), int(out6.shape[2])
+    modes = {"color": _capi.SPLAT_VIEW_COLOR, "depth": _capi.SPLAT_VIEW_DEPTH, "sil": _capi.SPLAT_VIEW_SILHOUETTE, "silhouette": _capi.SPLAT_VIEW_SILHOUETTE}
+    if mode not in modes:
+        raise ValueError(f"mode must be 'color', 'depth' or 'sil' (got {mode!r})")
+    a = _capi.SplatViewArgs()
+    a.width, a.height, a.out6, a.mode = W, H, out6.data_ptr(), modes[mode]
+    a.bg[:] = [float(c) for c in background]
+    a.vmin, a.vmax = float(depth_range[0]), float(depth_range[1])
+    for name, t, dtype, n in (("rgb8", rgb8, torch.uint8, 3 * H * W), ("points", points, torch.float32, 3 * H * W), ("colors", colors, torch.float32, 3 * H * W)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == dev and t.numel() == n and t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of {n} elements on {dev}")
+    if rgb8 is not None and modes[mode] == _capi.SPLAT_VIEW_DEPTH:
+        if not (isinstance(lut, torch.Tensor) and lut.dtype == torch.uint8 and lut.device == dev and tuple(lut.shape) == (256, 3) and lut.is_contiguous()):
+            raise RuntimeError(f"depth mode needs lut: a contiguous uint8 tensor of shape [256, 3] on {dev} (view.jet_lut() is the default table)")
+        a.lut = lut.data_ptr()
+    keep = []
+    if points is not None:
+        if intrinsics is None or w2c is None:
+            raise ValueError("points need intrinsics and w2c")
+        a.fx, a.fy, a.cx, a.cy = _intrinsics4(intrinsics)
+        a.w2c = _device_mat4(w2c, "w2c", dev, keep).data_ptr()
+    a.rgb8 = rgb8.data_ptr() if rgb8 is not None else None
+    a.points = points.data_ptr() if points is not None else None
+    a.colors = colors.data_ptr() if colors is not None else None
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_view_finish(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "splat_view_finish")
+    return rgb8, points, colors
 
 
 # ---------------------------------------------------------------------- frame preparation (csrc/frameprep.hip)

@@ -413,9 +413,9 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     if evaluate is not None:
         from . import evaluation
         opts = dict(evaluate)
-        unknown = set(opts) - {'eval_every', 'eval_dir', 'ms_ssim'}
+        unknown = set(opts) - {'eval_every', 'eval_dir', 'ms_ssim', 'save_frames'}
         if unknown:
-            raise ValueError(f"evaluate: unknown keys {sorted(unknown)} (eval_every, eval_dir, ms_ssim)")
+            raise ValueError(f"evaluate: unknown keys {sorted(unknown)} (eval_every, eval_dir, ms_ssim, save_frames)")
         box = [None]
         if rank == 0:
             with torch.no_grad():

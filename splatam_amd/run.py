@@ -102,6 +102,8 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4):
             if not ms_ssim:
                 print("frames with min(H, W) <= 160: MS-SSIM is not computed")
             opts = dict(eval_every=config['eval_every'], ms_ssim=ms_ssim)
+            if config.get('save_frames'):       # the reference's eval(..., save_frames=True): pictures under <run>/eval
+                opts.update(save_frames=True, eval_dir=os.path.join(config["workdir"], config["run_name"], "eval"))
         t0 = time.perf_counter()
         params, variables, stats = pipeline.rgbd_slam(dataset, config, engine=engine, num_frames=n, evaluate=opts,
                                                       tracking_dataset=tracking, densify_dataset=densify)

@@ -30,9 +30,15 @@ import time
 import numpy as np
 import torch
 
+from collections import namedtuple
+
 from . import pipeline, slam
 
 ENGINES = ("fused", "dropin", "plugin", "plugin_map_edits")
+HostView = namedtuple("HostView", "array event truncated")
+HostView.__doc__ = """``SlamSession.render_view(to_host=True)``: ``array`` [H, W, 3] uint8, a numpy view of a pinned slot, and ``truncated`` (a
+pinned int32 [1], != 0: the view's lists did not fit, the picture is incomplete -- ``view_check_overflow()``), both valid once
+``event.synchronize()`` returns and until the call after next."""
 
 
 class _StagingSlot:
@@ -106,6 +112,7 @@ class SlamSession:
         self._phase, self._sync_prepare = None, False       # the phase timer, made with the first frame (its device)
         self._tracking_frames = self._densify_frames = None
         self._raw = None                    # the raw path's buffers and sizes, made on its first frame
+        self._view = None                   # render_view's view camera and pinned slots, made on its first call
 
     # ------------------------------------------------------------------ life cycle
     def __enter__(self):
@@ -264,6 +271,72 @@ class SlamSession:
         if pose is not None:
             pose = torch.as_tensor(pose, dtype=torch.float32)
         return self._step(time_idx, curr, tracking_curr, densify_curr, pose, owned=dev.type == "cuda")
+
+    # ------------------------------------------------------------------ a picture of the map (csrc/view.hip)
+    def render_view(self, w2c=None, follow=False, time_idx=None, size=None, intrinsics=None, mode="color", background=(0.0, 0.0, 0.0),
+                    to_host=False, **kwargs):
+        """The map as it is now, as display bytes: ``FusedEngine.render_view`` on a view camera the session creates on first use
+        (``size`` = (height, width), default the loop's; fixed by the first call).  The pose is one of: ``w2c`` (float32 [4, 4] on the
+        device), ``follow=True`` -- the latest estimated pose seen from 0.5 m behind it, ``offset . first_frame_w2c . rel_w2c[latest]``
+        with the reference's online viewer's offset --, or ``time_idx``, the estimated pose of that frame.  ``intrinsics`` default
+        to the loop's, scaled to ``size``.  Further keywords (``depth_range``, ``lut``, ``max_timestep``, ``points``, ``offset``,
+        ``near``, ``far``) go to the engine's method; nothing is read on the host for the picture.
+
+        Returns the engine's ``ViewImage`` (tensors on the device, overwritten by the next call).  ``to_host=True``: returns a
+        ``HostView(array, event, truncated)`` instead -- ``rgb8`` and the truncation flag copied on the loop's stream into one of two
+        pinned slots used in turn; ``array`` is that slot's numpy view [H, W, 3] uint8, valid once ``event.synchronize()`` returns and
+        until the call after next.  The CALLER waits for the event; ``add_frame`` / ``add_raw_frame`` never do.  Between frames and
+        after ``finish()``; engine "fused" only.
+
+        The view's lists are sized for the map of the first call and are exact lists (scan, scatter and sort launches) until
+        ``view_check_overflow()`` has digested a render: call it once the first picture has been read, and again whenever
+        ``truncated`` comes back non-zero (the map outgrew the lists), then render again."""
+        if not self.fused:
+            raise NotImplementedError("render_view needs engine='fused'")
+        if self.engine is None:
+            raise RuntimeError("render_view before the first frame: there is no map")
+        eng = self.engine
+        V = self._view
+        if V is None:
+            H, W = (self.cam.image_height, self.cam.image_width) if size is None else (int(size[0]), int(size[1]))
+            k = self.intrinsics.detach().cpu().double().numpy()
+            k_view = (float(k[0][0]) * W / self.cam.image_width, float(k[1][1]) * H / self.cam.image_height,
+                      float(k[0][2]) * W / self.cam.image_width, float(k[1][2]) * H / self.cam.image_height)
+            from .view import follow_offset
+            V = self._view = dict(view=eng.view_camera(W, H), k=k_view, slots=[None, None], events=[None, None], turn=0,
+                                  follow=follow_offset())
+        elif size is not None and (int(size[0]), int(size[1])) != (V['view'].H, V['view'].W):
+            raise ValueError(f"the session's view is {V['view'].H} x {V['view'].W}: its size is fixed by the first render_view")
+        if sum((w2c is not None, bool(follow), time_idx is not None)) != 1:
+            raise ValueError("render_view takes one of w2c, follow=True, time_idx")
+        if follow:
+            time_idx = self.frames_seen - 1
+            kwargs.setdefault('offset', V['follow'])
+        pose = dict(w2c=w2c) if w2c is not None else dict(time_idx=time_idx, first_w2c=self.first_frame_w2c)
+        with torch.no_grad():
+            image = eng.render_view(V['view'], intrinsics=V['k'] if intrinsics is None else intrinsics, mode=mode,
+                                    background=background, **pose, **kwargs)
+        if not to_host:
+            return image
+        turn = V['turn']
+        V['turn'] ^= 1
+        if V['slots'][turn] is None:
+            V['slots'][turn] = (torch.empty(tuple(image.rgb8.shape), dtype=torch.uint8, pin_memory=True),
+                                torch.zeros(1, dtype=torch.int32, pin_memory=True))
+            V['events'][turn] = torch.cuda.Event()
+        pixels, flag = V['slots'][turn]
+        pixels.copy_(image.rgb8, non_blocking=True)
+        flag.copy_(image.truncated, non_blocking=True)
+        V['events'][turn].record(torch.cuda.current_stream(self.dev))
+        return HostView(pixels.numpy(), V['events'][turn], flag.numpy())
+
+    def view_check_overflow(self):
+        """The digest of the session's view camera (``ViewCamera.check_overflow``: two small host reads, between frames): True when its
+        renders since the last call ran on lists that did not fit -- they have been grown; render again.  Otherwise the list
+        statistics are learnt and later views take the bucketed lists (no scan, scatter and sort launches)."""
+        if self._view is None:
+            raise RuntimeError("view_check_overflow before the first render_view")
+        return self._view['view'].check_overflow()
 
     # ------------------------------------------------------------------ the raw path's buffers
     @staticmethod
