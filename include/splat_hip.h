@@ -718,6 +718,9 @@ int splat_eval_metrics(int32_t width, int32_t height, const float *rgb, const fl
 int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame, const SplatEvalConfig *cfg,
                     SplatIterWorkspace *ws, const SplatEvalWorkspace *ews, double *out_row, void *stream);
 
+/* The three frame entries below are ONE resampling pass (csrc/frameprep.hip, arithmetic in csrc/frame_math.h) under three contracts; their
+ * Python forms, on the device and in torch, are splatam_amd/frames.py. */
+
 /* Frame preparation: a frame as a dataset hands it over -- color_hwc [src_h][src_w][3] in 0..255, depth_hw [src_h][src_w] (the
  * trailing 1 of [H][W][1] changes nothing) -- to the planes every other entry takes: im_out [3][dst_h][dst_w] in 0..1 (one float32
  * division by 255), depth_out [dst_h][dst_w].  With dst == src this is the layout change alone.  Otherwise colour is resampled

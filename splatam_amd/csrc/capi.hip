@@ -348,28 +348,33 @@ int splat_iter_eval(const SplatCamera *cam, const SplatMap *map, const SplatFram
                                      *cfg, *ews, ws->st.status, out_row, (hipStream_t)stream));
 }
 
+// what the three frame entries share: positive sizes of at most 0x3fffffff pixels each, a positive scale, no NULL pointer
+static bool valid_frame_args(int32_t color_w, int32_t color_h, int32_t depth_w, int32_t depth_h, int32_t dst_w, int32_t dst_h, double scale,
+                             const void *color, const void *depth, const void *color_out, const void *depth_out) {
+    return color_w > 0 && color_h > 0 && depth_w > 0 && depth_h > 0 && dst_w > 0 && dst_h > 0 && (long long)color_w * color_h <= 0x3fffffffLL
+        && (long long)depth_w * depth_h <= 0x3fffffffLL && (long long)dst_w * dst_h <= 0x3fffffffLL && scale > 0.0
+        && color && depth && color_out && depth_out;
+}
+
 int splat_frame_prepare(int32_t src_w, int32_t src_h, const float *color_hwc, const float *depth_hw, int32_t dst_w, int32_t dst_h,
                         float *im_out, float *depth_out, void *stream) {
-    if (src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || (long long)src_w * src_h > 0x3fffffffLL || (long long)dst_w * dst_h > 0x3fffffffLL
-        || !color_hwc || !depth_hw || !im_out || !depth_out) return SPLAT_E_INVALID;
+    if (!valid_frame_args(src_w, src_h, src_w, src_h, dst_w, dst_h, 1.0, color_hwc, depth_hw, im_out, depth_out)) return SPLAT_E_INVALID;
     return check(launch_frame_prepare(src_w, src_h, color_hwc, depth_hw, dst_w, dst_h, im_out, depth_out, (hipStream_t)stream));
 }
 
 int splat_frame_ingest(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const uint16_t *depth_raw,
                        double png_depth_scale, int32_t dst_w, int32_t dst_h, float *color_out_hwc, float *depth_out, void *stream) {
-    if (color_w <= 0 || color_h <= 0 || depth_w <= 0 || depth_h <= 0 || dst_w <= 0 || dst_h <= 0 || (long long)color_w * color_h > 0x3fffffffLL
-        || (long long)depth_w * depth_h > 0x3fffffffLL || (long long)dst_w * dst_h > 0x3fffffffLL || !(png_depth_scale > 0.0)
-        || !rgb_hwc || !depth_raw || !color_out_hwc || !depth_out) return SPLAT_E_INVALID;
+    if (!valid_frame_args(color_w, color_h, depth_w, depth_h, dst_w, dst_h, png_depth_scale, rgb_hwc, depth_raw, color_out_hwc, depth_out))
+        return SPLAT_E_INVALID;
     return check(launch_frame_ingest(color_w, color_h, rgb_hwc, depth_w, depth_h, depth_raw, png_depth_scale, dst_w, dst_h, color_out_hwc,
                                      depth_out, (hipStream_t)stream));
 }
 
 int splat_frame_ingest_planes(int32_t color_w, int32_t color_h, const uint8_t *rgb_hwc, int32_t depth_w, int32_t depth_h, const void *depth_raw,
                               int32_t depth_type, double depth_scale, int32_t dst_w, int32_t dst_h, float *im_out, float *depth_out, void *stream) {
-    if (color_w <= 0 || color_h <= 0 || depth_w <= 0 || depth_h <= 0 || dst_w <= 0 || dst_h <= 0 || (long long)color_w * color_h > 0x3fffffffLL
-        || (long long)depth_w * depth_h > 0x3fffffffLL || (long long)dst_w * dst_h > 0x3fffffffLL || !(depth_scale > 0.0)
-        || (depth_type != SPLAT_DEPTH_U16 && depth_type != SPLAT_DEPTH_F32) || (depth_type == SPLAT_DEPTH_F32 && depth_scale != 1.0)
-        || !rgb_hwc || !depth_raw || !im_out || !depth_out) return SPLAT_E_INVALID;
+    if (!valid_frame_args(color_w, color_h, depth_w, depth_h, dst_w, dst_h, depth_scale, rgb_hwc, depth_raw, im_out, depth_out)
+        || (depth_type != SPLAT_DEPTH_U16 && depth_type != SPLAT_DEPTH_F32) || (depth_type == SPLAT_DEPTH_F32 && depth_scale != 1.0))
+        return SPLAT_E_INVALID;
     return check(launch_frame_ingest_planes(color_w, color_h, rgb_hwc, depth_w, depth_h, depth_raw, depth_type == SPLAT_DEPTH_F32, depth_scale,
                                             dst_w, dst_h, im_out, depth_out, (hipStream_t)stream));
 }

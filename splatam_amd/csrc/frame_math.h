@@ -2,7 +2,7 @@
 // loop's im[3][h][w] in 0..1, depth[1][h][w], at the same or at another size) and of frame ingest (a decoded image's bytes and a depth
 // PNG's integers -> such a dataset frame), written once as host/device inline functions:
 // frameprep.hip calls them per lane, tests/test_frame_math_cpu.py and tests/test_ingest_math_cpu.py compile the very same header with
-// g++ (tests/frame_math_shim.cpp, tests/ingest_math_shim.cpp) and check it against the float64 numpy form of the same definitions
+// g++ (tests/frame_math_shim.cpp) and check it against the float64 numpy form of the same definitions
 // (tests/frame_ref.py).
 //
 // Restates (in this project's words; nothing is copied) what the reference's datasets do to a frame on the host

@@ -10,7 +10,7 @@ here                                           reference (restated; nothing is c
 ``TUMDataset``                                 datasets/gradslam_datasets/tum.py (nearest-timestamp association, 1/32 s thinning)
 ``ScannetDataset``                             datasets/gradslam_datasets/scannet.py
 ``NeRFCaptureDataset``                         datasets/gradslam_datasets/nerfcapture.py (``transforms.json``, ``rgb/*``, ``depth/*``)
-``ingest_planes_cpu``                          scripts/iphone_demo.py:218-243 (a live frame's bytes and depth at the loop's sizes; the
+``ingest_planes_cpu`` (from ``frames``)        scripts/iphone_demo.py:218-243 (a live frame's bytes and depth at the loop's sizes; the
                                                host form of ``fused.ingest_planes``, which ``session.SlamSession.add_raw_frame`` runs)
 =============================================  =============================================
 
@@ -19,7 +19,7 @@ here                                           reference (restated; nothing is c
 
 Where the reference decodes to float64, resizes twice with OpenCV on one core and uploads floats, once per resolution, this decodes
 ONCE with PIL (ahead of the loop, on a few threads, into reused pinned buffers), uploads the raw bytes (4 MB at 1200 x 680 instead of
-13 MB) and lets one kernel, ``fused.ingest_frame`` (csrc/frameprep.hip, splat_frame_ingest), write the frame at every size wanted:
+13 MB) and lets one kernel, ``fused.ingest_frame`` (frames.py; csrc/frameprep.hip, splat_frame_ingest), write the frame at every size wanted:
 ``dataset.at_size(h, w)`` is a second dataset over the same files that shares the decoded and uploaded frame of the last index
 fetched.  With ``device="cpu"`` the same arithmetic runs in torch on the host (``ingest_frame_cpu``).  The resize rules are OpenCV's documented
 ones as csrc/frame_math.h restates them; they are not pinned against OpenCV, which is not available here.
@@ -39,6 +39,7 @@ import numpy as np
 import torch
 
 from . import slam
+from .frames import ingest_frame_cpu, ingest_planes_cpu  # noqa: F401  (the host forms of fused.ingest_frame / ingest_planes)
 
 SUPPORTED = ("replica", "replicav2", "tum", "scannet", "nerfcapture")
 MAX_WORKERS = 4             # decode threads (PIL releases the GIL while it inflates); never sized by the host's core count
@@ -76,67 +77,6 @@ def natural_sorted(names):
     def key(name):
         return [(0, int(part), "") if part.isdigit() else (1, 0, part.lower()) for part in re.split(r"(\d+)", name) if part != ""]
     return sorted(names, key=key)
-
-
-# --------------------------------------------------------------------------
-# the torch form of splat_frame_ingest
-# --------------------------------------------------------------------------
-
-def _blend_cpu(rgb, size):
-    """The colour half of ``ingest_frame_cpu``: uint8 [H, W, 3] -> float32 [h, w, 3] in 0..255, blended along x on both rows, then along y."""
-    H, W = int(rgb.shape[0]), int(rgb.shape[1])
-    h, w = size
-    c = rgb.to(torch.float32)
-    y0, y1, wy = slam._linear_taps(h, H, "cpu")
-    x0, x1, wx = slam._linear_taps(w, W, "cpu")
-    wx, wy = wx.view(1, w, 1), wy.view(h, 1, 1)
-    r0, r1 = c[y0], c[y1]
-    top = r0[:, x0] + wx * (r0[:, x1] - r0[:, x0])
-    bottom = r1[:, x0] + wx * (r1[:, x1] - r1[:, x0])
-    return (top + wy * (bottom - top)).contiguous()
-
-
-def ingest_frame_cpu(rgb_u8, depth_u16, png_depth_scale, size=None):
-    """``fused.ingest_frame`` in torch on the host, the kernel's operations in the kernel's order (the taps are
-    ``slam.prepare_frame``'s): colour blended in float32 along x on both rows and then along y, depth the nearest source pixel as
-    ``float32(float64(raw) / png_depth_scale)``.  Arrays or CPU tensors in (uint8 [H, W, 3], uint16 [H', W']), tensors out:
-    ``(color [h, w, 3] float32 in 0..255, depth [h, w, 1] float32)``."""
-    rgb, raw = torch.as_tensor(rgb_u8), torch.as_tensor(depth_u16)
-    H, W = int(rgb.shape[0]), int(rgb.shape[1])
-    zH, zW = int(raw.shape[0]), int(raw.shape[1])
-    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    near = raw.reshape(zH, zW).to(torch.int32)[slam._nearest_index(h, zH, "cpu")][:, slam._nearest_index(w, zW, "cpu")]
-    depth = (near.to(torch.float64) / float(png_depth_scale)).to(torch.float32)
-    return _blend_cpu(rgb, (h, w)), depth.reshape(h, w, 1)
-
-
-def ingest_planes_cpu(rgb_u8, depth_raw, depth_scale=None, size=None):
-    """``fused.ingest_planes`` in torch on the host, the kernel's operations in the kernel's order: the blend of ``ingest_frame_cpu``
-    on the bytes, one float32 division by 255, planar; depth the nearest source pixel -- a uint16 as
-    ``float32(float64(raw) / depth_scale)``, a float32 copied bit for bit (it is gathered as int32, so NaN payloads survive;
-    ``depth_scale`` must then be None or 1).  Arrays or CPU tensors in (uint8 [H, W, 3]; uint16 or float32 [H', W'] or [H', W', 1]),
-    tensors out: ``(im [3, h, w] float32 in 0..1, depth [1, h, w] float32)``."""
-    rgb, raw = torch.as_tensor(rgb_u8), torch.as_tensor(depth_raw)
-    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
-        raise RuntimeError(f"rgb_u8 must be uint8 [H, W, 3] (got {rgb.dtype}, {tuple(rgb.shape)})")
-    if raw.dtype not in (torch.uint16, torch.float32) or not (raw.dim() == 2 or (raw.dim() == 3 and raw.shape[2] == 1)):
-        raise RuntimeError(f"depth_raw must be uint16 or float32 [H, W] or [H, W, 1] (got {raw.dtype}, {tuple(raw.shape)})")
-    H, W = int(rgb.shape[0]), int(rgb.shape[1])
-    zH, zW = int(raw.shape[0]), int(raw.shape[1])
-    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    if h <= 0 or w <= 0:
-        raise RuntimeError(f"size must be positive (got {(h, w)})")
-    ys, xs = slam._nearest_index(h, zH, "cpu"), slam._nearest_index(w, zW, "cpu")
-    if raw.dtype == torch.float32:
-        if depth_scale is not None and float(depth_scale) != 1.0:
-            raise RuntimeError(f"float32 depth is in metres already: depth_scale must be None or 1 (got {depth_scale})")
-        depth = raw.contiguous().view(torch.int32).reshape(zH, zW)[ys][:, xs].contiguous().view(torch.float32)
-        color = _blend_cpu(rgb, (h, w))
-    else:
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise RuntimeError(f"uint16 depth needs a positive depth_scale (got {depth_scale})")
-        color, depth = ingest_frame_cpu(rgb, raw, depth_scale, size=(h, w))
-    return (color / 255.0).permute(2, 0, 1).contiguous(), depth.reshape(1, h, w)
 
 
 # --------------------------------------------------------------------------

@@ -24,6 +24,7 @@ from types import MappingProxyType
 import torch
 
 from . import _capi
+from .frames import ingest_frame, ingest_planes, prepare_frame  # noqa: F401  (the frame path lives in frames.py)
 from .rasterizer import _cached_contiguous
 
 PARAM_ORDER = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales")
@@ -1424,124 +1425,6 @@ def view_finish(out6, mode="color", background=(0.0, 0.0, 0.0), depth_range=(0.0
     with torch.cuda.device(dev):
         _capi.check(_capi.lib().splat_view_finish(C.byref(a), torch.cuda.current_stream(dev).cuda_stream), "splat_view_finish")
     return rgb8, points, colors
-
-
-# ---------------------------------------------------------------------- frame preparation (csrc/frameprep.hip)
-def prepare_frame(color, depth, size=None, out=None):
-    """A frame as the datasets hand it over -- ``color`` [H, W, 3] in 0..255, ``depth`` [H, W, 1] (or [H, W]), float32 on one
-    CUDA/HIP device -- as every entry of this module takes it: ``(im [3, h, w] in 0..1, depth [1, h, w])`` at ``size = (h, w)``
-    (default: the frame's own size, i.e. the loop's ``permute(2, 0, 1) / 255``).  At another size colour is resampled bilinearly
-    and depth by nearest source pixel (include/splat_hip.h splat_frame_prepare; ``slam.prepare_frame`` is the same arithmetic in
-    torch).  One launch on the current stream, nothing read back.  ``out = (im, depth)``: contiguous float32 tensors of those
-    shapes to write into (views into larger buffers are fine); otherwise two new tensors."""
-    if not isinstance(color, torch.Tensor) or color.device.type != "cuda":
-        raise RuntimeError("prepare_frame needs CUDA/HIP tensors; the HIP library has no CPU path (slam.prepare_frame is the torch form)")
-    dev = color.device
-    if color.dim() != 3 or color.shape[2] != 3:
-        raise RuntimeError(f"color must be [H, W, 3] (got {tuple(color.shape)})")
-    H, W = int(color.shape[0]), int(color.shape[1])
-    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    if h <= 0 or w <= 0:
-        raise RuntimeError(f"size must be positive (got {(h, w)})")
-    src = []
-    for name, t, n in (("color", color, 3 * H * W), ("depth", depth, H * W)):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and t.numel() == n):
-            got = f"{t.dtype}, {tuple(t.shape)}, {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise RuntimeError(f"{name} must be a float32 tensor of {n} elements on {dev} (got {got})")
-        src.append(t if t.is_contiguous() else t.contiguous())
-    if out is None:
-        out = (torch.empty(3, h, w, dtype=torch.float32, device=dev), torch.empty(1, h, w, dtype=torch.float32, device=dev))
-    for name, t, shape in (("out[0]", out[0], (3, h, w)), ("out[1]", out[1], (1, h, w))):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == shape and t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
-    with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_frame_prepare(W, H, src[0].data_ptr(), src[1].data_ptr(), w, h, out[0].data_ptr(), out[1].data_ptr(),
-                                                    torch.cuda.current_stream(dev).cuda_stream), "splat_frame_prepare")
-    return out[0], out[1]
-
-
-# ---------------------------------------------------------------------- frame ingest (csrc/frameprep.hip)
-def ingest_frame(rgb_u8, depth_u16, png_depth_scale, size=None, out=None):
-    """What an image decoder leaves -- ``rgb_u8`` [H, W, 3] uint8 and ``depth_u16`` [H', W'] (or [H', W', 1]) uint16, the integers
-    of a depth PNG, on one CUDA/HIP device; the two sizes may differ -- as the frame a dataset hands over: ``(color [h, w, 3] float32
-    in 0..255, depth [h, w, 1] float32 in metres)`` at ``size = (h, w)`` (default: the colour image's size).  Colour is resampled
-    bilinearly on the byte values (exactly the bytes at equal size), depth is the nearest source pixel as
-    ``float32(float64(raw) / png_depth_scale)`` (include/splat_hip.h splat_frame_ingest).  One launch on the current stream,
-    nothing read back.  ``out = (color, depth)``: contiguous float32 tensors of those shapes to write into (views into larger buffers
-    are fine); otherwise two new tensors."""
-    if not isinstance(rgb_u8, torch.Tensor) or rgb_u8.device.type != "cuda":
-        raise RuntimeError("ingest_frame needs CUDA/HIP tensors; the HIP library has no CPU path (datasets.ingest_frame_cpu is the torch form on the host)")
-    dev = rgb_u8.device
-    if rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.numel() == 0:
-        raise RuntimeError(f"rgb_u8 must be a uint8 tensor [H, W, 3] (got {rgb_u8.dtype}, {tuple(rgb_u8.shape)})")
-    H, W = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
-    if not (isinstance(depth_u16, torch.Tensor) and depth_u16.dtype == torch.uint16 and depth_u16.device == dev and depth_u16.numel() > 0
-            and (depth_u16.dim() == 2 or (depth_u16.dim() == 3 and depth_u16.shape[2] == 1))):
-        got = f"{depth_u16.dtype}, {tuple(depth_u16.shape)}, {depth_u16.device}" if isinstance(depth_u16, torch.Tensor) else type(depth_u16).__name__
-        raise RuntimeError(f"depth_u16 must be a uint16 tensor [H, W] or [H, W, 1] on {dev} (got {got})")
-    zH, zW = int(depth_u16.shape[0]), int(depth_u16.shape[1])
-    scale = float(png_depth_scale)
-    if not scale > 0.0:
-        raise RuntimeError(f"png_depth_scale must be positive (got {png_depth_scale})")
-    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    if h <= 0 or w <= 0:
-        raise RuntimeError(f"size must be positive (got {(h, w)})")
-    rgb = rgb_u8 if rgb_u8.is_contiguous() else rgb_u8.contiguous()
-    raw = depth_u16 if depth_u16.is_contiguous() else depth_u16.contiguous()
-    if out is None:
-        out = (torch.empty(h, w, 3, dtype=torch.float32, device=dev), torch.empty(h, w, 1, dtype=torch.float32, device=dev))
-    for name, t, shape in (("out[0]", out[0], (h, w, 3)), ("out[1]", out[1], (h, w, 1))):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == shape and t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
-    with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_frame_ingest(W, H, rgb.data_ptr(), zW, zH, raw.data_ptr(), scale, w, h, out[0].data_ptr(),
-                                                   out[1].data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "splat_frame_ingest")
-    return out[0], out[1]
-
-
-def ingest_planes(rgb_u8, depth_raw, depth_scale=None, size=None, out=None):
-    """What a sensor or a decoder delivers -- ``rgb_u8`` [H, W, 3] uint8 and ``depth_raw`` [H', W'] (or [H', W', 1]), float32 metres
-    (``depth_scale`` None or 1) or uint16 integers with their divisor ``depth_scale``, on one CUDA/HIP device; the depth image has a
-    size of its own and may be smaller than the output -- as the planes the loop works on: ``(im [3, h, w] in 0..1, depth [1, h, w] in
-    metres)`` at ``size = (h, w)`` (default: the colour image's size).  One launch (include/splat_hip.h splat_frame_ingest_planes),
-    bit-equal to ``prepare_frame(*ingest_frame(...))`` without the frame in between; a float32 depth is copied bit for bit.
-    Nothing read back.  ``out = (im, depth)``: contiguous float32 tensors of those shapes to write into (views into larger
-    buffers are fine); otherwise two new tensors.  ``datasets.ingest_planes_cpu`` is the torch form on the host."""
-    if not isinstance(rgb_u8, torch.Tensor) or rgb_u8.device.type != "cuda":
-        raise RuntimeError("ingest_planes needs CUDA/HIP tensors; the HIP library has no CPU path (datasets.ingest_planes_cpu is the torch form on the host)")
-    dev = rgb_u8.device
-    if rgb_u8.dtype != torch.uint8 or rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or rgb_u8.numel() == 0:
-        raise RuntimeError(f"rgb_u8 must be a uint8 tensor [H, W, 3] (got {rgb_u8.dtype}, {tuple(rgb_u8.shape)})")
-    H, W = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
-    if not (isinstance(depth_raw, torch.Tensor) and depth_raw.dtype in (torch.uint16, torch.float32) and depth_raw.device == dev
-            and depth_raw.numel() > 0 and (depth_raw.dim() == 2 or (depth_raw.dim() == 3 and depth_raw.shape[2] == 1))):
-        got = f"{depth_raw.dtype}, {tuple(depth_raw.shape)}, {depth_raw.device}" if isinstance(depth_raw, torch.Tensor) else type(depth_raw).__name__
-        raise RuntimeError(f"depth_raw must be a uint16 or float32 tensor [H, W] or [H, W, 1] on {dev} (got {got})")
-    zH, zW = int(depth_raw.shape[0]), int(depth_raw.shape[1])
-    if depth_raw.dtype == torch.float32:
-        kind, scale = _capi.SPLAT_DEPTH_F32, 1.0
-        if depth_scale is not None and float(depth_scale) != 1.0:
-            raise RuntimeError(f"float32 depth is in metres already: depth_scale must be None or 1 (got {depth_scale})")
-    else:
-        kind = _capi.SPLAT_DEPTH_U16
-        if depth_scale is None or not float(depth_scale) > 0.0:
-            raise RuntimeError(f"uint16 depth needs a positive depth_scale (got {depth_scale})")
-        scale = float(depth_scale)
-    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    if h <= 0 or w <= 0:
-        raise RuntimeError(f"size must be positive (got {(h, w)})")
-    rgb = rgb_u8 if rgb_u8.is_contiguous() else rgb_u8.contiguous()
-    raw = depth_raw if depth_raw.is_contiguous() else depth_raw.contiguous()
-    if out is None:
-        out = (torch.empty(3, h, w, dtype=torch.float32, device=dev), torch.empty(1, h, w, dtype=torch.float32, device=dev))
-    for name, t, shape in (("out[0]", out[0], (3, h, w)), ("out[1]", out[1], (1, h, w))):
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == shape and t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous float32 tensor of shape {shape} on {dev}")
-    with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_frame_ingest_planes(W, H, rgb.data_ptr(), zW, zH, raw.data_ptr(), kind, scale, w, h, out[0].data_ptr(),
-                                                          out[1].data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                    "splat_frame_ingest_planes")
-    return out[0], out[1]
 
 
 # ---------------------------------------------------------------------- evaluation metrics on planes (csrc/evalmetrics.hip)

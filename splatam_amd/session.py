@@ -16,7 +16,7 @@ here                                           reference
 
 A frame's path from sensor bytes to pose (``add_raw_frame`` on a HIP device): the caller's arrays are copied into one of two pinned
 staging slots, uploaded on the current stream (an event after the upload guards the slot's next use), and ONE launch per resolution
-(``fused.ingest_planes``: csrc/frameprep.hip P3) writes the planes the loop works on -- full size, the tracking size where it has
+(``fused.ingest_planes``, i.e. ``frames.ingest_planes``: csrc/frameprep.hip P3) writes the planes the loop works on -- full size, the tracking size where it has
 one of its own, and on frames that add Gaussians the densification size -- each from the RAW frame, into buffers the session keeps.
 Tracking then moves ``cam_unnorm_rots / cam_trans[..., time_idx]``; the returned ``w2c`` is built from them on the device.
 
@@ -32,7 +32,7 @@ import torch
 
 from collections import namedtuple
 
-from . import pipeline, slam
+from . import frames, pipeline, slam
 
 ENGINES = ("fused", "dropin", "plugin", "plugin_map_edits")
 HostView = namedtuple("HostView", "array event truncated")
@@ -244,18 +244,14 @@ class SlamSession:
         dev = R['device']
         adds = self._densifies(time_idx)
         if dev.type == "cuda":
-            from . import fused
             rgb, raw = self._upload(rgb, raw)
-            planes = {'full': fused.ingest_planes(rgb, raw, scale, R['full'], out=R['planes']['full'])}
-            for which in ('tracking', 'densify'):
-                if R[which] is not None and (which == 'tracking' or adds):
-                    planes[which] = fused.ingest_planes(rgb, raw, scale, R[which], out=R['planes'][which])
+            ingest = lambda which: frames.ingest_planes(rgb, raw, scale, R[which], out=R['planes'][which])        # noqa: E731
         else:
-            from . import datasets
-            planes = {'full': datasets.ingest_planes_cpu(rgb, raw, scale, R['full'])}
-            for which in ('tracking', 'densify'):
-                if R[which] is not None and (which == 'tracking' or adds):
-                    planes[which] = datasets.ingest_planes_cpu(rgb, raw, scale, R[which])
+            ingest = lambda which: frames.ingest_planes_cpu(rgb, raw, scale, R[which])                              # noqa: E731
+        planes = {'full': ingest('full')}
+        for which in ('tracking', 'densify'):
+            if R[which] is not None and (which == 'tracking' or adds):
+                planes[which] = ingest(which)
         im, d = planes['full']
         if time_idx == 0:
             make = lambda which: None if R[which] is None else pipeline._ReducedFrames(        # noqa: E731

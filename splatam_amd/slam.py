@@ -46,6 +46,8 @@ import math
 import torch
 import torch.nn.functional as F
 
+from .frames import _linear_taps, _nearest_index  # noqa: F401
+from .frames import prepare_frame_torch as prepare_frame  # noqa: F401  (the torch form of fused.prepare_frame)
 from .rasterizer import GaussianRasterizationSettings as Camera
 from .rasterizer import GaussianRasterizer as Renderer
 
@@ -102,46 +104,6 @@ def scale_intrinsics(k, h_ratio, w_ratio):
     out[..., 0, 2] *= w_ratio
     out[..., 1, 2] *= h_ratio
     return out
-
-
-def _linear_taps(dst, src, device):
-    """Per destination index along one axis: the two source indices and the weight of the second (csrc/frame_math.h
-    frame_linear_tap: f = (d + 0.5) * (src / dst) - 0.5 in double, clamped to the row with weight 0)."""
-    f = (torch.arange(dst, dtype=torch.float64) + 0.5) * (float(src) / float(dst)) - 0.5
-    fl = torch.floor(f)
-    s, w = fl.to(torch.int64), (f - fl).to(torch.float32)
-    out = (s < 0) | (s >= src - 1)
-    s = s.clamp(0, src - 1)
-    w = torch.where(out, torch.zeros_like(w), w)
-    return s.to(device), (s + 1).clamp(max=src - 1).to(device), w.to(device)
-
-
-def _nearest_index(dst, src, device):
-    """csrc/frame_math.h frame_nearest_index: min(floor(d * (1 / (dst / src))), src - 1), in double."""
-    inv = 1.0 / (float(dst) / float(src))
-    return torch.floor(torch.arange(dst, dtype=torch.float64) * inv).to(torch.int64).clamp(max=src - 1).to(device)
-
-
-def prepare_frame(color, depth, size=None):
-    """A frame as the datasets hand it over -- ``color`` [H, W, 3] in 0..255, ``depth`` [H, W, 1] -- as the loop uses it:
-    ``(im [3, h, w] in 0..1, depth [1, h, w])`` at ``size = (h, w)`` (default: the frame's own, the reference loop's
-    ``permute(2, 0, 1) / 255``).  At another size: colour bilinear on the 0..255 values with pixel centres at half-integers,
-    depth nearest, the rules of the two cv2.resize calls of the reference's datasets as OpenCV documents them (restated in
-    csrc/frame_math.h; not checked against OpenCV, which is not available here).  Torch form of splat_frame_prepare, same
-    operations in the same order in float32: the CPU / drop-in path of the frame loop."""
-    H, W = int(color.shape[0]), int(color.shape[1])
-    h, w = (H, W) if size is None else (int(size[0]), int(size[1]))
-    color, depth = color.to(torch.float32), depth.to(torch.float32)
-    dev = color.device
-    y0, y1, wy = _linear_taps(h, H, dev)
-    x0, x1, wx = _linear_taps(w, W, dev)
-    wx, wy = wx.view(1, w, 1), wy.view(h, 1, 1)
-    r0, r1 = color[y0], color[y1]
-    top = r0[:, x0] + wx * (r0[:, x1] - r0[:, x0])
-    bottom = r1[:, x0] + wx * (r1[:, x1] - r1[:, x0])
-    im = ((top + wy * (bottom - top)) / 255.0).permute(2, 0, 1).contiguous()
-    d = depth.reshape(H, W)[_nearest_index(h, H, dev)][:, _nearest_index(w, W, dev)]
-    return im, d.reshape(1, h, w).contiguous()
 
 
 def transform_to_frame(params, time_idx, gaussians_grad, camera_grad):

@@ -73,3 +73,78 @@ def seeded_frame(sw, sh, seed, integer):
     depth = (0.5 + 4.0 * rng.random((sh, sw, 1))).astype(np.float32)
     depth[rng.random((sh, sw, 1)) < 0.1] = 0.0
     return color, depth
+
+
+GUARD = 12345.0
+
+
+def run_guarded(entry, inputs, shapes, lead):
+    """``entry(*device inputs, out=(a, b))`` with both outputs as views inside ONE flat float32 buffer
+    [lead guards | a | 8 guards | b | 64 guards], on a side stream: lead 64 puts the views on a 16-byte boundary, lead 61 off it, so a
+    width divisible by 4 meets the 16-byte and the scalar stores.  The guards must stay as they were.  Returns the two outputs on the
+    host in ``shapes``."""
+    import torch
+    dev = torch.device("cuda")
+    n, m = int(np.prod(shapes[0])), int(np.prod(shapes[1]))
+    flat = torch.full((lead + n + 8 + m + 64,), GUARD, dtype=torch.float32, device=dev)
+    a, b = flat[lead:lead + n].view(shapes[0]), flat[lead + n + 8:lead + n + 8 + m].view(shapes[1])
+    src = [torch.from_numpy(x).to(dev) for x in inputs]
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        got = entry(*src, out=(a, b))
+    stream.synchronize()
+    assert got[0].data_ptr() == a.data_ptr() and got[1].data_ptr() == b.data_ptr()
+    host = flat.cpu().numpy()
+    guards = np.concatenate([host[:lead], host[lead + n:lead + n + 8], host[lead + n + 8 + m:]])
+    assert np.all(guards == np.float32(GUARD)), "a store left the output views"
+    return host[lead:lead + n].reshape(shapes[0]), host[lead + n + 8:lead + n + 8 + m].reshape(shapes[1])
+
+
+def seeded_raw(cw, ch, zw, zh, seed):
+    """(rgb [ch, cw, 3] uint8, raw [zh, zw] uint16 with some zeros): what a decoder leaves."""
+    rng = np.random.default_rng(seed)
+    rgb = rng.integers(0, 256, size=(ch, cw, 3), dtype=np.uint8)
+    raw = rng.integers(0, 65536, size=(zh, zw)).astype(np.uint16)
+    raw[rng.random((zh, zw)) < 0.1] = 0
+    return rgb, raw
+
+
+def special_floats(zw, zh, seed):
+    """float32 depth with 0, -0, -1, +inf, -inf, a NaN whose payload is not the default one, the smallest and the largest denormal."""
+    rng = np.random.default_rng(seed)
+    bits = (0.5 + 4.0 * rng.random((zh, zw))).astype(np.float32).view(np.uint32).reshape(-1).copy()
+    special = np.array([0x00000000, 0x80000000, 0xBF800000, 0x7F800000, 0xFF800000, 0x7FA12345, 0xFFC00001, 0x00000001, 0x007FFFFF, 0x80000123],
+                       dtype=np.uint32)
+    where = rng.permutation(bits.size)[:special.size]
+    bits[where] = special[:where.size]
+    return bits.reshape(zh, zw).view(np.float32)
+
+
+# ((colour w, h), (depth w, h), (destination w, h)): every SIZES pair with the depth at the colour's size and at a size of its own ...
+OTHER_DEPTH = (11, 7)
+RAW_CASES = (tuple((s, s, d) for s, d in SIZES) + tuple((s, OTHER_DEPTH, d) for s, d in SIZES)
+             + (((26, 20), (16, 12), (13, 9)),          # a depth image of a size of its own, both reduced
+                ((24, 16), (5, 3), (24, 16)),           # depth upsampled under an identity colour
+                ((1, 1), (1, 1), (4, 3)), ((1, 1), (3, 2), (4, 3))))
+GOLDEN_SCALE = 6553.5
+
+
+def golden_frame_kernel_runs(fused, lead):
+    """Every (key, im or colour, depth) that tests/golden/frame_kernels_reference.npz records, run now at ``lead``: the three entry
+    points over SIZES / RAW_CASES with the seeds of their own tests, uint16 depth at 6553.5 and the special-float depth."""
+    for i, ((sw, sh), (dw, dh)) in enumerate(SIZES):
+        color, depth = seeded_frame(sw, sh, seed=sw * 100 + dw, integer=False)
+        planes = ((3, dh, dw), (1, dh, dw))
+        yield (f"prepare/{i}",) + run_guarded(lambda c, z, out: fused.prepare_frame(c, z, size=(dh, dw), out=out), (color, depth), planes, lead)
+        yield (f"prepare_special/{i}",) + run_guarded(lambda c, z, out: fused.prepare_frame(c, z, size=(dh, dw), out=out),
+                                                      (color, special_floats(sw, sh, seed=sw * 10 + dw)), planes, lead)
+    for i, ((cw, ch), (zw, zh), (dw, dh)) in enumerate(RAW_CASES):
+        rgb, raw = seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
+        planes = ((3, dh, dw), (1, dh, dw))
+        yield (f"ingest/{i}",) + run_guarded(lambda c, z, out: fused.ingest_frame(c, z, GOLDEN_SCALE, size=(dh, dw), out=out), (rgb, raw),
+                                             ((dh, dw, 3), (dh, dw, 1)), lead)
+        yield (f"planes_u16/{i}",) + run_guarded(lambda c, z, out: fused.ingest_planes(c, z, GOLDEN_SCALE, size=(dh, dw), out=out), (rgb, raw),
+                                                 planes, lead)
+        yield (f"planes_f32/{i}",) + run_guarded(lambda c, z, out: fused.ingest_planes(c, z, None, size=(dh, dw), out=out),
+                                                 (rgb, special_floats(zw, zh, seed=zw * 10 + dw)), planes, lead)

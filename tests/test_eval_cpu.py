@@ -4,13 +4,13 @@ against the float64 torch restatement (tests/eval_ref.py), the torch mirror (``s
 (tests/golden/eval_reference.npz, made by tests/golden/make_golden_eval.py on the C oracle), and the C ABI of the evaluation."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from tests import eval_ref
+from tests.util import host_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = np.load(os.path.join(HERE, "golden", "eval_reference.npz"))
@@ -21,13 +21,7 @@ GOLD = np.load(os.path.join(HERE, "golden", "eval_reference.npz"))
 # ---------------------------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def shim():
-    out = os.path.join(HERE, "_build", "libeval_math_shim.so")
-    src = os.path.join(HERE, "eval_math_shim.cpp")
-    hdrs = [os.path.join(HERE, "..", "splatam_amd", "csrc", h) for h in ("splat_math.h", "eval_math.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
-    L = C.CDLL(out)
+    L = host_shim("eval_math_shim", "eval_math.h")
     L.em_pyramid_floats.restype = C.c_size_t
     return L
 

@@ -6,28 +6,20 @@ Depth is a copy: equal everywhere.  Colour: with integer-valued inputs at 2:1 an
 roundings at magnitude <= 255 lie between the float32 and the float64 evaluation, 12 * 2^-24 * 255 / 255 ~ 7e-7 on the [0, 1] image:
 1e-6 absolute."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import frame_ref
+from tests.util import host_shim
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 COLOUR_ATOL = 1e-6
 
 
 @pytest.fixture(scope="module")
 def shim():
-    out = os.path.join(HERE, "_build", "libframe_math_shim.so")
-    src = os.path.join(HERE, "frame_math_shim.cpp")
-    hdrs = [os.path.join(HERE, "..", "splatam_amd", "csrc", h) for h in ("splat_math.h", "frame_math.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
-    return C.CDLL(out)
+    return host_shim("frame_math_shim", "frame_math.h")
 
 
 def _p(a, t=C.c_float):

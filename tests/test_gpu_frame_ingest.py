@@ -14,45 +14,24 @@ import frame_ref
 
 pytestmark = pytest.mark.gpu
 COLOUR_ATOL = 255 * 1e-6
-GUARD = 12345.0
 SCALES = (6553.5, 5000.0, 1000.0, 1234.567)
 # ((colour w, h), (depth w, h), (destination w, h)): every frame_ref.SIZES pair, and a depth image of a size of its own
 CASES = tuple((s, s, d) for s, d in frame_ref.SIZES) + (((26, 20), (16, 12), (13, 9)),)
 
 
 def run_kernel(rgb, raw, scale, h, w, lead):
-    """Both outputs inside ONE flat buffer: [lead guards | colour 3hw | 8 guards | depth hw | 64 guards], on a side stream."""
+    """``fused.ingest_frame`` into guarded views (frame_ref.run_guarded): (colour [h, w, 3], depth [h, w]) on the host."""
     from splatam_amd import fused
-    dev = torch.device("cuda")
-    n = 3 * h * w
-    flat = torch.full((lead + n + 8 + h * w + 64,), GUARD, dtype=torch.float32, device=dev)
-    color, depth = flat[lead:lead + n].view(h, w, 3), flat[lead + n + 8:lead + n + 8 + h * w].view(h, w, 1)
-    c, z = torch.from_numpy(rgb).to(dev), torch.from_numpy(raw).to(dev)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):
-        got = fused.ingest_frame(c, z, scale, size=(h, w), out=(color, depth))
-    stream.synchronize()
-    assert got[0].data_ptr() == color.data_ptr() and got[1].data_ptr() == depth.data_ptr()
-    host = flat.cpu().numpy()
-    guards = np.concatenate([host[:lead], host[lead + n:lead + n + 8], host[lead + n + 8 + h * w:]])
-    assert np.all(guards == np.float32(GUARD)), "a store left the output views"
-    return host[lead:lead + n].reshape(h, w, 3), host[lead + n + 8:lead + n + 8 + h * w].reshape(h, w)
-
-
-def seeded_raw(cw, ch, zw, zh, seed):
-    rng = np.random.default_rng(seed)
-    rgb = rng.integers(0, 256, size=(ch, cw, 3), dtype=np.uint8)
-    raw = rng.integers(0, 65536, size=(zh, zw)).astype(np.uint16)
-    raw[rng.random((zh, zw)) < 0.1] = 0
-    return rgb, raw
+    color, depth = frame_ref.run_guarded(lambda c, z, out: fused.ingest_frame(c, z, scale, size=(h, w), out=out), (rgb, raw),
+                                         ((h, w, 3), (h, w, 1)), lead)
+    return color, depth[..., 0]
 
 
 @pytest.mark.parametrize("lead", (64, 61), ids=("aligned", "unaligned"))
 @pytest.mark.parametrize("case", CASES, ids=str)
 def test_kernel_against_the_float64_restatement(case, lead):
     (cw, ch), (zw, zh), (dw, dh) = case
-    rgb, raw = seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
+    rgb, raw = frame_ref.seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
     color, depth = run_kernel(rgb, raw, 6553.5, dh, dw, lead)
     assert np.array_equal(depth, (frame_ref.resize_nearest(raw, dh, dw).astype(np.float64) / 6553.5).astype(np.float32))
     err = np.abs(color.astype(np.float64) - frame_ref.resize_linear(rgb, dh, dw)).max()
@@ -79,7 +58,7 @@ def test_depth_is_bit_equal_for_every_uint16(scale, lead):
 
 def test_default_size_new_tensors_and_the_host_form_agree():
     from splatam_amd import datasets, fused
-    rgb, raw = seeded_raw(37, 23, 37, 23, seed=3)
+    rgb, raw = frame_ref.seeded_raw(37, 23, 37, 23, seed=3)
     c, z = torch.from_numpy(rgb).cuda(), torch.from_numpy(raw).cuda()
     color, depth = fused.ingest_frame(c, z, 5000.0)
     assert tuple(color.shape) == (23, 37, 3) and tuple(depth.shape) == (23, 37, 1) and color.dtype == depth.dtype == torch.float32

@@ -10,27 +10,12 @@ import frame_ref
 
 pytestmark = pytest.mark.gpu
 COLOUR_ATOL = 1e-6          # 12 float32 roundings at magnitude <= 255: 12 * 2^-24 ~ 7e-7 on the [0, 1] image
-GUARD = 12345.0
 
 
 def run_kernel(color, depth, h, w, lead):
-    """Both outputs inside ONE flat buffer: [lead guards | im 3hw | 8 guards | depth hw | 64 guards], on a side stream."""
+    """``fused.prepare_frame`` into guarded views (frame_ref.run_guarded): (im [3, h, w], depth [1, h, w]) on the host."""
     from splatam_amd import fused
-    dev = torch.device("cuda")
-    n = 3 * h * w
-    flat = torch.full((lead + n + 8 + h * w + 64,), GUARD, dtype=torch.float32, device=dev)
-    im, d = flat[lead:lead + n].view(3, h, w), flat[lead + n + 8:lead + n + 8 + h * w].view(1, h, w)
-    c, z = torch.from_numpy(color).to(dev), torch.from_numpy(depth).to(dev)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):
-        got = fused.prepare_frame(c, z, size=(h, w), out=(im, d))
-    stream.synchronize()
-    assert got[0].data_ptr() == im.data_ptr() and got[1].data_ptr() == d.data_ptr()
-    host = flat.cpu().numpy()
-    guards = np.concatenate([host[:lead], host[lead + n:lead + n + 8], host[lead + n + 8 + h * w:]])
-    assert np.all(guards == np.float32(GUARD)), "a store left the output views"
-    return host[lead:lead + n].reshape(3, h, w), host[lead + n + 8:lead + n + 8 + h * w].reshape(1, h, w)
+    return frame_ref.run_guarded(lambda c, z, out: fused.prepare_frame(c, z, size=(h, w), out=out), (color, depth), ((3, h, w), (1, h, w)), lead)
 
 
 @pytest.mark.parametrize("lead", (64, 61), ids=("aligned", "unaligned"))

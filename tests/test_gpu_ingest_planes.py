@@ -19,54 +19,16 @@ import frame_ref
 
 pytestmark = pytest.mark.gpu
 COLOUR_ATOL = 1e-6
-GUARD = 12345.0
 SCALES = (6553.5, 5000.0, 1000.0, 1234.567)
-OTHER_DEPTH = (11, 7)
-# ((colour w, h), (depth w, h), (destination w, h))
-CASES = (tuple((s, s, d) for s, d in frame_ref.SIZES) + tuple((s, OTHER_DEPTH, d) for s, d in frame_ref.SIZES)
-         + (((26, 20), (16, 12), (13, 9)),          # a depth image of a size of its own, both reduced
-            ((24, 16), (5, 3), (24, 16)),           # depth upsampled under an identity colour
-            ((1, 1), (1, 1), (4, 3)), ((1, 1), (3, 2), (4, 3))))
+CASES = frame_ref.RAW_CASES     # ((colour w, h), (depth w, h), (destination w, h))
 
 
 def run_kernel(rgb, raw, scale, h, w, lead):
-    """Both outputs inside ONE flat buffer: [lead guards | im 3hw | 8 guards | depth hw | 64 guards], on a side stream.  Returns the
-    planes on the host (im [3, h, w], depth [h, w])."""
+    """``fused.ingest_planes`` into guarded views (frame_ref.run_guarded): (im [3, h, w], depth [h, w]) on the host."""
     from splatam_amd import fused
-    dev = torch.device("cuda")
-    n = 3 * h * w
-    flat = torch.full((lead + n + 8 + h * w + 64,), GUARD, dtype=torch.float32, device=dev)
-    im, depth = flat[lead:lead + n].view(3, h, w), flat[lead + n + 8:lead + n + 8 + h * w].view(1, h, w)
-    c, z = torch.from_numpy(rgb).to(dev), torch.from_numpy(raw).to(dev)
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):
-        got = fused.ingest_planes(c, z, scale, size=(h, w), out=(im, depth))
-    stream.synchronize()
-    assert got[0].data_ptr() == im.data_ptr() and got[1].data_ptr() == depth.data_ptr()
-    host = flat.cpu().numpy()
-    guards = np.concatenate([host[:lead], host[lead + n:lead + n + 8], host[lead + n + 8 + h * w:]])
-    assert np.all(guards == np.float32(GUARD)), "a store left the output views"
-    return host[lead:lead + n].reshape(3, h, w), host[lead + n + 8:lead + n + 8 + h * w].reshape(h, w)
-
-
-def seeded_raw(cw, ch, zw, zh, seed):
-    rng = np.random.default_rng(seed)
-    rgb = rng.integers(0, 256, size=(ch, cw, 3), dtype=np.uint8)
-    raw = rng.integers(0, 65536, size=(zh, zw)).astype(np.uint16)
-    raw[rng.random((zh, zw)) < 0.1] = 0
-    return rgb, raw
-
-
-def special_floats(zw, zh, seed):
-    """float32 depth with 0, -0, -1, +inf, -inf, a NaN whose payload is not the default one, the smallest and the largest denormal."""
-    rng = np.random.default_rng(seed)
-    bits = (0.5 + 4.0 * rng.random((zh, zw))).astype(np.float32).view(np.uint32).reshape(-1).copy()
-    special = np.array([0x00000000, 0x80000000, 0xBF800000, 0x7F800000, 0xFF800000, 0x7FA12345, 0xFFC00001, 0x00000001, 0x007FFFFF, 0x80000123],
-                       dtype=np.uint32)
-    where = rng.permutation(bits.size)[:special.size]
-    bits[where] = special[:where.size]
-    return bits.reshape(zh, zw).view(np.float32)
+    im, depth = frame_ref.run_guarded(lambda c, z, out: fused.ingest_planes(c, z, scale, size=(h, w), out=out), (rgb, raw),
+                                      ((3, h, w), (1, h, w)), lead)
+    return im, depth[0]
 
 
 @pytest.mark.parametrize("lead", (64, 61), ids=("aligned", "unaligned"))
@@ -74,7 +36,7 @@ def special_floats(zw, zh, seed):
 def test_kernel_against_the_float64_restatement_and_the_two_kernels_it_replaces(case, lead):
     from splatam_amd import fused
     (cw, ch), (zw, zh), (dw, dh) = case
-    rgb, raw = seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
+    rgb, raw = frame_ref.seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
     im, depth = run_kernel(rgb, raw, 6553.5, dh, dw, lead)
     want_im, _ = frame_ref.prepare(rgb, raw, dh, dw) if (zw, zh) == (cw, ch) else frame_ref.prepare(rgb, np.zeros((ch, cw), np.uint16), dh, dw)
     err = np.abs(im.astype(np.float64) - want_im).max()
@@ -95,8 +57,8 @@ def test_kernel_against_the_float64_restatement_and_the_two_kernels_it_replaces(
 @pytest.mark.parametrize("case", CASES, ids=str)
 def test_float_depth_travels_bit_for_bit(case, lead):
     (cw, ch), (zw, zh), (dw, dh) = case
-    rgb, _ = seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
-    src = special_floats(zw, zh, seed=zw * 10 + dw)
+    rgb, _ = frame_ref.seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
+    src = frame_ref.special_floats(zw, zh, seed=zw * 10 + dw)
     im, depth = run_kernel(rgb, src, None, dh, dw, lead)
     assert np.array_equal(depth.view(np.uint32), frame_ref.resize_nearest(src.view(np.uint32), dh, dw))
     err = np.abs(im.astype(np.float64) - frame_ref.prepare(rgb, np.zeros((ch, cw), np.uint16), dh, dw)[0]).max()
@@ -106,7 +68,7 @@ def test_float_depth_travels_bit_for_bit(case, lead):
 
 @pytest.mark.parametrize("lead", (64, 61), ids=("aligned", "unaligned"))
 def test_every_special_float_survives_at_identity(lead):
-    src = special_floats(8, 5, seed=1)
+    src = frame_ref.special_floats(8, 5, seed=1)
     want = src.view(np.uint32)
     assert {0x7FA12345, 0xFFC00001, 0x00000001, 0x7F800000, 0xBF800000} <= set(want.reshape(-1).tolist())
     _, depth = run_kernel(np.zeros((5, 8, 3), np.uint8), src, 1.0, 5, 8, lead)
@@ -129,8 +91,8 @@ def test_depth_is_bit_equal_for_every_uint16(scale, lead):
 
 def test_default_size_new_tensors_and_the_host_form_agree():
     from splatam_amd import datasets, fused
-    rgb, raw = seeded_raw(37, 23, 16, 12, seed=3)
-    src = special_floats(16, 12, seed=4)
+    rgb, raw = frame_ref.seeded_raw(37, 23, 16, 12, seed=3)
+    src = frame_ref.special_floats(16, 12, seed=4)
     c = torch.from_numpy(rgb).cuda()
     im, depth = fused.ingest_planes(c, torch.from_numpy(src).cuda())
     assert tuple(im.shape) == (3, 23, 37) and tuple(depth.shape) == (1, 23, 37) and im.dtype == depth.dtype == torch.float32

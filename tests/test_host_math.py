@@ -3,27 +3,20 @@ compiled for the host with g++ and compared with the oracle -- CPU only, no
 kernel launches.  Catches projection / adjoint mistakes without GPU time."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import raster_ref as R
-from tests.util import scene, tilted_w2c
+from tests.util import host_shim, scene, tilted_w2c
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @pytest.fixture(scope="module")
 def shim():
-    out = os.path.join(HERE, "_build", "libhost_math_shim.so")
-    src = os.path.join(HERE, "host_math_shim.cpp")
-    hdrs = [os.path.join(HERE, "..", "splatam_amd", "csrc", h) for h in ("splat_math.h", "fused_math.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
-    return C.CDLL(out)
+    return host_shim("host_math_shim", "fused_math.h")
 
 
 def _p(a, t=C.c_float):

@@ -1,4 +1,4 @@
-"""Frame ingest without a GPU: splatam_amd/csrc/frame_math.h compiled for the host (tests/ingest_math_shim.cpp) against the float64
+"""Frame ingest without a GPU: splatam_amd/csrc/frame_math.h compiled for the host (tests/frame_math_shim.cpp) against the float64
 restatement tests/frame_ref.py and against ``datasets.ingest_frame_cpu``, the torch form the loaders use on the CPU.
 
 The reference's loaders cannot be executed here (cv2, imageio and natsort are absent), so the expected values are restated: depth is
@@ -7,15 +7,13 @@ bit for bit for every uint16; colour is tests/frame_ref.py's float64 bilinear fo
 float32 roundings at magnitude <= 255, the bound of tests/test_frame_math_cpu.py on the 0..255 scale) and equal to the bytes at
 equal size."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import frame_ref
+from tests.util import host_shim
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 SCALES = (6553.5, 5000.0, 1000.0, 1234.567)
 COLOUR_ATOL = 255 * 1e-6
 SIZES = frame_ref.SIZES + ((((26, 20), (16, 12)), (13, 9)),)         # ... and a depth image of a size of its own
@@ -23,13 +21,7 @@ SIZES = frame_ref.SIZES + ((((26, 20), (16, 12)), (13, 9)),)         # ... and a
 
 @pytest.fixture(scope="module")
 def shim():
-    out = os.path.join(HERE, "_build", "libingest_math_shim.so")
-    src = os.path.join(HERE, "ingest_math_shim.cpp")
-    hdrs = [os.path.join(HERE, "..", "splatam_amd", "csrc", h) for h in ("splat_math.h", "frame_math.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
-    lib = C.CDLL(out)
+    lib = host_shim("frame_math_shim", "frame_math.h")
     lib.im_depth_metres.argtypes = [C.c_int, C.c_void_p, C.c_double, C.c_void_p]
     lib.im_ingest.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     return lib
@@ -50,19 +42,11 @@ def _sizes(case):
     return (src, src, dst) if isinstance(src[0], int) else (src[0], src[1], dst)
 
 
-def seeded_raw(cw, ch, zw, zh, seed):
-    rng = np.random.default_rng(seed)
-    rgb = rng.integers(0, 256, size=(ch, cw, 3), dtype=np.uint8)
-    raw = rng.integers(0, 65536, size=(zh, zw)).astype(np.uint16)
-    raw[rng.random((zh, zw)) < 0.1] = 0
-    return rgb, raw
-
-
 @pytest.mark.parametrize("impl", ("frame_math.h", "datasets.ingest_frame_cpu"))
 @pytest.mark.parametrize("case", SIZES, ids=str)
 def test_ingest_against_the_float64_restatement(shim, impl, case):
     (cw, ch), (zw, zh), (dw, dh) = _sizes(case)
-    rgb, raw = seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
+    rgb, raw = frame_ref.seeded_raw(cw, ch, zw, zh, seed=cw * 100 + dw)
     scale = 6553.5
     if impl == "frame_math.h":
         color, depth = np.full((dh, dw, 3), np.nan, np.float32), np.full((dh, dw, 1), np.nan, np.float32)

@@ -8,13 +8,13 @@ V2 (bytes): equal to the restatement wherever the float64 value before the round
 1e-4 from a boundary, off by at most one nearer than that, at most 0.1 % of the elements that near (``view_ref.check_bytes``)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import view_ref
+from tests.util import host_shim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 W, H = 72, 40
@@ -31,13 +31,7 @@ OFFSET = np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0.5], [0, 0, 0, 1]], dt
 
 @pytest.fixture(scope="module")
 def shim():
-    out = os.path.join(HERE, "_build", "libview_math_shim.so")
-    src = os.path.join(HERE, "view_math_shim.cpp")
-    hdrs = [os.path.join(HERE, "..", "splatam_amd", "csrc", h) for h in ("splat_math.h", "view_math.h")]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max([os.path.getmtime(src)] + [os.path.getmtime(h) for h in hdrs]):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
-    return C.CDLL(out)
+    return host_shim("view_math_shim", "view_math.h")
 
 
 def _p(a, t=C.c_float):

@@ -1,8 +1,26 @@
 """Shared helpers for the parity tests (CPU side)."""
+import ctypes
+import os
+import subprocess
+
 import numpy as np
 import torch
 
 from oracle import raster_ref as R
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def host_shim(name, *headers):
+    """tests/<name>.cpp, which includes ``headers`` of splatam_amd/csrc (splat_math.h is always among them), compiled for the host
+    with g++ into tests/_build and loaded: rebuilt when the source or a header is newer.  -ffp-contract=off: no fused multiply-add
+    the device code does not ask for."""
+    out, src = os.path.join(HERE, "_build", f"lib{name}.so"), os.path.join(HERE, f"{name}.cpp")
+    deps = [src] + [os.path.join(HERE, "..", "splatam_amd", "csrc", h) for h in ("splat_math.h",) + headers]
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", out, src])
+    return ctypes.CDLL(out)
 
 
 def scene(n, W, H, f, seed=0, anisotropic=False, w2c=None, bg=(0.0, 0.0, 0.0), dtype=torch.float32):
