@@ -459,6 +459,56 @@ class FusedEngine:
         # (only_bucketed: a camera that holds a list length but no buckets drops it as well; rebind keeps it)
         self._keep_lists(keep_lists_within, only_bucketed=True)
 
+    def replace_map(self, params):
+        """A map read from a file takes the place of the engine's (the reference's checkpoint loader replaces ``params`` wholesale and
+        zeroes the per-Gaussian variables, ``timestep`` included: /root/reference/scripts/splatam.py:609-614).  ``params``: the seven
+        tensors; the two pose arrays must have the engine's number of frames.  Every camera forgets its list statistics."""
+        if not self.managed:
+            raise RuntimeError("replace_map is for engines that own their map (gaussian_capacity)")
+        P = int(params['means3D'].shape[0])
+        for k, w in zip(PARAM_ORDER, self._widths):
+            if tuple(params[k].shape) != (P, w):
+                raise ValueError(f"checkpoint entry '{k}' has shape {tuple(params[k].shape)}, this map's layout wants {(P, w)}")
+        for k in ("cam_unnorm_rots", "cam_trans"):
+            if tuple(params[k].shape) != tuple(self.params[k].shape):
+                raise ValueError(f"checkpoint entry '{k}' has shape {tuple(params[k].shape)}, the run was declared with "
+                                 f"{tuple(self.params[k].shape)} (num_frames = {self.num_frames})")
+        if P > self.Pcap:
+            self._grow_rows(P + P // 8 + 1024)
+        with torch.no_grad():
+            for k in PARAM_ORDER:
+                self.store[k][:P] = params[k].detach().to(self.dev, torch.float32)
+            for k in VARIABLE_KEYS:
+                self.store[k].zero_()
+            for k in ("cam_unnorm_rots", "cam_trans"):
+                self.params[k].copy_(params[k].detach().to(self.dev, torch.float32))
+        for k in PARAM_ORDER:
+            self._m_store[k].zero_()
+            self._v_store[k].zero_()
+        self.creation_order = False
+        self._set_rows(P, keep_lists_within=-1.0)
+
+    def list_sizing(self):
+        """What decides whether an iteration of this engine gets flagged, per camera in registration order: the lists' capacity, the
+        bucket stride, the longest list and the rows it was learnt on, the counters per tile.  Host integers (an exact checkpoint
+        keeps them: a flagged phase draws fresh random views for the iterations it runs again, so the loop's random stream depends on
+        them)."""
+        return [dict(H=c.H, W=c.W, capacity=c.capacity, tile_stride=c.tile_stride, max_list_hint=c.max_list_hint, learnt_P=c.learnt_P,
+                     sub_bins=c.sub_bins) for c in self._cams]
+
+    def set_list_sizing(self, sizing):
+        """Inverse of ``list_sizing`` on an engine with the same cameras in the same order."""
+        if len(sizing) != len(self._cams):
+            raise ValueError(f"list sizing of {len(sizing)} cameras, this engine has {len(self._cams)}")
+        for c, s in zip(self._cams, sizing):
+            if (c.H, c.W) != (int(s['H']), int(s['W'])):
+                raise ValueError(f"list sizing of a {s['H']} x {s['W']} camera, this engine's is {c.H} x {c.W}")
+            if int(s['capacity']) != c.capacity:
+                c.alloc_lists(int(s['capacity']), self.use_recs)
+            c.set_sub_bins(int(s['sub_bins']))
+            c.tile_stride, c.max_list_hint = int(s['tile_stride']), int(s['max_list_hint'])
+            c.learnt_P = None if s['learnt_P'] is None else int(s['learnt_P'])
+
     def _frame(self, curr_data, time_idx, images=True):
         """The SplatFrameData of ``curr_data`` at pose ``time_idx`` (``images``: with its planes); ``_frame_keep`` keeps what it names alive.
         curr_data['w2c'] as the kernels read it: 16 contiguous floats on the engine's device (row 2 is the depth channel of

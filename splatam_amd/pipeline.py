@@ -346,7 +346,7 @@ class _PhaseTimer:
 
 
 def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacity=None, verbose=False, evaluate=None,
-              tracking_dataset=None, densify_dataset=None):
+              tracking_dataset=None, densify_dataset=None, checkpoint_dir=None, resume_exact=None, exact_checkpoints=False):
     """Runs the SplaTAM frame loop over ``dataset`` -- the driver over ``session.SlamSession``, which holds the loop's set-up and its
     per-frame body: every frame is one ``add_frame(*dataset[i])`` -- and returns ``(params, variables, stats)`` with
     ``stats = {keyframe_time_indices, tracking_iters, mapping_iters, tracking_s, mapping_s, mapping_loop_s, num_gaussians,
@@ -389,25 +389,64 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     ``ms_ssim`` (True) -- the run's last act is the reference's (scripts/splatam.py:961-971): ``evaluation.evaluate`` on the final
     parameters with the mapping configuration's ``sil_thres`` / ``num_iters`` / ``add_new_gaussians``, returned as ``stats['eval']``
     (PSNR, depth L1, MS-SSIM per evaluated frame, ATE; LPIPS is not computed).  The fused engine evaluates on its own map, the other
-    engines' parameters get a throw-away ``FusedEngine``; with several ranks rank 0 evaluates and the dict is broadcast."""
+    engines' parameters get a throw-away ``FusedEngine``; with several ranks rank 0 evaluates and the dict is broadcast.
+
+    Checkpoints (splatam_amd/checkpoint.py; engines "fused" and "dropin", one rank).  With ``checkpoint_dir`` -- default
+    ``workdir/run_name`` where the config has both -- the reference's four keys are honoured as it honours them:
+    ``save_checkpoints`` writes ``params<t>.npz`` and ``keyframe_time_indices<t>.npy`` after every frame with
+    ``t % checkpoint_interval == 0`` (scripts/splatam.py:927-931); ``load_checkpoint`` with ``checkpoint_time_idx = t`` does what
+    :604-640 do (``SlamSession.load_reference_checkpoint``): the loop restarts AT ``t``, so that frame is tracked and mapped again.
+    Without a directory and with the keys off nothing changes.  ``resume_exact=t``: ``SlamSession.restore`` of the exact checkpoint
+    ``SlamSession.save_checkpoint`` wrote after frame ``t`` in that directory, continued at ``t + 1`` as if the run had never
+    stopped (``stats`` cover the whole run).  ``exact_checkpoints=True``: the frames on which ``save_checkpoints`` writes the pair get
+    the exact checkpoint (the pair plus ``session<t>.npz``; keyframe planes are read from ``dataset`` again).
+    ``config['load_checkpoint']`` always means the reference's form."""
+    from . import checkpoint
     from . import dist as sdist
     from .session import SlamSession
     world, rank = sdist.world_size(), sdist.get_rank()
     num_frames = len(dataset) if num_frames is None else min(num_frames, len(dataset))
+    if checkpoint_dir is None:
+        checkpoint_dir = checkpoint.default_directory(config)
+    saves = bool(config.get('save_checkpoints')) and checkpoint_dir is not None
+    loads = bool(config.get('load_checkpoint')) and checkpoint_dir is not None
+    start = 0
+    if resume_exact is not None:
+        if checkpoint_dir is None:
+            raise ValueError("resume_exact needs checkpoint_dir (or config['workdir'] and config['run_name'])")
+        if loads:
+            raise ValueError("resume_exact and config['load_checkpoint'] are two different ways to resume: choose one")
+        session = SlamSession.restore(config, checkpoint_dir, int(resume_exact), num_frames=num_frames, dataset=dataset, engine=engine,
+                                      gaussian_capacity=gaussian_capacity, verbose=verbose, return_pose=False, reference_division=True)
+        start = session.frames_seen
+    else:
+        session = SlamSession(config, num_frames, engine=engine, gaussian_capacity=gaussian_capacity, verbose=verbose, return_pose=False,
+                              reference_division=True)
     # the loop body and its set-up live in session.SlamSession: this is the driver over a finished sequence
-    with SlamSession(config, num_frames, engine=engine, gaussian_capacity=gaussian_capacity, verbose=verbose, return_pose=False,
-                     reference_division=True) as session:
+    with session:
+        if loads:
+            start = int(config['checkpoint_time_idx'])
+            session.load_reference_checkpoint(checkpoint_dir, start, dataset,
+                                              tracking_item=None if tracking_dataset is None else tracking_dataset[0],
+                                              densify_item=None if densify_dataset is None else densify_dataset[0])
+        elif saves:
+            session._refuse_checkpoints("save_checkpoints")
         # (the keyframe rule asks whether a pose is finite: answered once, from the dataset's host copy of the poses where it keeps one)
         host_poses = getattr(dataset, 'poses', None)
         finite = torch.isfinite(host_poses[:num_frames]).flatten(1).all(dim=1).tolist() \
             if isinstance(host_poses, torch.Tensor) and host_poses.device.type == "cpu" and host_poses.shape[0] >= num_frames else None
-        for time_idx in range(num_frames):
+        for time_idx in range(start, num_frames):
             session._begin_frame()               # (reading the frame counts towards its prepare_frames phase and its frame_s)
             item = dataset[time_idx]
             tracking_item = tracking_dataset[time_idx] if tracking_dataset is not None else None
             densify_item = densify_dataset[time_idx] if densify_dataset is not None and session._densifies(time_idx) else None
             session.add_frame(*item, tracking_item=tracking_item, densify_item=densify_item,
                               _pose_finite=None if finite is None else bool(finite[time_idx]))
+            if saves and time_idx % config['checkpoint_interval'] == 0:
+                if exact_checkpoints:
+                    session.save_checkpoint(checkpoint_dir, keyframes=False)
+                else:
+                    session.save_reference_checkpoint(checkpoint_dir, time_idx)
         params, variables, stats = session.finish()
     fused, eng, cam, mcfg = engine == "fused", session.engine, session.cam, config['mapping']
     if evaluate is not None:

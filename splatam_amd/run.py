@@ -4,7 +4,8 @@ The file is one of the reference's own (configs/<dataset>/*.py: a Python module 
 ``scripts/splatam.py`` loads with ``SourceFileLoader``, :992-1001); this package ships none of them.  What happens here is what that
 script does around its frame loop, restated: the defaults of :458-464 and :494-517, the seeding of utils/common_utils.py:8-22, the
 datasets (``datasets.get_dataset`` at the full size, ``at_size`` siblings where tracking or densification have a size of their own),
-``pipeline.rgbd_slam``, the evaluation as the run's last act, and ``params.npz`` under ``workdir/run_name`` with the reference's extra
+``pipeline.rgbd_slam`` (with the reference's checkpoint keys: saving every ``checkpoint_interval`` frames, ``load_checkpoint``), the
+evaluation as the run's last act, and ``params.npz`` under ``workdir/run_name`` with the reference's extra
 entries (:973-986).  Keys the loop cannot honour stop the run with a message that names them.
 """
 from __future__ import annotations
@@ -68,16 +69,21 @@ def check_supported(config):
     """Stops with the name of a key this loop cannot honour."""
     if config.get('use_wandb'):
         raise SystemExit("config['use_wandb'] = True: wandb logging is not supported; set it to False")
-    if config.get('load_checkpoint'):
-        raise SystemExit("config['load_checkpoint'] = True: resuming from a checkpoint is not supported; set it to False")
+    if config.get('load_checkpoint') and 'checkpoint_time_idx' not in config:
+        raise SystemExit("config['load_checkpoint'] = True needs config['checkpoint_time_idx']: the frame whose checkpoint is loaded")
+    if config.get('save_checkpoints') and 'checkpoint_interval' not in config:
+        raise SystemExit("config['save_checkpoints'] = True needs config['checkpoint_interval']")
     if config['tracking'].get('visualize_tracking_loss'):
         raise SystemExit("config['tracking']['visualize_tracking_loss']: the tracking-loss viewer is not supported; set it to False")
     if config.get('mean_sq_dist_method') != "projective":
         raise SystemExit(f"config['mean_sq_dist_method'] = {config.get('mean_sq_dist_method')!r}: only \"projective\" is supported")
 
 
-def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4):
-    """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``."""
+def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False):
+    """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``.  The reference's four
+    checkpoint keys (``save_checkpoints``, ``checkpoint_interval``, ``load_checkpoint``, ``checkpoint_time_idx``) are honoured under
+    ``workdir/run_name``; ``exact_checkpoints=True`` makes every checkpoint ``save_checkpoints`` writes an exact one (``session<t>.npz``
+    beside the pair) and ``resume_exact=t`` continues from the exact checkpoint of frame ``t`` there (``pipeline.rgbd_slam``)."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -106,7 +112,9 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4):
                 opts.update(save_frames=True, eval_dir=os.path.join(config["workdir"], config["run_name"], "eval"))
         t0 = time.perf_counter()
         params, variables, stats = pipeline.rgbd_slam(dataset, config, engine=engine, num_frames=n, evaluate=opts,
-                                                      tracking_dataset=tracking, densify_dataset=densify)
+                                                      tracking_dataset=tracking, densify_dataset=densify,
+                                                      checkpoint_dir=os.path.join(config["workdir"], config["run_name"]),
+                                                      resume_exact=resume_exact, exact_checkpoints=exact_checkpoints)
         if device.type == "cuda":
             torch.cuda.synchronize(device)
         stats['run_s'] = time.perf_counter() - t0
@@ -133,11 +141,16 @@ def main(argv=None):
     parser.add_argument("--engine", default="fused", choices=("fused", "dropin", "plugin", "plugin_map_edits"))
     parser.add_argument("--num-frames", type=int, default=None, help="overrides config['data']['num_frames'] (-1 = all)")
     parser.add_argument("--no-eval", action="store_true", help="skip the evaluation of the final map")
+    parser.add_argument("--resume-exact", type=int, default=None, metavar="T",
+                        help="continue at frame T + 1 from the exact checkpoint (session<T>.npz) under workdir/run_name")
+    parser.add_argument("--exact-checkpoints", action="store_true",
+                        help="with config['save_checkpoints']: also write session<t>.npz, the state --resume-exact continues from")
     args = parser.parse_args(argv)
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
-    _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval)
+    _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
+                            exact_checkpoints=args.exact_checkpoints)
     ev = stats.get('eval')
     if ev is not None:
         print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"

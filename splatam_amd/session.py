@@ -25,6 +25,7 @@ modules at call time: a wrapper installed there later (``plugin.install``, a rec
 """
 from __future__ import annotations
 
+import json
 import time
 
 import numpy as np
@@ -32,7 +33,7 @@ import torch
 
 from collections import namedtuple
 
-from . import frames, pipeline, slam
+from . import checkpoint, frames, pipeline, slam
 
 ENGINES = ("fused", "dropin", "plugin", "plugin_map_edits")
 HostView = namedtuple("HostView", "array event truncated")
@@ -113,6 +114,9 @@ class SlamSession:
         self._tracking_frames = self._densify_frames = None
         self._raw = None                    # the raw path's buffers and sizes, made on its first frame
         self._view = None                   # render_view's view camera and pinned slots, made on its first call
+        # checkpoints: the writer thread, the pinned host copies and the keyframe planes already copied (all made by the first save_checkpoint)
+        self._writer = self._host = None
+        self._kf_host, self._raw_restored, self.last_checkpoint = [], False, None
 
     # ------------------------------------------------------------------ life cycle
     def __enter__(self):
@@ -122,13 +126,15 @@ class SlamSession:
         self.close()
 
     def close(self):
-        """Undoes ``plugin.install`` (its counters go to ``stats['plugin']``); the session takes no more frames."""
+        """Undoes ``plugin.install`` (its counters go to ``stats['plugin']``) and waits for a checkpoint still being written; the session
+        takes no more frames."""
         self._finished = True
         if self._installed is not None:
             from . import plugin
             self.stats['plugin'] = plugin.session_stats()
             self._installed.uninstall()
             self._installed = None
+        self.join_checkpoint()                  # (a failed write raises here)
 
     def finish(self):
         """``(params, variables, stats)``; before ``num_frames`` frames the pose arrays are cut to ``stats['frames_seen']``."""
@@ -143,6 +149,277 @@ class SlamSession:
             for k in ('cam_unnorm_rots', 'cam_trans'):
                 params[k] = torch.nn.Parameter(params[k].detach()[..., :n].clone())
         return params, self.variables, self.stats
+
+    # ------------------------------------------------------------------ checkpoints (splatam_amd/checkpoint.py)
+    def _refuse_checkpoints(self, key):
+        from . import dist as sdist
+        if self.plugged:
+            raise NotImplementedError(f"{key}: checkpoints are not supported with engine='{self.engine_name}' (use 'fused' or 'dropin')")
+        if sdist.world_size() > 1:
+            raise NotImplementedError(f"{key}: checkpoints are not supported in the multi-rank frame loop")
+
+    def join_checkpoint(self):
+        """Waits for the checkpoint being written, if any; a failed write raises here.  Returns the bytes written per file kind
+        (``reference``, ``session``, ``keyframes``) of the latest checkpoint."""
+        if self._writer is None:
+            return {}
+        self._writer.join()
+        return dict(self._writer.bytes_written)
+
+    def _host_copies(self, directory, key):
+        self._refuse_checkpoints(key)
+        if self.frames_seen == 0 or self.params is None:
+            raise RuntimeError(f"{key}: a checkpoint before the first frame: there is no map")
+        if self._writer is None:
+            self._writer, self._host = checkpoint.Writer(), checkpoint.HostCopies(self.dev)
+        self._writer.join()                     # (the pinned copies are the previous checkpoint's until its files are written)
+        return {k: self._host.copy(k, self.params[k]) for k in checkpoint.MAP_KEYS}
+
+    def save_reference_checkpoint(self, directory, time_idx=None):
+        """The reference's checkpoint of the state after the latest frame (scripts/splatam.py:927-931): ``params<t>.npz`` with every
+        entry of ``params`` and ``keyframe_time_indices<t>.npy``, written on the background thread.  Between frames."""
+        t = self.frames_seen - 1 if time_idx is None else int(time_idx)
+        host = self._host_copies(directory, "save_checkpoints")
+        self._host.wait()
+        indices = list(self.keyframe_time_indices)
+        self._writer.submit([("reference", lambda: checkpoint.write_reference(directory, t, host, indices))])
+        return checkpoint.reference_paths(directory, t)
+
+    def load_reference_checkpoint(self, directory, time_idx, dataset, tracking_item=None, densify_item=None):
+        """``load_checkpoint`` as the reference does it (scripts/splatam.py:604-640), before the first frame: the first frame's set-up
+        runs on ``dataset[0]`` (camera, ``scene_radius``, first-frame point cloud; ``tracking_item`` / ``densify_item``: the first
+        items of datasets at those sizes), then the parameters are replaced by the file's, ``max_2D_radius``,
+        ``means2D_gradient_accum``, ``denom`` AND ``timestep`` become zeros of the loaded row count, the keyframe list is rebuilt for
+        the listed indices BELOW ``time_idx`` (frames from ``dataset``, ``est_w2c`` from the loaded poses) while
+        ``keyframe_time_indices`` keeps the file's list, and the next frame the session takes is ``time_idx`` itself: it is tracked
+        and mapped a second time, and where it is a keyframe frame its index ends up in the list twice.  Random streams are left as
+        they are."""
+        self._refuse_checkpoints("load_checkpoint")
+        if self.params is not None or self.frames_seen:
+            raise RuntimeError("load_checkpoint: the session has taken frames already")
+        time_idx = int(time_idx)
+        if not 0 <= time_idx < self.num_frames:
+            raise ValueError(f"checkpoint_time_idx = {time_idx} is outside the run's {self.num_frames} frames")
+        loaded, indices = checkpoint.load_reference(directory, time_idx, "cpu")        # (a missing file is named before any work)
+        missing = [k for k in checkpoint.MAP_KEYS if k not in loaded]
+        if missing:
+            raise ValueError(f"{checkpoint.reference_paths(directory, time_idx)[0]} has no entry {missing[0]!r}")
+        color, depth, intrinsics, pose = dataset[0]
+        self._first_item(color, depth, intrinsics, pose, *self._item_planes(color, depth), tracking_item, densify_item)
+        if self.fused:
+            self.engine.replace_map(loaded)
+        else:
+            for k in ('cam_unnorm_rots', 'cam_trans'):
+                if tuple(loaded[k].shape) != tuple(self.params[k].shape):
+                    raise ValueError(f"checkpoint entry '{k}' has shape {tuple(loaded[k].shape)}, the run was declared with "
+                                     f"{tuple(self.params[k].shape)} (num_frames = {self.num_frames})")
+            self.params = {k: v.detach().to(self.dev).requires_grad_(True) for k, v in loaded.items()}
+            rows = self.params['means3D'].shape[0]
+            for k in ('max_2D_radius', 'means2D_gradient_accum', 'denom', 'timestep'):
+                self.variables[k] = torch.zeros(rows, device=self.dev)
+        with torch.no_grad():
+            for t in range(time_idx):
+                if t in indices:
+                    color, depth = dataset[t][:2]
+                    im, d = self._item_planes(color, depth)
+                    self.keyframe_list.append({'id': t, 'est_w2c': pipeline._est_w2c(self.params, t), 'color': im, 'depth': d})
+        self.keyframe_time_indices = list(indices)
+        self.frames_seen, self._t_frame = time_idx, None
+        return self
+
+    def save_checkpoint(self, directory, keyframes=None):
+        """An exact checkpoint of the session after its latest frame ``t``, between frames: the reference's pair (``params<t>.npz``,
+        ``keyframe_time_indices<t>.npy``) plus ``session<t>.npz`` -- every entry of ``variables`` (``timestep`` too), ``frames_seen``,
+        ``first_frame_w2c``, intrinsics, the frame size and the reduced sizes, every keyframe's ``est_w2c``, ``stats`` so far, the state
+        of Python's, numpy's and torch's CPU random streams and of the device generator, and on the fused engine the list sizing
+        of every camera (``FusedEngine.list_sizing``: it decides whether an iteration gets flagged, a flagged phase draws fresh
+        random views for the iterations it runs again, so the random stream depends on it).  ``SlamSession.restore`` continues at
+        ``t + 1`` as if the run had never stopped.  Arrays and JSON strings only; nothing is pickled.
+
+        ``keyframes``: also write ``keyframes<t>.npz`` with every keyframe's colour and depth planes as float32, copied bit for bit:
+        16 bytes per pixel and keyframe, 13 MB per keyframe at 1200 x 680.  Default: True for a session fed by ``add_raw_frame``
+        (nothing to read them from again), False for an ``add_frame`` session (``restore`` reads them from a dataset).
+
+        Device tensors are copied into pinned host buffers the session keeps (a keyframe's planes once: later checkpoints reuse the
+        copy) with ONE synchronisation; the files are written by one background thread that the next ``save_checkpoint``,
+        ``join_checkpoint``, ``finish()`` and ``close()`` join -- a failed write raises there.  Frames that do not checkpoint
+        synchronise and allocate nothing for it.  Returns ``{time_idx, paths}``."""
+        t0 = time.perf_counter()
+        host = self._host_copies(directory, "save_checkpoint")
+        t = self.frames_seen - 1
+        if keyframes is None:
+            keyframes = self._raw is not None or self._raw_restored
+        H = self._host
+        arrays = {f"var/{k}": H.copy(f"var/{k}", v) for k, v in self.variables.items() if isinstance(v, torch.Tensor) and k != 'means2D'}
+        arrays['first_frame_w2c'] = H.copy('first_frame_w2c', self.first_frame_w2c)
+        arrays['intrinsics'] = H.copy('intrinsics', self.intrinsics)
+        kfs = self.keyframe_list
+        if kfs:
+            arrays['keyframe_est_w2c'] = H.copy('keyframe_est_w2c', torch.stack([kf['est_w2c'] for kf in kfs]))
+        else:
+            arrays['keyframe_est_w2c'] = np.zeros((0, 4, 4), dtype=np.float32)
+        arrays['keyframe_ids'] = np.array([kf['id'] for kf in kfs], dtype=np.int64)
+        arrays['keyframe_time_indices'] = np.array(self.keyframe_time_indices, dtype=np.int64)
+        reduced = {}
+        for which, fr in (('tracking', self._tracking_frames), ('densify', self._densify_frames)):
+            reduced[which] = None if fr is None else dict(size=list(fr.size), from_items=bool(fr.from_items))
+            if fr is not None:
+                arrays[f"{which}_intrinsics"] = H.copy(f"{which}_intrinsics", fr.intrinsics)
+        planes = None
+        if keyframes:
+            for i in range(len(self._kf_host), len(kfs)):       # (a stored keyframe never changes: each is copied once)
+                self._kf_host.append((H.copy(None, kfs[i]['color'], keep=True), H.copy(None, kfs[i]['depth'], keep=True)))
+            planes = dict(count=np.array(len(kfs), dtype=np.int64))
+            for i, (c, d) in enumerate(self._kf_host[:len(kfs)]):
+                planes[f"color{i}"], planes[f"depth{i}"] = c, d
+        rng_arrays, rng_meta = checkpoint.capture_random(self.dev)
+        arrays.update(rng_arrays)
+        H.wait()                                # the checkpoint's one synchronisation
+        cam = self.cam
+        meta = dict(format=checkpoint.FORMAT, time_idx=t, frames_seen=self.frames_seen, num_frames=self.num_frames,
+                    engine=self.engine_name, engine_family="fused" if self.fused else "statements", device=str(self.dev),
+                    gaussian_distribution=self.dist_kind, frame_size=[int(cam.image_height), int(cam.image_width)], reduced=reduced,
+                    reference_division=self.reference_division, raw=bool(self._raw is not None or self._raw_restored),
+                    keyframes_stored=bool(keyframes), rng=rng_meta, stats=self.stats)
+        if self.fused:
+            eng = self.engine
+            meta['fused'] = dict(list_sizing=eng.list_sizing(), gaussian_capacity=int(eng.Pcap), creation_order=bool(eng.creation_order))
+        arrays['meta'] = np.array(json.dumps(meta))
+        indices = list(self.keyframe_time_indices)
+        jobs = [("reference", lambda: checkpoint.write_reference(directory, t, host, indices)),
+                ("session", lambda: checkpoint._write_npz(checkpoint.session_path(directory, t), arrays))]
+        if planes is not None:
+            jobs.append(("keyframes", lambda: checkpoint._write_npz(checkpoint.keyframes_path(directory, t), planes)))
+        self._writer.submit(jobs)
+        paths = checkpoint.reference_paths(directory, t) + (checkpoint.session_path(directory, t),)
+        if planes is not None:
+            paths += (checkpoint.keyframes_path(directory, t),)
+        self.last_checkpoint = dict(time_idx=t, paths=paths, host_ms=1e3 * (time.perf_counter() - t0))
+        return self.last_checkpoint
+
+    @classmethod
+    def restore(cls, config, directory, time_idx, num_frames=None, dataset=None, engine="fused", gaussian_capacity=None, verbose=False,
+                device=None, return_pose=True, reference_division=None):
+        """The session ``save_checkpoint`` put down after frame ``time_idx``: its next frame is ``time_idx + 1``.
+
+        Keyframe planes come from ``keyframes<t>.npz`` where the checkpoint has one, else from ``dataset`` (its full-size frames, through
+        the path ``add_frame`` took -- ``reference_division`` is the checkpoint's; passing another value raises); with neither it
+        raises.  A checkpoint whose ``frame_size``, ``tracking_size`` / ``densification_size``, ``gaussian_distribution`` or
+        ``engine_family`` disagrees with ``config`` / ``engine`` is refused with a message that names the entry.  ``num_frames`` may be
+        LARGER than the saved one -- the two pose arrays are extended with the rows ``initialize_params`` writes (identity quaternion,
+        zero translation): a finished map is continued with more frames -- and not smaller.  The random streams are set from the
+        checkpoint as the last act: the state of the calling process does not matter.  ``device``: default the checkpoint's."""
+        arrays, meta = checkpoint.load_session(directory, time_idx)
+        where = checkpoint.session_path(directory, time_idx)
+        saved_frames = int(meta['num_frames'])
+        num_frames = saved_frames if num_frames is None else int(num_frames)
+        if num_frames < saved_frames:
+            raise ValueError(f"{where}: num_frames = {num_frames} is smaller than the checkpoint's num_frames = {saved_frames}")
+        if reference_division is not None and bool(reference_division) != bool(meta['reference_division']):
+            raise ValueError(f"{where}: reference_division = {bool(meta['reference_division'])} in the checkpoint, {bool(reference_division)} asked for")
+        self = cls(config, num_frames, engine=engine, gaussian_capacity=gaussian_capacity, verbose=verbose, device=device,
+                   return_pose=return_pose, reference_division=bool(meta['reference_division']))
+        self._refuse_checkpoints("restore")
+        dev = torch.device(meta['device']) if device is None else torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        family = "fused" if self.fused else "statements"
+        if family != meta['engine_family']:
+            raise ValueError(f"{where}: engine_family = {meta['engine_family']!r} (engine {meta['engine']!r}), engine={engine!r} asked for")
+        if self.dist_kind != meta['gaussian_distribution']:
+            raise ValueError(f"{where}: gaussian_distribution = {meta['gaussian_distribution']!r}, the config says {self.dist_kind!r}")
+        data = config.get('data') or {}
+        H, W = (int(x) for x in meta['frame_size'])
+        if "desired_image_height" in data and (int(data["desired_image_height"]), int(data["desired_image_width"])) != (H, W):
+            raise ValueError(f"{where}: frame_size = {(H, W)}, the config's desired_image_height / _width say "
+                             f"{(int(data['desired_image_height']), int(data['desired_image_width']))}")
+        for which, key in (('tracking', "tracking"), ('densify', "densification")):
+            saved = meta['reduced'][which]
+            if saved is not None and saved['from_items']:
+                continue                        # (the size was a dataset's own: the items of the frames to come carry it)
+            asked = (int(data[f"{key}_image_height"]), int(data[f"{key}_image_width"])) if f"{key}_image_height" in data else None
+            asked = None if asked == (H, W) else asked
+            have = None if saved is None else tuple(saved['size'])
+            if asked != have:
+                raise ValueError(f"{where}: {key}_size = {have}, the config's {key}_image_height / _width say {asked}")
+        planes = checkpoint.load_keyframes(directory, time_idx)
+        ids = [int(x) for x in arrays['keyframe_ids']]
+        if planes is None and dataset is None and ids:
+            raise ValueError(f"{checkpoint.keyframes_path(directory, time_idx)} does not exist and no dataset was passed: nothing to "
+                             f"restore the planes of keyframes {ids} from")
+        loaded, _ = checkpoint.load_reference(directory, time_idx, "cpu")
+        on_dev = lambda a: torch.from_numpy(np.array(a, order="C")).to(dev)                   # noqa: E731
+        with torch.no_grad():
+            for k, first in (('cam_unnorm_rots', 1.0), ('cam_trans', 0.0)):
+                if num_frames > saved_frames:
+                    more = torch.zeros(1, loaded[k].shape[1], num_frames - saved_frames)
+                    more[:, 0, :] = first
+                    loaded[k] = torch.cat((loaded[k].detach(), more), dim=-1)
+            params = {k: torch.nn.Parameter(loaded[k].detach().to(dev).contiguous().requires_grad_(True)) for k in checkpoint.MAP_KEYS}
+        variables = {k[4:]: on_dev(v) for k, v in arrays.items() if k.startswith("var/")}
+        intrinsics, first_frame_w2c = on_dev(arrays['intrinsics']), on_dev(arrays['first_frame_w2c']).float().contiguous()
+        cam = slam.setup_camera(W, H, intrinsics.cpu().numpy(), first_frame_w2c.cpu().numpy(), device=dev)
+        reduced = {}
+        for which in ('tracking', 'densify'):
+            saved = meta['reduced'][which]
+            reduced[which] = None
+            if saved is not None:
+                fr = pipeline._ReducedFrames(None, saved['size'], (H, W), None, intrinsics=on_dev(arrays[f"{which}_intrinsics"]))
+                fr.from_items = bool(saved['from_items'])
+                fr.cam = slam.setup_camera(fr.size[1], fr.size[0], fr.intrinsics.cpu().numpy(), first_frame_w2c.cpu().numpy(), device=dev)
+                reduced[which] = fr
+        if self.fused:
+            from .fused import FusedEngine
+            sizing = meta['fused']
+            cap = max(int(sizing['gaussian_capacity']), int(gaussian_capacity or 0))
+            eng = FusedEngine(params, cam, gaussian_capacity=cap, variables=variables)
+            eng.keep_map_grads = False
+            for fr in (reduced['tracking'], reduced['densify']):        # (the order _start registers them in)
+                if fr is not None:
+                    eng.add_camera(fr.cam)
+            eng.select_camera(cam)
+            eng.set_list_sizing(sizing['list_sizing'])
+            eng.creation_order = bool(sizing['creation_order'])
+            self.engine = eng
+        self.scene_radius = variables['scene_radius']
+        self.params, self.variables, self.cam, self.dev = params, variables, cam, dev
+        self.intrinsics, self.first_frame_w2c = intrinsics, first_frame_w2c
+        self._tracking_frames, self._densify_frames, self._densify0 = reduced['tracking'], reduced['densify'], None
+        self._phase = pipeline._PhaseTimer(dev)
+        self._sync_prepare = reduced['tracking'] is not None or reduced['densify'] is not None
+        self._raw_restored = bool(meta['raw'])
+        est = on_dev(arrays['keyframe_est_w2c'])
+        for i, t in enumerate(ids):
+            if planes is not None:
+                im, d = on_dev(planes[i][0]), on_dev(planes[i][1])
+            else:
+                color, depth = dataset[t][:2]
+                if color.device != dev:
+                    raise ValueError(f"the dataset's frames are on {color.device}, the checkpoint is restored on {dev}")
+                im, d = self._item_planes(color, depth)
+            if tuple(im.shape) != (3, H, W):
+                raise ValueError(f"{where}: frame_size = {(H, W)}, keyframe {t} restored as {tuple(im.shape[1:])}")
+            self.keyframe_list.append({'id': t, 'est_w2c': est[i].clone(), 'color': im, 'depth': d})
+        self.keyframe_time_indices = [int(x) for x in arrays['keyframe_time_indices']]
+        stats = meta['stats']
+        for decided in stats.get('decisions', []):
+            decided['prunes'] = [tuple(p) for p in decided['prunes']]
+        self.stats = stats
+        self.frames_seen = int(meta['frames_seen'])
+        checkpoint.restore_random(arrays, meta['rng'], dev)
+        return self
+
+    def _check_raw_sizes(self):
+        """A restored raw session's first raw frame: the sizes its buffers were just made for are the checkpoint's."""
+        R = self._raw
+        have = dict(full=(int(self.cam.image_height), int(self.cam.image_width)),
+                    tracking=None if self._tracking_frames is None else tuple(self._tracking_frames.size),
+                    densify=None if self._densify_frames is None else tuple(self._densify_frames.size))
+        for which in ('full', 'tracking', 'densify'):
+            if R[which] != have[which]:
+                self._raw = None
+                raise ValueError(f"the raw frame and config['data'] give a {which} size of {R[which]}, the restored session's is {have[which]}")
 
     def _densifies(self, time_idx):
         """Does frame ``time_idx`` read a densification frame (the first frame's point cloud, ``add_new_gaussians`` afterwards)?"""
@@ -178,27 +455,34 @@ class SlamSession:
         sizes come from ``config['data']`` and the reduced frames are derived from the full one.  ``_pose_finite``: the driver's hook
         (``rgbd_slam`` answers the keyframe rule's question from the dataset's host copy of the poses, where it has one)."""
         time_idx = self._admit(pose)
-        dev = color.device
-        if self.fused and dev.type == "cuda" and not self.reference_division and color.dtype == depth.dtype == torch.float32:
-            # one launch (csrc/frameprep.hip P1) and a correctly rounded division: the planes add_raw_frame writes for the same bytes
-            from . import fused
-            im, d = fused.prepare_frame(color, depth)
-        else:
-            im, d = (color.permute(2, 0, 1) / 255).contiguous(), depth.permute(2, 0, 1).contiguous()
-        if time_idx == 0:
-            full_size = (int(color.shape[0]), int(color.shape[1]))
-            tracking = pipeline._reduced_frames("tracking", tracking_item, self.config, full_size, intrinsics)
-            densify = pipeline._reduced_frames("densification", densify_item, self.config, full_size, intrinsics)
-            densify0 = None
-            if densify is not None:
-                densify0 = densify.frame(0, color, depth, densify_item) + (densify.intrinsics,)
-            self._start(dev, im, d, intrinsics, pose, tracking, densify, densify0)
+        im, d = self._item_planes(color, depth)
+        if self.params is None:
+            self._first_item(color, depth, intrinsics, pose, im, d, tracking_item, densify_item)
         tf, df = self._tracking_frames, self._densify_frames
         curr = self._curr_data(time_idx, im, d)
         tracking_curr = curr if tf is None else tf.curr_data(time_idx, color, depth, self.first_frame_w2c, tracking_item)
         densify_curr = curr if (df is None or not self._will_add(time_idx)) else \
             df.curr_data(time_idx, color, depth, self.first_frame_w2c, densify_item)
         return self._step(time_idx, curr, tracking_curr, densify_curr, pose, owned=False, pose_finite=_pose_finite)
+
+    def _item_planes(self, color, depth):
+        """(im [3, H, W] in 0..1, depth [1, H, W]) of a dataset item's colour and depth: the path ``add_frame`` takes (a keyframe
+        restored from a dataset goes through it again)."""
+        if self.fused and color.device.type == "cuda" and not self.reference_division and color.dtype == depth.dtype == torch.float32:
+            # one launch (csrc/frameprep.hip P1) and a correctly rounded division: the planes add_raw_frame writes for the same bytes
+            from . import fused
+            return fused.prepare_frame(color, depth)
+        return (color.permute(2, 0, 1) / 255).contiguous(), depth.permute(2, 0, 1).contiguous()
+
+    def _first_item(self, color, depth, intrinsics, pose, im, d, tracking_item, densify_item):
+        """The set-up on the first dataset item (``im``, ``d``: its planes)."""
+        full_size = (int(color.shape[0]), int(color.shape[1]))
+        tracking = pipeline._reduced_frames("tracking", tracking_item, self.config, full_size, intrinsics)
+        densify = pipeline._reduced_frames("densification", densify_item, self.config, full_size, intrinsics)
+        densify0 = None
+        if densify is not None:
+            densify0 = densify.frame(0, color, depth, densify_item) + (densify.intrinsics,)
+        self._start(color.device, im, d, intrinsics, pose, tracking, densify, densify0)
 
     def add_raw_frame(self, rgb_u8, depth_raw, intrinsics, pose=None, depth_scale=None):
         """What a sensor or a decoder delivers: ``rgb_u8`` [H, W, 3] uint8 and ``depth_raw`` [H', W'] at a size of its own -- float32
@@ -235,9 +519,11 @@ class SlamSession:
                 raise ValueError(f"uint16 depth needs its positive depth_scale (got {depth_scale})")
             scale = float(depth_scale)
         if self._raw is None:
-            if time_idx != 0:
+            if time_idx != 0 and not self._raw_restored:
                 raise RuntimeError("the session started with add_frame: its frames are dataset items")
             self._raw = self._raw_setup(rgb, raw, intrinsics)
+            if self._raw_restored:
+                self._check_raw_sizes()
         R = self._raw
         if (tuple(rgb.shape[:2]), tuple(raw.shape), raw.dtype) != R['shapes']:
             raise ValueError(f"frame {time_idx}: raw sizes {tuple(rgb.shape[:2])}, {tuple(raw.shape)} ({raw.dtype}) differ from the first frame's {R['shapes']}")
@@ -253,7 +539,7 @@ class SlamSession:
             if R[which] is not None and (which == 'tracking' or adds):
                 planes[which] = ingest(which)
         im, d = planes['full']
-        if time_idx == 0:
+        if self.params is None:
             make = lambda which: None if R[which] is None else pipeline._ReducedFrames(        # noqa: E731
                 None, R[which], R['full'], R['k_full'], intrinsics=R['k_' + which])
             tracking, densify = make('tracking'), make('densify')
