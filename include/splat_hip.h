@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define SPLAT_ABI_VERSION 16       /* 16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
+#define SPLAT_ABI_VERSION 17       /* 17: the hole count of a novel view (SplatEvalConfig.holes, SPLAT_EVAL_HOLES);
+                                      16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
                                       15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
                                       14: frame ingest (splat_frame_ingest);
                                       13: frame preparation (splat_frame_prepare);
@@ -675,6 +676,10 @@ int splat_map_duplicate(SplatMapStore *store, const SplatDensifyArgs *args, void
  *     levels, 2 x 2 average pooling between them (an odd dimension is zero-padded in front), weights 0.0448 0.2856 0.3001 0.2363
  *     0.1333 (restated in splatam_amd/slam.py `ms_ssim`; upstream asserts min(H, W) > 160, and so does this).
  * A count of zero valid pixels or a NaN in a plane gives what the torch expressions give (inf / NaN); no special cases.
+ * With cfg->holes (eval_nvs(), /root/reference/utils/eval_helpers.py:708-712) the first-level kernel also counts the HOLES of a novel view,
+ *   pixels with gt_depth > 0 && !(silhouette > sil_thres) -- the frame has depth where the map shows nothing; a NaN silhouette is a hole --,
+ *   into row slot SPLAT_EVAL_HOLES.  The count does not depend on sil_mask or ms_ssim, costs no pass and no launch, and needs the silhouette.
+ *   The reference counts a frame towards its novel-view averages unless holes / (H * W) * 100 > 0.1 in float32.
  * LPIPS is not computed (it needs network weights this library does not carry).
  * ------------------------------------------------------------------------------------------------------------ */
 #define SPLAT_EVAL_ROW 8         /* doubles per output row */
@@ -685,14 +690,16 @@ int splat_map_duplicate(SplatMapStore *store, const SplatDensifyArgs *args, void
 #define SPLAT_EVAL_VALID 4       /* number of pixels with gt_depth > 0 */
 #define SPLAT_EVAL_FLAGGED 5     /* != 0: the render behind this row ran on truncated / unsorted lists (st.status OVERFLOW or STALE_HINT):
                                     re-size the lists and evaluate the frame again (splat_iter_eval only; 0 from splat_eval_metrics) */
+#define SPLAT_EVAL_HOLES 6       /* number of holes when cfg->holes is set, otherwise 0 */
 #define SPLAT_EVAL_LEVELS 5
-#define SPLAT_EVAL_SUMS 40       /* doubles per copy of SplatEvalWorkspace.sums: [0..2] squared error per channel, [3] depth term, [4] valid count,
+#define SPLAT_EVAL_SUMS 40       /* doubles per copy of SplatEvalWorkspace.sums: [0..2] squared error per channel, [3] depth term, [4] valid count, [5] hole count (cfg->holes),
                                     [8 + 6 level + 2 channel] sum of the contrast-structure term, [... + 1] sum of ssim over the level's window positions */
 
 typedef struct SplatEvalConfig {
     float sil_thres;
     int32_t sil_mask;            /* 1: presence * valid weighting (see above) */
     int32_t ms_ssim;             /* 0: PSNR and depth only (one kernel less per level; any frame size) */
+    int32_t holes;               /* != 0: also count the holes into SPLAT_EVAL_HOLES (needs the silhouette) */
 } SplatEvalConfig;
 
 /* The evaluation's own scratch (it borrows nothing of SplatIterWorkspace: map edits and iterations own ssim_maps / sums). */
@@ -708,7 +715,7 @@ int splat_eval_workspace_layout(int32_t width, int32_t height, int32_t flags, Sp
 int splat_eval_workspace_bind(SplatEvalWorkspace *ews, void *slab, const SplatArrayInfo *arrays, int32_t n);
 
 /* The metric kernels alone, on caller-supplied planes (a render of the drop-in rasterizer, or of anything else): rgb [3][H][W],
- * depth [H][W], silhouette [H][W] (may be NULL with sil_mask 0), gt_im [3][H][W], gt_depth [H][W]; out_row: SPLAT_EVAL_ROW device doubles.
+ * depth [H][W], silhouette [H][W] (may be NULL with sil_mask 0 and holes 0), gt_im [3][H][W], gt_depth [H][W]; out_row: SPLAT_EVAL_ROW device doubles.
  * At most six launches (five levels + finish), two without MS-SSIM.  SPLAT_E_INVALID with cfg->ms_ssim when min(width, height) <= 160. */
 int splat_eval_metrics(int32_t width, int32_t height, const float *rgb, const float *depth, const float *silhouette, const float *gt_im,
                        const float *gt_depth, const SplatEvalConfig *cfg, const SplatEvalWorkspace *ews, double *out_row, void *stream);

@@ -18,7 +18,7 @@ SPLAT_MAX_CHANNELS = 8
 SPLAT_GRAD_STRIDE = 16
 SPLAT_COUNTER_STRIDE = 32
 SPLAT_GROUP_TILES = 2
-ABI_VERSION = 16
+ABI_VERSION = 17
 SPLAT_DEPTH_U16, SPLAT_DEPTH_F32 = 0, 1
 SPLAT_VIEW_COLOR, SPLAT_VIEW_DEPTH, SPLAT_VIEW_SILHOUETTE = 0, 1, 2
 
@@ -119,7 +119,7 @@ class SplatArrayInfo(C.Structure):
 
 
 class SplatEvalConfig(C.Structure):
-    _fields_ = [("sil_thres", C.c_float), ("sil_mask", C.c_int32), ("ms_ssim", C.c_int32)]
+    _fields_ = [("sil_thres", C.c_float), ("sil_mask", C.c_int32), ("ms_ssim", C.c_int32), ("holes", C.c_int32)]
 
 
 class SplatEvalWorkspace(C.Structure):
@@ -159,7 +159,7 @@ SPLAT_REPORT_DROT, SPLAT_REPORT_DTRANS, SPLAT_REPORT_LOSS, SPLAT_REPORT_SUMS = 0
 SPLAT_REPORT_FLAG, SPLAT_REPORT_MEDIAN, SPLAT_REPORT_DEPTH_TERM, SPLAT_REPORT_IM_TERM = 12, 13, 14, 15
 SPLAT_REPORT_STATUS, SPLAT_REPORT_FLAGGED, SPLAT_REPORT_SKIPPED = 16, 20, 21
 SPLAT_EVAL_ROW, SPLAT_EVAL_LEVELS, SPLAT_EVAL_SUMS, SPLAT_EVAL_LAYOUT_MS_SSIM = 8, 5, 40, 1
-SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED = 0, 1, 2, 3, 4, 5
+SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
 
 
 def lists_sorted_by_composite(max_list_hint: int) -> bool:

@@ -333,7 +333,7 @@ static bool valid_eval(int32_t width, int32_t height, const SplatEvalConfig *cfg
 
 int splat_eval_metrics(int32_t width, int32_t height, const float *rgb, const float *depth, const float *silhouette, const float *gt_im,
                        const float *gt_depth, const SplatEvalConfig *cfg, const SplatEvalWorkspace *ews, double *out_row, void *stream) {
-    if (!valid_eval(width, height, cfg, ews, out_row) || !rgb || !depth || !gt_im || !gt_depth || (cfg->sil_mask && !silhouette)) return SPLAT_E_INVALID;
+    if (!valid_eval(width, height, cfg, ews, out_row) || !rgb || !depth || !gt_im || !gt_depth || ((cfg->sil_mask || cfg->holes) && !silhouette)) return SPLAT_E_INVALID;
     return check(launch_eval_metrics(width, height, rgb, depth, silhouette, gt_im, gt_depth, *cfg, *ews, nullptr, out_row, (hipStream_t)stream));
 }
 

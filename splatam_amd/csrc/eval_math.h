@@ -22,6 +22,7 @@ constexpr int kEvalTaps = 11;
 constexpr int kEvalSumSq = 0;        // [0..2] sum over ALL pixels of (weighted_im - weighted_gt)^2, per channel
 constexpr int kEvalSumDepth = 3;     // sum of the masked |depth difference|
 constexpr int kEvalSumValid = 4;     // number of pixels with ground-truth depth > 0
+constexpr int kEvalSumHoles = 5;     // number of holes (eval_hole), with SplatEvalConfig.holes; otherwise 0
 constexpr int kEvalSumLevels = 8;    // [8 + 6 level + 2 channel]: sum of cs, + 1: sum of ssim, over the level's (H - 10) x (W - 10) window positions
 constexpr int kEvalSums = 40;
 SPLAT_HD int eval_level_slot(int level, int ch) { return kEvalSumLevels + 6 * level + 2 * ch; }
@@ -76,6 +77,13 @@ SPLAT_HD float eval_depth_term(float rendered, float gt_depth, const EvalPixel &
     return fabsf(sil_mask ? d * m.pf : d) * m.vf;
 }
 
+// A hole of a novel view (eval_nvs(): ~(presence_sil_mask | ~valid_depth_mask)): the frame has depth here and the map does not
+// cover the pixel.  A NaN silhouette compares false and is therefore a hole, as in torch; the rule does not depend on sil_mask.
+SPLAT_HD bool eval_hole(float gt_depth, float sil, float sil_thres) { return gt_depth > 0.f && !(sil > sil_thres); }
+// The frame counts towards the novel-view averages unless holes / (H * W) * 100 > 0.1, evaluated in float32 as torch evaluates
+// the reference's expression (an integer tensor divided by a Python int is a float32 tensor).
+SPLAT_HD bool eval_nvs_valid(long long holes, int W, int H) { return !((float)holes / (float)((long long)W * H) * 100.f > 0.1f); }
+
 // One window position: mu1 = G*x, mu2 = G*y, e11 = G*(x x), e22 = G*(y y), e12 = G*(x y).  Returns ssim, *cs = the
 // contrast-structure term.  IEEE divisions: sigma^2 = e - mu^2 cancels to ~1e-3 of its operands on flat regions, a 1-ulp
 // reciprocal on top of that would show in the level means.
@@ -101,7 +109,7 @@ SPLAT_HD double eval_level_factor(const double *tot, int W, int H, int level, in
     v = v > 0.0 ? v : (v == v ? 0.0 : v);          // relu (a NaN stays)
     return pow(v, eval_level_weight(level));
 }
-// row: 8 doubles, [0] psnr, [1] depth_rmse, [2] depth_l1, [3] ms_ssim (NaN when off), [4] valid count; [5..7] are the caller's.
+// row: 8 doubles, [0] psnr, [1] depth_rmse, [2] depth_l1, [3] ms_ssim (NaN when off), [4] valid count; [5..7] are the caller's ([6]: the hole count, from the totals).
 // psnr: [3] by channel; factor: [3][kEvalLevels] by channel, level (not read when ms_ssim is off)
 SPLAT_HD void eval_row(const double *tot, const double *psnr, const double *factor, bool ms_ssim, double *row) {
     row[0] = (psnr[0] + psnr[1] + psnr[2]) / 3.0;

@@ -3,7 +3,8 @@
 //
 //   Q1 eval_level_kernel<L0>   one pyramid level: 11x11 "valid" window statistics -> sums of cs and ssim per channel, the
 //                              2x2-pooled X and Y of the next level; level 0 forms weighted_im / weighted_gt on the fly from the
-//                              rendered planes, the frame and the two masks, and takes the PSNR and depth sums
+//                              rendered planes, the frame and the two masks, and takes the PSNR and depth sums -- and, with
+//                              SplatEvalConfig.holes, the count of valid-depth pixels the map does not cover
 //   Q2 eval_finish_kernel      totals the copies of the sums, forms the row in double (eval_math.h: eval_finish), zeroes the sums
 //
 // The level kernel runs the window pass of window_sums.h on an UNPADDED window that starts at the tile's origin (a tile's 32 x 24 outputs
@@ -28,7 +29,7 @@ struct LevelArgs {
     double *sums;                   // [SPLAT_ITER_SUM_COPIES][SPLAT_EVAL_SUMS]
     int W, H, PW, PH, level;
     float sil_thres;
-    int sil_mask;
+    int sil_mask, holes;
     float win[kEvalTaps];
 };
 
@@ -48,7 +49,7 @@ __device__ __forceinline__ f2 level_pixel(const LevelArgs &a, const float *X, co
 template <bool L0, bool SSIM>
 __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
     __shared__ WindowLds<2> S;                      // vertical sums of (x, y), (x x, y y) and x y
-    __shared__ double s_part[5 * (kBlock / 64)];
+    __shared__ double s_part[6 * (kBlock / 64)];
     float g[kWinTaps];
 #pragma unroll
     for (int k = 0; k < kWinTaps; ++k) g[k] = a.win[k];
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
     const size_t HW = (size_t)H * W;
     const float *X = a.x + ch * HW, *Y = a.y + ch * HW;
     const bool sil_mask = a.sil_mask != 0;
-    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};       // squared error, depth term, valid count (owned pixels); cs, ssim (owned window positions)
+    float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // squared error, depth term, valid count (owned pixels); cs, ssim (owned window positions); holes (owned pixels)
     {   // vertical pass: thread = (window column, group of kWinTR output rows); the thread's first kWinTR rows of the tile's first kWinTW
         // columns are pixels the tile owns
         const int grp = tid / kWinCols, col = tid - grp * kWinCols;
@@ -85,6 +86,7 @@ __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
                         const float term = eval_depth_term(a.depth[off], a.gt_depth[off], m, sil_mask);
                         acc[1] += in ? term : 0.f;
                         acc[2] += in ? m.vf : 0.f;
+                        if (a.holes) acc[5] += in && eval_hole(a.gt_depth[off], a.sil[off], a.sil_thres) ? 1.f : 0.f;
                     }
                 }
             }
@@ -137,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void eval_level_kernel(LevelArgs a) {
     double *const copy = sum_copy(a.sums, SPLAT_EVAL_SUMS);
     const int base = eval_level_slot(a.level, ch);
     if constexpr (L0) {
-        block_sums_to<5, double>(copy, acc, s_part, [&](int k) { return k == 0 ? kEvalSumSq + ch : k == 1 ? kEvalSumDepth : k == 2 ? kEvalSumValid : base + k - 3; });
+        block_sums_to<6, double>(copy, acc, s_part, [&](int k) { return k == 0 ? kEvalSumSq + ch : k == 1 ? kEvalSumDepth : k == 2 ? kEvalSumValid : k == 5 ? kEvalSumHoles : base + k - 3; });
     } else {
         const float v[2] = {acc[3], acc[4]};
         block_sums_to<2, double>(copy, v, s_part, [&](int k) { return base + k; });
@@ -177,7 +179,8 @@ __global__ __launch_bounds__(64 * kFinishWaves) void eval_finish_kernel(double *
         double r[SPLAT_EVAL_ROW];
         eval_row(s_tot, s_psnr, s_factor, ms_ssim != 0, r);
         r[5] = status && (status[SPLAT_STATUS_OVERFLOW] != 0 || status[SPLAT_STATUS_STALE_HINT] != 0) ? 1.0 : 0.0;
-        r[6] = r[7] = 0.0;
+        r[6] = s_tot[kEvalSumHoles];                // (0 without SplatEvalConfig.holes: nothing was added)
+        r[7] = 0.0;
         for (int k = 0; k < SPLAT_EVAL_ROW; ++k) row[k] = r[k];
     }
 }
@@ -197,6 +200,7 @@ hipError_t launch_eval_metrics(int W, int H, const float *rgb, const float *dept
     a.sums = ews.sums;
     a.sil_thres = cfg.sil_thres;
     a.sil_mask = cfg.sil_mask;
+    a.holes = cfg.holes;
     a.W = W; a.H = H;
     if (!cfg.ms_ssim) {
         hipLaunchKernelGGL((eval_level_kernel<true, false>), xcd_tile_grid(W, H), dim3(kBlock), 0, s, a);

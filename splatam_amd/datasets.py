@@ -4,11 +4,13 @@
 here                                           reference (restated; nothing is copied)
 =============================================  =============================================
 ``load_dataset_config``                        datasets/gradslam_datasets/dataconfig.py:5-54 (YAML with recursive ``inherit_from``)
-``get_dataset``                                scripts/splatam.py:40-64 (replica, replicav2, tum, scannet, nerfcapture)
+``get_dataset``                                scripts/splatam.py:40-64 (replica, replicav2, tum, scannet, scannetpp, nerfcapture)
 ``RGBDDataset``                                datasets/gradslam_datasets/basedataset.py:105-341
-``ReplicaDataset`` / ``ReplicaV2Dataset``      datasets/gradslam_datasets/replica.py
+``ReplicaDataset`` / ``ReplicaV2Dataset``      datasets/gradslam_datasets/replica.py (ReplicaV2: the train split and the held-out one)
 ``TUMDataset``                                 datasets/gradslam_datasets/tum.py (nearest-timestamp association, 1/32 s thinning)
 ``ScannetDataset``                             datasets/gradslam_datasets/scannet.py
+``ScannetPPDataset``                           datasets/gradslam_datasets/scannetpp.py (``dslr/``: split lists, nerfstudio transforms,
+                                               undistorted images and depths; the train split and the held-out one)
 ``NeRFCaptureDataset``                         datasets/gradslam_datasets/nerfcapture.py (``transforms.json``, ``rgb/*``, ``depth/*``)
 ``ingest_planes_cpu`` (from ``frames``)        scripts/iphone_demo.py:218-243 (a live frame's bytes and depth at the loop's sizes; the
                                                host form of ``fused.ingest_planes``, which ``session.SlamSession.add_raw_frame`` runs)
@@ -16,6 +18,8 @@ here                                           reference (restated; nothing is c
 
 ``dataset[i]`` is ``(color [H, W, 3] float32 in 0..255, depth [H, W, 1] float32 in metres, intrinsics [4, 4], pose [4, 4])`` on
 ``device``, poses camera-to-world relative to the first retained frame: what ``pipeline.rgbd_slam`` and ``evaluation.evaluate`` take.
+A held-out split (``use_train_split=False`` of ScanNet++ and ReplicaV2) starts with the FIRST TRAINING FRAME, the map's origin, so that
+every held-out pose is relative to it: what ``evaluation.evaluate_novel_views`` takes.
 
 Where the reference decodes to float64, resizes twice with OpenCV on one core and uploads floats, once per resolution, this decodes
 ONCE with PIL (ahead of the loop, on a few threads, into reused pinned buffers), uploads the raw bytes (4 MB at 1200 x 680 instead of
@@ -25,7 +29,7 @@ fetched.  With ``device="cpu"`` the same arithmetic runs in torch on the host (`
 ones as csrc/frame_math.h restates them; they are not pinned against OpenCV, which is not available here.
 
 Not supported (NotImplementedError): lens undistortion (``camera_params.distortion``; every data config the reference ships has it
-commented out, and cv2.undistort cannot be pinned here), ``.exr`` depth, the ReplicaV2 test split, embeddings.
+commented out, and cv2.undistort cannot be pinned here), ``.exr`` depth, embeddings.
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ import torch
 from . import slam
 from .frames import ingest_frame_cpu, ingest_planes_cpu  # noqa: F401  (the host forms of fused.ingest_frame / ingest_planes)
 
-SUPPORTED = ("replica", "replicav2", "tum", "scannet", "nerfcapture")
+SUPPORTED = ("replica", "replicav2", "tum", "scannet", "scannetpp", "nerfcapture")
 MAX_WORKERS = 4             # decode threads (PIL releases the GIL while it inflates); never sized by the host's core count
 MAX_DEPTH = 4               # frames decoded ahead
 
@@ -340,23 +344,35 @@ class ReplicaDataset(RGBDDataset):
 
 
 class ReplicaV2Dataset(RGBDDataset):
-    """The train split: ``<basedir>/<sequence>/imap/00/rgb/rgb_*.png``, ``depth/depth_*.png``, ``traj_w_c.txt``."""
+    """The train split: ``<basedir>/<sequence>/imap/00/rgb/rgb_*.png``, ``depth/depth_*.png``, ``traj_w_c.txt``.  The held-out split
+    (``use_train_split=False``): the first training frame (``imap/00/rgb/rgb_0.png``, ``depth/depth_0.png``, line 0 of its trajectory)
+    followed by the frames of ``imap/01`` with the first lines of ``imap/01/traj_w_c.txt``."""
 
     def __init__(self, config_dict, basedir, sequence, use_train_split=True, stride=None, start=0, end=-1, desired_height=480,
                  desired_width=640, **kwargs):
-        if not use_train_split:
-            raise NotImplementedError("the ReplicaV2 test split (use_train_split=False) is not supported")
-        self.input_folder = os.path.join(basedir, sequence, "imap", "00")
+        self.use_train_split = bool(use_train_split)
+        self.train_input_folder = os.path.join(basedir, sequence, "imap", "00")
+        self.train_pose_path = os.path.join(self.train_input_folder, "traj_w_c.txt")
+        self.input_folder = self.train_input_folder if self.use_train_split else os.path.join(basedir, sequence, "imap", "01")
         self.pose_path = os.path.join(self.input_folder, "traj_w_c.txt")
+        if not os.path.isdir(self.input_folder) and not self.use_train_split:
+            # (the exception callers of the earlier releases caught for use_train_split=False, kept for a sequence that has no such split)
+            raise NotImplementedError(f"{self.input_folder}: this sequence has no held-out split (use_train_split=False reads imap/01)")
         super().__init__(config_dict, stride=stride, start=start, end=end, desired_height=desired_height, desired_width=desired_width,
                          **kwargs)
 
     def _filepaths(self):
-        return (natural_sorted(glob.glob(os.path.join(self.input_folder, "rgb", "rgb_*.png"))),
-                natural_sorted(glob.glob(os.path.join(self.input_folder, "depth", "depth_*.png"))))
+        color = natural_sorted(glob.glob(os.path.join(self.input_folder, "rgb", "rgb_*.png")))
+        depth = natural_sorted(glob.glob(os.path.join(self.input_folder, "depth", "depth_*.png")))
+        if not self.use_train_split:
+            color.insert(0, os.path.join(self.train_input_folder, "rgb", "rgb_0.png"))
+            depth.insert(0, os.path.join(self.train_input_folder, "depth", "depth_0.png"))
+        return color, depth
 
     def _load_poses(self, num_imgs):
-        return _read_trajectory(self.pose_path, num_imgs)
+        if self.use_train_split:
+            return _read_trajectory(self.pose_path, num_imgs)
+        return _read_trajectory(self.train_pose_path, 1) + _read_trajectory(self.pose_path, num_imgs - 1)
 
 
 class ScannetDataset(RGBDDataset):
@@ -442,6 +458,79 @@ class TUMDataset(RGBDDataset):
         return out
 
 
+def _read_json(path):
+    import json
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path}: no such file")
+    with open(path, "r") as f:
+        return json.load(f)
+
+
+class ScannetPPDataset(RGBDDataset):
+    """A ScanNet++ scene's DSLR capture, ``<basedir>/<sequence>/dslr/``: ``train_test_lists.json`` (``{"train": [...], "test": [...]}``),
+    ``nerfstudio/transforms_undistorted.json`` (``h``, ``w``, ``fl_x``, ``fl_y``, ``cx``, ``cy``; ``frames[]`` for the train names and
+    ``test_frames[]`` for the held-out ones, each with ``file_path``, a camera-to-world ``transform_matrix`` in OpenGL axes and
+    ``is_bad``), colour in ``undistorted_images/<name>``, depth in ``undistorted_depths/<name with .JPG replaced by .png>`` with 1000
+    units per metre.  Frames come in the ORDER OF THE LIST (not sorted); ``ignore_bad`` drops the entries marked ``is_bad``.  Poses are
+    ``P @ c2w @ P.T`` with P = diag(1, -1, -1, 1).
+
+    ``use_train_split=False``: item 0 is the first name of the TRAIN list (looked up in ``frames[]``, kept whatever its ``is_bad``
+    says), then the test names (looked up in ``test_frames[]``): with ``relative_pose`` every held-out pose is relative to the first
+    training frame, the origin of a map built on the train split.  The camera comes from the capture: ``config_dict`` is accepted
+    for ``get_dataset`` and not read."""
+
+    def __init__(self, config_dict=None, basedir=None, sequence=None, ignore_bad=False, use_train_split=True, stride=None, start=0,
+                 end=-1, desired_height=1168, desired_width=1752, **kwargs):
+        self.input_folder = os.path.join(basedir, sequence)
+        self.ignore_bad, self.use_train_split = bool(ignore_bad), bool(use_train_split)
+        self.lists_path = os.path.join(self.input_folder, "dslr", "train_test_lists.json")
+        self.cams_path = os.path.join(self.input_folder, "dslr", "nerfstudio", "transforms_undistorted.json")
+        self.train_test_split = _read_json(self.lists_path)
+        self.cams_metadata = meta = _read_json(self.cams_path)
+        own = {"dataset_name": "scannetpp",
+               "camera_params": {"png_depth_scale": 1000.0, "image_height": meta["h"], "image_width": meta["w"],
+                                 "fx": meta["fl_x"], "fy": meta["fl_y"], "cx": meta["cx"], "cy": meta["cy"]}}
+        super().__init__(own, stride=1 if stride is None else stride, start=start, end=end, desired_height=desired_height,
+                         desired_width=desired_width, **kwargs)
+
+    def _entries(self, key):
+        return {frame["file_path"]: frame for frame in self.cams_metadata.get(key, [])}
+
+    def _filepaths(self):
+        base = os.path.join(self.input_folder, "dslr")
+        flip = np.diag([1.0, -1.0, -1.0, 1.0])
+        color_paths, depth_paths, self._poses = [], [], []
+
+        def take(name, entries, key, droppable):
+            if name not in entries:
+                raise ValueError(f"{self.cams_path}: no entry with file_path {name!r} in {key}[] ({len(entries)} listed), "
+                                 f"named by {self.lists_path}")
+            if droppable and self.ignore_bad and entries[name]["is_bad"]:
+                return
+            color_paths.append(os.path.join(base, "undistorted_images", name))
+            depth_paths.append(os.path.join(base, "undistorted_depths", name.replace(".JPG", ".png")))
+            c2w = np.asarray(entries[name]["transform_matrix"], dtype=np.float64).astype(np.float32).astype(np.float64).reshape(4, 4)
+            self._poses.append((flip @ c2w @ flip.T).astype(np.float32))
+
+        for split in ("train",) if self.use_train_split else ("train", "test"):
+            if split not in self.train_test_split:
+                raise ValueError(f"{self.lists_path}: no {split!r} list")
+        if self.use_train_split:
+            names, entries, key = self.train_test_split["train"], self._entries("frames"), "frames"
+        else:
+            train = self.train_test_split["train"]
+            if not train:
+                raise ValueError(f"{self.lists_path}: the train list is empty (its first frame is the origin of the held-out poses)")
+            take(train[0], self._entries("frames"), "frames", droppable=False)
+            names, entries, key = self.train_test_split["test"], self._entries("test_frames"), "test_frames"
+        for name in names:
+            take(name, entries, key, droppable=True)
+        return color_paths, depth_paths
+
+    def _load_poses(self, num_imgs):
+        return self._poses
+
+
 class NeRFCaptureDataset(RGBDDataset):
     """A capture of the NeRFCapture app as the reference's demo writes it: ``<basedir>/<sequence>/transforms.json`` (``w``, ``h``,
     ``fl_x``, ``fl_y``, ``cx``, ``cy`` and ``frames[]`` with ``file_path`` = ``rgb/<name>`` and a camera-to-world ``transform_matrix``
@@ -483,7 +572,7 @@ class NeRFCaptureDataset(RGBDDataset):
 
 
 _DATASETS = {"replica": ReplicaDataset, "replicav2": ReplicaV2Dataset, "tum": TUMDataset, "scannet": ScannetDataset,
-             "nerfcapture": NeRFCaptureDataset}
+             "scannetpp": ScannetPPDataset, "nerfcapture": NeRFCaptureDataset}
 
 
 def get_dataset(config_dict, basedir, sequence, **kwargs):

@@ -15,6 +15,10 @@ Kept from the reference, quirks included (each is pinned by tests/golden/eval_re
 splat_view_finish (csrc/view.hip); the depth pictures carry matplotlib's jet, not ``cv2.COLORMAP_JET`` (``splatam_amd.view``).
 Not kept: the plots, and LPIPS -- it needs AlexNet weights that this package does not carry; the result says
 ``lpips: None`` instead of a made-up number.  A failure in the trajectory error is raised, not replaced by 100.0.
+
+``evaluate_novel_views`` is the reference's ``eval_nvs`` (utils/eval_helpers.py:626-825) in the same manner: the finished map scored
+at HELD-OUT poses (a dataset's test split, whose item 0 is the first training frame), one ``FusedEngine.evaluate_view`` per frame,
+the table read once; frames with holes -- pixels that have depth where the map shows nothing -- stay out of the averages.
 """
 from __future__ import annotations
 
@@ -93,9 +97,12 @@ class _FrameSaver:
     SLOTS, WORKERS = 4, 4
     NAMES = (("rendered_rgb", "gs"), ("rendered_depth", "gs"), ("rgb", "gt"), ("depth", "gt"))
 
-    def __init__(self, eval_dir, dev, H, W):
+    def __init__(self, eval_dir, dev, H, W, rendered_prefix="gs"):
         from concurrent.futures import ThreadPoolExecutor
         from .view import jet_lut
+        if torch.device(dev).type != "cuda":
+            raise ValueError(f"save_frames forms the pictures on a HIP device (the frames are on {dev})")
+        self.names = tuple((d, rendered_prefix if d.startswith("rendered_") else p) for d, p in self.NAMES)    # (eval_nvs: splatam_%04d.png)
         self.dirs = [os.path.join(eval_dir, d) for d, _ in self.NAMES]
         for d in self.dirs:
             os.makedirs(d, exist_ok=True)
@@ -127,7 +134,7 @@ class _FrameSaver:
 
         def write(i):
             event.synchronize()
-            Image.fromarray(host[i]).save(os.path.join(self.dirs[i], f"{self.NAMES[i][1]}_{t:04d}.png"))
+            Image.fromarray(host[i]).save(os.path.join(self.dirs[i], f"{self.names[i][1]}_{t:04d}.png"))
         slot['jobs'] = self.by_frame[t] = [self.pool.submit(write, i) for i in range(4)]
 
     def close(self):
@@ -247,4 +254,164 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
         os.makedirs(eval_dir, exist_ok=True)
         for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')):
             np.savetxt(os.path.join(eval_dir, name), out[k])
+    return out
+
+
+# ---------------------------------------------------------------------- novel views (the reference's eval_nvs)
+def novel_view_indices(num_frames, eval_every=1):
+    """Held-out indices k = t - 1 the reference scores among items 1 .. num_frames - 1 of a test split (item 0 is the first training
+    frame): k = 0 and every k with (k + 1) % eval_every == 0."""
+    return [k for k in range(max(int(num_frames) - 1, 0)) if k == 0 or (k + 1) % int(eval_every) == 0]
+
+
+def percent_holes(holes, height, width):
+    """``holes / (H W) * 100`` as torch evaluates the reference's expression: an integer count divided by a Python int is float32."""
+    return np.asarray(holes).astype(np.float32) / np.float32(int(height) * int(width)) * np.float32(100)
+
+
+def _rigid_inverse(m):
+    """inv of a rigid [4, 4] as [R^T, -R^T t]: elementwise work that enqueues without a host read (``torch.linalg.inv`` reads its status)."""
+    rt = m[:3, :3].t()
+    return torch.cat([torch.cat([rt, -(rt @ m[:3, 3:4])], dim=1), m[3:4]], dim=0)        # (the last row of a rigid matrix is its own)
+
+
+def _mirror_nvs_row(params, curr_data, gt_w2c, sil_thres, sil_mask, ms_ssim):
+    """One held-out frame by the torch mirror, rendered the way eval_nvs renders it: the centres are moved by ``gt_w2c`` (and for an
+    anisotropic map the rotations composed with its quaternion), then seen through the first frame's camera and depth row.  Returns
+    (row, planes [5, H, W]: r, g, b, depth, silhouette)."""
+    with torch.no_grad():
+        p = {k: v.detach() for k, v in params.items()}
+        pts = p['means3D']
+        pts4 = torch.cat((pts, torch.ones_like(pts[:, :1])), dim=1)
+        tg = {'means3D': (gt_w2c @ pts4.T).T[:, :3]}
+        if p['log_scales'].shape[1] == 1:
+            tg['unnorm_rotations'] = p['unnorm_rotations']
+        else:
+            q = F.normalize(slam.matrix_to_quaternion(gt_w2c[:3, :3]).unsqueeze(0))
+            tg['unnorm_rotations'] = slam.quat_mult(q, F.normalize(p['unnorm_rotations']))
+        depth_sil, _, _ = slam.Renderer(raster_settings=curr_data['cam'])(**slam.transformed_params2depthplussilhouette(p, curr_data['w2c'], tg))
+        im, _, _ = slam.Renderer(raster_settings=curr_data['cam'])(**slam.transformed_params2rendervar(p, tg))
+        m = slam.eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=ms_ssim)
+        holes = (~((depth_sil[1] > sil_thres) | ~(curr_data['depth'][0] > 0))).sum()
+    nan = torch.full((), float("nan"))
+    zero = torch.zeros((), dtype=torch.float64)
+    vals = [m['psnr'], m['depth_rmse'], m['depth_l1'], m['ms_ssim'] if ms_ssim else nan, m['valid'], zero, holes, zero]
+    return torch.stack([v.detach().double().cpu() for v in vals]), torch.cat([im, depth_sil[0:2]]).contiguous()
+
+
+def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every=1, engine=None, eval_dir=None,
+                         ms_ssim=True, save_frames=False):
+    """Novel-view synthesis of a finished map, with the semantics of the reference's ``eval_nvs``.  ``dataset`` is a held-out split:
+    item 0 is the first training frame -- it only supplies ``first_frame_w2c = inv(pose_0)`` and the camera, and is not scored --,
+    items 1 .. num_frames - 1 are the held-out frames; index k = t - 1 is scored when ``k == 0 or (k + 1) % eval_every == 0``.  The
+    effective world-to-camera of item t is ``first_frame_w2c @ inv(pose_t)`` (eval_nvs moves the Gaussians by ``inv(pose_t)`` and
+    looks at them through the camera and the depth row of ``first_frame_w2c``).  Mask variant and metrics as in ``evaluate`` (the
+    "RMSE" that equals L1 included); ``params`` needs no trajectory.
+
+    A frame is VALID unless ``holes / (H W) * 100 > 0.1`` (in float32, as torch evaluates it), holes = pixels with depth > 0 whose
+    silhouette is not above ``sil_thres``.  Returns the dict of ``evaluate`` without ``ate_rmse`` -- ``frames`` are the scored k,
+    the per-frame arrays hold ALL scored frames, the four averages run over the VALID frames only (NaN when there is none) -- and
+    ``holes`` (int64 per frame), ``percent_holes`` (float32), ``valid_nvs_frames`` (bool), ``lpips: None``.  With ``eval_dir``:
+    psnr.txt, rmse.txt, l1.txt, ssim.txt and valid_nvs_frames.npy; with ``save_frames`` also the four picture directories with
+    ``splatam_%04d.png`` (rendered) and ``gt_%04d.png``, numbered by k.
+
+    ``engine``: a ``FusedEngine`` that holds the map, ``None`` (a throw-away one) or ``"mirror"`` (torch, runs without a GPU: the
+    parity target).  On an engine a view camera of the frame's size is moved from pose to pose (``evaluate_view``: the engine's own
+    camera, map and optimiser state stay untouched; the poses must be rigid); host synchronisation as in ``evaluate``: one read to
+    learn the view's list statistics on the first held-out pose, every frame enqueued, one table read, flagged rows again."""
+    from .fused import FusedEngine, _intrinsics4
+    t_start = time.perf_counter()
+    num_frames = min(int(num_frames), len(dataset))
+    if num_frames < 1:
+        raise ValueError("a held-out split starts with the first training frame: the dataset is empty")
+    frames = novel_view_indices(num_frames, eval_every)
+    sil_mask = uses_silhouette_mask(mapping_iters, add_new_gaussians)
+    color0, depth0, intrinsics, pose0 = _frame(dataset, 0)
+    dev = depth0.device
+    H, W = int(color0.shape[1]), int(color0.shape[2])
+    first_frame_w2c = torch.linalg.inv(pose0).to(dev).float().contiguous()
+    mirror = isinstance(engine, str)
+    if mirror and engine != "mirror":
+        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {engine!r})")
+    if not mirror and engine is not None and not isinstance(engine, FusedEngine):
+        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {type(engine).__name__})")
+    if ms_ssim and min(H, W) <= 160:
+        raise ValueError(f"MS-SSIM needs frames with min(H, W) > 160 (got {(H, W)}); pass ms_ssim=False")
+    if save_frames and eval_dir is None:
+        raise ValueError("save_frames needs eval_dir")
+    cam = None
+    if mirror or engine is None:
+        cam = slam.setup_camera(W, H, intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
+    if engine is None:
+        engine = FusedEngine({k: v.detach().float().contiguous() for k, v in params.items()}, cam)
+    k_host = _intrinsics4(intrinsics)                                     # (on the host once: a device matrix would be read per view)
+
+    def curr(t, color, depth):
+        return {'cam': cam, 'im': color, 'depth': depth, 'id': t, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
+
+    repeated = []
+    row_of = {k: i for i, k in enumerate(frames)}
+    saver = _FrameSaver(eval_dir, dev, H, W, rendered_prefix="splatam") if save_frames else None
+    with saver if saver is not None else contextlib.nullcontext():
+        if mirror:
+            rows = []
+            for t in range(1, num_frames):
+                if t - 1 not in row_of:
+                    continue
+                color, depth, _, pose = _frame(dataset, t)
+                row, planes = _mirror_nvs_row(params, curr(t, color, depth), torch.linalg.inv(pose), sil_thres, sil_mask, ms_ssim)
+                rows.append(row)
+                if saver is not None:
+                    saver.save(t - 1, planes, color, depth)
+            host = torch.stack(rows).numpy() if rows else np.zeros((0, _capi.SPLAT_EVAL_ROW))
+        else:
+            view = engine.view_camera(W, H)
+            table = torch.zeros(max(len(frames), 1), _capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)[:len(frames)]
+            learnt = False
+            for t in range(1, num_frames):
+                if t - 1 not in row_of:
+                    continue
+                color, depth, _, pose = _frame(dataset, t)
+                w2c = (first_frame_w2c @ _rigid_inverse(pose.to(dev).float())).contiguous()
+                if not learnt:                                                # (one read: sizes the view's list buckets for the map as it is)
+                    engine.relearn_lists(curr(t, color, depth), 0, view=view, w2c=w2c, intrinsics=k_host)
+                    learnt = True
+                engine.evaluate_view(view, w2c, curr(t, color, depth), table[row_of[t - 1]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim,
+                                     holes=True, intrinsics=k_host)
+                if saver is not None:
+                    saver.save(t - 1, view.camera.buf['out6'], color, depth)
+            host = _read_table(table)
+            for i, k in enumerate(frames):
+                if host[i, _capi.SPLAT_EVAL_FLAGGED] == 0:
+                    continue
+                # this view's lists outgrew the buckets learnt on the first held-out pose: re-learn on this view and evaluate it again
+                repeated.append(k)
+                color, depth, _, pose = _frame(dataset, k + 1)
+                w2c = (first_frame_w2c @ _rigid_inverse(pose.to(dev).float())).contiguous()
+                for name in ('status', 'tile_count', 'group_count'):
+                    view.camera.buf[name].zero_()
+                engine.relearn_lists(curr(k + 1, color, depth), 0, view=view, w2c=w2c, intrinsics=k_host)
+                again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
+                engine.evaluate_view(view, w2c, curr(k + 1, color, depth), again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=True,
+                                     intrinsics=k_host)
+                host[i] = _read_table(again)
+                if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
+                    raise RuntimeError(f"held-out frame {k}: the per-tile lists could not be sized for its evaluation render")
+                if saver is not None:
+                    saver.save(k, view.camera.buf['out6'], color, depth)
+    t_metrics = time.perf_counter() - t_start
+    holes = np.rint(host[:, _capi.SPLAT_EVAL_HOLES]).astype(np.int64)
+    percent = percent_holes(holes, H, W)
+    valid = ~(percent > np.float32(0.1))
+    out = {'frames': list(frames), 'eval_s': t_metrics, 'eval_ms_per_frame': 1e3 * t_metrics / max(len(frames), 1), 'psnr': host[:, _capi.SPLAT_EVAL_PSNR].copy(),
+           'depth_rmse': host[:, _capi.SPLAT_EVAL_DEPTH_RMSE].copy(), 'depth_l1': host[:, _capi.SPLAT_EVAL_DEPTH_L1].copy(),
+           'ms_ssim': host[:, _capi.SPLAT_EVAL_MS_SSIM].copy(), 'valid_pixels': host[:, _capi.SPLAT_EVAL_VALID].copy(), 'lpips': None,
+           'repeated': repeated, 'sil_mask': bool(sil_mask), 'holes': holes, 'percent_holes': percent, 'valid_nvs_frames': valid}
+    for k in ('psnr', 'depth_rmse', 'depth_l1', 'ms_ssim'):
+        out['avg_' + k] = float(out[k][valid].mean()) if valid.any() else float("nan")       # (numpy's mean of nothing, without its warning)
+    if eval_dir is not None:
+        os.makedirs(eval_dir, exist_ok=True)
+        for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')):
+            np.savetxt(os.path.join(eval_dir, name), out[k])
+        np.save(os.path.join(eval_dir, "valid_nvs_frames.npy"), valid)
     return out

@@ -575,9 +575,28 @@ class FusedEngine:
             _capi.check(self.L.splat_iter_eval(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(cfg), C.byref(ws), C.byref(ews),
                                                out_row.data_ptr(), self._stream()), "splat_iter_eval")
 
-    def evaluate_metrics(self, rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True):
+    def evaluate_metrics(self, rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True, holes=False):
         """``evaluate_metrics`` of this module (the metric kernels alone, on caller-supplied planes of any size)."""
-        return evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
+        return evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=holes)
+
+    def evaluate_view(self, view, w2c, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True, holes=True, intrinsics=None):
+        """A held-out frame scored at ITS pose (the per-frame part of the reference's eval_nvs()): ``render_view(view, w2c=w2c,
+        rgb8=False)`` -- the view camera moves to ``w2c`` (float32 [4, 4] on the device: the frame's effective world-to-camera), the
+        unchanged splat_iter_render composites the map there -- followed by ``evaluate_metrics`` of the view's planes against
+        ``curr_data['im']`` / ``['depth']`` (of the view's size) into ``out_row``, with the hole count (``holes``) in slot
+        SPLAT_EVAL_HOLES and the view's truncation status in slot SPLAT_EVAL_FLAGGED.  ``intrinsics``: the view's (default
+        ``curr_data['intrinsics']``, which must then be on the host).  Nothing is read on the host and nothing is allocated after the
+        view's first call; the current camera, the map, its Adam state and ``variables`` stay untouched (``render_view``).  Returns the
+        ``ViewImage`` (its ``out6`` holds the planes the row was formed from)."""
+        _check_eval_row(out_row, self.dev)
+        for name, t, c in (("im", curr_data['im'], 3), ("depth", curr_data['depth'], 1)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, view.H, view.W)):
+                raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {view.H}, {view.W}] on {self.dev}")
+        img = self.render_view(view, w2c=w2c, intrinsics=curr_data['intrinsics'] if intrinsics is None else intrinsics, rgb8=False)
+        o = img.out6
+        evaluate_metrics(o[0:3], o[3], o[4], curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=holes)
+        out_row[_capi.SPLAT_EVAL_FLAGGED:_capi.SPLAT_EVAL_FLAGGED + 1].copy_(img.truncated)     # (after the finish kernel, which leaves 0 there)
+        return img
 
     def lists_known(self, curr_data=None):
         """The per-tile list statistics (bucket stride, longest list) are usable for the map as it is: an edit kept them (_set_rows).
@@ -586,10 +605,18 @@ class FusedEngine:
             self._check_cam(curr_data)
         return self._camera.tile_stride > 0 and self._camera.max_list_hint > 0
 
-    def relearn_lists(self, curr_data, time_idx):
+    def relearn_lists(self, curr_data, time_idx, view=None, w2c=None, intrinsics=None):
         """One probe render with exact lists + ``check_overflow()``: sizes the list capacity and the per-tile buckets
         for the map as it is now (call after an edit that did not keep them -- ``lists_known()``; one D2H read).
-        Of the camera of ``curr_data``."""
+        Of the camera of ``curr_data`` -- or, with ``view`` (a ``view_camera``), of that view at pose ``w2c`` (``render_view`` with
+        ``intrinsics``, default ``curr_data['intrinsics']``, and ``view.check_overflow()``; ``time_idx`` is then not read)."""
+        if view is not None:
+            view.camera.tile_stride, view.camera.max_list_hint = 0, 0
+            for _ in range(3):
+                self.render_view(view, w2c=w2c, intrinsics=curr_data['intrinsics'] if intrinsics is None else intrinsics, rgb8=False)
+                if not view.check_overflow():
+                    return
+            raise RuntimeError("per-tile lists could not be sized")
         self._check_cam(curr_data)
         self._camera.tile_stride, self._camera.max_list_hint = 0, 0
         for _ in range(3):
@@ -1497,9 +1524,9 @@ def eval_workspace(dev, width, height, ms_ssim):
     return ews, sums
 
 
-def _eval_config(sil_thres, sil_mask, ms_ssim):
+def _eval_config(sil_thres, sil_mask, ms_ssim, holes=False):
     c = _capi.SplatEvalConfig()
-    c.sil_thres, c.sil_mask, c.ms_ssim = float(sil_thres), int(bool(sil_mask)), int(bool(ms_ssim))
+    c.sil_thres, c.sil_mask, c.ms_ssim, c.holes = float(sil_thres), int(bool(sil_mask)), int(bool(ms_ssim)), int(bool(holes))
     return c
 
 
@@ -1509,11 +1536,12 @@ def _check_eval_row(out_row, dev):
         raise RuntimeError(f"out_row must be a contiguous float64 tensor of {_capi.SPLAT_EVAL_ROW} elements on {dev}")
 
 
-def evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True):
+def evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True, holes=False):
     """The metric kernels alone: ``rgb`` [3,H,W], ``depth`` [1,H,W] or [H,W], ``sil`` [H,W] (the two renders of the drop-in
     rasterizer, say) against ``curr_data['im']`` / ``['depth']``, all float32 on one CUDA/HIP device; the row
-    (include/splat_hip.h SPLAT_EVAL_*; slot 5 is 0) goes to ``out_row`` (8 float64 on that device).  Enqueues on the current
-    stream and reads nothing.  Returns the evaluation's sums buffer, whose last row holds the frame's totals once the kernels have
+    (include/splat_hip.h SPLAT_EVAL_*; slot 5 is 0) goes to ``out_row`` (8 float64 on that device).  ``holes``: the same first-level
+    kernel also counts the pixels with ``gt_depth > 0 and not sil > sil_thres`` (the holes of a novel view, eval_nvs()) into slot
+    SPLAT_EVAL_HOLES, which is 0 otherwise; the other slots do not depend on it.  Enqueues on the current stream and reads nothing.  Returns the evaluation's sums buffer, whose last row holds the frame's totals once the kernels have
     run (level means = totals / window positions).  MS-SSIM needs min(H, W) > 160 (RuntimeError otherwise, before any launch)."""
     if not isinstance(rgb, torch.Tensor) or rgb.device.type != "cuda":
         raise RuntimeError("evaluate_metrics needs CUDA/HIP tensors; the HIP library has no CPU path")
@@ -1528,7 +1556,7 @@ def evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=Fa
             raise RuntimeError(f"{name} must be a float32 tensor of {n} x {H} x {W} elements on {dev} (got {got})")
         planes.append(t if t.is_contiguous() else t.contiguous())
     ews, sums = eval_workspace(dev, W, H, ms_ssim)
-    cfg = _eval_config(sil_thres, sil_mask, ms_ssim)
+    cfg = _eval_config(sil_thres, sil_mask, ms_ssim, holes)
     with torch.cuda.device(dev):
         _capi.check(_capi.lib().splat_eval_metrics(W, H, planes[0].data_ptr(), planes[1].data_ptr(), planes[2].data_ptr(),
                                                    planes[3].data_ptr(), planes[4].data_ptr(), C.byref(cfg), C.byref(ews),

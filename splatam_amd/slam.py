@@ -75,6 +75,23 @@ def quat_mult(q1: torch.Tensor, q2: torch.Tensor) -> torch.Tensor:
                         w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2], dim=-1)
 
 
+def matrix_to_quaternion(R: torch.Tensor) -> torch.Tensor:
+    """A rotation matrix [3, 3] as a quaternion [4] (w, x, y, z), not normalised beyond what the formula gives.  Of the four ways to
+    read the quaternion off the matrix -- each divides by twice one component, |w|, |x|, |y| or |z| = sqrt(1 +- R00 +- R11 +- R22) / 2
+    -- the one with the largest divisor is taken (the best conditioned; the convention of pytorch3d's function of this name, which the
+    reference's eval_nvs() applies to a held-out pose)."""
+    R = R.reshape(3, 3)
+    tr = torch.stack([1 + R[0, 0] + R[1, 1] + R[2, 2], 1 + R[0, 0] - R[1, 1] - R[2, 2],
+                      1 - R[0, 0] + R[1, 1] - R[2, 2], 1 - R[0, 0] - R[1, 1] + R[2, 2]])
+    mag = torch.sqrt(torch.clamp(tr, min=0))                    # 2 |w|, 2 |x|, 2 |y|, 2 |z|
+    rows = torch.stack([torch.stack([mag[0] ** 2, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]]),
+                        torch.stack([R[2, 1] - R[1, 2], mag[1] ** 2, R[1, 0] + R[0, 1], R[0, 2] + R[2, 0]]),
+                        torch.stack([R[0, 2] - R[2, 0], R[1, 0] + R[0, 1], mag[2] ** 2, R[1, 2] + R[2, 1]]),
+                        torch.stack([R[1, 0] - R[0, 1], R[2, 0] + R[0, 2], R[2, 1] + R[1, 2], mag[3] ** 2])])
+    best = int(torch.argmax(mag))
+    return rows[best] / (2.0 * torch.clamp(mag[best], min=0.1))
+
+
 def setup_camera(w, h, k, w2c, near=0.01, far=100, device="cuda"):
     """Settings tuple for an intrinsics matrix ``k`` and a world-to-camera ``w2c``;
     viewmatrix = w2c^T (kept as the non-contiguous transposed view the reference
