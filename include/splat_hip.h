@@ -31,6 +31,9 @@ extern "C" {
 #endif
 
 #define SPLAT_ABI_VERSION 17       /* 17: the hole count of a novel view (SplatEvalConfig.holes, SPLAT_EVAL_HOLES);
+                                      ADDED WITHIN 17 (no struct changed, no symbol removed, so the number stays and every binding built against
+                                      17 keeps working): SplatLossConfigEx, SPLAT_LOSS_SPLATAM / SPLAT_LOSS_GS, splat_iter_loss_backward_ex,
+                                      splat_iter_mapping_step_ex -- the mapping loss of the refinement script (get_loss_gs);
                                       16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
                                       15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
                                       14: frame ingest (splat_frame_ingest);
@@ -528,6 +531,28 @@ int splat_iter_fold_sums(double *sums, void *stream);
  * exchanged between splat_iter_loss_backward and splat_iter_adam_map. */
 int splat_iter_mapping_step(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
                             const SplatLossConfig *cfg, SplatIterWorkspace *ws, const SplatAdamMap *adam, void *stream);
+
+/* ---- added within ABI 17: the loss of the refinement script ------------------------------------------------------------------
+ * get_loss_gs (/root/reference/scripts/post_splatam_opt.py:111-147) is get_loss(mapping=True) with another depth term: the mask is
+ * gt_depth != 0 (not > 0, no NaN mask), the term is the masked sum of |depth - gt_depth| over ALL H W pixels (not over the mask
+ * count), its gradient per valid pixel w_depth * sign / (H W); no silhouette, no outlier rejection, no pose gradient.  The image
+ * term (0.8 L1 + 0.2 (1 - SSIM)) is get_loss'.  SplatLossConfig has no room for the choice and ABI 17 is pinned by its callers, so
+ * the mode travels in a struct of its own that EMBEDS the old one, and through entry points of its own; the old entry points are
+ * the new ones with SPLAT_LOSS_SPLATAM.  With SPLAT_LOSS_GS: base.tracking, base.camera_grad, base.ignore_outlier_depth_loss and
+ * base.defer_finish must be clear and base.gaussians_grad set (SPLAT_E_INVALID otherwise); SPLAT_REPORT_LOSS / _DEPTH_TERM /
+ * _IM_TERM report the gs values, SPLAT_REPORT_SUMS the same raw sums (the mask count is gt_depth != 0's). */
+#define SPLAT_LOSS_SPLATAM 0     /* get_loss (/root/reference/scripts/splatam.py:214-347) */
+#define SPLAT_LOSS_GS 1          /* get_loss_gs */
+typedef struct SplatLossConfigEx {
+    SplatLossConfig base;
+    int32_t loss_mode;           /* SPLAT_LOSS_* */
+    int32_t reserved[3];         /* zero */
+} SplatLossConfigEx;
+/* splat_iter_loss_backward / splat_iter_mapping_step under cfg->loss_mode */
+int splat_iter_loss_backward_ex(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
+                                const SplatLossConfigEx *cfg, SplatIterWorkspace *ws, void *stream);
+int splat_iter_mapping_step_ex(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
+                               const SplatLossConfigEx *cfg, SplatIterWorkspace *ws, const SplatAdamMap *adam, void *stream);
 
 /* Kernel-only timing helper for bench.py on the fused path: fn 0 = 6-channel composite forward reading published lists, 1 = 6-channel
  * composite backward (the kernel alone: the launches accumulate on top of each other and the accumulator is zeroed again AFTER the

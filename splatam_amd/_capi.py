@@ -75,6 +75,10 @@ class SplatLossConfig(C.Structure):
                 ("defer_finish", C.c_int32), ("fused_composite", C.c_int32)]
 
 
+class SplatLossConfigEx(C.Structure):       # (added within ABI 17: the loss of the refinement script, include/splat_hip.h)
+    _fields_ = [("base", SplatLossConfig), ("loss_mode", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class SplatIterWorkspace(C.Structure):
     _fields_ = [("st", SplatState), ("feat8", _fp), ("out6", _fp), ("dL_dout6", _fp), ("accum", _fp),
                 ("ssim_maps", _fp), ("sums", _fp), ("max_2D_radius", _fp),
@@ -136,8 +140,8 @@ class SplatViewArgs(C.Structure):
                 ("lut", _fp), ("rgb8", _fp), ("points", _fp), ("colors", _fp)]
 
 
-MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatIterWorkspace,
-                    SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
+MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
+                    SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
                     SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs)
 
 
@@ -145,6 +149,7 @@ SPLAT_ADD_VALID_DEPTH = 0
 SPLAT_ADD_NON_PRESENCE = 1
 SPLAT_DENSIFY_CLONE = 0
 SPLAT_DENSIFY_SPLIT = 1
+SPLAT_LOSS_SPLATAM, SPLAT_LOSS_GS = 0, 1
 SPLAT_ITER_SUMS = 32
 SPLAT_ITER_SUM_COPIES = 64
 SPLAT_POSE_STATE = 24
@@ -184,6 +189,7 @@ EXPORTS = (
     "splat_eval_workspace_layout", "splat_eval_workspace_bind", "splat_eval_metrics", "splat_iter_eval",
     "splat_frame_prepare", "splat_frame_ingest", "splat_frame_ingest_planes",
     "splat_view_camera", "splat_view_finish",
+    "splat_iter_loss_backward_ex", "splat_iter_mapping_step_ex",
 )
 
 _lib = None
@@ -241,6 +247,12 @@ def lib():
     L.splat_iter_mapping_step.restype = C.c_int
     L.splat_iter_mapping_step.argtypes = [cam, C.POINTER(SplatMap), C.POINTER(SplatFrameData), C.POINTER(SplatLossConfig),
                                           C.POINTER(SplatIterWorkspace), C.POINTER(SplatAdamMap), _fp]
+    L.splat_iter_loss_backward_ex.restype = C.c_int
+    L.splat_iter_loss_backward_ex.argtypes = [cam, C.POINTER(SplatMap), C.POINTER(SplatFrameData), C.POINTER(SplatLossConfigEx),
+                                              C.POINTER(SplatIterWorkspace), _fp]
+    L.splat_iter_mapping_step_ex.restype = C.c_int
+    L.splat_iter_mapping_step_ex.argtypes = [cam, C.POINTER(SplatMap), C.POINTER(SplatFrameData), C.POINTER(SplatLossConfigEx),
+                                             C.POINTER(SplatIterWorkspace), C.POINTER(SplatAdamMap), _fp]
     L.splat_iter_finish.restype = C.c_int
     L.splat_iter_finish.argtypes = [cam, C.POINTER(SplatMap), C.POINTER(SplatFrameData), C.POINTER(SplatLossConfig),
                                     C.POINTER(SplatIterWorkspace), C.POINTER(SplatPoseAdam), _fp]

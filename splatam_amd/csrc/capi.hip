@@ -56,7 +56,7 @@ size_t splat_sizeof(const char *name) {
     if (!name) return 0;
 #define SPLAT_SIZEOF_CASE(T) if (strcmp(name, #T) == 0) return sizeof(T)
     SPLAT_SIZEOF_CASE(SplatCamera); SPLAT_SIZEOF_CASE(SplatGaussians); SPLAT_SIZEOF_CASE(SplatState); SPLAT_SIZEOF_CASE(SplatGrads);
-    SPLAT_SIZEOF_CASE(SplatMap); SPLAT_SIZEOF_CASE(SplatFrameData); SPLAT_SIZEOF_CASE(SplatLossConfig); SPLAT_SIZEOF_CASE(SplatIterWorkspace);
+    SPLAT_SIZEOF_CASE(SplatMap); SPLAT_SIZEOF_CASE(SplatFrameData); SPLAT_SIZEOF_CASE(SplatLossConfig); SPLAT_SIZEOF_CASE(SplatLossConfigEx); SPLAT_SIZEOF_CASE(SplatIterWorkspace);
     SPLAT_SIZEOF_CASE(SplatAdamMap); SPLAT_SIZEOF_CASE(SplatPoseAdam); SPLAT_SIZEOF_CASE(SplatMapStore); SPLAT_SIZEOF_CASE(SplatAddArgs);
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
@@ -172,8 +172,12 @@ int splat_time_kernel(int fn, int iters, const SplatCamera *cam, const SplatGaus
 
 static int iter_loss_backward_impl(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
                                    const SplatLossConfig *cfg, SplatIterWorkspace *ws, const SplatPoseAdam *adam, void *stream,
-                                   const SplatAdamMap *map_adam = nullptr) {
+                                   const SplatAdamMap *map_adam = nullptr, int loss_mode = SPLAT_LOSS_SPLATAM) {
     if (!cam || !map || !frame || !cfg || !ws) return SPLAT_E_INVALID;
+    if (loss_mode != SPLAT_LOSS_SPLATAM && loss_mode != SPLAT_LOSS_GS) return SPLAT_E_INVALID;
+    // get_loss_gs: a mapping loss without pose gradient, outlier rejection or a deferred finish
+    if (loss_mode == SPLAT_LOSS_GS && (cfg->tracking || cfg->camera_grad || !cfg->gaussians_grad || cfg->ignore_outlier_depth_loss || cfg->defer_finish || adam))
+        return SPLAT_E_INVALID;
     if (map->P < 0 || cam->image_width <= 0 || cam->image_height <= 0 || !cam->viewmatrix || !cam->projmatrix) return SPLAT_E_INVALID;
     if (map->num_frames <= 0 || frame->time_idx < 0 || frame->time_idx >= map->num_frames) return SPLAT_E_INVALID;
     if (!map->cam_unnorm_rots || !map->cam_trans || !frame->im || !frame->depth || !frame->w2c) return SPLAT_E_INVALID;
@@ -192,7 +196,7 @@ static int iter_loss_backward_impl(const SplatCamera *cam, const SplatMap *map, 
         st.tile_row_end > (cam->image_height + SPLAT_TILE - 1) / SPLAT_TILE)
         return SPLAT_E_INVALID;
     if (st.tile_row_end > st.tile_row_begin && (!cfg->tracking || cfg->ignore_outlier_depth_loss || map_adam)) return SPLAT_E_INVALID;
-    return check(launch_iter_loss_backward(*cam, *map, *frame, *cfg, *ws, (hipStream_t)stream, adam, map_adam));
+    return check(launch_iter_loss_backward(*cam, *map, *frame, *cfg, *ws, (hipStream_t)stream, adam, map_adam, loss_mode));
 }
 
 int splat_iter_loss_backward(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
@@ -220,8 +224,9 @@ int splat_iter_fold_sums(double *sums, void *stream) {
     return check(launch_iter_fold_sums(sums, (hipStream_t)stream));
 }
 
-int splat_iter_mapping_step(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
-                            const SplatLossConfig *cfg, SplatIterWorkspace *ws, const SplatAdamMap *adam, void *stream) {
+// splat_iter_mapping_step under either loss: ONE check for the old entry point and the extended one
+static int mapping_step_impl(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame, const SplatLossConfig *cfg,
+                             SplatIterWorkspace *ws, const SplatAdamMap *adam, void *stream, int loss_mode) {
     if (!cfg || cfg->tracking || !cfg->gaussians_grad || !adam || !ws) return SPLAT_E_INVALID;
     // a stepped group (adam->grad[k] != NULL) takes the gradient this iteration forms in registers; adam->grad[k] names the buffer it is
     // ALSO written to -- or, when the workspace carries no buffer for the group (ws->d_* NULL), it is not stored at all (a loop that
@@ -229,7 +234,28 @@ int splat_iter_mapping_step(const SplatCamera *cam, const SplatMap *map, const S
     const float *const grads[5] = {ws->d_means3D, ws->d_rgb_colors, ws->d_unnorm_rotations, ws->d_logit_opacities, ws->d_log_scales};
     for (int k = 0; k < 5; ++k)
         if (adam->grad[k] && ((grads[k] && adam->grad[k] != grads[k]) || !adam->exp_avg[k] || !adam->exp_avg_sq[k])) return SPLAT_E_INVALID;
-    return iter_loss_backward_impl(cam, map, frame, cfg, ws, nullptr, stream, adam);
+    return iter_loss_backward_impl(cam, map, frame, cfg, ws, nullptr, stream, adam, loss_mode);
+}
+
+int splat_iter_mapping_step(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
+                            const SplatLossConfig *cfg, SplatIterWorkspace *ws, const SplatAdamMap *adam, void *stream) {
+    return mapping_step_impl(cam, map, frame, cfg, ws, adam, stream, SPLAT_LOSS_SPLATAM);
+}
+
+static bool valid_config_ex(const SplatLossConfigEx *cfg) {
+    return cfg && cfg->reserved[0] == 0 && cfg->reserved[1] == 0 && cfg->reserved[2] == 0;
+}
+
+int splat_iter_loss_backward_ex(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
+                                const SplatLossConfigEx *cfg, SplatIterWorkspace *ws, void *stream) {
+    if (!valid_config_ex(cfg)) return SPLAT_E_INVALID;
+    return iter_loss_backward_impl(cam, map, frame, &cfg->base, ws, nullptr, stream, nullptr, cfg->loss_mode);
+}
+
+int splat_iter_mapping_step_ex(const SplatCamera *cam, const SplatMap *map, const SplatFrameData *frame,
+                               const SplatLossConfigEx *cfg, SplatIterWorkspace *ws, const SplatAdamMap *adam, void *stream) {
+    if (!valid_config_ex(cfg)) return SPLAT_E_INVALID;
+    return mapping_step_impl(cam, map, frame, &cfg->base, ws, adam, stream, cfg->loss_mode);
 }
 
 int splat_iter_adam_map(const SplatMap *map, const SplatAdamMap *opt, void *stream) {

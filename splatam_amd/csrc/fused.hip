@@ -12,6 +12,7 @@
 //   F4 ssim_forward_kernel       mapping: separable 11x11 SSIM statistics -> map sum + three partial-derivative maps,
 //                                image L1 sum, masked depth L1 sum and mask count
 //   F5 map_loss_backward_kernel  mapping: blur of the partial maps -> dL/d(rgb), depth gradient with the final count
+//      F4 / F5 / F7 <GS>         the refinement script's loss (get_loss_gs): depth mask gt != 0, depth sum over H W; forms of their own
 //      K7<6 channels>            (render.hip)
 //   F6 fused_backward_kernel     K8+K9 + adjoint of F1's glue + camera-pose partial sums (block reduce, f64 atomics);
 //                                single-view mapping step: + the Adam step of the map
@@ -440,7 +441,9 @@ __device__ __forceinline__ void load_window_column(const float *const (&plane)[N
 }
 
 // VEC: W % 4 == 0 and every plane 16-byte aligned (the launcher checks): whole float4 loads / stores of a thread's four pixels
-template <bool VEC>
+// GS: the depth term of get_loss_gs (fused_math.h: depth_pixel_gs) instead of get_loss'; a compile-time form of its own
+// (a template parameter, not a branch: the instantiations of get_loss are instruction for instruction what they were without it)
+template <bool VEC, bool GS>
 __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W, int H) {
     __shared__ WindowLds<2> S;                  // vertical sums of (x, y), (x x, y y) and x y
     __shared__ double s_part[4 * (kBlock / 64)];
@@ -476,7 +479,7 @@ __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W
         load_px4<VEC>(Y, y0 + hr, x0 + hc, W, H, own_y);
     }
     __syncthreads();
-    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
+    const float median = !GS && a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};        // depth L1 (masked), image L1, mask count, SSIM map sum
     if (tid < kWinItems) {
         f2 o[2][4];                             // (mu1, mu2), (E11, E22)
@@ -508,7 +511,7 @@ __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const bool ok = yy < H && x0 + hc + j < W;
-            const Pixel px = depth_pixel(a.cfg, pre[0][j], pre[1][j], pre[2][j], pre[3][j], median);
+            const Pixel px = GS ? depth_pixel_gs(pre[0][j], pre[3][j]) : depth_pixel(a.cfg, pre[0][j], pre[1][j], pre[2][j], pre[3][j], median);
             acc[0] += ok ? px.d_err : 0.f;
             acc[2] += ok && px.mask ? 1.f : 0.f;
         }
@@ -516,7 +519,7 @@ __global__ __launch_bounds__(kBlock) void ssim_forward_kernel(FusedArgs a, int W
     block_sums_to<4>(sum_copy(a.ws.sums, SPLAT_ITER_SUMS), acc, s_part);
 }
 
-template <bool VEC>
+template <bool VEC, bool GS>
 __global__ __launch_bounds__(kBlock) void map_loss_backward_kernel(FusedArgs a, int W, int H) {
     __shared__ WindowLds<1> S;                  // vertical sums of (d/dmu1, d/dE11) and d/dE12
     __shared__ float s_count;
@@ -529,7 +532,7 @@ __global__ __launch_bounds__(kBlock) void map_loss_backward_kernel(FusedArgs a, 
     const int x0 = bx * kWinTW, y0 = by * kWinTH;
     const size_t HW = (size_t)H * W;
     const float *M = a.ws.ssim_maps + (size_t)(3 * ch) * HW;
-    if (tid < 64) {
+    if (!GS && tid < 64) {         // (get_loss_gs divides by the pixel count: nothing to wait for)
         const double c = sum_total(a.ws.sums, 2);
         if (tid == 0) s_count = (float)c;
     }
@@ -554,8 +557,8 @@ __global__ __launch_bounds__(kBlock) void map_loss_backward_kernel(FusedArgs a, 
     __syncthreads();
     if (tid >= kWinItems) return;
     const float inv_n = 1.0f / (3.0f * (float)HW);
-    const float median = a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
-    const float count = s_count;
+    const float median = !GS && a.cfg.ignore_outlier_depth_loss ? a.ws.d_cam[SPLAT_REPORT_MEDIAN] : 0.f;
+    const float count = map_depth_divisor(GS, GS ? 0.f : s_count, (float)HW);
     f2 o[1][4];
     float oC[4];
     window_horizontal<1>(g, S, hr, hc, o, oC);
@@ -575,8 +578,8 @@ __global__ __launch_bounds__(kBlock) void map_loss_backward_kernel(FusedArgs a, 
         load_px4<VEC>(a.frame.depth, y0 + hr, x0 + hc, W, H, pre[3]);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const Pixel px = depth_pixel(a.cfg, pre[0][j], pre[1][j], pre[2][j], pre[3][j], median);
-            dout[j] = a.cfg.use_l1 ? a.cfg.w_depth * px.d_sign / count : 0.f;
+            const Pixel px = GS ? depth_pixel_gs(pre[0][j], pre[3][j]) : depth_pixel(a.cfg, pre[0][j], pre[1][j], pre[2][j], pre[3][j], median);
+            dout[j] = map_depth_grad(a.cfg.use_l1 != 0, a.cfg.w_depth, px.d_sign, count);
         }
         store_px4<VEC>(a.ws.dL_dout6 + 3 * HW, y0 + hr, x0 + hc, W, H, dout);
     }
@@ -638,6 +641,8 @@ __device__ __forceinline__ void pose_adam_step(const SplatMap &map, int time_idx
 // Workgroups 1..8 (launched when the state carries SplatState.tile_work / tile_order) have nothing to do with the pose: each turns the
 // forward composite's per-tile work estimates of ITS XCD band into the band's launch order for the next iteration's composites -- a
 // 5 us kernel of its own on the iteration's critical path otherwise, here it runs beside the single workgroup that closes the iteration.
+// GS: the mapping loss is get_loss_gs' (its depth sum over the pixel count)
+template <bool GS>
 __global__ __launch_bounds__(256) void pose_finish_kernel(FusedArgs a, int HW, PoseAdam pa) {
     static_assert(SPLAT_ITER_SUMS * 8 == 256 && SPLAT_ITER_SUM_COPIES == 64, "thread t: sum k = t / 8, copies (t % 8) * 8 .. + 7");
     if (blockIdx.x > 0) {
@@ -692,13 +697,13 @@ __global__ __launch_bounds__(256) void pose_finish_kernel(FusedArgs a, int HW, P
     for (int k = 0; k < 3; ++k) out[SPLAT_REPORT_DTRANS + k] = dt[k];
     float loss, w_depth_term, w_im_term;
     const float l_depth = a.cfg.use_l1 ? (float)S[0] : 0.f;
-    if (a.cfg.tracking) {
+    if (!GS && a.cfg.tracking) {
         w_depth_term = a.cfg.w_depth * l_depth;
         w_im_term = a.cfg.w_im * (float)S[1];
     } else {
         const float n = 3.0f * (float)HW;
         const float l_im = 0.8f * ((float)S[1] / n) + 0.2f * (1.0f - (float)S[3] / n);
-        w_depth_term = a.cfg.w_depth * (a.cfg.use_l1 ? l_depth / (float)S[2] : 0.f);
+        w_depth_term = a.cfg.w_depth * (a.cfg.use_l1 ? l_depth / map_depth_divisor(GS, (float)S[2], (float)HW) : 0.f);
         w_im_term = a.cfg.w_im * l_im;
     }
     loss = w_depth_term + w_im_term;
@@ -990,7 +995,8 @@ static void launch_fused_preprocess(const FusedArgs &a, hipStream_t s) {
 
 hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map, const SplatFrameData &frame,
                                      const SplatLossConfig &cfg, SplatIterWorkspace &ws_in, hipStream_t s, const SplatPoseAdam *pose_adam,
-                                     const SplatAdamMap *map_adam) {
+                                     const SplatAdamMap *map_adam, int loss_mode) {
+    const bool gs = loss_mode == SPLAT_LOSS_GS;         // (mapping only, pixel-local, never deferred: the C entry points check)
     SplatIterWorkspace ws = ws_in;          // (copy: the binning mode is decided per call)
     if (!group_binning(ws.st, cam)) ws.st.group_stride = 0;
     FusedArgs a{cam, map, frame, cfg, ws, {}};
@@ -1048,12 +1054,19 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
             }
         } else {
             const dim3 grid = xcd_tile_grid(W, H);
-            if ((W & 3) == 0 && aligned16(ws.out6) && aligned16(frame.im) && aligned16(frame.depth) && aligned16(ws.ssim_maps) && aligned16(ws.dL_dout6)) {
-                hipLaunchKernelGGL(ssim_forward_kernel<true>, grid, dim3(kBlock), 0, s, a, W, H);
-                hipLaunchKernelGGL(map_loss_backward_kernel<true>, grid, dim3(kBlock), 0, s, a, W, H);
+            const bool vec = (W & 3) == 0 && aligned16(ws.out6) && aligned16(frame.im) && aligned16(frame.depth) && aligned16(ws.ssim_maps) && aligned16(ws.dL_dout6);
+            if (gs && vec) {
+                hipLaunchKernelGGL((ssim_forward_kernel<true, true>), grid, dim3(kBlock), 0, s, a, W, H);
+                hipLaunchKernelGGL((map_loss_backward_kernel<true, true>), grid, dim3(kBlock), 0, s, a, W, H);
+            } else if (gs) {
+                hipLaunchKernelGGL((ssim_forward_kernel<false, true>), grid, dim3(kBlock), 0, s, a, W, H);
+                hipLaunchKernelGGL((map_loss_backward_kernel<false, true>), grid, dim3(kBlock), 0, s, a, W, H);
+            } else if (vec) {
+                hipLaunchKernelGGL((ssim_forward_kernel<true, false>), grid, dim3(kBlock), 0, s, a, W, H);
+                hipLaunchKernelGGL((map_loss_backward_kernel<true, false>), grid, dim3(kBlock), 0, s, a, W, H);
             } else {
-                hipLaunchKernelGGL(ssim_forward_kernel<false>, grid, dim3(kBlock), 0, s, a, W, H);
-                hipLaunchKernelGGL(map_loss_backward_kernel<false>, grid, dim3(kBlock), 0, s, a, W, H);
+                hipLaunchKernelGGL((ssim_forward_kernel<false, false>), grid, dim3(kBlock), 0, s, a, W, H);
+                hipLaunchKernelGGL((map_loss_backward_kernel<false, false>), grid, dim3(kBlock), 0, s, a, W, H);
             }
         }
         e = launch_render_backward_feat8(cam, ws.feat8, ws.st, ws.dL_dout6, ws.accum, P, false, sums, s);
@@ -1075,7 +1088,8 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
         else if (iso) hipLaunchKernelGGL((fused_backward_kernel<false, false, true>), grid, block, 0, s, a, opt);
         else hipLaunchKernelGGL((fused_backward_kernel<false, false, false>), grid, block, 0, s, a, opt);
     }
-    if (!cfg.defer_finish) hipLaunchKernelGGL(pose_finish_kernel, dim3(finish_blocks(ws.st)), dim3(256), 0, s, a, HW, pa);
+    if (gs) hipLaunchKernelGGL(pose_finish_kernel<true>, dim3(finish_blocks(ws.st)), dim3(256), 0, s, a, HW, pa);
+    else if (!cfg.defer_finish) hipLaunchKernelGGL(pose_finish_kernel<false>, dim3(finish_blocks(ws.st)), dim3(256), 0, s, a, HW, pa);
     return hipGetLastError();
 }
 
@@ -1087,7 +1101,7 @@ hipError_t launch_iter_finish(const SplatCamera &cam, const SplatMap &map, const
     if (pose_adam)
         pa = PoseAdam{pose_adam->state, pose_adam->beta1, pose_adam->beta2, pose_adam->eps, pose_adam->bc2_sqrt, pose_adam->step_size_rot,
                       pose_adam->step_size_trans};
-    hipLaunchKernelGGL(pose_finish_kernel, dim3(finish_blocks(ws.st)), dim3(256), 0, s, a, cam.image_width * cam.image_height, pa);
+    hipLaunchKernelGGL(pose_finish_kernel<false>, dim3(finish_blocks(ws.st)), dim3(256), 0, s, a, cam.image_width * cam.image_height, pa);
     return hipGetLastError();
 }
 

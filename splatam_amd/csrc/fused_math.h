@@ -11,6 +11,7 @@
 //   quat_mult                                /root/reference/utils/slam_helpers.py:21-29
 //   _ssim (per-pixel part)                   /root/reference/utils/slam_external.py:75-97
 //   get_loss (the masked L1 terms, per pixel) /root/reference/scripts/splatam.py:256-288
+//   get_loss_gs (its depth term)             /root/reference/scripts/post_splatam_opt.py:129-137
 // and their hand-derived adjoints (what torch.autograd computes for the reference).
 #pragma once
 
@@ -192,6 +193,27 @@ SPLAT_HD Pixel depth_pixel(bool reject_outliers, bool use_sil, float sil_thres, 
     r.d_sign = m ? ((diff > 0.f) ? -1.f : ((diff < 0.f) ? 1.f : 0.f)) : 0.f;
     return r;
 }
+
+// ---- the "gs" mapping loss of the refinement script (get_loss_gs, /root/reference/scripts/post_splatam_opt.py:111-147) --------
+// It is get_loss(mapping=True) with another depth term: valid = gt != 0 (NOT > 0: a negative depth counts, a NaN one too; there
+// is no NaN mask on the render), depth = depth * valid, and the term is the mean over ALL H W pixels of |depth - gt| -- the masked
+// sum divided by H W, not by the mask count.  A pixel outside the mask contributes |0 * depth - 0| = 0 and has no gradient
+// (for a finite render: 0 * NaN is NaN upstream, here the pixel is skipped).  No silhouette, no outlier rejection.
+SPLAT_HD Pixel depth_pixel_gs(float depth, float gt) {
+    Pixel r;
+    const bool m = gt != 0.f;
+    const float diff = gt - depth;
+    r.mask = m;
+    r.d_err = m ? fabsf(diff) : 0.f;
+    r.d_sign = m ? ((diff > 0.f) ? -1.f : ((diff < 0.f) ? 1.f : 0.f)) : 0.f;
+    return r;
+}
+
+// What the masked depth L1 sum of a mapping loss is divided by: the mask count (get_loss) or the pixel count (get_loss_gs)
+SPLAT_HD float map_depth_divisor(bool gs, float mask_count, float num_pixels) { return gs ? num_pixels : mask_count; }
+
+// dL/d(depth) of one pixel of a mapping loss: the sign of (depth - gt) on the mask, over the divisor
+SPLAT_HD float map_depth_grad(bool use_l1, float w_depth, float d_sign, float divisor) { return use_l1 ? w_depth * d_sign / divisor : 0.f; }
 
 // The tracking loss of one pixel (get_loss with tracking=True): o = the six rendered channels r, g, b, depth, silhouette, depth^2.
 // The colour terms take the depth mask when the silhouette or outlier rejection is in use, every pixel otherwise.  The silhouette

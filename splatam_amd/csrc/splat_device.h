@@ -74,7 +74,7 @@ hipError_t launch_render_backward_feat8(const SplatCamera &cam, const float *fea
                                         float *accum, int P, bool zero_accum, IterSums sums, hipStream_t s);
 hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map, const SplatFrameData &frame,
                                      const SplatLossConfig &cfg, SplatIterWorkspace &ws, hipStream_t s, const SplatPoseAdam *pose_adam = nullptr,
-                                     const SplatAdamMap *map_adam = nullptr);
+                                     const SplatAdamMap *map_adam = nullptr, int loss_mode = SPLAT_LOSS_SPLATAM);
 hipError_t launch_iter_finish(const SplatCamera &cam, const SplatMap &map, const SplatFrameData &frame, const SplatLossConfig &cfg,
                               SplatIterWorkspace &ws, hipStream_t s, const SplatPoseAdam *pose_adam);
 hipError_t launch_iter_adam_map(const SplatMap &map, const SplatAdamMap &opt, hipStream_t s);

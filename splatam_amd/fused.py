@@ -1071,7 +1071,27 @@ class FusedEngine:
         return torch.cuda.current_stream(self.dev).cuda_stream
 
     @staticmethod
+    def uses_gs_loss(cfg):
+        """``cfg['loss'] == 'gs'``: the iteration forms get_loss_gs (/root/reference/scripts/post_splatam_opt.py:111-147) instead of
+        get_loss(mapping=True) -- of ``cfg`` it reads ``loss_weights`` (and ``lrs`` where a step is taken), nothing else."""
+        loss = cfg.get('loss', 'splatam')
+        if loss not in ('splatam', 'gs'):
+            raise ValueError(f"cfg['loss'] must be 'splatam' or 'gs' (got {loss!r})")
+        return loss == 'gs'
+
+    @staticmethod
     def loss_config(cfg, tracking, do_ba=False, defer_finish=False, fused_composite=0):
+        """The SplatLossConfig of ``cfg``; with ``cfg['loss'] == 'gs'`` a SplatLossConfigEx around it (mapping only)."""
+        if FusedEngine.uses_gs_loss(cfg):
+            if tracking or do_ba or defer_finish:
+                raise ValueError("cfg['loss'] = 'gs' is a mapping loss without pose gradient: not with tracking, do_ba or tile rows")
+            ex = _capi.SplatLossConfigEx()
+            ex.loss_mode = _capi.SPLAT_LOSS_GS
+            c = ex.base
+            c.gaussians_grad, c.use_l1 = 1, 1
+            c.sil_thres = float(cfg.get('sil_thres', 0.5))
+            c.w_im, c.w_depth = float(cfg['loss_weights']['im']), float(cfg['loss_weights']['depth'])
+            return ex
         c = _capi.SplatLossConfig()
         c.defer_finish = int(defer_finish)
         c.fused_composite = int(fused_composite)
@@ -1107,14 +1127,23 @@ class FusedEngine:
         cam._tile_rows = tile_rows          # a band: the iteration stops before its last kernel (finish_iteration completes it)
         cam._stats_partial = tile_rows is not None
         self._lc_keep = lc
-        if lc.ignore_outlier_depth_loss and 'outlier_err' not in cam.buf:
+        gs = isinstance(lc, _capi.SplatLossConfigEx)
+        if gs and pose_adam is not None:
+            raise ValueError("cfg['loss'] = 'gs' takes no pose step")
+        if not gs and lc.ignore_outlier_depth_loss and 'outlier_err' not in cam.buf:
             cam.alloc_outlier_scratch()
         if self.tile_order_on and self.order_per_view:
             cam.select_order(int(time_idx))
         ws = self._workspace(map_grads, with_ssim=not tracking)
         m = self._map_struct()
         with torch.cuda.device(self.dev):
-            if pose_adam is not None:
+            if gs and map_adam is not None:
+                _capi.check(self.L.splat_iter_mapping_step_ex(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
+                                                              C.byref(map_adam), self._stream()), "splat_iter_mapping_step_ex")
+            elif gs:
+                _capi.check(self.L.splat_iter_loss_backward_ex(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
+                                                               self._stream()), "splat_iter_loss_backward_ex")
+            elif pose_adam is not None:
                 _capi.check(self.L.splat_iter_tracking_step(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(lc), C.byref(ws),
                                                             C.byref(pose_adam), self._stream()), "splat_iter_tracking_step")
             elif map_adam is not None:

@@ -19,6 +19,9 @@ here                                           reference
 ``transformed_params2depthplussilhouette``     utils/slam_helpers.py:234-249
 ``l1_loss_v1`` / ``calc_ssim``                 utils/slam_helpers.py:5-6 / utils/slam_external.py:54-97
 ``get_loss``                                   scripts/splatam.py:214-347
+``get_loss_gs``                                scripts/post_splatam_opt.py:111-147 (``params2rendervar`` / ``params2depthplussilhouette``:
+                                               utils/gs_helpers.py:189-198 / 275-284)
+``get_expon_lr_func`` / ``update_learning_rate``  utils/gs_external.py:269-302 / 260-266
 ``initialize_optimizer``                       scripts/splatam.py:160-166
 ``tracking_iteration`` / ``mapping_iteration``  scripts/splatam.py:690-711 / 828-869 (loop bodies)
 ``get_pointcloud``                             scripts/splatam.py:67-116
@@ -284,6 +287,83 @@ def get_loss(params, curr_data, variables, iter_time_idx, loss_weights, use_sil_
     return loss, variables, weighted_losses
 
 
+def params2rendervar(params):
+    """The colour render's variables of the refinement script: the WORLD-frame Gaussians as they are (the camera carries the pose)."""
+    return {
+        'means3D': params['means3D'],
+        'colors_precomp': params['rgb_colors'],
+        'rotations': F.normalize(params['unnorm_rotations']),
+        'opacities': torch.sigmoid(params['logit_opacities']),
+        'scales': _scales3(params),
+        'means2D': torch.zeros_like(params['means3D'], requires_grad=True) + 0,
+    }
+
+
+def params2depthplussilhouette(params, w2c):
+    """... and the depth / silhouette render's: [z, 1, z^2] of the centres under ``w2c``, the frame's own world-to-camera matrix."""
+    rv = params2rendervar(params)
+    rv['colors_precomp'] = get_depth_and_silhouette(params['means3D'], w2c)
+    return rv
+
+
+def get_loss_gs(params, curr_data, variables, loss_weights):
+    """The objective of the refinement script (post_splatam_opt.py's get_loss_gs): world-frame Gaussians through the camera
+    ``curr_data['cam']`` built AT the frame's pose (``curr_data['w2c']``), and against get_loss(mapping=True)
+      * the depth mask is ``gt_depth != 0`` (not ``> 0``; no NaN mask) and multiplies the RENDER,
+      * the depth term is the mean of |depth * valid - gt_depth| over ALL pixels (the masked sum over H W, not over the mask count),
+      * no silhouette term, no outlier rejection, no pose gradient.
+    Returns (loss, variables, weighted_losses); the colour render's ``means2D`` is retained for densification."""
+    rendervar = params2rendervar(params)
+    depth_sil_rendervar = params2depthplussilhouette(params, curr_data['w2c'])
+
+    rendervar['means2D'].retain_grad()
+    im, radius, _ = Renderer(raster_settings=curr_data['cam'])(**rendervar)
+    variables['means2D'] = rendervar['means2D']
+
+    depth_sil, _, _ = Renderer(raster_settings=curr_data['cam'])(**depth_sil_rendervar)
+    valid_depth_mask = curr_data['depth'] != 0.0
+    depth = depth_sil[0:1] * valid_depth_mask
+
+    losses = {'im': 0.8 * l1_loss_v1(im, curr_data['im']) + 0.2 * (1.0 - calc_ssim(im, curr_data['im'])),
+              'depth': l1_loss_v1(depth, curr_data['depth'])}
+    weighted_losses = {k: v * loss_weights[k] for k, v in losses.items()}
+    loss = sum(weighted_losses.values())
+
+    seen = radius > 0
+    variables['max_2D_radius'] = torch.where(seen, torch.max(radius.to(variables['max_2D_radius'].dtype),
+                                                             variables['max_2D_radius']), variables['max_2D_radius'])
+    variables['seen'] = seen
+    weighted_losses['loss'] = loss
+    return loss, variables, weighted_losses
+
+
+def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):
+    """Log-linear interpolation from ``lr_init`` (step 0) to ``lr_final`` (``max_steps``), in numpy float64 as upstream; with
+    ``lr_delay_steps > 0`` scaled by a sine ramp from ``lr_delay_mult`` to 1 over that many steps (the refinement script passes no
+    ``lr_delay_steps``, so its ``lr_delay_mult`` has no effect: kept)."""
+    import numpy as np
+
+    def helper(step):
+        if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+            return 0.0
+        if lr_delay_steps > 0:
+            delay_rate = lr_delay_mult + (1 - lr_delay_mult) * np.sin(0.5 * np.pi * np.clip(step / lr_delay_steps, 0, 1))
+        else:
+            delay_rate = 1.0
+        t = np.clip(step / max_steps, 0, 1)
+        return delay_rate * np.exp(np.log(lr_init) * (1 - t) + np.log(lr_final) * t)
+    return helper
+
+
+def update_learning_rate(optimizer, means3D_scheduler, iteration):
+    """Sets the rate of the optimizer's ``means3D`` group for ``iteration`` and returns it."""
+    for group in optimizer.param_groups:
+        if group["name"] == "means3D":
+            lr = means3D_scheduler(iteration)
+            group['lr'] = lr
+            return lr
+
+
 # --------------------------------------------------------------------------
 # optimiser + loop bodies
 # --------------------------------------------------------------------------
@@ -532,7 +612,9 @@ def _cat_rows(new_rows, params, optimizer):
 def densify(params, variables, optimizer, iter, densify_dict):
     """Gradient-based densification (3D Gaussian Splatting's): clone the small Gaussians with a large accumulated
     screen-space gradient, split the large ones into ``num_to_split_into`` samples of themselves, then prune by opacity
-    and size; optional opacity reset.  Draws from the global torch RNG exactly where the reference does."""
+    and size; optional opacity reset.  Draws from the global torch RNG exactly where the reference does.
+    ``variables['timestep']``, when present, is extended by the cloned / split rows' own values, as the refinement script's copy of
+    this function does (utils/gs_external.py:202-205, :219-222; utils/slam_external.py's never extends it and fails in remove_points)."""
     if iter > densify_dict['stop_after']:
         return params, variables
     variables = accumulate_mean2d_gradient(variables)
@@ -542,6 +624,8 @@ def densify(params, variables, optimizer, iter, densify_dict):
         grads[grads.isnan()] = 0.0
         small = torch.exp(params['log_scales']).max(dim=1).values <= 0.01 * variables['scene_radius']
         to_clone = (grads >= thr) & small
+        if 'timestep' in variables:
+            variables['timestep'] = torch.cat((variables['timestep'], variables['timestep'][to_clone]), dim=0)
         params = _cat_rows({k: params[k].detach()[to_clone] for k in GAUSSIAN_KEYS}, params, optimizer)
         n_pts = params['means3D'].shape[0]
         dev = params['means3D'].device
@@ -550,6 +634,8 @@ def densify(params, variables, optimizer, iter, densify_dict):
         to_split = (padded >= thr) & (torch.exp(params['log_scales']).max(dim=1).values > 0.01 * variables['scene_radius'])
         n = densify_dict['num_to_split_into']
         rows = {k: params[k].detach()[to_split].repeat(n, 1) for k in GAUSSIAN_KEYS}
+        if 'timestep' in variables:
+            variables['timestep'] = torch.cat((variables['timestep'], variables['timestep'][to_split].repeat(n)), dim=0)
         stds = torch.exp(params['log_scales'].detach())[to_split].repeat(n, 3)
         samples = torch.normal(mean=torch.zeros((stds.size(0), 3), device=dev), std=stds)
         rots = build_rotation(params['unnorm_rotations'].detach()[to_split]).repeat(n, 1, 1)
