@@ -118,7 +118,7 @@ def alternation(workload, views, alternations, steps, warmup, dev):
             t = order[it % len(order)]
             eng.loss_backward(frames[t], t, cfg, tracking=False)
             eng.accumulate_mean2d_gradient()
-            scheduled = it >= dd['start_after'] and it % dd['densify_every'] == 0
+            scheduled = slam.edit_schedule(it, dd, 'densify_every').edits
             edited = eng.densify(it, dd, scene_radius, accumulate=False)
             if edited and not eng.lists_known():
                 eng.relearn_lists(frames[t], t)

@@ -23,7 +23,7 @@ from types import MappingProxyType
 
 import torch
 
-from . import _capi
+from . import _capi, slam
 from .frames import ingest_frame, ingest_planes, prepare_frame  # noqa: F401  (the frame path lives in frames.py)
 from .rasterizer import _cached_contiguous
 
@@ -612,18 +612,20 @@ class FusedEngine:
         ``intrinsics``, default ``curr_data['intrinsics']``, and ``view.check_overflow()``; ``time_idx`` is then not read)."""
         if view is not None:
             view.camera.tile_stride, view.camera.max_list_hint = 0, 0
-            for _ in range(3):
-                self.render_view(view, w2c=w2c, intrinsics=curr_data['intrinsics'] if intrinsics is None else intrinsics, rgb8=False)
-                if not view.check_overflow():
-                    return
-            raise RuntimeError("per-tile lists could not be sized")
+            k = curr_data['intrinsics'] if intrinsics is None else intrinsics
+            return self._fit_lists(lambda: self.render_view(view, w2c=w2c, intrinsics=k, rgb8=False), view.check_overflow, "per-tile lists could not be sized")
         self._check_cam(curr_data)
         self._camera.tile_stride, self._camera.max_list_hint = 0, 0
+        self._fit_lists(lambda: self.render(curr_data, time_idx), self.check_overflow, "per-tile lists could not be sized")
+
+    @staticmethod
+    def _fit_lists(render, digest, message):
+        """``render()`` until its lists fitted -- ``digest()``, which re-sizes them, says whether they overflowed -- three times at most."""
         for _ in range(3):
-            self.render(curr_data, time_idx)
-            if not self.check_overflow():
+            render()
+            if not digest():
                 return
-        raise RuntimeError("per-tile lists could not be sized")
+        raise RuntimeError(message)
 
     def _append(self, mode, curr_data, time_idx, sil_thres, w2c=None):
         if not self.managed:
@@ -675,12 +677,8 @@ class FusedEngine:
         if depth_sil is None:
             # the densification render must come from complete, sorted lists: a spilled bucket / stale list-length hint would
             # permanently add wrong Gaussians (the status words are overwritten by the next relearn_lists)
-            for _ in range(3):
-                self.render(curr_data, time_idx)
-                if not self.check_overflow():
-                    break
-            else:
-                raise RuntimeError("add_new_gaussians: the per-tile lists could not be sized for the densification render")
+            self._fit_lists(lambda: self.render(curr_data, time_idx), self.check_overflow,
+                            "add_new_gaussians: the per-tile lists could not be sized for the densification render")
         else:
             out6 = self._camera.buf['out6']
             out6[3], out6[4] = depth_sil[0], depth_sil[1]
@@ -726,17 +724,14 @@ class FusedEngine:
 
     def prune_gaussians(self, iter, prune_dict, scene_radius):
         """prune_gaussians (/root/reference/utils/slam_external.py:169-196) on the schedule of ``prune_dict``."""
+        sched = slam.edit_schedule(iter, prune_dict, 'prune_every')
         removed = 0
-        if iter <= prune_dict['stop_after']:
-            if iter >= prune_dict['start_after'] and iter % prune_dict['prune_every'] == 0:
-                thr = prune_dict['final_removal_opacity_threshold'] if iter == prune_dict['stop_after'] \
-                    else prune_dict['removal_opacity_threshold']
-                # 0.1 * variables['scene_radius'] as the reference forms it (a float32 tensor product when given a tensor)
-                big = float(0.1 * scene_radius) if iter >= prune_dict['remove_big_after'] else None
-                removed = self.remove_points(None, thr, big)
-            if iter > 0 and iter % prune_dict['reset_opacities_every'] == 0 and prune_dict['reset_opacities']:
-                with torch.no_grad():
-                    self._reset_opacities()
+        if sched.edits:
+            # 0.1 * variables['scene_radius'] as the reference forms it (a float32 tensor product when given a tensor)
+            removed = self.remove_points(None, sched.opacity_threshold, float(0.1 * scene_radius) if sched.remove_big else None)
+        if sched.resets:
+            with torch.no_grad():
+                self._reset_opacities()
         return removed
 
     def _reset_opacities(self):
@@ -826,7 +821,8 @@ class FusedEngine:
         (between backward() and optimizer.step()): accumulate the screen-space gradient; on the schedule clone the small /
         split the large Gaussians whose mean gradient reaches ``grad_thresh``, reset the three per-Gaussian variables, remove
         the split originals, prune by opacity / size; optional opacity reset.  Returns True when the number of rows changed."""
-        if iter > densify_dict['stop_after']:
+        sched = slam.edit_schedule(iter, densify_dict, 'densify_every')
+        if not sched.active:
             return False
         if accumulate:
             # re-runs the RGB backward composite over THIS iteration's workspace (lists, radii, feat8 indexed by the rows the
@@ -834,7 +830,7 @@ class FusedEngine:
             # (accumulate_mean2d_gradient(), then densify(..., accumulate=False)) -- pipeline._map_frame does
             self.accumulate_mean2d_gradient()
         changed = False
-        if iter >= densify_dict['start_after'] and iter % densify_dict['densify_every'] == 0:
+        if sched.edits:
             thr, small = densify_dict['grad_thresh'], float(0.01 * scene_radius)
             P0 = self.P
             self._select_and_append(_capi.SPLAT_DENSIFY_CLONE, thr, small, P0)
@@ -847,12 +843,9 @@ class FusedEngine:
                 to_remove = torch.zeros(self.P, dtype=torch.uint8, device=self.dev)
                 to_remove[:P1] = self.map_buf['flags'][:P1]
                 self.remove_points(to_remove)
-            op_thr = densify_dict['final_removal_opacity_threshold'] if iter == densify_dict['stop_after'] \
-                else densify_dict['removal_opacity_threshold']
-            big = float(0.1 * scene_radius) if iter >= densify_dict['remove_big_after'] else None
-            self.remove_points(None, op_thr, big)
+            self.remove_points(None, sched.opacity_threshold, float(0.1 * scene_radius) if sched.remove_big else None)
             changed = True
-        if iter > 0 and iter % densify_dict['reset_opacities_every'] == 0 and densify_dict['reset_opacities']:
+        if sched.resets:
             with torch.no_grad():
                 self._reset_opacities()
         return changed
@@ -1336,6 +1329,25 @@ class FusedEngine:
         stat = self._camera.buf['status'].tolist()
         rep = self._camera.buf['d_cam'].cpu()
         return self._digest(stat, float(rep[_REPORT_FLAG]) != 0.0, int(rep.view(torch.int32)[_REPORT_SKIPPED]), grow)
+
+    def settle(self, steps, ranks=None, grow=True):
+        """End of a phase: ``check_overflow(grow)`` and, when iterations were flagged, the host-side step count they advanced
+        (``steps``: "map" or "pose") taken back by as many, because the device took none of those steps.  Returns that number -- the
+        iterations the caller runs again -- or 0.  ``ranks`` (``splatam_amd.dist``, or anything with its ``any_rank`` and ``max_int``):
+        the flag of any rank and the largest count hold for every rank."""
+        flagged = self.check_overflow(grow)
+        if ranks is not None:
+            flagged = ranks.any_rank(flagged, self.dev)
+        if not flagged:
+            return 0
+        lost = max(self.skipped_iterations if ranks is None else ranks.max_int(self.skipped_iterations, self.dev), 1)
+        self._take_back(steps, lost)
+        return lost
+
+    def _take_back(self, steps, n):
+        """``n`` steps the device skipped never happened: the bias corrections of the "map" / "pose" optimizer are taken again."""
+        name = {"map": "map_step", "pose": "pose_step"}[steps]
+        setattr(self, name, max(getattr(self, name) - int(n), 0))
 
     def digest_report(self, report, grow=True):
         """check_overflow() from a HOST copy of an iteration's report (``buf['d_cam']``, SPLAT_ITER_DCAM floats: the status words

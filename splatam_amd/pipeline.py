@@ -22,6 +22,7 @@ re-creates the parameters, so the iterations on the pruning schedule take NO Ada
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import math
 import os
@@ -316,16 +317,20 @@ def _reduced_frames(which, first_item, config, full_size, full_k):
 
 class _PhaseTimer:
     """Wall time per named phase of the frame being processed (a device synchronisation on either side: ~10 per frame; ``sync=False``:
-    host time only, for a phase whose device work the next synchronised phase waits for anyway)."""
+    host time only, for a phase whose device work the next synchronised phase waits for anyway).  ``on=False``: every phase is the
+    same empty context -- nothing is timed and nothing synchronised."""
+    _off = contextlib.nullcontext()
 
-    def __init__(self, dev):
-        self.dev, self.frame, self._open = dev, {}, []
+    def __init__(self, dev, on=True):
+        self.dev, self.on, self.frame, self._open = dev, on, {}, []
 
     def _sync(self):
         if self.dev.type == "cuda":
             torch.cuda.synchronize(self.dev)
 
     def __call__(self, name, sync=True):
+        if not self.on:
+            return self._off
         self._name, self._sync_next = name, sync
         return self
 
@@ -469,19 +474,6 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     return params, variables, stats
 
 
-def _settle_lists(eng, dev, stats, what):
-    """End of a phase on the fused engine: were iterations flagged (on any rank)?  Returns how many took no Adam step -- the lists
-    have been re-sized; the caller runs that many again."""
-    from . import dist as sdist
-    if not sdist.any_rank(eng.check_overflow(), dev):
-        return 0
-    lost = sdist.max_int(eng.skipped_iterations, dev)
-    stats['redone_iterations'] += lost
-    if stats['redone_iterations'] > 100000:
-        raise RuntimeError(f"{what}: the per-tile lists keep overflowing")
-    return max(lost, 1)
-
-
 def _track_frame(params, variables, curr_data, time_idx, tcfg, eng, stats):
     """Tracking iterations of one frame incl. the reference's doubling of the budget when the depth loss stays above
     ``depth_loss_thres`` (scripts/splatam.py:727-735).  Returns the number of iterations run."""
@@ -495,7 +487,6 @@ def _track_frame(params, variables, curr_data, time_idx, tcfg, eng, stats):
     # takes the same Adam step on the pose (FusedEngine.tracking_iteration); the outlier-rejecting loss needs the whole render
     from . import dist as sdist
     world, rank = sdist.world_size(), sdist.get_rank()
-    dev = params['cam_trans'].device
     shard = (rank, world) if (eng is not None and world > 1 and not tcfg['ignore_outlier_depth_loss']) else None
     it, todo, doubled, rounds = 0, num_iters, False, 0
     while todo:
@@ -507,12 +498,14 @@ def _track_frame(params, variables, curr_data, time_idx, tcfg, eng, stats):
         it += todo
         todo = 0
         if eng is not None:
-            lost = _settle_lists(eng, dev, stats, f"frame {time_idx} tracking")
+            lost = eng.settle("pose", sdist)       # (flagged iterations took no Adam step: the lists are re-sized, they are run again)
             if lost:
+                stats['redone_iterations'] += lost
+                if stats['redone_iterations'] > 100000:
+                    raise RuntimeError(f"frame {time_idx} tracking: the per-tile lists keep overflowing")
                 rounds += 1
                 if rounds > 3:
                     raise RuntimeError(f"frame {time_idx}: the per-tile lists overflowed three times in a row")
-                eng.pose_step = max(eng.pose_step - lost, 0)     # (the skipped steps never happened: their bias corrections are taken again)
                 it -= lost
                 todo = lost
                 continue
@@ -599,9 +592,9 @@ def _map_frame(params, variables, curr_data, time_idx, selected, keyframe_list, 
         decided['views'].append(int(iter_time_idx))
         # the reference prunes between backward() and step(); remove_points re-creates the parameters without their
         # gradients, so an iteration on the pruning schedule takes no Adam step
-        on_schedule = prune and it <= pd['stop_after'] and it >= pd['start_after'] and it % pd['prune_every'] == 0
-        # prune_gaussians also resets the opacities on its own schedule (utils/slam_external.py:186-190)
-        resets = prune and it <= pd['stop_after'] and it > 0 and it % pd['reset_opacities_every'] == 0 and pd['reset_opacities']
+        # (prune_gaussians also resets the opacities on its own schedule: utils/slam_external.py:186-190)
+        sched = slam.edit_schedule(it, pd, 'prune_every') if prune else None
+        on_schedule, resets = prune and sched.edits, prune and sched.resets
         if eng is not None and world == 1 and not on_schedule and not resets and not mcfg.get('use_gaussian_splatting_densification'):
             # nothing between backward() and step() in this iteration: one call, the Adam step rides in the last kernel
             eng.mapping_iteration(iter_data, iter_time_idx, mcfg)
@@ -611,8 +604,8 @@ def _map_frame(params, variables, curr_data, time_idx, selected, keyframe_list, 
                 # (with every rank's capacity flag in the bucket's header: a rank whose lists overflowed stops ALL replicas' steps)
                 eng.exchange_gradients(sdist.all_reduce_mean_flat)
             edited = False
-            densifying = bool(mcfg.get('use_gaussian_splatting_densification'))
-            if densifying and it <= mcfg['densify_dict']['stop_after']:
+            dens = slam.edit_schedule(it, mcfg['densify_dict'], 'densify_every') if mcfg.get('use_gaussian_splatting_densification') else None
+            if dens is not None and dens.active:
                 # the colour pass' screen-space gradient is accumulated from THIS iteration's workspace (lists, radii, features
                 # indexed by the rows the render saw): before any row is removed
                 eng.accumulate_mean2d_gradient()
@@ -622,11 +615,9 @@ def _map_frame(params, variables, curr_data, time_idx, selected, keyframe_list, 
                     edited = bool(eng.prune_gaussians(it, pd, scene_radius))
                 if on_schedule:
                     decided['prunes'].append((it, rows, eng.P))
-            if densifying:                                               # scripts/splatam.py:864-867
-                dd = mcfg['densify_dict']
-                dens_sched = it <= dd['stop_after'] and it >= dd['start_after'] and it % dd['densify_every'] == 0
-                edited = bool(eng.densify(it, dd, scene_radius, accumulate=False)) or edited
-                on_schedule = on_schedule or dens_sched                   # re-created parameters carry no gradient: no Adam step
+            if dens is not None:                                         # scripts/splatam.py:864-867
+                edited = bool(eng.densify(it, mcfg['densify_dict'], scene_radius, accumulate=False)) or edited
+                on_schedule = on_schedule or dens.edits                   # re-created parameters carry no gradient: no Adam step
             if edited:
                 sdist.assert_replicated_count(eng.P, f"map edit (frame {time_idx}, iteration {it})", dev)
                 if not eng.lists_known():
@@ -664,25 +655,17 @@ def _map_frame(params, variables, curr_data, time_idx, selected, keyframe_list, 
             it += 1
         todo = 0
         if eng is not None:
-            todo = _settle_lists(eng, dev, stats, f"frame {time_idx} mapping")
+            todo = eng.settle("map", sdist)
             if todo:
+                stats['redone_iterations'] += todo
+                if stats['redone_iterations'] > 100000:
+                    raise RuntimeError(f"frame {time_idx} mapping: the per-tile lists keep overflowing")
                 rounds += 1
                 if rounds > 3:
                     raise RuntimeError(f"frame {time_idx}: the per-tile lists overflowed three times in a row")
-                eng.map_step = max(eng.map_step - todo, 0)
 
 
 def _matrix_to_quaternion(R):
-    """Rotation matrix -> (w, x, y, z), the branch-free form the reference imports from pytorch3d-style helpers
-    (utils/slam_external.py: matrix_to_quaternion) for ``use_gt_poses``."""
-    m = R.reshape(3, 3).double()
-    t = torch.stack([1 + m[0, 0] + m[1, 1] + m[2, 2], 1 + m[0, 0] - m[1, 1] - m[2, 2],
-                     1 - m[0, 0] + m[1, 1] - m[2, 2], 1 - m[0, 0] - m[1, 1] + m[2, 2]]).clamp_min(0).sqrt()
-    cand = torch.stack([
-        torch.stack([t[0] ** 2, m[2, 1] - m[1, 2], m[0, 2] - m[2, 0], m[1, 0] - m[0, 1]]),
-        torch.stack([m[2, 1] - m[1, 2], t[1] ** 2, m[1, 0] + m[0, 1], m[0, 2] + m[2, 0]]),
-        torch.stack([m[0, 2] - m[2, 0], m[1, 0] + m[0, 1], t[2] ** 2, m[2, 1] + m[1, 2]]),
-        torch.stack([m[1, 0] - m[0, 1], m[2, 0] + m[0, 2], m[2, 1] + m[1, 2], t[3] ** 2])])
-    best = int(torch.argmax(t))
-    q = cand[best] / (2.0 * t[best].clamp_min(0.1))
-    return q.float().reshape(1, 4)
+    """``slam.matrix_to_quaternion`` in double, as the [1, 4] float32 row of ``cam_unnorm_rots`` that ``use_gt_poses`` writes
+    (scripts/splatam.py:745-754)."""
+    return slam.matrix_to_quaternion(R.reshape(3, 3).double()).float().reshape(1, 4)

@@ -59,7 +59,7 @@ import operator
 
 import torch
 
-from . import _capi
+from . import _capi, slam
 from .fused import PARAM_ORDER, FusedEngine
 
 # the iteration report's slots (include/splat_hip.h), bound once for the host paths
@@ -318,7 +318,7 @@ class _Session:
             return                                              # (tracking: repeat_tracking re-runs the iteration instead)
         if self.map_edits:
             for eng in {id(e): e for e in self.engines.values()}.values():      # (one engine, filed under every camera size)
-                eng.map_step = max(eng.map_step - int(skipped), 0)
+                eng._take_back("map", skipped)
         for g in opt.param_groups:             # (the pose groups carry state only when bundle adjustment steps them)
             st = opt.state.get(g['params'][0])
             if st is not None and 'step' in st:
@@ -357,7 +357,7 @@ class _Session:
             eng.loss_backward(curr_data, iter_time_idx, cfg, tracking=True, do_ba=do_ba, keep_planes=False, map_grads=bool(self.track_steps_gaussians))
             if rep.stepped is not False:
                 lr, opt, bound = rep.stepped
-                eng.pose_step -= 1
+                eng._take_back("pose", 1)
                 eng.adam_pose(*lr)
                 if opt is not None:                 # (the skipped step counted: take it back, then step)
                     for g in opt.param_groups:
@@ -585,9 +585,9 @@ def prune_gaussians(params, variables, optimizer, iter, prune_dict):
     engine's map, moments and per-Gaussian variables.  On the pruning schedule the reference re-creates every parameter whether or not
     a row goes, so the ``optimizer.step()`` that follows moves none of them: remembered for that step."""
     s = _session
-    on_schedule = iter <= prune_dict['stop_after'] and iter >= prune_dict['start_after'] and iter % prune_dict['prune_every'] == 0
-    resets = iter <= prune_dict['stop_after'] and iter > 0 and iter % prune_dict['reset_opacities_every'] == 0 and prune_dict['reset_opacities']
-    if not (on_schedule or resets):
+    sched = slam.edit_schedule(iter, prune_dict, 'prune_every')
+    on_schedule = sched.edits
+    if not (on_schedule or sched.resets):
         return params, variables
     if s.current is None:
         raise RuntimeError("prune_gaussians() before any get_loss()")

@@ -98,23 +98,6 @@ def _datasets(config, device):
     return datasets.get_dataset(stride=data["stride"], **common), datasets.get_dataset(stride=data["eval_stride"], **common)
 
 
-class _Phases:
-    """Wall time per phase of the fused loop, each bracket closed by a device synchronisation (``timed`` runs only)."""
-
-    def __init__(self, dev, on):
-        self.dev, self.on, self.s = dev, on, {}
-
-    def __call__(self, name, fn, *a, **k):
-        if not self.on:
-            return fn(*a, **k)
-        torch.cuda.synchronize(self.dev)
-        t0 = time.perf_counter()
-        out = fn(*a, **k)
-        torch.cuda.synchronize(self.dev)
-        self.s[name] = self.s.get(name, 0.0) + time.perf_counter() - t0
-        return out
-
-
 def post_splatam_opt(config, engine="fused", dataset=None, eval_dataset=None, num_iters=None, evaluate=True, check_every=500,
                      timed=False, record_losses=False):
     """Runs the refinement ``config`` describes; returns ``(params, variables, stats, path of params.npz)``.
@@ -209,7 +192,7 @@ def post_splatam_opt(config, engine="fused", dataset=None, eval_dataset=None, nu
                     if densifying:
                         rows = int(params['means3D'].shape[0])
                         params, variables = slam.densify(params, variables, optimizer, it, dd)
-                        if it <= dd['stop_after'] and it >= dd['start_after'] and it % dd['densify_every'] == 0:
+                        if slam.edit_schedule(it, dd, 'densify_every').edits:
                             stats['rows'].append((it, rows, int(params['means3D'].shape[0])))
                     optimizer.step()
                     optimizer.zero_grad(set_to_none=True)
@@ -248,6 +231,7 @@ def _fused_loop(params, variables, frames, cam_args, device, n_iters, time_idx, 
     """The iterations on one FusedEngine that owns the map.  Returns (params, variables, engine)."""
     from . import _capi
     from .fused import FusedEngine
+    from .pipeline import _PhaseTimer
     W, H, k_host = cam_args
     cam = slam.setup_camera(W, H, k_host, np.eye(4, dtype=np.float32), device=device)
     for fr in frames:
@@ -257,7 +241,7 @@ def _fused_loop(params, variables, frames, cam_args, device, n_iters, time_idx, 
     eng.keep_map_grads = False                     # (the loop discards its gradients after the step, :320)
     eng.reset_map_optimizer()
     cfg = {'loss': 'gs', 'loss_weights': weights, 'lrs': lrs}
-    phase = _Phases(device, timed)
+    phase = _PhaseTimer(device, on=timed)
     pending = 0                                    # iterations since the capacity flag was last read
     losses = torch.zeros(n_iters, dtype=torch.float32, device=device) if record_losses else None
 
@@ -266,13 +250,11 @@ def _fused_loop(params, variables, frames, cam_args, device, n_iters, time_idx, 
         nonlocal pending
         pending = 0
         rounds = 0
-        while eng.check_overflow():
-            lost = max(int(eng.skipped_iterations), 1)
+        while lost := eng.settle("map"):
             stats['redone_iterations'] += lost
             rounds += 1
             if rounds > 3:
                 raise RuntimeError(f"iteration {it}: the per-tile lists overflowed three times in a row")
-            eng.map_step = max(eng.map_step - lost, 0)
             for _ in range(lost):
                 t = random.randint(0, time_idx)
                 stats['redone_views'].append((it, t))
@@ -283,24 +265,29 @@ def _fused_loop(params, variables, frames, cam_args, device, n_iters, time_idx, 
         t = random.randint(0, time_idx)
         stats['views'].append(t)
         fr = frames[t]
-        accumulating = dd is not None and it <= dd['stop_after']
-        if not accumulating:
+        sched = slam.edit_schedule(it, dd, 'densify_every') if dd is not None else None
+        if sched is None or not sched.active:
             # nothing between backward() and step(): one call, the Adam step rides in the last kernel
-            phase("iteration", eng.mapping_iteration, fr, t, cfg)
+            with phase("iteration"):
+                eng.mapping_iteration(fr, t, cfg)
         else:
-            scheduled = it >= dd['start_after'] and it % dd['densify_every'] == 0
-            phase("loss_backward", eng.loss_backward, fr, t, cfg, tracking=False)
-            phase("means2d_accumulate", eng.accumulate_mean2d_gradient)
-            if scheduled:
+            with phase("loss_backward"):
+                eng.loss_backward(fr, t, cfg, tracking=False)
+            with phase("means2d_accumulate"):
+                eng.accumulate_mean2d_gradient()
+            if sched.edits:
                 settle(it)                         # (densify reads its counts anyway; the selection must not see a flagged iteration's map)
                 rows = eng.P
-            edited = phase("densify", eng.densify, it, dd, scene_radius, accumulate=False)
-            if scheduled:
+            with phase("densify"):
+                edited = eng.densify(it, dd, scene_radius, accumulate=False)
+            if sched.edits:
                 stats['rows'].append((it, rows, eng.P))
             if edited and not eng.lists_known():
-                phase("relearn_lists", eng.relearn_lists, fr, t)
-            if not scheduled:                      # re-created parameters carry no gradient: no Adam step
-                phase("adam", eng.adam_map, lrs)
+                with phase("relearn_lists"):
+                    eng.relearn_lists(fr, t)
+            if not sched.edits:                    # re-created parameters carry no gradient: no Adam step
+                with phase("adam"):
+                    eng.adam_map(lrs)
         if losses is not None:                     # (a device-side copy of the report's slot: nothing is read here)
             losses[it:it + 1].copy_(eng.buf['d_cam'][_capi.SPLAT_REPORT_LOSS:_capi.SPLAT_REPORT_LOSS + 1])
         pending += 1
@@ -308,7 +295,7 @@ def _fused_loop(params, variables, frames, cam_args, device, n_iters, time_idx, 
             settle(it)
         if it + 1 == EVAL_AT:
             stats['eval_7k'] = run_eval({k: v.detach().clone() for k, v in eng.params.items()}, eng, "eval_7k")
-    stats['phase_s'] = dict(phase.s)
+    stats['phase_s'] = {k: 1e-3 * ms for k, ms in phase.frame.items()}
     stats['engine'] = eng
     if losses is not None:
         stats['losses'] = losses.cpu().tolist()

@@ -45,6 +45,7 @@ per-iteration host sync).  The rasterizer is always the HIP one
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -570,18 +571,37 @@ def remove_points(to_remove, params, variables, optimizer):
     return params, variables
 
 
+EditSchedule = namedtuple("EditSchedule", "active edits resets opacity_threshold remove_big")
+
+
+def edit_schedule(it, d, every):
+    """What iteration ``it`` does to the map under ``d``, a ``pruning_dict`` (``every`` = 'prune_every') or a ``densify_dict``
+    ('densify_every'), as /root/reference/utils/slam_external.py:169-240 decide it -- the one statement of these rules for every
+    loop and engine.  ``active``: the dictionary still applies; ``edits``: rows go / come, which re-creates the parameters, so this
+    iteration takes no Adam step; ``resets``: the opacities are reset; rows less opaque than ``opacity_threshold`` go, and with
+    ``remove_big`` those larger than 0.1 x the scene radius."""
+    active = it <= d['stop_after']
+    return EditSchedule(active, active and it >= d['start_after'] and it % d[every] == 0,
+                        active and it > 0 and it % d['reset_opacities_every'] == 0 and bool(d['reset_opacities']),
+                        d['final_removal_opacity_threshold'] if it == d['stop_after'] else d['removal_opacity_threshold'],
+                        it >= d['remove_big_after'])
+
+
+def _faint_or_big(params, variables, sched):
+    """The rows ``sched`` removes by opacity and size."""
+    to_remove = (torch.sigmoid(params['logit_opacities']) < sched.opacity_threshold).squeeze(-1)
+    if sched.remove_big:
+        to_remove = to_remove | (torch.exp(params['log_scales']).max(dim=1).values > 0.1 * variables['scene_radius'])
+    return to_remove
+
+
 def prune_gaussians(params, variables, optimizer, iter, prune_dict):
     """Opacity / size pruning on the schedule of ``prune_dict`` (+ the optional opacity reset)."""
-    if iter <= prune_dict['stop_after']:
-        if iter >= prune_dict['start_after'] and iter % prune_dict['prune_every'] == 0:
-            thr = prune_dict['final_removal_opacity_threshold'] if iter == prune_dict['stop_after'] \
-                else prune_dict['removal_opacity_threshold']
-            to_remove = (torch.sigmoid(params['logit_opacities']) < thr).squeeze(-1)
-            if iter >= prune_dict['remove_big_after']:
-                to_remove = to_remove | (torch.exp(params['log_scales']).max(dim=1).values > 0.1 * variables['scene_radius'])
-            params, variables = remove_points(to_remove, params, variables, optimizer)
-        if iter > 0 and iter % prune_dict['reset_opacities_every'] == 0 and prune_dict['reset_opacities']:
-            params = _reset_opacities(params, optimizer)
+    sched = edit_schedule(iter, prune_dict, 'prune_every')
+    if sched.edits:
+        params, variables = remove_points(_faint_or_big(params, variables, sched), params, variables, optimizer)
+    if sched.resets:
+        params = _reset_opacities(params, optimizer)
     return params, variables
 
 
@@ -615,11 +635,12 @@ def densify(params, variables, optimizer, iter, densify_dict):
     and size; optional opacity reset.  Draws from the global torch RNG exactly where the reference does.
     ``variables['timestep']``, when present, is extended by the cloned / split rows' own values, as the refinement script's copy of
     this function does (utils/gs_external.py:202-205, :219-222; utils/slam_external.py's never extends it and fails in remove_points)."""
-    if iter > densify_dict['stop_after']:
+    sched = edit_schedule(iter, densify_dict, 'densify_every')
+    if not sched.active:
         return params, variables
     variables = accumulate_mean2d_gradient(variables)
     thr = densify_dict['grad_thresh']
-    if iter >= densify_dict['start_after'] and iter % densify_dict['densify_every'] == 0:
+    if sched.edits:
         grads = variables['means2D_gradient_accum'] / variables['denom']
         grads[grads.isnan()] = 0.0
         small = torch.exp(params['log_scales']).max(dim=1).values <= 0.01 * variables['scene_radius']
@@ -647,13 +668,8 @@ def densify(params, variables, optimizer, iter, densify_dict):
             variables[k] = torch.zeros(n_pts, device=dev)
         to_remove = torch.cat((to_split, torch.zeros(n * int(to_split.sum()), dtype=torch.bool, device=dev)))
         params, variables = remove_points(to_remove, params, variables, optimizer)
-        op_thr = densify_dict['final_removal_opacity_threshold'] if iter == densify_dict['stop_after'] \
-            else densify_dict['removal_opacity_threshold']
-        to_remove = (torch.sigmoid(params['logit_opacities']) < op_thr).squeeze(-1)
-        if iter >= densify_dict['remove_big_after']:
-            to_remove = to_remove | (torch.exp(params['log_scales']).max(dim=1).values > 0.1 * variables['scene_radius'])
-        params, variables = remove_points(to_remove, params, variables, optimizer)
-    if iter > 0 and iter % densify_dict['reset_opacities_every'] == 0 and densify_dict['reset_opacities']:
+        params, variables = remove_points(_faint_or_big(params, variables, sched), params, variables, optimizer)
+    if sched.resets:
         params = _reset_opacities(params, optimizer)
     return params, variables
 

@@ -838,7 +838,8 @@ def test_tile_row_sharded_tracking_equals_whole_frame_tracking(lists, world, fir
 def test_flagged_iterations_take_no_adam_step_and_are_counted():
     """A capacity flag raised on the device (per-tile lists that did not fit) holds back every Adam step until the host has dealt
     with it (include/splat_hip.h, d_cam[12]): the map, the pose, the moments and the best-candidate record stay as they were, d_cam[21]
-    counts the iterations, check_overflow() reports them (skipped_iterations) and re-sizes the lists; the loop then goes on."""
+    counts the iterations, settle() reports them (skipped_iterations), re-sizes the lists and takes the host-side step count back to
+    where it stood before them; the loop then goes on."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
     params, variables, frame, cam = _scene(12000, 256, 192, seed=21)
@@ -852,6 +853,8 @@ def test_flagged_iterations_take_no_adam_step_and_are_counted():
     good = (eng.tile_stride, eng.max_list_hint)
     snap = {k: v.detach().clone() for k, v in p.items()}
     m_snap = {k: eng.exp_avg[k].clone() for k in eng.exp_avg}
+    steps_before = eng.map_step
+    assert steps_before == 2
     eng.tile_stride, eng.max_list_hint = 64, 40                     # buckets far too small: every list overflows
     for _ in range(3):
         eng.mapping_iteration(frame, 1, mcfg)                       # Adam inside the per-Gaussian backward kernel: gated
@@ -865,16 +868,20 @@ def test_flagged_iterations_take_no_adam_step_and_are_counted():
         assert torch.equal(p[k].detach(), snap[k]), k
     for k in m_snap:
         assert torch.equal(eng.exp_avg[k], m_snap[k]), k
-    assert eng.check_overflow() and eng.skipped_iterations == 4 and eng.tile_stride == 0
-    eng.map_step -= eng.skipped_iterations
+    assert eng.map_step == steps_before + 4
+    assert eng.settle("map") == 4 and eng.skipped_iterations == 4 and eng.tile_stride == 0
+    assert eng.map_step == steps_before
     eng.mapping_iteration(frame, 1, mcfg)                           # exact lists: valid again, steps again
-    assert not eng.check_overflow() and eng.skipped_iterations == 0 and eng.tile_stride > 0
+    assert eng.settle("map") == 0 and eng.map_step == steps_before + 1          # a clean phase: nothing is taken back
+    assert eng.skipped_iterations == 0 and eng.tile_stride > 0
     assert not torch.equal(p['means3D'].detach(), snap['means3D'])
     # tracking: the pose's step rides in the last kernel of the iteration (and as a kernel of its own)
     eng.begin_tracking(1)
     eng.tracking_iteration(frame, tcfg)
     torch.cuda.synchronize()
     pose = (p['cam_unnorm_rots'].detach().clone(), p['cam_trans'].detach().clone(), eng.buf['pose_state'].clone())
+    steps_before = eng.pose_step
+    assert steps_before == 1
     eng.tile_stride, eng.max_list_hint = 64, 40
     eng.tracking_iteration(frame, tcfg)
     eng.loss_backward(frame, 1, tcfg, tracking=True)
@@ -882,11 +889,12 @@ def test_flagged_iterations_take_no_adam_step_and_are_counted():
     torch.cuda.synchronize()
     assert torch.equal(p['cam_unnorm_rots'].detach(), pose[0]) and torch.equal(p['cam_trans'].detach(), pose[1])
     assert torch.equal(eng.buf['pose_state'], pose[2])
-    assert eng.check_overflow() and eng.skipped_iterations == 2
-    eng.pose_step -= 2
+    assert eng.settle("pose") == 2 and eng.skipped_iterations == 2
+    assert eng.pose_step == steps_before
     eng.tracking_iteration(frame, tcfg)
     torch.cuda.synchronize()
-    assert not torch.equal(p['cam_trans'].detach(), pose[1]) and not eng.check_overflow()
+    assert not torch.equal(p['cam_trans'].detach(), pose[1])
+    assert eng.settle("pose") == 0 and eng.pose_step == steps_before + 1
     assert (eng.tile_stride, eng.max_list_hint)[0] > 0 and good[0] > 0
 
 

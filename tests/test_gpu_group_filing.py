@@ -192,10 +192,11 @@ def test_a_full_group_bucket_raises_the_overflow_flag_and_gates_adam():
     assert int(rep.view(torch.int32)[_capi.SPLAT_REPORT_STATUS + _capi.SPLAT_STATUS_OVERFLOW]) == 1      # the status snapshot: overflow
     for k in snap:
         assert torch.equal(p[k].detach(), snap[k]), k
-    assert eng.check_overflow() and eng.skipped_iterations == 1 and eng.tile_stride == 0
-    eng.map_step -= eng.skipped_iterations
+    steps_before = eng.map_step - 1                                 # (the gated iteration advanced the host-side count)
+    assert eng.settle("map") == 1 and eng.skipped_iterations == 1 and eng.tile_stride == 0
+    assert eng.map_step == steps_before == 2
     eng.mapping_iteration(frame, 1, cfg)
-    assert not eng.check_overflow()
+    assert eng.settle("map") == 0 and eng.map_step == steps_before + 1
     assert not torch.equal(p['means3D'].detach(), snap['means3D'])
 
 

@@ -228,8 +228,7 @@ def test_buckets_learnt_on_one_pose_hold_or_flag_on_the_others():
             for key in KEYS:
                 assert torch.equal(p[key].detach(), snap[0][key]), (t, key)
                 assert torch.equal(eb.exp_avg[key], snap[1][key]) and torch.equal(eb.exp_avg_sq[key], snap[2][key]), (t, key)
-            assert eb.check_overflow() and eb.skipped_iterations == 1
-            eb.map_step -= 1
+            assert eb.settle("map") == 1 and eb.skipped_iterations == 1
         else:
             held += 1
             assert torch.equal(eb.buf['out6'], exact[i]['out6']), f"view {t}: bucketed lists render differently from exact lists"

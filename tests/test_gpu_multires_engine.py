@@ -208,8 +208,7 @@ def test_overflow_protocol_is_per_camera():
     torch.cuda.synchronize()
     assert (eng.H, eng.W) == SIZES[0] and eng.capacity == 100
     assert all(torch.equal(before[k], eng.params[k].detach()) for k in PARAM_KEYS)          # no Adam step on truncated lists
-    assert eng.check_overflow() and eng.skipped_iterations == 1 and eng.capacity > 100
-    eng.map_step -= 1
+    assert eng.settle("map") == 1 and eng.skipped_iterations == 1 and eng.capacity > 100 and eng.map_step == 0
     for size in SIZES[1:]:
         eng.select_camera(cams[size])
         assert (eng.tile_stride, eng.max_list_hint, eng.capacity, eng.buf['keys'].data_ptr()) == others[size], size

@@ -255,6 +255,25 @@ def test_fused_driver_takes_no_opacity_step_on_a_reset_iteration(tmp_path):
         assert not torch.equal(p4[k], p3[k].detach()), k
 
 
+def test_fused_driver_runs_flagged_iterations_again(tmp_path, monkeypatch):
+    """The engine starts the loop on per-tile buckets far too small (stride 64, longest list 40: a flag, not a fault), the flag is
+    read every 2 iterations: the iterations the device skipped are run again as plain ones, each recorded with the frame it drew, and
+    the mapping optimizer's step count ends at the number of iterations -- the skipped steps were taken back."""
+    from splatam_amd import fused
+
+    class SmallBuckets(fused.FusedEngine):
+        def __init__(self, *args, **kwargs):
+            super().__init__(*args, **kwargs)
+            self.tile_stride, self.max_list_hint = 64, 40
+    monkeypatch.setattr(fused, "FusedEngine", SmallBuckets)
+    cfg, params, variables, stats, path = run_fused("dens", tmp_path, evaluate=False, num_iters=6, check_every=2)
+    print(f"redone iterations {stats['redone_iterations']}, views {stats['redone_views']}, map_step {stats['engine'].map_step}")
+    assert stats['redone_iterations'] > 0
+    assert len(stats['redone_views']) == stats['redone_iterations']
+    assert stats['engine'].map_step == 6
+    assert not stats['engine'].check_overflow(grow=False)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the C ABI: additions inside version 17
 # ---------------------------------------------------------------------------------------------------------------------------------

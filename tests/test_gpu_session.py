@@ -162,6 +162,34 @@ def test_a_densification_size_of_its_own_is_written_from_the_raw_frame(map_every
     assert stats['num_gaussians'][0] <= 32 * 48                    # the first point cloud came from the densification frame
 
 
+def test_a_flagged_phase_is_run_again_by_the_frame_loop():
+    """Per-tile buckets forced far too small between two frames (stride 64, longest list 40, on a map of one Gaussian per pixel: the
+    means of test_gpu_fused.py::test_flagged_iterations_take_no_adam_step_and_are_counted -- a flag, not a fault): every tracking
+    iteration of frame 1 is flagged and takes no Adam step, ``FusedEngine.settle`` takes the pose optimizer's step count back, and the
+    loop runs the phase again on exact lists.  The frame then reports the configured number of iterations, both step counts stand
+    where an undisturbed frame leaves them, and no flag is left behind.  (The mapping optimizer's count of such a frame is 3, not 4:
+    iteration 0 is on the Replica pruning schedule -- ``start_after=0, prune_every=20`` -- and an iteration that prunes takes no Adam
+    step; frame 0, which nothing disturbs, is held to the same number.)"""
+    from splatam_amd import pipeline, session
+    W, H, f = 256, 192, 224.0
+    ds = pipeline.SyntheticRGBDSequence(12000, W, H, f, f, W / 2 - 0.5, H / 2 - 0.5, num_frames=2, seed=2, step_m=0.012, step_deg=0.4)
+    cfg = pipeline.replica_config(tracking_iters=4, mapping_iters=4)
+    seed_everything(cfg['seed'])
+    with session.SlamSession(cfg, 2, engine="fused") as s:
+        s.add_frame(*ds[0])
+        eng = s.engine
+        assert s.stats['redone_iterations'] == 0 and eng.map_step == 3
+        eng.tile_stride, eng.max_list_hint = 64, 40
+        r = s.add_frame(*ds[1])
+        stats = s.stats
+        print(f"redone iterations {stats['redone_iterations']}, pose_step {eng.pose_step}, map_step {eng.map_step}")
+        assert stats['redone_iterations'] > 0                       # the premise: a phase of the loop was flagged and run again
+        assert r['tracking_iters'] == 4 and stats['decisions'][1]['tracking_iters'] == 4
+        assert eng.pose_step == 4 and eng.map_step == 3
+        assert not eng.check_overflow(grow=False)
+        s.finish()
+
+
 def test_an_early_finish_and_a_frame_too_many():
     n = GOLD["base/frames/color"].shape[0]
     params, stats, _, _ = run_base(raw=True, num_frames=n, frames=n - 3)
