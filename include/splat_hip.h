@@ -838,6 +838,55 @@ typedef struct SplatViewArgs {
 int splat_view_camera(const SplatViewArgs *view, void *stream);
 int splat_view_finish(const SplatViewArgs *view, void *stream);
 
+/* The mesh layer (csrc/tsdf.hip, arithmetic in csrc/tsdf_math.h; added within ABI 17): composites of the map at known poses fused into
+ * a truncated signed distance volume on the device, and the volume's zero surface as a triangle mesh.
+ *
+ * The volume: grid points p(i, j, k) = origin + voxel (i, j, k), nx ny nz of them (fewer than 2^40), x fastest; five float32 arrays of
+ * that many elements in the caller's memory: tsdf (reset 1), weight (reset 0), r, g, b (reset 0).  splat_tsdf_bytes: the bytes of
+ * all five together (0 for a volume that would be refused).  splat_tsdf_reset: one launch.
+ *
+ * splat_tsdf_integrate: one launch per view.  For every grid point: pc = w2c p (w2c: 16 device floats, row-major, as
+ * splat_view_camera writes them); skip unless pc.z > 0; the pixel is (floor(fx pc.x / pc.z + cx + 0.5), floor(fy pc.y / pc.z + cy + 0.5)),
+ * skip outside the image; s = out6's silhouette there, skip unless s > sil_thres; d = depth / s, skip unless d > 0 and (depth_max > 0)
+ * d <= depth_max; sdf = d - pc.z, skip when sdf < -trunc; f = min(1, sdf / trunc); W' = W + 1, tsdf = (tsdf W + f) / W', r / g / b the
+ * same running mean of clamp(rgb / s, 0, 1); W = min(W', weight_max) when weight_max > 0.  Bricks of the grid outside the view's
+ * frustum are not touched; 16-byte volume accesses where nx is a multiple of 4 and the five arrays start on 16 bytes, a scalar path
+ * otherwise; out6 ([>= 5][height][width]) may be a view into a larger buffer.  `skip` (device int32, or NULL): when it holds a
+ * non-zero value -- the truncation status of the render behind out6 -- the launch leaves the volume as it is and adds 1 to `skipped`
+ * (device int32): nothing is read on the host per view.
+ *
+ * splat_tsdf_triangles: marching tetrahedra on Kuhn's split (six tetrahedra along the paths c -> c + e_a -> c + e_a + e_b -> c + (1, 1, 1))
+ * of every cell whose eight corners have weight >= min_weight; a corner is inside when tsdf < 0.  Each triangle is three VERTEX KEYS,
+ * key = linear(a) 8 + (dx + 2 dy + 4 dz) for the vertex on the grid edge from corner a to a + (dx, dy, dz), wound with the normal
+ * towards positive tsdf (by the sign pattern alone; zero-area triangles at corners that are exactly zero are kept: the surface stays
+ * closed).  keys: [capacity][3] int64; count: one device int64 that receives the number of triangles the volume asks for, whether or
+ * not they fit (the call zeroes it first); nothing is written at or beyond `capacity`, in no particular order below it.
+ * splat_tsdf_vertices: vertices [n][3] (and colors [n][3], or NULL) of n keys: p(a) + t (p(b) - p(a)) with t = f_a / (f_a - f_b), the
+ * colour interpolated alike.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for non-positive sizes, voxel or trunc, NULL
+ * pointers, and nx ny nz >= 2^40. */
+typedef struct SplatTsdfVolume {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float voxel, trunc;
+    float *tsdf, *weight, *r, *g, *b;
+} SplatTsdfVolume;
+typedef struct SplatTsdfView {
+    int32_t width, height;
+    float fx, fy, cx, cy;
+    float sil_thres, depth_max, weight_max;
+    const float *out6;
+    const float *w2c;
+    const int32_t *skip;
+    int32_t *skipped;
+} SplatTsdfView;
+size_t splat_tsdf_bytes(const SplatTsdfVolume *volume);
+int splat_tsdf_reset(const SplatTsdfVolume *volume, void *stream);
+int splat_tsdf_integrate(const SplatTsdfVolume *volume, const SplatTsdfView *view, void *stream);
+int splat_tsdf_triangles(const SplatTsdfVolume *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
+int splat_tsdf_vertices(const SplatTsdfVolume *volume, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream);
+
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup
  * wall-clock stamps into the buffer of splat_debug_stamps, 2 = stage the batches but visit nothing, 4 = no accumulator atomics,

@@ -140,9 +140,20 @@ class SplatViewArgs(C.Structure):
                 ("lut", _fp), ("rgb8", _fp), ("points", _fp), ("colors", _fp)]
 
 
+class SplatTsdfVolume(C.Structure):        # (added within ABI 17: the mesh layer, csrc/tsdf.hip)
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float),
+                ("tsdf", _fp), ("weight", _fp), ("r", _fp), ("g", _fp), ("b", _fp)]
+
+
+class SplatTsdfView(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("sil_thres", C.c_float), ("depth_max", C.c_float), ("weight_max", C.c_float),
+                ("out6", _fp), ("w2c", _fp), ("skip", _fp), ("skipped", _fp)]
+
+
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
-                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs)
+                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -190,6 +201,7 @@ EXPORTS = (
     "splat_frame_prepare", "splat_frame_ingest", "splat_frame_ingest_planes",
     "splat_view_camera", "splat_view_finish",
     "splat_iter_loss_backward_ex", "splat_iter_mapping_step_ex",
+    "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
 )
 
 _lib = None
@@ -307,6 +319,17 @@ def lib():
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = [C.POINTER(SplatViewArgs), _fp]
+    vol = C.POINTER(SplatTsdfVolume)
+    L.splat_tsdf_bytes.restype = C.c_size_t
+    L.splat_tsdf_bytes.argtypes = [vol]
+    L.splat_tsdf_reset.restype = C.c_int
+    L.splat_tsdf_reset.argtypes = [vol, _fp]
+    L.splat_tsdf_integrate.restype = C.c_int
+    L.splat_tsdf_integrate.argtypes = [vol, C.POINTER(SplatTsdfView), _fp]
+    L.splat_tsdf_triangles.restype = C.c_int
+    L.splat_tsdf_triangles.argtypes = [vol, C.c_float, _fp, C.c_int64, _fp, _fp]
+    L.splat_tsdf_vertices.restype = C.c_int
+    L.splat_tsdf_vertices.argtypes = [vol, _fp, C.c_int64, _fp, _fp, _fp]
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int

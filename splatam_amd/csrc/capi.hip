@@ -60,6 +60,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatAdamMap); SPLAT_SIZEOF_CASE(SplatPoseAdam); SPLAT_SIZEOF_CASE(SplatMapStore); SPLAT_SIZEOF_CASE(SplatAddArgs);
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
+    SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -420,6 +421,40 @@ int splat_view_finish(const SplatViewArgs *v, void *stream) {
     if (v->points && (!v->w2c || !(v->fx > 0.0) || !(v->fy > 0.0))) return SPLAT_E_INVALID;
     if (!v->rgb8 && !v->points && !v->colors) return SPLAT_OK;
     return check(launch_view_finish(*v, (hipStream_t)stream));
+}
+
+// the mesh layer (csrc/tsdf.hip)
+static bool valid_tsdf_grid(const SplatTsdfVolume *v) {
+    if (!v || v->nx <= 0 || v->ny <= 0 || v->nz <= 0 || !(v->voxel > 0.f) || !(v->trunc > 0.f)) return false;
+    return (long long)v->nx * v->ny < (1ll << 40) && (long long)v->nx * v->ny * (long long)v->nz < (1ll << 40);
+}
+static bool valid_tsdf_volume(const SplatTsdfVolume *v) {
+    return valid_tsdf_grid(v) && v->tsdf && v->weight && v->r && v->g && v->b;
+}
+
+size_t splat_tsdf_bytes(const SplatTsdfVolume *v) {
+    return valid_tsdf_grid(v) ? 5 * sizeof(float) * (size_t)v->nx * (size_t)v->ny * (size_t)v->nz : 0;
+}
+
+int splat_tsdf_reset(const SplatTsdfVolume *v, void *stream) {
+    if (!valid_tsdf_volume(v)) return SPLAT_E_INVALID;
+    return check(launch_tsdf_reset(*v, (hipStream_t)stream));
+}
+
+int splat_tsdf_integrate(const SplatTsdfVolume *v, const SplatTsdfView *w, void *stream) {
+    if (!valid_tsdf_volume(v) || !w || w->width <= 0 || w->height <= 0 || (long long)w->width * w->height > 0x3fffffffLL) return SPLAT_E_INVALID;
+    if (!w->out6 || !w->w2c || (w->skip && !w->skipped)) return SPLAT_E_INVALID;
+    return check(launch_tsdf_integrate(*v, *w, (hipStream_t)stream));
+}
+
+int splat_tsdf_triangles(const SplatTsdfVolume *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
+    if (!valid_tsdf_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    return check(launch_tsdf_triangles(*v, min_weight, keys, (long long)capacity, count, (hipStream_t)stream));
+}
+
+int splat_tsdf_vertices(const SplatTsdfVolume *v, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream) {
+    if (!valid_tsdf_volume(v) || n < 0 || (n > 0 && (!keys || !vertices))) return SPLAT_E_INVALID;
+    return check(launch_tsdf_vertices(*v, keys, (long long)n, vertices, colors, (hipStream_t)stream));
 }
 
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }

@@ -102,6 +102,11 @@ hipError_t launch_frame_ingest_planes(int cw, int ch, const uint8_t *rgb, int zw
 // and a point cloud
 hipError_t launch_view_camera(const SplatViewArgs &v, hipStream_t s);
 hipError_t launch_view_finish(const SplatViewArgs &v, hipStream_t s);
+// tsdf.hip: rendered depth fused into a truncated signed distance volume, and the volume's zero surface as vertex keys and vertices
+hipError_t launch_tsdf_reset(const SplatTsdfVolume &v, hipStream_t s);
+hipError_t launch_tsdf_integrate(const SplatTsdfVolume &v, const SplatTsdfView &w, hipStream_t s);
+hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, hipStream_t s);
+hipError_t launch_tsdf_vertices(const SplatTsdfVolume &v, const int64_t *keys, long long n, float *vertices, float *colors, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

@@ -40,3 +40,34 @@ def export_params_ply(params, path):
         v = params[k]
         return v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
     return save_ply(path, a('means3D'), a('log_scales'), a('unnorm_rotations'), a('rgb_colors'), a('logit_opacities'))
+
+
+def save_mesh_ply(path, vertices, faces, colors=None):
+    """A triangle mesh as binary little-endian PLY: ``vertices`` [V, 3] as float x, y, z, ``colors`` [V, 3] in 0..1 as uchar red, green,
+    blue (rounded to nearest; left out when None), ``faces`` [F, 3] as ``list uchar int vertex_indices``.  What MeshLab, Open3D and
+    trimesh open; written without the ``plyfile`` package, the tables in one piece each."""
+    vertices = np.ascontiguousarray(np.asarray(vertices, dtype='<f4').reshape(-1, 3))
+    faces = np.asarray(faces).reshape(-1, 3)
+    if faces.size and (faces.min() < 0 or faces.max() >= vertices.shape[0]):
+        raise ValueError("faces index vertices that do not exist")
+    fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % vertices.shape[0]
+    if colors is not None:
+        colors = np.asarray(colors, dtype=np.float32).reshape(-1, 3)
+        if colors.shape[0] != vertices.shape[0]:
+            raise ValueError(f"{colors.shape[0]} colours for {vertices.shape[0]} vertices")
+        fields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+        header += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % faces.shape[0]
+    vt = np.zeros(vertices.shape[0], dtype=fields)
+    vt['x'], vt['y'], vt['z'] = vertices[:, 0], vertices[:, 1], vertices[:, 2]
+    if colors is not None:
+        bytes3 = np.rint(np.clip(np.nan_to_num(colors), 0.0, 1.0) * 255.0).astype(np.uint8)
+        vt['red'], vt['green'], vt['blue'] = bytes3[:, 0], bytes3[:, 1], bytes3[:, 2]
+    ft = np.zeros(faces.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    ft['n'], ft['v'] = 3, faces
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vt.tobytes())
+        f.write(ft.tobytes())
+    return path

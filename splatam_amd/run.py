@@ -79,11 +79,12 @@ def check_supported(config):
         raise SystemExit(f"config['mean_sq_dist_method'] = {config.get('mean_sq_dist_method')!r}: only \"projective\" is supported")
 
 
-def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False):
+def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False, mesh=False):
     """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``.  The reference's four
     checkpoint keys (``save_checkpoints``, ``checkpoint_interval``, ``load_checkpoint``, ``checkpoint_time_idx``) are honoured under
     ``workdir/run_name``; ``exact_checkpoints=True`` makes every checkpoint ``save_checkpoints`` writes an exact one (``session<t>.npz``
-    beside the pair) and ``resume_exact=t`` continues from the exact checkpoint of frame ``t`` there (``pipeline.rgbd_slam``)."""
+    beside the pair) and ``resume_exact=t`` continues from the exact checkpoint of frame ``t`` there (``pipeline.rgbd_slam``).
+    ``mesh=True`` (or a dict of ``mesh.mesh_from_params`` keywords): ``mesh.ply`` next to ``params.npz``, from the saved map."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -130,6 +131,10 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
         out['gt_w2c_all_frames'] = np.stack([torch.linalg.inv(dataset.transformed_poses[t]).cpu().numpy() for t in range(n)], axis=0)
         out['keyframe_time_indices'] = np.array(stats['keyframe_time_indices'])
         path = pipeline.save_params(out, os.path.join(config["workdir"], config["run_name"]))
+        if mesh:
+            from .mesh import mesh_from_params
+            stats['mesh'] = os.path.join(os.path.dirname(path), "mesh.ply")
+            mesh_from_params(path, stats['mesh'], device=device, **(mesh if isinstance(mesh, dict) else {}))
     finally:
         dataset.close()
     return params, variables, stats, path
@@ -145,12 +150,13 @@ def main(argv=None):
                         help="continue at frame T + 1 from the exact checkpoint (session<T>.npz) under workdir/run_name")
     parser.add_argument("--exact-checkpoints", action="store_true",
                         help="with config['save_checkpoints']: also write session<t>.npz, the state --resume-exact continues from")
+    parser.add_argument("--mesh", action="store_true", help="write mesh.ply next to params.npz (python -m splatam_amd.mesh on the saved map)")
     args = parser.parse_args(argv)
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
-                            exact_checkpoints=args.exact_checkpoints)
+                            exact_checkpoints=args.exact_checkpoints, mesh=args.mesh)
     ev = stats.get('eval')
     if ev is not None:
         print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"

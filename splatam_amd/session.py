@@ -554,6 +554,32 @@ class SlamSession:
             pose = torch.as_tensor(pose, dtype=torch.float32)
         return self._step(time_idx, curr, tracking_curr, densify_curr, pose, owned=dev.type == "cuda")
 
+    # ------------------------------------------------------------------ a mesh of the map (csrc/tsdf.hip)
+    def extract_mesh(self, frames=None, size=None, path=None, **kwargs):
+        """A triangle mesh of the map as it is now: ``mesh.extract_mesh`` at the estimated poses of ``frames`` (time indices; default
+        the keyframes so far), rendered at ``size`` = (height, width) (default the loop's) with the loop's intrinsics scaled to it.
+        Further keywords (``voxel_size``, ``trunc``, ``bounds``, ``max_bytes``, ``sil_thres``, ``depth_max``, ``weight_max``,
+        ``min_weight``) go to ``mesh.extract_mesh``.  ``path``: also written there as a PLY.  Returns the ``Mesh`` (on the device).
+        Between frames and after ``finish()``; engine "fused" only.  The map, the optimiser state and the loop's cameras are left
+        as they were."""
+        if not self.fused:
+            raise NotImplementedError("extract_mesh needs engine='fused'")
+        if self.engine is None:
+            raise RuntimeError("extract_mesh before the first frame: there is no map")
+        from . import mesh as mesh_mod
+        H, W = (self.cam.image_height, self.cam.image_width) if size is None else (int(size[0]), int(size[1]))
+        k = self.intrinsics.detach().cpu().double().numpy()
+        k_view = (float(k[0][0]) * W / self.cam.image_width, float(k[1][1]) * H / self.cam.image_height,
+                  float(k[0][2]) * W / self.cam.image_width, float(k[1][2]) * H / self.cam.image_height)
+        if frames is None:
+            frames = list(self.keyframe_time_indices) or list(range(self.frames_seen))
+        with torch.no_grad():
+            result = mesh_mod.extract_mesh(self.engine, frames, (W, H), k_view, first_w2c=self.first_frame_w2c.contiguous(), **kwargs)
+        if path is not None:
+            from .export import save_mesh_ply
+            save_mesh_ply(path, result.vertices.cpu().numpy(), result.faces.cpu().numpy(), result.colors.cpu().numpy())
+        return result
+
     # ------------------------------------------------------------------ a picture of the map (csrc/view.hip)
     def render_view(self, w2c=None, follow=False, time_idx=None, size=None, intrinsics=None, mode="color", background=(0.0, 0.0, 0.0),
                     to_host=False, **kwargs):
