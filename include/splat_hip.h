@@ -887,6 +887,57 @@ int splat_tsdf_integrate(const SplatTsdfVolume *volume, const SplatTsdfView *vie
 int splat_tsdf_triangles(const SplatTsdfVolume *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
 int splat_tsdf_vertices(const SplatTsdfVolume *volume, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream);
 
+/* The mesh score layer (csrc/meshscore.hip, arithmetic in csrc/meshscore_math.h; added within ABI 17): points sampled uniformly by area
+ * on a triangle mesh, and the exact nearest target of every query through a uniform grid -- what accuracy, completion and completion
+ * ratio of a reconstruction against a ground-truth mesh are made of.
+ *
+ * splat_mesh_areas: area [num_faces] double of faces [num_faces][3] int32 over vertices [num_vertices][3] float32: half the norm of
+ * (b - a) x (c - a), formed in double from the float32 vertices; 0 for a face with an index outside the vertices or an area that is
+ * not > 0.  The caller forms the INCLUSIVE prefix sum.
+ * splat_mesh_sample: sample i of n (points [n][3] float32, face [n] int32): (u0, u1, u2) = Philox4x32-10 of the counter (i, 0) under the
+ * key `seed`, words 0..2 as (word >> 8) 2^-24; the face is the first whose prefix exceeds (double)u0 prefix[num_faces - 1] (a zero-area
+ * face is never chosen); (u1, u2) become (1 - u1, 1 - u2) when u1 + u2 > 1; the point is (a + u1 (b - a)) + u2 (c - a) in float32, one
+ * operation per step.  Sample i depends on (seed, i) alone.  A mesh without area: face -1, point 0.
+ *
+ * SplatNnGrid: cells of edge `cell` from `lo`, dims[0] dims[1] dims[2] <= SPLAT_NN_MAX_CELLS of them; the cell of a point is
+ * floor((p - lo) / cell) per axis in float32, clamped into the grid (so every point has one); key = (z dims[1] + y) dims[0] + x.
+ * splat_nn_cell_keys: key [n] int32 of points [n][3] -- targets and queries alike; the caller sorts both by key (a stable sort).
+ * splat_nn_cell_starts: from the `count` targets' sorted keys and the sort's permutation `order` (sorted position -> original index):
+ * records [count] of 16 bytes (x, y, z float32, original index int32; 16-byte aligned) and start [cells + 1] int32, start[k] the first
+ * sorted position with key >= k.  The grid's `records` and `start` are those two arrays.
+ * splat_nn_query: for query order[i] (order == NULL: i), i < n: dist2 and index of its nearest target, stored at the query's ORIGINAL
+ * position.  d2 = (dx dx + dy dy) + dz dz in float32; the least d2 wins, the lowest original index among equals.  The search walks
+ * Chebyshev shells of cells outward from the query's (clamped) cell and stops only when best d2 < b^2 (1 - 2^-20), b the query's
+ * distance to the complement of the box of the shells searched, with its planes moved towards the query by 4 2^-24 of their offset
+ * from `lo` (the float32 rounding of the cell assignment) and b = 0 while the query is outside the box or b <= 1e-15 -- or when the
+ * shells cover the grid.  Exact: the result is that of comparing every target, no distance clamp.  No target: dist2 +inf, index -1.  `account`
+ * (or NULL): [n][2] int32, candidates evaluated and shells walked per query.
+ * splat_nn_reduce: row[0..3] = (sum of d, count of d < threshold, max of d, n) over d = sqrt((double)dist2[i]) as doubles, through
+ * `partials` (3 SPLAT_NN_REDUCE_ROWS doubles of scratch) in a fixed order, without atomics: the same bits on every run.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for negative sizes, NULL pointers where
+ * something would be read or written, a grid with a non-positive or non-finite cell, non-finite lo, non-positive dims or more than
+ * SPLAT_NN_MAX_CELLS cells, and records that are not 16-byte aligned. */
+#define SPLAT_NN_MAX_CELLS (1 << 21)
+#define SPLAT_NN_REDUCE_ROWS 256
+typedef struct SplatNnGrid {
+    float lo[3];
+    float cell;
+    int32_t dims[3];
+    int32_t count;
+    const float *records;
+    const int32_t *start;
+} SplatNnGrid;
+int splat_mesh_areas(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, double *area, void *stream);
+int splat_mesh_sample(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const double *prefix, uint64_t seed,
+                      int64_t n, float *points, int32_t *face, void *stream);
+int splat_nn_cell_keys(const SplatNnGrid *grid, const float *points, int64_t n, int32_t *key, void *stream);
+int splat_nn_cell_starts(const SplatNnGrid *grid, const int32_t *sorted_key, const int32_t *order, const float *points, float *records,
+                         int32_t *start, void *stream);
+int splat_nn_query(const SplatNnGrid *grid, const float *points, const int32_t *order, int64_t n, float *dist2, int32_t *index, int32_t *account,
+                   void *stream);
+int splat_nn_reduce(const float *dist2, int64_t n, double threshold, double *partials, double *row, void *stream);
+
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup
  * wall-clock stamps into the buffer of splat_debug_stamps, 2 = stage the batches but visit nothing, 4 = no accumulator atomics,

@@ -151,9 +151,13 @@ class SplatTsdfView(C.Structure):
                 ("out6", _fp), ("w2c", _fp), ("skip", _fp), ("skipped", _fp)]
 
 
+class SplatNnGrid(C.Structure):            # (added within ABI 17: the mesh score layer, csrc/meshscore.hip)
+    _fields_ = [("lo", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int32 * 3), ("count", C.c_int32), ("records", _fp), ("start", _fp)]
+
+
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
-                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView)
+                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -175,6 +179,7 @@ SPLAT_REPORT_DROT, SPLAT_REPORT_DTRANS, SPLAT_REPORT_LOSS, SPLAT_REPORT_SUMS = 0
 SPLAT_REPORT_FLAG, SPLAT_REPORT_MEDIAN, SPLAT_REPORT_DEPTH_TERM, SPLAT_REPORT_IM_TERM = 12, 13, 14, 15
 SPLAT_REPORT_STATUS, SPLAT_REPORT_FLAGGED, SPLAT_REPORT_SKIPPED = 16, 20, 21
 SPLAT_EVAL_ROW, SPLAT_EVAL_LEVELS, SPLAT_EVAL_SUMS, SPLAT_EVAL_LAYOUT_MS_SSIM = 8, 5, 40, 1
+SPLAT_NN_MAX_CELLS, SPLAT_NN_REDUCE_ROWS = 1 << 21, 256
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -202,6 +207,7 @@ EXPORTS = (
     "splat_view_camera", "splat_view_finish",
     "splat_iter_loss_backward_ex", "splat_iter_mapping_step_ex",
     "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
+    "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
 )
 
 _lib = None
@@ -330,6 +336,18 @@ def lib():
     L.splat_tsdf_triangles.argtypes = [vol, C.c_float, _fp, C.c_int64, _fp, _fp]
     L.splat_tsdf_vertices.restype = C.c_int
     L.splat_tsdf_vertices.argtypes = [vol, _fp, C.c_int64, _fp, _fp, _fp]
+    nn = C.POINTER(SplatNnGrid)
+    for name, args in (
+        ("splat_mesh_areas", [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp]),
+        ("splat_mesh_sample", [_fp, C.c_int32, _fp, C.c_int32, _fp, C.c_uint64, C.c_int64, _fp, _fp, _fp]),
+        ("splat_nn_cell_keys", [nn, _fp, C.c_int64, _fp, _fp]),
+        ("splat_nn_cell_starts", [nn, _fp, _fp, _fp, _fp, _fp, _fp]),
+        ("splat_nn_query", [nn, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp]),
+        ("splat_nn_reduce", [_fp, C.c_int64, C.c_double, _fp, _fp, _fp]),
+    ):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = args
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int

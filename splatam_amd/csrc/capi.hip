@@ -60,7 +60,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatAdamMap); SPLAT_SIZEOF_CASE(SplatPoseAdam); SPLAT_SIZEOF_CASE(SplatMapStore); SPLAT_SIZEOF_CASE(SplatAddArgs);
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
-    SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView);
+    SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -455,6 +455,51 @@ int splat_tsdf_triangles(const SplatTsdfVolume *v, float min_weight, int64_t *ke
 int splat_tsdf_vertices(const SplatTsdfVolume *v, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream) {
     if (!valid_tsdf_volume(v) || n < 0 || (n > 0 && (!keys || !vertices))) return SPLAT_E_INVALID;
     return check(launch_tsdf_vertices(*v, keys, (long long)n, vertices, colors, (hipStream_t)stream));
+}
+
+// the mesh score layer (csrc/meshscore.hip)
+static bool valid_nn_grid(const SplatNnGrid *g) {
+    if (!g || g->count < 0) return false;
+    if (!(g->cell > 0.f) || !(g->cell <= 3.0e38f) || g->dims[0] <= 0 || g->dims[1] <= 0 || g->dims[2] <= 0) return false;
+    for (int k = 0; k < 3; ++k)
+        if (!(g->lo[k] >= -3.0e38f && g->lo[k] <= 3.0e38f)) return false;
+    return (long long)g->dims[0] * g->dims[1] <= SPLAT_NN_MAX_CELLS && (long long)g->dims[0] * g->dims[1] * (long long)g->dims[2] <= SPLAT_NN_MAX_CELLS;
+}
+
+int splat_mesh_areas(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, double *area, void *stream) {
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && (!faces || !area)) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    return check(launch_mesh_areas(vertices, num_vertices, faces, num_faces, area, (hipStream_t)stream));
+}
+
+int splat_mesh_sample(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const double *prefix, uint64_t seed,
+                      int64_t n, float *points, int32_t *face, void *stream) {
+    if (num_vertices < 0 || num_faces < 0 || n < 0 || (num_faces > 0 && (!faces || !prefix)) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (n > 0 && (!points || !face)) return SPLAT_E_INVALID;
+    return check(launch_mesh_sample(vertices, num_vertices, faces, num_faces, prefix, seed, (long long)n, points, face, (hipStream_t)stream));
+}
+
+int splat_nn_cell_keys(const SplatNnGrid *grid, const float *points, int64_t n, int32_t *key, void *stream) {
+    if (!valid_nn_grid(grid) || n < 0 || (n > 0 && (!points || !key))) return SPLAT_E_INVALID;
+    return check(launch_nn_cell_keys(*grid, points, (long long)n, key, (hipStream_t)stream));
+}
+
+int splat_nn_cell_starts(const SplatNnGrid *grid, const int32_t *sorted_key, const int32_t *order, const float *points, float *records,
+                         int32_t *start, void *stream) {
+    if (!valid_nn_grid(grid) || !start) return SPLAT_E_INVALID;
+    if (grid->count > 0 && (!sorted_key || !order || !points || !records || ((uintptr_t)records & 15) != 0)) return SPLAT_E_INVALID;
+    return check(launch_nn_cell_starts(*grid, sorted_key, order, points, records, start, (hipStream_t)stream));
+}
+
+int splat_nn_query(const SplatNnGrid *grid, const float *points, const int32_t *order, int64_t n, float *dist2, int32_t *index, int32_t *account,
+                   void *stream) {
+    if (!valid_nn_grid(grid) || !grid->start || (grid->count > 0 && (!grid->records || ((uintptr_t)grid->records & 15) != 0))) return SPLAT_E_INVALID;
+    if (n < 0 || (n > 0 && (!points || !dist2 || !index))) return SPLAT_E_INVALID;
+    return check(launch_nn_query(*grid, points, order, (long long)n, dist2, index, account, (hipStream_t)stream));
+}
+
+int splat_nn_reduce(const float *dist2, int64_t n, double threshold, double *partials, double *row, void *stream) {
+    if (n < 0 || (n > 0 && !dist2) || !partials || !row) return SPLAT_E_INVALID;
+    return check(launch_nn_reduce(dist2, (long long)n, threshold, partials, row, (hipStream_t)stream));
 }
 
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }

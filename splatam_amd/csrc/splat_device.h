@@ -107,6 +107,16 @@ hipError_t launch_tsdf_reset(const SplatTsdfVolume &v, hipStream_t s);
 hipError_t launch_tsdf_integrate(const SplatTsdfVolume &v, const SplatTsdfView &w, hipStream_t s);
 hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, hipStream_t s);
 hipError_t launch_tsdf_vertices(const SplatTsdfVolume &v, const int64_t *keys, long long n, float *vertices, float *colors, hipStream_t s);
+// meshscore.hip: points sampled by area on a triangle mesh, and exact nearest neighbours through a uniform grid
+hipError_t launch_mesh_areas(const float *vertices, int32_t V, const int32_t *faces, int32_t F, double *area, hipStream_t s);
+hipError_t launch_mesh_sample(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const double *prefix, uint64_t seed, long long n,
+                              float *points, int32_t *face, hipStream_t s);
+hipError_t launch_nn_cell_keys(const SplatNnGrid &g, const float *points, long long n, int32_t *key, hipStream_t s);
+hipError_t launch_nn_cell_starts(const SplatNnGrid &g, const int32_t *sorted_key, const int32_t *order, const float *points, float *records,
+                                 int32_t *start, hipStream_t s);
+hipError_t launch_nn_query(const SplatNnGrid &g, const float *points, const int32_t *order, long long n, float *dist2, int32_t *index,
+                           int32_t *account, hipStream_t s);
+hipError_t launch_nn_reduce(const float *dist2, long long n, double threshold, double *partials, double *row, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

@@ -71,3 +71,127 @@ def save_mesh_ply(path, vertices, faces, colors=None):
         f.write(vt.tobytes())
         f.write(ft.tobytes())
     return path
+
+
+PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+             'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def _fan(counts, flat):
+    """Triangles of polygons given as ``counts`` [F] and the concatenated ``flat`` indices: a fan from each polygon's first vertex."""
+    counts = counts.astype(np.int64)
+    if counts.size and (counts == counts[0]).all() and counts[0] >= 3:          # the usual file: all triangles, or all quads
+        poly = flat.reshape(-1, int(counts[0]))
+        return np.stack([poly[:, [0, k, k + 1]] for k in range(1, poly.shape[1] - 1)], axis=1).reshape(-1, 3)
+    first = np.concatenate(([0], np.cumsum(counts)[:-1]))
+    tris, owner = [np.zeros((0, 3), dtype=flat.dtype)], [np.zeros(0, dtype=np.int64)]
+    for k in range(1, int(counts.max(initial=0)) - 1):                   # triangle k of every polygon that has one
+        m = np.nonzero(counts > k + 1)[0]
+        tris.append(np.stack((flat[first[m]], flat[first[m] + k], flat[first[m] + k + 1]), axis=1))
+        owner.append(m)
+    return np.concatenate(tris, axis=0)[np.argsort(np.concatenate(owner), kind="stable")]           # (polygon by polygon, in file order)
+
+
+def load_mesh_ply(path):
+    """``(vertices float32 [V, 3], faces int32 [F, 3], colors float32 [V, 3] in 0..1 or None)`` of an ASCII or binary little-endian PLY:
+    any scalar vertex properties (x, y, z and, when all three are there, red, green, blue are used), a face list of any integer count
+    and index type, polygons fan-triangulated from their first vertex (Replica's own meshes are quads).  Elements other than vertex and
+    face may follow the two.  ValueError, naming the file, for a big-endian file, a file without faces and anything that is not such a
+    PLY.  numpy only; reads back what ``save_mesh_ply`` writes."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.find(b"end_header")
+    nl = data.find(b"\n", end)
+    if not data.startswith(b"ply") or end < 0 or nl < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    for line in data[:end].decode("ascii", "replace").splitlines()[1:]:
+        w = line.split()
+        if not w or w[0] in ("comment", "obj_info"):
+            continue
+        if w[0] == "format":
+            fmt = w[1]
+        elif w[0] == "element":
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == "property" and elements:
+            if w[1] == "list":
+                elements[-1][2].append((w[4], PLY_TYPES.get(w[2]), PLY_TYPES.get(w[3])))
+            else:
+                elements[-1][2].append((w[2], PLY_TYPES.get(w[1]), None))
+    if fmt == "binary_big_endian":
+        raise ValueError(f"{path}: big-endian PLY files are not read; convert the file to binary_little_endian or ascii")
+    if fmt not in ("ascii", "binary_little_endian"):
+        raise ValueError(f"{path}: unknown PLY format {fmt!r}")
+    names = [e[0] for e in elements]
+    if names[:1] != ["vertex"]:
+        raise ValueError(f"{path}: the first element of a mesh PLY must be vertex")
+    if names[1:2] != ["face"] or elements[1][1] == 0:
+        raise ValueError(f"{path}: the file has no faces (a point cloud cannot be scored as a mesh)")
+    (_, V, vprops), (_, F, fprops) = elements[0], elements[1]
+    if any(t is None or l is not None for _, t, l in vprops) or len(fprops) < 1 or fprops[0][2] is None or fprops[0][1] is None \
+            or fprops[0][1][0] == 'f' or fprops[0][2][0] == 'f' or any(t is None for _, t, _ in fprops[1:]):
+        raise ValueError(f"{path}: vertex properties must be scalars and the first face property an integer list")
+    vnames = [n for n, _, _ in vprops]
+    if not all(a in vnames for a in "xyz"):
+        raise ValueError(f"{path}: the vertices have no x, y, z")
+    body = data[nl + 1:]
+    if fmt == "ascii":
+        tokens = body.split()
+        nv = V * len(vprops)
+        table = np.array(tokens[:nv], dtype=np.float64).reshape(V, len(vprops))
+        cols = {n: table[:, k] for k, n in enumerate(vnames)}
+        rest, counts, flat, pos = tokens[nv:], np.zeros(F, dtype=np.int64), [], 0
+        extra = len(fprops) - 1                                          # (scalar face properties after the list)
+        if any(l is not None for _, _, l in fprops[1:]):
+            raise ValueError(f"{path}: a second list property on the faces is not read")
+        for m in range(F):
+            c = int(rest[pos])
+            counts[m] = c
+            flat.extend(rest[pos + 1:pos + 1 + c])
+            pos += 1 + c + extra
+        flat = np.array(flat, dtype=np.int64)
+    else:
+        vdtype = np.dtype([(n, '<' + t) for n, t, _ in vprops])
+        if len(body) < V * vdtype.itemsize:
+            raise ValueError(f"{path}: the file ends inside the vertices")
+        table = np.frombuffer(body, dtype=vdtype, count=V)
+        cols = {n: table[n] for n in vnames}
+        fb = body[V * vdtype.itemsize:]
+        ct, it = np.dtype('<' + fprops[0][1]), np.dtype('<' + fprops[0][2])
+        if len(fprops) != 1:
+            raise ValueError(f"{path}: binary faces with properties besides the index list are not read")
+        if len(fb) < ct.itemsize:
+            raise ValueError(f"{path}: the file ends inside the faces")
+        c0 = int(np.frombuffer(fb, dtype=ct, count=1)[0])
+        rec = np.dtype([('n', ct), ('v', it, (c0,))])
+        uniform = None
+        if c0 >= 1 and len(fb) >= F * rec.itemsize:
+            uniform = np.frombuffer(fb, dtype=rec, count=F)
+            if not (uniform['n'] == c0).all():
+                uniform = None
+        if uniform is not None:
+            counts, flat = np.full(F, c0, dtype=np.int64), uniform['v'].reshape(-1).astype(np.int64)
+        else:                                                            # mixed polygons: one face at a time
+            counts, flat, pos = np.zeros(F, dtype=np.int64), [], 0
+            for m in range(F):
+                if pos + ct.itemsize > len(fb):
+                    raise ValueError(f"{path}: the file ends inside the faces")
+                c = int(np.frombuffer(fb, dtype=ct, count=1, offset=pos)[0])
+                pos += ct.itemsize
+                if pos + c * it.itemsize > len(fb):
+                    raise ValueError(f"{path}: the file ends inside the faces")
+                flat.append(np.frombuffer(fb, dtype=it, count=c, offset=pos).astype(np.int64))
+                counts[m] = c
+                pos += c * it.itemsize
+            flat = np.concatenate(flat) if flat else np.zeros(0, dtype=np.int64)
+    vertices = np.stack([np.asarray(cols[a], dtype=np.float32) for a in "xyz"], axis=1)
+    colors = None
+    if all(a in cols for a in ("red", "green", "blue")):
+        scale = {n: (255.0 if t[0] in "iu" else 1.0) for n, t, _ in vprops}
+        colors = np.stack([np.asarray(cols[a], dtype=np.float32) / np.float32(scale[a]) for a in ("red", "green", "blue")], axis=1)
+    faces = _fan(counts, flat)
+    if faces.shape[0] == 0:
+        raise ValueError(f"{path}: the file has no faces (a point cloud cannot be scored as a mesh)")
+    if faces.min() < 0 or faces.max() >= V:
+        raise ValueError(f"{path}: faces index vertices that do not exist")
+    return np.ascontiguousarray(vertices), np.ascontiguousarray(faces.astype(np.int32)), colors

@@ -1,0 +1,325 @@
+"""A reconstructed mesh against a ground-truth mesh: ``python -m splatam_amd.mesh_score REC.ply GT.ply [--samples N] [--threshold M]
+[--seed S] [--transform FILE] [--device DEV]``.
+
+The three figures of the NICE-SLAM evaluation protocol, which SplaTAM's comparison tables use: ACCURACY, the mean distance in cm from
+the reconstruction to the ground truth; COMPLETION, the mean distance in cm from the ground truth to the reconstruction; COMPLETION
+RATIO, the percentage of ground-truth samples within 5 cm of the reconstruction -- each over 200 000 points sampled uniformly by area
+on either surface -- and the precision / recall / F-score at the same threshold.
+
+Everything runs on the device (csrc/meshscore.hip, arithmetic in csrc/meshscore_math.h): triangle areas, a counter-based sampler
+(Philox4x32-10: sample ``i`` depends on ``(seed, i)`` alone), a uniform grid over the targets (cell keys, ``torch.sort``, cell starts,
+16-byte records) and an exact nearest-neighbour search that walks shells of cells outward, then a reduction without atomics.  Both
+meshes are sampled with the SAME seed, so a mesh scored against itself gives exactly 0.
+
+The map lives in the first camera's frame and a ground-truth mesh in the world frame: ``transform`` (``--transform``, a text file of
+4 x 4 numbers) is the first frame's ABSOLUTE camera-to-world pose, applied to the reconstruction's vertices.  The dataset loaders make
+poses relative to frame 0 and keep no absolute pose: for Replica the matrix is the first line of the sequence's ``traj.txt`` (16
+numbers, row-major).
+
+Not here: culling the meshes to the frusta the run saw, ICP alignment, depth L1 on views rendered from the meshes, marching cubes.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _capi
+from .mesh import Mesh          # noqa: F401  (re-exported: what score_mesh takes)
+
+MAX_CELLS = _capi.SPLAT_NN_MAX_CELLS
+# points per non-empty cell the default cell size aims for (profiles/mesh_score.md 4: 1 .. 16 measured at 200 000 x 200 000; the box's
+# own area underestimates a room's surface, so the cells end up holding somewhat more)
+POINTS_PER_CELL = 2.0
+KEYS = ("accuracy_cm", "completion_cm", "completion_ratio", "precision", "recall", "fscore", "max_rec_to_gt", "max_gt_to_rec", "samples")
+
+
+def _dims(lo, hi, cell):
+    return tuple(int(math.floor((h - l) / cell)) + 1 for l, h in zip(lo, hi))
+
+
+def plan_grid(lo, hi, count, cell=None, per_cell=POINTS_PER_CELL):
+    """(lo, cell, dims) of the grid over the box ``lo`` .. ``hi`` of ``count`` targets: ``lo`` and ``cell`` as float32 values, ``dims`` =
+    floor(extent / cell) + 1 per axis.  ``cell=None``: the targets are taken to lie on a surface of about the box's own area
+    A = 2 (ex ey + ey ez + ez ex), which has A / cell^2 non-empty cells: cell = sqrt(per_cell A / count).  Whatever the cell, it grows
+    until the grid has at most 2^21 cells, so the walk of a stray query is bounded."""
+    lo = tuple(float(np.float32(v)) for v in lo)
+    hi = tuple(float(np.float32(v)) for v in hi)
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(v) for v in lo + hi) or not all(h >= l for l, h in zip(lo, hi)):
+        raise ValueError(f"a grid needs a finite box (got {lo} .. {hi})")
+    e = [h - l for l, h in zip(lo, hi)]
+    if cell is None:
+        area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0])
+        cell = math.sqrt(per_cell * area / max(int(count), 1)) if area > 0 else max(e) / max(int(count), 1)
+        if not cell > 0:
+            cell = 1.0
+    cell = float(np.float32(cell))
+    if not (cell > 0 and math.isfinite(cell)):
+        raise ValueError(f"a grid needs a positive cell size (got {cell})")
+    cell = max(cell, float(np.float32(max(e) / 2.0 ** 30)))             # (dims stay far inside int32)
+    dims = _dims(lo, hi, cell)
+    while dims[0] * dims[1] * dims[2] > MAX_CELLS:
+        cell = float(np.float32(cell * 1.125))
+        dims = _dims(lo, hi, cell)
+    return lo, cell, dims
+
+
+def _points(t, dev, what):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and t.dim() == 2 and t.shape[1] == 3):
+        raise RuntimeError(f"{what} must be a float32 tensor [n, 3] on {dev}")
+    return t.contiguous()
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _device(device):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("the mesh score needs a CUDA/HIP device; the HIP library has no CPU path")
+    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+
+
+def surface_prefix(vertices, faces):
+    """The inclusive double prefix sum of the triangle areas (M0, then ``torch.cumsum``) of a mesh on the device: [F] float64."""
+    dev = vertices.device
+    L = _capi.lib()
+    V, F = int(vertices.shape[0]), int(faces.shape[0])
+    area = torch.empty(F, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(L.splat_mesh_areas(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F, area.data_ptr() if F else None,
+                                       _stream(dev)), "splat_mesh_areas")
+    return area, torch.cumsum(area, 0)
+
+
+def sample_surface(vertices, faces, n, seed=0, prefix=None):
+    """``n`` points uniformly by area on the mesh ``vertices`` [V, 3] float32, ``faces`` [F, 3] int32 (device tensors): ``(points [n, 3]
+    float32, face [n] int32)``.  Sample ``i`` depends on ``(seed, i)`` alone -- not on ``n``, not on the launch.  Zero-area triangles
+    get no sample.  Enqueued on the current stream; nothing is read."""
+    dev = vertices.device
+    if dev.type != "cuda":
+        raise RuntimeError("sample_surface needs a CUDA/HIP device; the HIP library has no CPU path")
+    vertices = _points(vertices, dev, "vertices")
+    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.device == dev and faces.dim() == 2 and faces.shape[1] == 3):
+        raise RuntimeError(f"faces must be an int32 tensor [F, 3] on {dev}")
+    faces = faces.contiguous()
+    V, F, n = int(vertices.shape[0]), int(faces.shape[0]), int(n)
+    if F == 0 or n < 0:
+        raise ValueError("sample_surface needs a mesh with faces and n >= 0")
+    if prefix is None:
+        prefix = surface_prefix(vertices, faces)[1]
+    points = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_mesh_sample(vertices.data_ptr() if V else None, V, faces.data_ptr(), F, prefix.data_ptr(),
+                                                  int(seed) & (2 ** 64 - 1), n, points.data_ptr() if n else None, face.data_ptr() if n else None,
+                                                  _stream(dev)), "splat_mesh_sample")
+    return points, face
+
+
+class NearestGrid:
+    """A uniform grid over ``targets`` [M, 3] float32 on the device for exact nearest-neighbour queries.  ``cell=None`` picks the cell
+    size from the target count and bounding box (``plan_grid``); ``bounds`` = (lo, hi) of the targets when the caller knows them
+    (otherwise ONE host read of the box).  Built by three enqueued steps: cell keys (M2), ``torch.sort(stable=True)``, cell starts and
+    records (M3)."""
+
+    def __init__(self, targets, cell=None, bounds=None):
+        dev = targets.device if isinstance(targets, torch.Tensor) else None
+        if dev is None or dev.type != "cuda":
+            raise RuntimeError("NearestGrid needs a float32 tensor [M, 3] on a CUDA/HIP device; the HIP library has no CPU path")
+        self.dev = dev
+        self.targets = targets = _points(targets, dev, "targets")
+        M = self.count = int(targets.shape[0])
+        if M >= 2 ** 31:
+            raise ValueError(f"{M} targets do not fit int32 indices")
+        if bounds is None:
+            if M:
+                box = torch.stack((targets.min(dim=0).values, targets.max(dim=0).values)).double().cpu().numpy()
+                bounds = (box[0], box[1])
+            else:
+                bounds = ((0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+        self.lo, self.cell, self.dims = plan_grid(bounds[0], bounds[1], M, cell)
+        self.cells = self.dims[0] * self.dims[1] * self.dims[2]
+        g = self.struct = _capi.SplatNnGrid()
+        g.lo[:] = self.lo
+        g.cell = self.cell
+        g.dims[:] = self.dims
+        g.count = M
+        self.L = _capi.lib()
+        self.records = torch.empty(max(M, 1), 4, dtype=torch.float32, device=dev)
+        self.start = torch.empty(self.cells + 1, dtype=torch.int32, device=dev)
+        key, order = self._sorted_keys(targets)
+        with torch.cuda.device(dev):
+            _capi.check(self.L.splat_nn_cell_starts(C.byref(g), key.data_ptr() if M else None, order.data_ptr() if M else None,
+                                                    targets.data_ptr() if M else None, self.records.data_ptr(), self.start.data_ptr(),
+                                                    _stream(dev)), "splat_nn_cell_starts")
+        g.records, g.start = self.records.data_ptr(), self.start.data_ptr()
+
+    def _sorted_keys(self, points):
+        n = int(points.shape[0])
+        key = torch.empty(n, dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_nn_cell_keys(C.byref(self.struct), points.data_ptr() if n else None, n, key.data_ptr() if n else None,
+                                                  _stream(self.dev)), "splat_nn_cell_keys")
+        key, order = torch.sort(key, stable=True)
+        return key, order.to(torch.int32)
+
+    def query(self, points, account=False, sort=True):
+        """``(dist2 [n] float32, index [n] int32)`` of ``points`` [n, 3] float32, in their order: the squared distance to the nearest
+        target (``(dx dx + dy dy) + dz dz`` in float32) and its index, the lowest among equals.  Exact.  The queries are sorted by cell
+        first (``sort=False``: taken as they come), so that a wave's lanes read the same cells.  ``account=True`` adds an int32 [n, 2]
+        of (candidates evaluated, shells walked).  Enqueued; nothing is read."""
+        points = _points(points, self.dev, "points")
+        n = int(points.shape[0])
+        dist2 = torch.empty(n, dtype=torch.float32, device=self.dev)
+        index = torch.empty(n, dtype=torch.int32, device=self.dev)
+        acc = torch.empty(n, 2, dtype=torch.int32, device=self.dev) if account else None
+        order = self._sorted_keys(points)[1] if sort and n else None
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_nn_query(C.byref(self.struct), points.data_ptr() if n else None, order.data_ptr() if order is not None else None,
+                                              n, dist2.data_ptr() if n else None, index.data_ptr() if n else None,
+                                              acc.data_ptr() if account and n else None, _stream(self.dev)), "splat_nn_query")
+        return (dist2, index, acc) if account else (dist2, index)
+
+
+def reduce_distances(dist2, threshold, row, partials=None):
+    """M5: ``row`` (4 float64 on the device) = (sum of d, count of d < threshold, max of d, n) over d = sqrt((double)dist2): a fixed
+    order, no atomics, the same bits on every run.  Enqueued; nothing is read."""
+    dev = dist2.device
+    if not (dist2.dtype == torch.float32 and dist2.dim() == 1 and dist2.is_contiguous()):
+        raise RuntimeError("dist2 must be a contiguous float32 vector")
+    if not (row.dtype == torch.float64 and row.device == dev and row.numel() == 4 and row.is_contiguous()):
+        raise RuntimeError(f"row must be 4 contiguous float64 on {dev}")
+    if partials is None:
+        partials = torch.empty(3 * _capi.SPLAT_NN_REDUCE_ROWS, dtype=torch.float64, device=dev)
+    n = int(dist2.shape[0])
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_nn_reduce(dist2.data_ptr() if n else None, n, float(threshold), partials.data_ptr(), row.data_ptr(),
+                                                _stream(dev)), "splat_nn_reduce")
+    return row
+
+
+def _load(mesh, dev, transform, what):
+    """(vertices float32 [V, 3] on dev, faces int32 [F, 3] on dev, bounds or None): a path or host arrays go through numpy (bounds known
+    without a device read), device tensors stay there."""
+    if isinstance(mesh, (str, os.PathLike)):
+        from .export import load_mesh_ply
+        mesh = load_mesh_ply(mesh)
+    vertices, faces = mesh[0], mesh[1]
+    if isinstance(vertices, torch.Tensor) and vertices.device.type == "cuda":
+        v = vertices.detach().to(dev).reshape(-1, 3)
+        if transform is not None:
+            m = torch.as_tensor(np.asarray(transform, dtype=np.float64), device=dev)
+            v = (v.double() @ m[:3, :3].T + m[:3, 3]).float()
+        v, f, bounds = v.float().contiguous(), faces.detach().to(dev).to(torch.int32).reshape(-1, 3).contiguous(), None
+    else:
+        v = np.asarray(vertices.detach().cpu() if isinstance(vertices, torch.Tensor) else vertices, dtype=np.float32).reshape(-1, 3)
+        f = np.asarray(faces.detach().cpu() if isinstance(faces, torch.Tensor) else faces).reshape(-1, 3)
+        if transform is not None:
+            m = np.asarray(transform, dtype=np.float64)
+            v = (v.astype(np.float64) @ m[:3, :3].T + m[:3, 3]).astype(np.float32)
+        if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+            raise ValueError(f"{what}: faces index vertices that do not exist")
+        bounds = (v.min(axis=0).astype(np.float64), v.max(axis=0).astype(np.float64)) if v.shape[0] else None
+        v, f = torch.from_numpy(np.ascontiguousarray(v)).to(dev), torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(dev)
+    if f.shape[0] == 0 or v.shape[0] == 0:
+        raise ValueError(f"{what}: a mesh without faces cannot be sampled")
+    return v, f, bounds
+
+
+def _transform(transform):
+    if transform is None:
+        return None
+    m = np.asarray(transform.detach().cpu() if isinstance(transform, torch.Tensor) else transform, dtype=np.float64)
+    if m.shape != (4, 4) or not np.isfinite(m).all():
+        raise ValueError("transform must be a finite 4 x 4 matrix")
+    return m
+
+
+def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cell=None):
+    """The reconstruction ``rec`` against the ground truth ``gt`` (each a ``Mesh`` tuple -- device tensors or host arrays -- or the path
+    of a PLY): a dict of ``accuracy_cm`` (mean distance rec -> gt, cm), ``completion_cm`` (gt -> rec, cm), ``completion_ratio`` (percent
+    of gt samples with a distance below ``threshold`` metres), ``precision`` / ``recall`` / ``fscore`` at ``threshold`` (fractions),
+    ``max_rec_to_gt`` / ``max_gt_to_rec`` (metres) and ``samples``.  ``transform``: a 4 x 4 applied to the reconstruction's vertices (in
+    float64, rounded once) -- the first frame's absolute camera-to-world pose, for a map in the first camera's frame.
+
+    ``samples`` points are drawn on either surface with the same ``seed``; both directions are enqueued and the table of their rows is
+    read with ONE host read (meshes given as device tensors cost one more read before, of their boxes).  No engine and no map is
+    touched: the inputs are meshes."""
+    dev = _device(device)
+    samples = int(samples)
+    if samples <= 0 or not float(threshold) > 0:
+        raise ValueError("score_mesh needs samples > 0 and threshold > 0")
+    rv, rf, rb = _load(rec, dev, _transform(transform), "the reconstruction")
+    gv, gf, gb = _load(gt, dev, None, "the ground truth")
+    if rb is None or gb is None:                                        # device meshes: both boxes with one read
+        box = torch.stack((rv.min(dim=0).values, rv.max(dim=0).values, gv.min(dim=0).values, gv.max(dim=0).values)).double().cpu().numpy()
+        rb, gb = (box[0], box[1]), (box[2], box[3])
+    table = torch.zeros(3, 4, dtype=torch.float64, device=dev)          # rec -> gt, gt -> rec, (area rec, area gt, 0, 0)
+    partials = torch.empty(3 * _capi.SPLAT_NN_REDUCE_ROWS, dtype=torch.float64, device=dev)
+    pts = []
+    for n, (v, f) in enumerate(((rv, rf), (gv, gf))):
+        prefix = surface_prefix(v, f)[1]
+        table[2, n:n + 1].copy_(prefix[-1:])
+        pts.append(sample_surface(v, f, samples, seed, prefix=prefix)[0])
+    for n, (queries, targets, bounds) in enumerate(((pts[0], pts[1], gb), (pts[1], pts[0], rb))):
+        dist2, _ = NearestGrid(targets, cell=cell, bounds=bounds).query(queries)
+        reduce_distances(dist2, threshold, table[n], partials)
+    t = table.cpu().numpy()                                             # the one read
+    if not (t[2, 0] > 0 and t[2, 1] > 0 and np.isfinite(t[2, :2]).all()):
+        raise ValueError(f"a mesh without surface area cannot be scored (areas {t[2, 0]}, {t[2, 1]})")
+    n = float(samples)
+    precision, recall = t[0, 1] / n, t[1, 1] / n
+    return {"accuracy_cm": 100.0 * t[0, 0] / n, "completion_cm": 100.0 * t[1, 0] / n, "completion_ratio": 100.0 * recall,
+            "precision": precision, "recall": recall, "fscore": 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0,
+            "max_rec_to_gt": float(t[0, 2]), "max_gt_to_rec": float(t[1, 2]), "samples": samples}
+
+
+def load_transform(path):
+    """A 4 x 4 matrix from a text file of 16 numbers (any whitespace; further lines -- a whole ``traj.txt`` -- are ignored)."""
+    with open(path) as f:
+        values = f.read().split()[:16]
+    try:
+        m = np.array([float(v) for v in values], dtype=np.float64)
+    except ValueError:
+        raise ValueError(f"{path}: not a matrix of numbers") from None
+    if m.size != 16:
+        raise ValueError(f"{path}: a 4 x 4 matrix needs 16 numbers, the file has {m.size}")
+    return m.reshape(4, 4)
+
+
+def format_score(score):
+    return (f"Accuracy: {score['accuracy_cm']:.4f} cm\nCompletion: {score['completion_cm']:.4f} cm\n"
+            f"Completion ratio: {score['completion_ratio']:.4f} %\nF-score: {score['fscore']:.6f} "
+            f"(precision {score['precision']:.6f}, recall {score['recall']:.6f}; {score['samples']} samples)")
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(prog="python -m splatam_amd.mesh_score", description=__doc__.split("\n\n")[1])
+    parser.add_argument("rec", help="the reconstruction (PLY)")
+    parser.add_argument("gt", help="the ground truth (PLY)")
+    parser.add_argument("--samples", type=int, default=200_000, help="points sampled on either surface")
+    parser.add_argument("--threshold", type=float, default=0.05, help="metres: completion ratio and F-score")
+    parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--transform", default=None, metavar="FILE",
+                        help="text file of a 4 x 4 matrix applied to the reconstruction: the first frame's absolute camera-to-world pose")
+    parser.add_argument("--device", default="cuda:0")
+    args = parser.parse_args(argv)
+    try:
+        transform = load_transform(args.transform) if args.transform else None
+        score = score_mesh(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
+                           device=args.device)
+    except (ValueError, OSError) as e:
+        raise SystemExit(str(e)) from None
+    print(format_score(score), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

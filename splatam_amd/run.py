@@ -79,12 +79,16 @@ def check_supported(config):
         raise SystemExit(f"config['mean_sq_dist_method'] = {config.get('mean_sq_dist_method')!r}: only \"projective\" is supported")
 
 
-def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False, mesh=False):
+def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False, mesh=False, gt_mesh=None,
+        gt_transform=None):
     """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``.  The reference's four
     checkpoint keys (``save_checkpoints``, ``checkpoint_interval``, ``load_checkpoint``, ``checkpoint_time_idx``) are honoured under
     ``workdir/run_name``; ``exact_checkpoints=True`` makes every checkpoint ``save_checkpoints`` writes an exact one (``session<t>.npz``
     beside the pair) and ``resume_exact=t`` continues from the exact checkpoint of frame ``t`` there (``pipeline.rgbd_slam``).
-    ``mesh=True`` (or a dict of ``mesh.mesh_from_params`` keywords): ``mesh.ply`` next to ``params.npz``, from the saved map."""
+    ``mesh=True`` (or a dict of ``mesh.mesh_from_params`` keywords): ``mesh.ply`` next to ``params.npz``, from the saved map.
+    ``gt_mesh`` (with ``mesh``): the path of a ground-truth PLY; ``stats['mesh_score']`` is ``mesh_score.score_mesh`` of the written mesh
+    against it, with ``gt_transform`` (a 4 x 4, or the path of a text file of one) applied to the reconstruction: the first frame's
+    ABSOLUTE camera-to-world pose, which the loaders do not keep (Replica: the first line of ``traj.txt``)."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -135,6 +139,10 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
             from .mesh import mesh_from_params
             stats['mesh'] = os.path.join(os.path.dirname(path), "mesh.ply")
             mesh_from_params(path, stats['mesh'], device=device, **(mesh if isinstance(mesh, dict) else {}))
+            if gt_mesh is not None:
+                from .mesh_score import load_transform, score_mesh
+                transform = load_transform(gt_transform) if isinstance(gt_transform, (str, os.PathLike)) else gt_transform
+                stats['mesh_score'] = score_mesh(stats['mesh'], gt_mesh, transform=transform, device=device)
     finally:
         dataset.close()
     return params, variables, stats, path
@@ -151,17 +159,27 @@ def main(argv=None):
     parser.add_argument("--exact-checkpoints", action="store_true",
                         help="with config['save_checkpoints']: also write session<t>.npz, the state --resume-exact continues from")
     parser.add_argument("--mesh", action="store_true", help="write mesh.ply next to params.npz (python -m splatam_amd.mesh on the saved map)")
+    parser.add_argument("--gt-mesh", default=None, metavar="GT.ply",
+                        help="with --mesh: score mesh.ply against this ground-truth mesh (python -m splatam_amd.mesh_score)")
+    parser.add_argument("--gt-transform", default=None, metavar="FILE",
+                        help="text file of the 4 x 4 first-frame camera-to-world pose that takes the map into the ground truth's frame "
+                             "(Replica: the first line of traj.txt)")
     args = parser.parse_args(argv)
+    if args.gt_mesh and not args.mesh:
+        parser.error("--gt-mesh needs --mesh")
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
-                            exact_checkpoints=args.exact_checkpoints, mesh=args.mesh)
+                            exact_checkpoints=args.exact_checkpoints, mesh=args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform)
     ev = stats.get('eval')
     if ev is not None:
         print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"
               f"Average Depth L1: {100 * ev['avg_depth_l1']:.2f} cm\nAverage MS-SSIM: {ev['avg_ms_ssim']:.3f}\n"
               f"Final Average ATE RMSE: {100 * ev['ate_rmse']:.2f} cm")
+    if stats.get('mesh_score') is not None:
+        from .mesh_score import format_score
+        print(format_score(stats['mesh_score']))
     loop_s = sum(stats['frame_s'])
     print(f"{stats['frames']} frames, {stats['num_gaussians'][-1]} Gaussians, keyframes {stats['keyframe_time_indices']}: "
           f"{stats['frames'] / loop_s:.2f} frames/s in the loop")
