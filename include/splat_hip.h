@@ -342,7 +342,8 @@ typedef struct SplatMap {
     int32_t num_frames;
 } SplatMap;
 
-/* `curr_data` of get_loss. */
+/* `curr_data` of get_loss.  im and depth may be any contiguous view: they need the 4-byte alignment of a float only (the loss kernels
+ * take their 16-byte loads only where every plane they touch starts on 16 bytes, and read scalar-wise otherwise). */
 typedef struct SplatFrameData {
     const float *im;             /* [3][H][W] */
     const float *depth;          /* [1][H][W] */
@@ -402,7 +403,8 @@ typedef struct SplatIterWorkspace {
     float *accum;                /* [P][SPLAT_GRAD_STRIDE] */
     float *ssim_maps;            /* [9][H][W] mapping only (NULL for tracking) */
     double *sums;                /* [SPLAT_ITER_SUM_COPIES][SPLAT_ITER_SUMS]: [0] masked depth L1 sum, [1] image L1 sum,
-                                    [2] mask count, [3] SSIM map sum, [8..23] camera-pose partial sums, [31] != 0: a capacity flag was
+                                    [2] mask count, [3] SSIM map sum ([2], [3]: mapping only -- the tracking loss divides by nothing
+                                    and forms neither: 0), [8..23] camera-pose partial sums, [31] != 0: a capacity flag was
                                     raised on some band of a tile-row-sharded iteration (cfg.defer_finish) */
     float *max_2D_radius;        /* [P] variables['max_2D_radius'], updated in place, or NULL */
     /* gradients of the map (written when non-NULL; means3D / unnorm_rotations only with gaussians_grad) */

@@ -1045,7 +1045,8 @@ hipError_t launch_iter_loss_backward(const SplatCamera &cam, const SplatMap &map
         if (cfg.tracking && loss_done) {
             // nothing: see the epilogue above
         } else if (cfg.tracking) {
-            if (HW % 4 == 0) {
+            // the float4 form needs every plane it touches on a 16-byte boundary: a caller's frame may be any contiguous view
+            if (HW % 4 == 0 && aligned16(ws.out6) && aligned16(ws.dL_dout6) && aligned16(frame.im) && aligned16(frame.depth)) {
                 const int blocks = min((HW / 4 + kBlock - 1) / kBlock, 2048);
                 hipLaunchKernelGGL(track_loss_kernel<4>, dim3(blocks), dim3(kBlock), 0, s, a, HW);
             } else {

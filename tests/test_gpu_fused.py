@@ -290,8 +290,9 @@ def test_missing_outlier_scratch_is_an_invalid_argument():
 
 
 def test_edge_shapes_and_empty_map():
-    """Image not a multiple of the tile / SSIM block sizes, odd pixel count (scalar loss path), and a map with no
-    visible Gaussian: finite results, zero gradients where nothing is rendered."""
+    """Image not a multiple of the tile / SSIM block sizes, odd pixel count (F4 / F5 pixel by pixel; the tracking loss is formed in
+    the composite's epilogue here -- the scalar form of the loss kernel is reached only with outlier rejection, in
+    tests/test_gpu_loss_configs.py), and a map with no visible Gaussian: finite results, zero gradients where nothing is rendered."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
     params, variables, frame, cam = _scene(3000, 203, 117, aniso=True, seed=31)          # 203*117 is odd

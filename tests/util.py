@@ -421,3 +421,55 @@ def view_partition(radii_per_view, params, forward_view, min_frac=0.03, what="",
         assert v.mean() >= min_frac, (what, k, int(v.sum()))
     assert not seen[forward_view - 1][groups['behind the near plane (forward view)']].any(), "a row behind the near plane was rendered"
     return groups, seen
+
+
+# get_loss on given planes (tests/test_host_math.py, tests/test_loss_ref_cpu.py)
+class PlanesRenderer:
+    """Stands in for the rasterizer inside slam.get_loss: the colour pass returns ``im``, the depth-silhouette pass ``depth_sil``."""
+    planes = None
+
+    def __init__(self, raster_settings):
+        pass
+
+    def __call__(self, **rendervar):
+        n = rendervar['means3D'].shape[0]
+        return PlanesRenderer.planes.pop(0), torch.ones(n, dtype=torch.int32), None
+
+
+def track_pixel_planes(nan_depth):
+    """512 random pixels (most of them valid and present) with the special ones placed by hand; returns the planes and the indices.
+    nan_depth: one rendered depth is NaN (not together with outlier rejection: torch.median of the frame's errors would be NaN)."""
+    g = torch.Generator().manual_seed(11)
+    H, W = 16, 32
+    n = H * W
+    gt = 1.0 + 3.0 * torch.rand(n, generator=g)
+    depth = gt + 0.05 * torch.randn(n, generator=g)
+    sil = torch.where(torch.rand(n, generator=g) < 0.85, torch.ones(n), torch.rand(n, generator=g))
+    depth_sq = depth * depth + 0.01 * torch.rand(n, generator=g)
+    gt_im = torch.rand(3, n, generator=g)
+    im = (gt_im + 0.1 * torch.randn(3, n, generator=g)).clamp(0, 1)
+    gt[torch.rand(n, generator=g) < 0.1] = 0.0                      # holes of the depth sensor
+    at = dict(gt_zero=3, nan_depth=40, nan_unc=41, sil_at=70, sil_below=71, sil_above=72, depth_equal=100, colour_equal=130,
+              outlier_in=200, outlier_out=201)
+    for k in at.values():
+        gt[k], sil[k] = 2.0, 1.0
+        depth[k] = 2.03125
+        depth_sq[k] = depth[k] * depth[k] + 0.001
+    gt[at['gt_zero']] = 0.0
+    if nan_depth:
+        depth[at['nan_depth']] = float('nan')
+    depth_sq[at['nan_unc']] = float('nan')                          # depth^2 channel not a number: the uncertainty is NaN, the depth is not
+    sil[at['sil_at']] = 0.99
+    sil[at['sil_below']] = float(np.nextafter(np.float32(0.99), np.float32(0)))
+    sil[at['sil_above']] = float(np.nextafter(np.float32(0.99), np.float32(1)))
+    depth[at['depth_equal']] = gt[at['depth_equal']]
+    im[1, at['colour_equal']] = gt_im[1, at['colour_equal']]
+    # either side of 10 * median: both errors lie far above the median itself, so placing them does not move it
+    err = ((gt - depth).abs() * (gt > 0)).nan_to_num(0.0)
+    med = float(err.median())
+    depth[at['outlier_in']] = 2.0 + 9.9 * med
+    depth[at['outlier_out']] = 2.0 + 10.1 * med
+    err = ((gt - depth).abs() * (gt > 0)).nan_to_num(0.0)
+    assert float(err.median()) == med and err[at['outlier_in']] < 10 * err.median() < err[at['outlier_out']]
+    out6 = torch.cat([im, depth[None], sil[None], depth_sq[None]])
+    return H, W, out6, gt_im, gt, err.median(), at
