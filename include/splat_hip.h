@@ -940,10 +940,66 @@ int splat_nn_query(const SplatNnGrid *grid, const float *points, const int32_t *
                    void *stream);
 int splat_nn_reduce(const float *dist2, int64_t n, double threshold, double *partials, double *row, void *stream);
 
+/* The mesh render layer (csrc/meshrender.hip, arithmetic in csrc/meshrender_math.h; added within ABI 17): the depth image of a triangle
+ * mesh, how many of a set of views see each vertex, and the sums depth L1 between two depth images is made of -- what culling a mesh to
+ * the frusta a run saw and the protocol's depth L1 on rendered mesh views are made of.
+ *
+ * The camera is splat_tsdf_integrate's: w2c is 16 device floats, row-major, as splat_view_camera writes them; pc = w2c p per row as
+ * ((m0 x + m1 y) + m2 z) + m3; pixel (i, j) looks along d = ((i - cx) / fx, (j - cy) / fy, 1); a point lands on pixel
+ * (floor(fx x / z + cx + 0.5), floor(fy y / z + cy + 0.5)).  All float32, one operation per step.
+ *
+ * splat_mesh_depth: depth [height][width] float32 of faces [num_faces][3] int32 over vertices [num_vertices][3] float32 seen by `view`:
+ * the smallest camera-space z with near_z <= z < +inf at which the pixel's ray meets a triangle, 0 where it meets none (the datasets'
+ * "no depth").  Both faces of a triangle count.  With a, b, c the camera-space vertices: the edge plane of (a, b) is a x b (each
+ * component one product minus one product), ALWAYS formed from the endpoint of lower vertex index first and negated when the triangle
+ * names them the other way round, so the two triangles of a shared edge hold exact negatives; E(d) = (dx e0 + dy e1) + e2; the pixel is
+ * covered when E_ab, E_bc, E_ca are all >= 0 or all <= 0; the hit is z = (n . a) / (n . d), n = (b - a) x (c - a),
+ * n . a = (n0 ax + n1 ay) + n2 az, n . d = (dx n0 + dy n1) + n2.  There is no near-plane clipping: a triangle behind the camera gives
+ * z < near_z, one that crosses z = 0 is decided by the same three signs.  A face with an index outside the vertices or a non-finite
+ * vertex renders nothing.  Pixels tested per face: the box ceil(min u - 0.5) .. floor(max u + 0.5) of the projected vertices (v alike)
+ * clipped to the image when all three have z > near_z; otherwise the same box of the face's part at z >= near_z (its vertices there and
+ * the points where its edges meet the plane z = near_z), grown by 1 + 2^-16 max|u| pixels, or the whole image when a projection is not
+ * a number.  A face whose box holds at most 16 pixels is walked by one lane; a larger one, and every face with a vertex at z <= near_z,
+ * by a wave (16 was measured; splat_debug_option(5, n) moves it for measurements, the plane does not depend on it).  The plane is cleared to the bits of +inf, lowered by an
+ * integer atomic min on the floats' bits and finished to 0 by the same call: the result does not depend on order and is the same bits
+ * on every run.  `depth` may be one plane of a [k][height][width] buffer.  num_faces == 0 or num_vertices == 0: a plane of zeros.
+ *
+ * splat_mesh_seen: seen [num_vertices] int32 is INCREMENTED, per vertex, by the number of the `n` views w2c [n][16] (one size, one set
+ * of intrinsics: `view`, whose own w2c and near_z are not read) in which the vertex has z > 0, lands on a pixel with
+ * edge <= i <= width - 1 - edge and edge <= j <= height - 1 - edge and -- when `depth` ([n][height][width], or NULL) is given -- has
+ * d = depth[view][j][i] > 0 and z <= d + eps (one float32 addition).  One lane per vertex, no atomics: exact and the same on every
+ * run; incrementing lets a caller feed a long sequence in chunks of planes.
+ *
+ * splat_mesh_depth_compare: row[0..7] doubles from the planes a (ground truth) and b (reconstruction) of n pixels, a value that is not
+ * > 0 being a hole and counting as 0: sum |a - b| over all pixels; sum |a - b| over the pixels where both are > 0; the count of those;
+ * holes of a; holes of b; n; max |a - b|; 0.  Through `partials` (SPLAT_MESH_COMPARE_PARTIALS doubles of scratch) in a fixed order,
+ * without atomics: the same bits on every run.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for a NULL view, a non-positive size or more
+ * than 2^30 - 1 pixels, fx or fy that is zero or not finite, cx / cy not finite, near_z that is not a positive finite number
+ * (splat_mesh_depth), a negative edge, eps or count, eps that is not a number, and NULL pointers where something would be
+ * read or written. */
+#define SPLAT_MESH_COMPARE_ROWS 256
+#define SPLAT_MESH_COMPARE_PARTIALS (6 * SPLAT_MESH_COMPARE_ROWS)
+typedef struct SplatMeshView {
+    int32_t width, height;
+    float fx, fy, cx, cy;
+    float near_z;
+    const float *w2c;
+} SplatMeshView;
+int splat_mesh_depth(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const SplatMeshView *view, float *depth,
+                     void *stream);
+int splat_mesh_seen(const float *vertices, int32_t num_vertices, const SplatMeshView *view, const float *w2c, int32_t n, int32_t edge,
+                    const float *depth, float eps, int32_t *seen, void *stream);
+int splat_mesh_depth_compare(const float *a, const float *b, int64_t n, double *partials, double *row, void *stream);
+
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup
  * wall-clock stamps into the buffer of splat_debug_stamps, 2 = stage the batches but visit nothing, 4 = no accumulator atomics,
- * 8 = phase 1 only; results are then invalid; 0 = the product kernel).  Returns the previous value, -1 for an unknown key. */
+ * 8 = phase 1 only; results are then invalid; 0 = the product kernel); key 5 = the largest pixel box one lane of splat_mesh_depth walks
+ * alone (0 = the library's 16; the result does not depend on it); key 6 = measurement builds of splat_mesh_depth's raster kernel
+ * (1 = a plain load in front of the atomic min spares it where the pixel already holds something nearer: the same result; 2 = a plain
+ * store in place of the atomic: results are then invalid; 0 = the product kernel).  Returns the previous value, -1 for an unknown key. */
 int splat_debug_option(int key, int value);
 /* device buffer of 2 x (workgroups of the launch) int64 for splat_debug_option(4, 1): (start, end) of every workgroup in
  * wall_clock64() ticks (100 MHz); NULL switches it off. */

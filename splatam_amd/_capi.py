@@ -155,9 +155,14 @@ class SplatNnGrid(C.Structure):            # (added within ABI 17: the mesh scor
     _fields_ = [("lo", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int32 * 3), ("count", C.c_int32), ("records", _fp), ("start", _fp)]
 
 
+class SplatMeshView(C.Structure):          # (added within ABI 17: the mesh render layer, csrc/meshrender.hip)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_z", C.c_float), ("w2c", _fp)]
+
+
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
-                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid)
+                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -180,6 +185,7 @@ SPLAT_REPORT_FLAG, SPLAT_REPORT_MEDIAN, SPLAT_REPORT_DEPTH_TERM, SPLAT_REPORT_IM
 SPLAT_REPORT_STATUS, SPLAT_REPORT_FLAGGED, SPLAT_REPORT_SKIPPED = 16, 20, 21
 SPLAT_EVAL_ROW, SPLAT_EVAL_LEVELS, SPLAT_EVAL_SUMS, SPLAT_EVAL_LAYOUT_MS_SSIM = 8, 5, 40, 1
 SPLAT_NN_MAX_CELLS, SPLAT_NN_REDUCE_ROWS = 1 << 21, 256
+SPLAT_MESH_COMPARE_ROWS, SPLAT_MESH_COMPARE_PARTIALS = 256, 6 * 256
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -208,6 +214,7 @@ EXPORTS = (
     "splat_iter_loss_backward_ex", "splat_iter_mapping_step_ex",
     "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
+    "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
 )
 
 _lib = None
@@ -344,6 +351,14 @@ def lib():
         ("splat_nn_cell_starts", [nn, _fp, _fp, _fp, _fp, _fp, _fp]),
         ("splat_nn_query", [nn, _fp, _fp, C.c_int64, _fp, _fp, _fp, _fp]),
         ("splat_nn_reduce", [_fp, C.c_int64, C.c_double, _fp, _fp, _fp]),
+    ):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = args
+    for name, args in (
+        ("splat_mesh_depth", [_fp, C.c_int32, _fp, C.c_int32, C.POINTER(SplatMeshView), _fp, _fp]),
+        ("splat_mesh_seen", [_fp, C.c_int32, C.POINTER(SplatMeshView), _fp, C.c_int32, C.c_int32, _fp, C.c_float, _fp, _fp]),
+        ("splat_mesh_depth_compare", [_fp, _fp, C.c_int64, _fp, _fp, _fp]),
     ):
         f = getattr(L, name)
         f.restype = C.c_int

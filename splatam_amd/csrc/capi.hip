@@ -60,7 +60,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatAdamMap); SPLAT_SIZEOF_CASE(SplatPoseAdam); SPLAT_SIZEOF_CASE(SplatMapStore); SPLAT_SIZEOF_CASE(SplatAddArgs);
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
-    SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid);
+    SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid); SPLAT_SIZEOF_CASE(SplatMeshView);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -502,6 +502,32 @@ int splat_nn_reduce(const float *dist2, int64_t n, double threshold, double *par
     return check(launch_nn_reduce(dist2, (long long)n, threshold, partials, row, (hipStream_t)stream));
 }
 
+// the mesh render layer (csrc/meshrender.hip)
+static bool finite_f(float x) { return x >= -3.0e38f && x <= 3.0e38f; }
+static bool valid_mesh_view(const SplatMeshView *v) {
+    if (!v || v->width <= 0 || v->height <= 0 || (long long)v->width * v->height > 0x3fffffffLL) return false;
+    return finite_f(v->fx) && finite_f(v->fy) && v->fx != 0.f && v->fy != 0.f && finite_f(v->cx) && finite_f(v->cy);
+}
+
+int splat_mesh_depth(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const SplatMeshView *view, float *depth,
+                     void *stream) {
+    if (!valid_mesh_view(view) || !view->w2c || !(view->near_z > 0.f) || !finite_f(view->near_z) || !depth) return SPLAT_E_INVALID;
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    return check(launch_mesh_depth(vertices, num_vertices, faces, num_faces, *view, depth, (hipStream_t)stream));
+}
+
+int splat_mesh_seen(const float *vertices, int32_t num_vertices, const SplatMeshView *view, const float *w2c, int32_t n, int32_t edge,
+                    const float *depth, float eps, int32_t *seen, void *stream) {
+    if (!valid_mesh_view(view) || num_vertices < 0 || n < 0 || edge < 0 || !(eps >= 0.f)) return SPLAT_E_INVALID;
+    if ((num_vertices > 0 && (!vertices || !seen)) || (n > 0 && !w2c)) return SPLAT_E_INVALID;
+    return check(launch_mesh_seen(vertices, num_vertices, *view, w2c, n, edge, depth, eps, seen, (hipStream_t)stream));
+}
+
+int splat_mesh_depth_compare(const float *a, const float *b, int64_t n, double *partials, double *row, void *stream) {
+    if (n < 0 || (n > 0 && (!a || !b)) || !partials || !row) return SPLAT_E_INVALID;
+    return check(launch_mesh_depth_compare(a, b, (long long)n, partials, row, (hipStream_t)stream));
+}
+
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }
 
 static bool valid_store(const SplatMapStore *st) {
@@ -569,6 +595,8 @@ int splat_map_duplicate(SplatMapStore *store, const SplatDensifyArgs *a, void *s
 int splat_debug_option(int key, int value) {
     if (key == 0) { const int old = g_debug_skip_count; g_debug_skip_count = value; return old; }
     if (key == 4) { const int old = g_debug_k7_bits; g_debug_k7_bits = value; return old; }
+    if (key == 5) { const int old = g_debug_mesh_split; g_debug_mesh_split = value > 0 ? value : 0; return old; }
+    if (key == 6) { const int old = g_debug_mesh_bits; g_debug_mesh_bits = value; return old; }
     return -1;
 }
 

@@ -117,6 +117,12 @@ hipError_t launch_nn_cell_starts(const SplatNnGrid &g, const int32_t *sorted_key
 hipError_t launch_nn_query(const SplatNnGrid &g, const float *points, const int32_t *order, long long n, float *dist2, int32_t *index,
                            int32_t *account, hipStream_t s);
 hipError_t launch_nn_reduce(const float *dist2, long long n, double threshold, double *partials, double *row, hipStream_t s);
+// meshrender.hip: the depth image of a triangle mesh (z-buffer), views that see each vertex, and the sums of a depth comparison
+hipError_t launch_mesh_depth(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const SplatMeshView &view, float *depth,
+                             hipStream_t s);
+hipError_t launch_mesh_seen(const float *vertices, int32_t V, const SplatMeshView &view, const float *w2c, int32_t n, int32_t edge,
+                            const float *depth, float eps, int32_t *seen, hipStream_t s);
+hipError_t launch_mesh_depth_compare(const float *a, const float *b, long long n, double *partials, double *row, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);
@@ -130,6 +136,8 @@ size_t map_scratch_words(long long n);
 int map_row_floats(const SplatMapStore &st);
 extern int g_debug_skip_count;
 extern int g_debug_k7_bits;
+extern int g_debug_mesh_split;
+extern int g_debug_mesh_bits;
 extern long long *g_debug_stamps;
 hipError_t launch_selftest(int which, const void *in, void *out, int n, hipStream_t s);
 

@@ -1,5 +1,6 @@
 """A reconstructed mesh against a ground-truth mesh: ``python -m splatam_amd.mesh_score REC.ply GT.ply [--samples N] [--threshold M]
-[--seed S] [--transform FILE] [--device DEV]``.
+[--seed S] [--transform FILE] [--device DEV] [--cull-poses TRAJ.txt [--cull-every N] [--cull-size WxH] [--cull-intrinsics FX FY CX CY]
+[--occlusion]] [--depth-l1 N]``.
 
 The three figures of the NICE-SLAM evaluation protocol, which SplaTAM's comparison tables use: ACCURACY, the mean distance in cm from
 the reconstruction to the ground truth; COMPLETION, the mean distance in cm from the ground truth to the reconstruction; COMPLETION
@@ -16,7 +17,11 @@ The map lives in the first camera's frame and a ground-truth mesh in the world f
 poses relative to frame 0 and keep no absolute pose: for Replica the matrix is the first line of the sequence's ``traj.txt`` (16
 numbers, row-major).
 
-Not here: culling the meshes to the frusta the run saw, ICP alignment, depth L1 on views rendered from the meshes, marching cubes.
+The protocol's preprocessing and its fourth figure live in ``splatam_amd.mesh_render``: ``--cull-poses`` removes from BOTH meshes what
+the trajectory's frusta did not see (``--occlusion``: nor what the ground truth itself hides in every frame) before a point is sampled,
+and ``--depth-l1 N`` adds the depth L1 between the two meshes rendered at ``N`` virtual views.  Both are off unless asked for.
+
+Not here: ICP alignment, marching cubes.
 """
 from __future__ import annotations
 
@@ -281,6 +286,21 @@ def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None,
             "max_rec_to_gt": float(t[0, 2]), "max_gt_to_rec": float(t[1, 2]), "samples": samples}
 
 
+def score_culled_in_map_frame(rec, gt, w2c, intrinsics, size, gt_transform=None, device="cuda:0", **score):
+    """``score_mesh`` of a reconstruction in the MAP's frame against a ground truth in the world frame, both culled first to the frusta of
+    ``w2c`` ([n, 4, 4] world-to-camera poses in the map's frame: a run's own).  ``gt_transform`` is what ``score_mesh`` would apply to the
+    reconstruction, the first frame's absolute camera-to-world pose; its INVERSE brings the ground truth into the map's frame, where
+    both are culled and scored -- distances do not change under a rigid motion.  Further keywords go to ``score_mesh``."""
+    from .mesh_render import cull_mesh
+    to_map = None if gt_transform is None else np.linalg.inv(_transform(gt_transform))
+    rec_c = cull_mesh(rec, w2c, intrinsics, size, device=device)
+    gt_c = cull_mesh(gt, w2c, intrinsics, size, transform=to_map, device=device)
+    for m, what in ((rec_c, "reconstruction"), (gt_c, "ground truth")):
+        if m.faces.shape[0] == 0:
+            raise ValueError(f"the run's views see nothing of the {what}: is the transform the first frame's camera-to-world pose?")
+    return score_mesh(rec_c, gt_c, device=device, **score)
+
+
 def load_transform(path):
     """A 4 x 4 matrix from a text file of 16 numbers (any whitespace; further lines -- a whole ``traj.txt`` -- are ignored)."""
     with open(path) as f:
@@ -295,9 +315,39 @@ def load_transform(path):
 
 
 def format_score(score):
-    return (f"Accuracy: {score['accuracy_cm']:.4f} cm\nCompletion: {score['completion_cm']:.4f} cm\n"
+    text = (f"Accuracy: {score['accuracy_cm']:.4f} cm\nCompletion: {score['completion_cm']:.4f} cm\n"
             f"Completion ratio: {score['completion_ratio']:.4f} %\nF-score: {score['fscore']:.6f} "
             f"(precision {score['precision']:.6f}, recall {score['recall']:.6f}; {score['samples']} samples)")
+    if score.get("depth_l1_cm") is not None:                            # (only when mesh_render.depth_l1 was asked for)
+        text += (f"\nDepth L1: {score['depth_l1_cm']:.4f} cm (where both have depth {score['depth_l1_valid_cm']:.4f} cm; holes "
+                 f"{score['holes_gt']} gt, {score['holes_rec']} rec; {score['views']} views)")
+    return text
+
+
+# Replica as the NICE-SLAM protocol renders it: 1200 x 680, focal length 600, the principal point at the image's centre
+CULL_SIZE, CULL_INTRINSICS = "1200x680", (600.0, 600.0, 599.5, 339.5)
+
+
+def score_with_views(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cull_w2c=None, intrinsics=CULL_INTRINSICS,
+                     size=(1200, 680), occlusion=False, depth_l1_views=0):
+    """``score_mesh`` behind the protocol's preprocessing: with ``cull_w2c`` ([n, 4, 4] world-to-camera in the ground truth's frame) both
+    meshes are culled to those views first (``mesh_render.cull_mesh``; ``occlusion``: each against renders of the ground truth), and
+    ``depth_l1_views`` > 0 adds ``mesh_render.depth_l1`` at that many views from ``mesh_render.sample_views`` (same ``seed``).  Without
+    either this is ``score_mesh``."""
+    from . import mesh_render as MR
+    if cull_w2c is None and not depth_l1_views:
+        return score_mesh(rec, gt, samples=samples, threshold=threshold, seed=seed, transform=transform, device=device)
+    r, g = MR.to_device_mesh(rec, device, _transform(transform)), MR.to_device_mesh(gt, device, None)
+    if cull_w2c is not None:                                            # (occlusion: both against ONE set of renders of the ground truth)
+        r, g = MR.cull_meshes([r, g], cull_w2c, intrinsics, size, occlusion=1 if occlusion else None, device=device)
+        for m, what in ((r, "reconstruction"), (g, "ground truth")):
+            if m.faces.shape[0] == 0:
+                raise ValueError(f"the views see nothing of the {what}: are the poses in the ground truth's frame (--transform)?")
+    score = score_mesh(r, g, samples=samples, threshold=threshold, seed=seed, device=device)
+    if depth_l1_views:
+        views = MR.sample_views(g, depth_l1_views, intrinsics, size, seed=seed, device=device)
+        score.update(MR.depth_l1(r, g, views, intrinsics, size, device=device))
+    return score
 
 
 def main(argv=None):
@@ -310,11 +360,28 @@ def main(argv=None):
     parser.add_argument("--transform", default=None, metavar="FILE",
                         help="text file of a 4 x 4 matrix applied to the reconstruction: the first frame's absolute camera-to-world pose")
     parser.add_argument("--device", default="cuda:0")
+    parser.add_argument("--cull-poses", default=None, metavar="FILE",
+                        help="text file of 4 x 4 camera-to-world matrices, one per line (a Replica traj.txt), in the ground truth's frame: "
+                             "both meshes are culled to these frusta first")
+    parser.add_argument("--cull-every", type=int, default=1, metavar="N", help="use every N-th pose of --cull-poses")
+    parser.add_argument("--cull-size", default=CULL_SIZE, metavar="WxH", help="image size of the culling and depth L1 views")
+    parser.add_argument("--cull-intrinsics", type=float, nargs=4, default=CULL_INTRINSICS, metavar=("FX", "FY", "CX", "CY"))
+    parser.add_argument("--occlusion", action="store_true", help="with --cull-poses: also cull what the ground truth hides in every frame")
+    parser.add_argument("--depth-l1", type=int, default=0, metavar="N", help="add depth L1 over N virtual views rendered from both meshes")
     args = parser.parse_args(argv)
+    if args.occlusion and not args.cull_poses:
+        parser.error("--occlusion needs --cull-poses")
     try:
         transform = load_transform(args.transform) if args.transform else None
-        score = score_mesh(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
-                           device=args.device)
+        if args.cull_poses or args.depth_l1:
+            from .mesh_render import load_poses, parse_size
+            score = score_with_views(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
+                                     device=args.device, cull_w2c=load_poses(args.cull_poses, args.cull_every) if args.cull_poses else None,
+                                     intrinsics=tuple(args.cull_intrinsics), size=parse_size(args.cull_size), occlusion=args.occlusion,
+                                     depth_l1_views=args.depth_l1)
+        else:
+            score = score_mesh(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
+                               device=args.device)
     except (ValueError, OSError) as e:
         raise SystemExit(str(e)) from None
     print(format_score(score), flush=True)

@@ -80,7 +80,7 @@ def check_supported(config):
 
 
 def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False, mesh=False, gt_mesh=None,
-        gt_transform=None):
+        gt_transform=None, cull=False):
     """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``.  The reference's four
     checkpoint keys (``save_checkpoints``, ``checkpoint_interval``, ``load_checkpoint``, ``checkpoint_time_idx``) are honoured under
     ``workdir/run_name``; ``exact_checkpoints=True`` makes every checkpoint ``save_checkpoints`` writes an exact one (``session<t>.npz``
@@ -88,7 +88,9 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     ``mesh=True`` (or a dict of ``mesh.mesh_from_params`` keywords): ``mesh.ply`` next to ``params.npz``, from the saved map.
     ``gt_mesh`` (with ``mesh``): the path of a ground-truth PLY; ``stats['mesh_score']`` is ``mesh_score.score_mesh`` of the written mesh
     against it, with ``gt_transform`` (a 4 x 4, or the path of a text file of one) applied to the reconstruction: the first frame's
-    ABSOLUTE camera-to-world pose, which the loaders do not keep (Replica: the first line of ``traj.txt``)."""
+    ABSOLUTE camera-to-world pose, which the loaders do not keep (Replica: the first line of ``traj.txt``).  ``cull`` (with ``gt_mesh``):
+    both meshes are first culled to the frusta of the dataset's poses in the MAP's frame, where those poses live, the inverse of
+    ``gt_transform`` bringing the ground truth there (``mesh_score.score_culled_in_map_frame``)."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -140,9 +142,17 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
             stats['mesh'] = os.path.join(os.path.dirname(path), "mesh.ply")
             mesh_from_params(path, stats['mesh'], device=device, **(mesh if isinstance(mesh, dict) else {}))
             if gt_mesh is not None:
-                from .mesh_score import load_transform, score_mesh
+                from .mesh_score import load_transform, score_culled_in_map_frame, score_mesh
                 transform = load_transform(gt_transform) if isinstance(gt_transform, (str, os.PathLike)) else gt_transform
-                stats['mesh_score'] = score_mesh(stats['mesh'], gt_mesh, transform=transform, device=device)
+                if cull:
+                    try:
+                        stats['mesh_score'] = score_culled_in_map_frame(
+                            stats['mesh'], gt_mesh, out['gt_w2c_all_frames'], out['intrinsics'],
+                            (data["desired_image_width"], data["desired_image_height"]), gt_transform=transform, device=device)
+                    except ValueError as e:
+                        raise SystemExit(f"--cull: {e}") from None
+                else:
+                    stats['mesh_score'] = score_mesh(stats['mesh'], gt_mesh, transform=transform, device=device)
     finally:
         dataset.close()
     return params, variables, stats, path
@@ -164,14 +174,19 @@ def main(argv=None):
     parser.add_argument("--gt-transform", default=None, metavar="FILE",
                         help="text file of the 4 x 4 first-frame camera-to-world pose that takes the map into the ground truth's frame "
                              "(Replica: the first line of traj.txt)")
+    parser.add_argument("--cull", action="store_true",
+                        help="with --gt-mesh: cull both meshes to the frusta of the dataset's poses before scoring (splatam_amd.mesh_render)")
     args = parser.parse_args(argv)
     if args.gt_mesh and not args.mesh:
         parser.error("--gt-mesh needs --mesh")
+    if args.cull and not args.gt_mesh:
+        parser.error("--cull needs --gt-mesh")
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
-                            exact_checkpoints=args.exact_checkpoints, mesh=args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform)
+                            exact_checkpoints=args.exact_checkpoints, mesh=args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
+                            cull=args.cull)
     ev = stats.get('eval')
     if ev is not None:
         print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"
