@@ -993,6 +993,52 @@ int splat_mesh_seen(const float *vertices, int32_t num_vertices, const SplatMesh
                     const float *depth, float eps, int32_t *seen, void *stream);
 int splat_mesh_depth_compare(const float *a, const float *b, int64_t n, double *partials, double *row, void *stream);
 
+/* The ICP layer (csrc/icp.hip, arithmetic in csrc/icp_math.h; added within ABI 17): point-to-point registration of a source cloud onto
+ * the targets of a SplatNnGrid -- the alignment the NICE-SLAM mesh protocol runs before it measures (threshold 0.1 m, identity start, at
+ * most 30 iterations, stop when fitness and inlier RMSE both change by less than 1e-6).  One iteration is splat_icp_transform,
+ * splat_nn_query on `moved`, splat_icp_accumulate, splat_icp_solve; all arithmetic is double, one operation per step.
+ *
+ * state: SPLAT_ICP_STATE doubles on the device: T [16] row-major (bottom row 0 0 0 1), then SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS
+ * (0 running, 1 converged, 2 iteration limit, 3 fewer than three correspondences), SPLAT_ICP_FITNESS / SPLAT_ICP_RMSE of the current
+ * evaluation, SPLAT_ICP_PREV_FITNESS / SPLAT_ICP_PREV_RMSE of the one before, SPLAT_ICP_COUNT (correspondences), SPLAT_ICP_POINTS (n).
+ * The caller writes T and zeros before the first iteration.  history: [max_iterations + 1][4] doubles, row k = (count, fitness,
+ * inlier RMSE, status after this evaluation) of iteration k.
+ *
+ * splat_icp_transform: moved[i] = float32(R p + t), p the float32 source point widened, per row ((r0 x + r1 y) + r2 z) + t, T read from
+ * `state` on the device.
+ * splat_icp_accumulate: point i is a correspondence when 0 <= index[i] < num_targets and sqrt((double)dist2[i]) < threshold (dist2 /
+ * index: what splat_nn_query returned for `moved`; the comparison is splat_nn_reduce's).  partials [SPLAT_ICP_ROWS][SPLAT_ICP_SUMS]:
+ * per workgroup the count, sum of (double)dist2, sum of (p' - c) [3], sum of (q - c) [3], sum of (p' - c)(q - c)^T [9] (row: p') over
+ * its correspondences, p' = R p + t formed in double again (not the rounded `moved`), q = targets[index[i]] widened, c = origin: 3 HOST
+ * doubles near the points (the centre of the targets' box), which only limit cancellation.  Fixed assignment of points to lanes, fixed
+ * order of the wave and workgroup reductions, no atomics: the same bits on every run.  n == 0: one row of zeros.
+ * splat_icp_solve (one workgroup; n, origin as given to splat_icp_accumulate): returns at once when the status is not 0 -- T is frozen,
+ * iterations enqueued after the end change nothing.  Otherwise adds the rows in order; fitness = count / n, inlier RMSE =
+ * sqrt(sum d2 / count), both 0 without correspondences; writes the history row; status 1 when iteration > 0 and both changed by less
+ * than relative_fitness / relative_rmse since the evaluation before, else 2 when iteration == max_iterations, else 3 when count < 3;
+ * while it stays 0: the proper rotation U and translation u that minimise sum |U p' + u - q|^2 (Horn's quaternion form: the eigenvector
+ * of the largest eigenvalue of a symmetric 4 x 4 matrix by cyclic Jacobi sweeps; det U = +1 whatever the sums), T <- (U, u) T, current
+ * becomes previous, iteration + 1.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for negative sizes or max_iterations, a
+ * threshold or relative_* that is not a number, and NULL pointers where something would be read or written. */
+#define SPLAT_ICP_STATE 24
+#define SPLAT_ICP_ROWS 256
+#define SPLAT_ICP_SUMS 17
+#define SPLAT_ICP_ITERATION 16
+#define SPLAT_ICP_STATUS 17
+#define SPLAT_ICP_FITNESS 18
+#define SPLAT_ICP_RMSE 19
+#define SPLAT_ICP_PREV_FITNESS 20
+#define SPLAT_ICP_PREV_RMSE 21
+#define SPLAT_ICP_COUNT 22
+#define SPLAT_ICP_POINTS 23
+int splat_icp_transform(const float *source, int64_t n, const double *state, float *moved, void *stream);
+int splat_icp_accumulate(const float *source, const float *targets, int64_t num_targets, const float *dist2, const int32_t *index, int64_t n,
+                         double threshold, const double *origin, const double *state, double *partials, void *stream);
+int splat_icp_solve(const double *partials, int64_t n, int32_t max_iterations, double relative_fitness, double relative_rmse,
+                    const double *origin, double *state, double *history, void *stream);
+
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup
  * wall-clock stamps into the buffer of splat_debug_stamps, 2 = stage the batches but visit nothing, 4 = no accumulator atomics,

@@ -186,6 +186,9 @@ SPLAT_REPORT_STATUS, SPLAT_REPORT_FLAGGED, SPLAT_REPORT_SKIPPED = 16, 20, 21
 SPLAT_EVAL_ROW, SPLAT_EVAL_LEVELS, SPLAT_EVAL_SUMS, SPLAT_EVAL_LAYOUT_MS_SSIM = 8, 5, 40, 1
 SPLAT_NN_MAX_CELLS, SPLAT_NN_REDUCE_ROWS = 1 << 21, 256
 SPLAT_MESH_COMPARE_ROWS, SPLAT_MESH_COMPARE_PARTIALS = 256, 6 * 256
+SPLAT_ICP_STATE, SPLAT_ICP_ROWS, SPLAT_ICP_SUMS = 24, 256, 17      # (added within ABI 17: the ICP layer, csrc/icp.hip)
+SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS, SPLAT_ICP_FITNESS, SPLAT_ICP_RMSE = 16, 17, 18, 19
+SPLAT_ICP_PREV_FITNESS, SPLAT_ICP_PREV_RMSE, SPLAT_ICP_COUNT, SPLAT_ICP_POINTS = 20, 21, 22, 23
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -215,6 +218,7 @@ EXPORTS = (
     "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
     "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
+    "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
 )
 
 _lib = None
@@ -359,6 +363,14 @@ def lib():
         ("splat_mesh_depth", [_fp, C.c_int32, _fp, C.c_int32, C.POINTER(SplatMeshView), _fp, _fp]),
         ("splat_mesh_seen", [_fp, C.c_int32, C.POINTER(SplatMeshView), _fp, C.c_int32, C.c_int32, _fp, C.c_float, _fp, _fp]),
         ("splat_mesh_depth_compare", [_fp, _fp, C.c_int64, _fp, _fp, _fp]),
+    ):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = args
+    for name, args in (
+        ("splat_icp_transform", [_fp, C.c_int64, _fp, _fp, _fp]),
+        ("splat_icp_accumulate", [_fp, _fp, C.c_int64, _fp, _fp, C.c_int64, C.c_double, C.POINTER(C.c_double), _fp, _fp, _fp]),
+        ("splat_icp_solve", [_fp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double), _fp, _fp, _fp]),
     ):
         f = getattr(L, name)
         f.restype = C.c_int

@@ -502,6 +502,28 @@ int splat_nn_reduce(const float *dist2, int64_t n, double threshold, double *par
     return check(launch_nn_reduce(dist2, (long long)n, threshold, partials, row, (hipStream_t)stream));
 }
 
+// the ICP layer (csrc/icp.hip)
+int splat_icp_transform(const float *source, int64_t n, const double *state, float *moved, void *stream) {
+    if (n < 0 || !state || (n > 0 && (!source || !moved))) return SPLAT_E_INVALID;
+    return check(launch_icp_transform(source, (long long)n, state, moved, (hipStream_t)stream));
+}
+
+int splat_icp_accumulate(const float *source, const float *targets, int64_t num_targets, const float *dist2, const int32_t *index, int64_t n,
+                         double threshold, const double *origin, const double *state, double *partials, void *stream) {
+    if (n < 0 || num_targets < 0 || !origin || !state || !partials || !(threshold == threshold)) return SPLAT_E_INVALID;
+    if (n > 0 && (!source || !dist2 || !index || (num_targets > 0 && !targets))) return SPLAT_E_INVALID;
+    return check(launch_icp_accumulate(source, targets, (long long)num_targets, dist2, index, (long long)n, threshold, origin, state, partials,
+                                       (hipStream_t)stream));
+}
+
+int splat_icp_solve(const double *partials, int64_t n, int32_t max_iterations, double relative_fitness, double relative_rmse,
+                    const double *origin, double *state, double *history, void *stream) {
+    if (n < 0 || max_iterations < 0 || !partials || !origin || !state || !history) return SPLAT_E_INVALID;
+    if (!(relative_fitness == relative_fitness) || !(relative_rmse == relative_rmse)) return SPLAT_E_INVALID;
+    return check(launch_icp_solve(partials, (long long)n, max_iterations, relative_fitness, relative_rmse, origin, state, history,
+                                  (hipStream_t)stream));
+}
+
 // the mesh render layer (csrc/meshrender.hip)
 static bool finite_f(float x) { return x >= -3.0e38f && x <= 3.0e38f; }
 static bool valid_mesh_view(const SplatMeshView *v) {

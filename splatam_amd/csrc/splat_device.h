@@ -117,6 +117,12 @@ hipError_t launch_nn_cell_starts(const SplatNnGrid &g, const int32_t *sorted_key
 hipError_t launch_nn_query(const SplatNnGrid &g, const float *points, const int32_t *order, long long n, float *dist2, int32_t *index,
                            int32_t *account, hipStream_t s);
 hipError_t launch_nn_reduce(const float *dist2, long long n, double threshold, double *partials, double *row, hipStream_t s);
+// icp.hip: point-to-point ICP on the correspondences splat_nn_query finds
+hipError_t launch_icp_transform(const float *source, long long n, const double *state, float *moved, hipStream_t s);
+hipError_t launch_icp_accumulate(const float *source, const float *targets, long long num_targets, const float *dist2, const int32_t *index,
+                                 long long n, double threshold, const double *origin, const double *state, double *partials, hipStream_t s);
+hipError_t launch_icp_solve(const double *partials, long long n, int32_t max_iterations, double relative_fitness, double relative_rmse,
+                            const double *origin, double *state, double *history, hipStream_t s);
 // meshrender.hip: the depth image of a triangle mesh (z-buffer), views that see each vertex, and the sums of a depth comparison
 hipError_t launch_mesh_depth(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const SplatMeshView &view, float *depth,
                              hipStream_t s);

@@ -1,6 +1,6 @@
 """A reconstructed mesh against a ground-truth mesh: ``python -m splatam_amd.mesh_score REC.ply GT.ply [--samples N] [--threshold M]
 [--seed S] [--transform FILE] [--device DEV] [--cull-poses TRAJ.txt [--cull-every N] [--cull-size WxH] [--cull-intrinsics FX FY CX CY]
-[--occlusion]] [--depth-l1 N]``.
+[--occlusion]] [--depth-l1 N] [--align [--align-threshold M] [--align-iterations N]]``.
 
 The three figures of the NICE-SLAM evaluation protocol, which SplaTAM's comparison tables use: ACCURACY, the mean distance in cm from
 the reconstruction to the ground truth; COMPLETION, the mean distance in cm from the ground truth to the reconstruction; COMPLETION
@@ -21,7 +21,11 @@ The protocol's preprocessing and its fourth figure live in ``splatam_amd.mesh_re
 the trajectory's frusta did not see (``--occlusion``: nor what the ground truth itself hides in every frame) before a point is sampled,
 and ``--depth-l1 N`` adds the depth L1 between the two meshes rendered at ``N`` virtual views.  Both are off unless asked for.
 
-Not here: ICP alignment, marching cubes.
+The protocol's registration step is ``align_icp`` (csrc/icp.hip, arithmetic in csrc/icp_math.h): ``--align`` registers the
+reconstruction's vertices to the ground truth's by point-to-point ICP -- after ``--transform`` and the culling, before a point is sampled
+-- and prints an ``Alignment:`` line in front of the figures.  Off unless asked for.
+
+Not here: marching cubes; point-to-plane or coloured ICP, scale, a global registration in front of the ICP.
 """
 from __future__ import annotations
 
@@ -175,17 +179,27 @@ class NearestGrid:
         key, order = torch.sort(key, stable=True)
         return key, order.to(torch.int32)
 
-    def query(self, points, account=False, sort=True):
+    def cell_order(self, points):
+        """The permutation that sorts ``points`` by cell (int32 [n]): what ``query`` computes for itself unless given one."""
+        return self._sorted_keys(_points(points, self.dev, "points"))[1]
+
+    def query(self, points, account=False, sort=True, order=None):
         """``(dist2 [n] float32, index [n] int32)`` of ``points`` [n, 3] float32, in their order: the squared distance to the nearest
         target (``(dx dx + dy dy) + dz dz`` in float32) and its index, the lowest among equals.  Exact.  The queries are sorted by cell
         first (``sort=False``: taken as they come), so that a wave's lanes read the same cells.  ``account=True`` adds an int32 [n, 2]
-        of (candidates evaluated, shells walked).  Enqueued; nothing is read."""
+        of (candidates evaluated, shells walked).  ``order`` (int32 [n], a permutation, e.g. an earlier ``cell_order``) replaces the sort:
+        it only sets the processing order, never the result.  Enqueued; nothing is read."""
         points = _points(points, self.dev, "points")
         n = int(points.shape[0])
         dist2 = torch.empty(n, dtype=torch.float32, device=self.dev)
         index = torch.empty(n, dtype=torch.int32, device=self.dev)
         acc = torch.empty(n, 2, dtype=torch.int32, device=self.dev) if account else None
-        order = self._sorted_keys(points)[1] if sort and n else None
+        if order is not None:
+            if not (isinstance(order, torch.Tensor) and order.dtype == torch.int32 and order.device == self.dev and order.shape == (n,)
+                    and order.is_contiguous()):
+                raise RuntimeError(f"order must be a contiguous int32 vector of {n} on {self.dev}")
+        else:
+            order = self._sorted_keys(points)[1] if sort and n else None
         with torch.cuda.device(self.dev):
             _capi.check(self.L.splat_nn_query(C.byref(self.struct), points.data_ptr() if n else None, order.data_ptr() if order is not None else None,
                                               n, dist2.data_ptr() if n else None, index.data_ptr() if n else None,
@@ -208,6 +222,130 @@ def reduce_distances(dist2, threshold, row, partials=None):
         _capi.check(_capi.lib().splat_nn_reduce(dist2.data_ptr() if n else None, n, float(threshold), partials.data_ptr(), row.data_ptr(),
                                                 _stream(dev)), "splat_nn_reduce")
     return row
+
+
+ICP_STATUS = ("running", "converged", "iteration limit", "fewer than three correspondences")
+# the queries are re-sorted by cell when this many iterations have passed since the last sort (profiles/icp.md 3)
+ICP_RESORT_EVERY = 5
+
+
+def _rigid(init):
+    m = np.asarray(init.detach().cpu() if isinstance(init, torch.Tensor) else init, dtype=np.float64)
+    if m.shape != (4, 4) or not np.isfinite(m).all():
+        raise ValueError("init must be a finite 4 x 4 matrix")
+    R = m[:3, :3]
+    if np.abs(R @ R.T - np.eye(3)).max() > 1e-6 or not np.linalg.det(R) > 0 or not np.array_equal(m[3], (0.0, 0.0, 0.0, 1.0)):
+        raise ValueError("init must be a rigid motion: a proper rotation, a translation and the bottom row 0 0 0 1")
+    return m
+
+
+def motion_of(T):
+    """(translation in cm, rotation in degrees) of the rigid motion ``T`` [4, 4]."""
+    T = np.asarray(T, dtype=np.float64)
+    R = T[:3, :3]
+    skew = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return 100.0 * float(np.linalg.norm(T[:3, 3])), math.degrees(math.atan2(float(np.linalg.norm(skew)), 0.5 * (float(np.trace(R)) - 1.0)))
+
+
+def apply_state(source, state, out=None):
+    """I1: ``float32(R p + t)`` of ``source`` [n, 3] float32, the motion read from the ICP state row on the device (one rounding).
+    Enqueued; nothing is read."""
+    dev = source.device
+    n = int(source.shape[0])
+    moved = torch.empty(n, 3, dtype=torch.float32, device=dev) if out is None else out
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_icp_transform(source.data_ptr() if n else None, n, state.data_ptr(), moved.data_ptr() if n else None,
+                                                    _stream(dev)), "splat_icp_transform")
+    return moved
+
+
+def accumulate_moments(source, targets, dist2, index, threshold, origin, state, partials=None):
+    """I2: ``partials`` [SPLAT_ICP_ROWS, 17] float64 of the correspondences among ``source`` (``dist2`` / ``index``: what the grid's query
+    returned for the moved source).  Enqueued; nothing is read."""
+    dev = source.device
+    n, m = int(source.shape[0]), int(targets.shape[0])
+    if partials is None:
+        partials = torch.zeros(_capi.SPLAT_ICP_ROWS, _capi.SPLAT_ICP_SUMS, dtype=torch.float64, device=dev)
+    c = (C.c_double * 3)(*[float(v) for v in origin])
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().splat_icp_accumulate(source.data_ptr() if n else None, targets.data_ptr() if m else None, m,
+                                                     dist2.data_ptr() if n else None, index.data_ptr() if n else None, n, float(threshold), c,
+                                                     state.data_ptr(), partials.data_ptr(), _stream(dev)), "splat_icp_accumulate")
+    return partials
+
+
+def align_icp(source, target, threshold=0.1, init=None, max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6, check_every=5,
+              grid=None, target_bounds=None):
+    """Point-to-point ICP of ``source`` [n, 3] onto ``target`` [m, 3] (float32 device tensors) as the NICE-SLAM protocol runs it (Open3D's
+    ``registration_icp`` settings: correspondences closer than ``threshold`` metres, start at ``init`` or the identity, at most
+    ``max_iterations`` updates, stop when fitness and inlier RMSE both change by less than ``relative_*``): a dict of ``transformation``
+    ([4, 4] float64 numpy, source -> target), ``fitness`` (correspondences / n), ``inlier_rmse`` (metres), ``correspondences``,
+    ``iterations`` (updates applied), ``status`` (1 converged, 2 iteration limit, 3 fewer than three correspondences) and ``history``
+    ([k, 4]: count, fitness, inlier RMSE, status per evaluation).
+
+    Each iteration is I1 (move by the device's T), the grid's exact query, I2 (17 moments, no atomics), I3 (stop test, Horn's solve,
+    T <- U T), all enqueued; ``check_every`` iterations go between two host reads of the state row, and because T freezes on the device
+    once the loop has stopped the result is the same bits whatever ``check_every``.  ``grid``: a ``NearestGrid`` over ``target`` built
+    earlier; ``target_bounds`` = (lo, hi) spares the grid's one read of the box."""
+    dev = source.device if isinstance(source, torch.Tensor) else None
+    if dev is None or dev.type != "cuda" or not isinstance(target, torch.Tensor) or target.device.type != "cuda":
+        raise RuntimeError("align_icp needs float32 tensors [n, 3] on a CUDA/HIP device; the HIP library has no CPU path")
+    source, target = _points(source, dev, "source"), _points(target, dev, "target")
+    n, m = int(source.shape[0]), int(target.shape[0])
+    if n == 0 or m == 0:
+        raise ValueError("align_icp needs at least one source and one target point")
+    threshold, max_iterations, check_every = float(threshold), int(max_iterations), int(check_every)
+    if not (threshold > 0 and math.isfinite(threshold)):
+        raise ValueError(f"align_icp needs a positive finite threshold (got {threshold})")
+    if max_iterations < 0 or check_every < 1 or not (relative_fitness >= 0 and relative_rmse >= 0):
+        raise ValueError("align_icp needs max_iterations >= 0, check_every >= 1 and relative_fitness, relative_rmse >= 0")
+    T0 = np.eye(4) if init is None else _rigid(init)
+    if grid is None:
+        grid = NearestGrid(target, bounds=target_bounds)
+    elif grid.dev != dev or grid.count != m:
+        raise ValueError("grid was not built over these targets")
+    origin = [grid.lo[k] + 0.5 * grid.cell * grid.dims[k] for k in range(3)]             # about the centre of the targets' box
+    L = _capi.lib()
+    ns, rows = _capi.SPLAT_ICP_STATE, max_iterations + 1
+    host = np.zeros(ns + 4 * rows)
+    host[:16] = T0.reshape(-1)
+    buf = torch.from_numpy(host).to(dev)                                # the state row and the history behind it: one read fetches both
+    state, history = buf[:ns], buf[ns:]
+    partials = torch.empty(_capi.SPLAT_ICP_ROWS, _capi.SPLAT_ICP_SUMS, dtype=torch.float64, device=dev)
+    moved = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    c = (C.c_double * 3)(*origin)
+    order, done, got = None, 0, None
+    for _ in range(-(-rows // check_every)):
+        for _ in range(min(check_every, rows - done)):
+            apply_state(source, state, out=moved)
+            if done % ICP_RESORT_EVERY == 0:
+                order = grid.cell_order(moved)
+            dist2, index = grid.query(moved, order=order)
+            accumulate_moments(source, target, dist2, index, threshold, origin, state, partials)
+            with torch.cuda.device(dev):
+                _capi.check(L.splat_icp_solve(partials.data_ptr(), n, max_iterations, float(relative_fitness), float(relative_rmse), c,
+                                              state.data_ptr(), history.data_ptr(), _stream(dev)), "splat_icp_solve")
+            done += 1
+        got = buf.cpu().numpy()                                         # the one read of this block
+        if got[_capi.SPLAT_ICP_STATUS] != 0:
+            break
+    assert got is not None and got[_capi.SPLAT_ICP_STATUS] != 0, "the iteration limit ends the loop"
+    it = int(got[_capi.SPLAT_ICP_ITERATION])
+    return {"transformation": got[:16].reshape(4, 4).copy(), "fitness": float(got[_capi.SPLAT_ICP_FITNESS]),
+            "inlier_rmse": float(got[_capi.SPLAT_ICP_RMSE]), "correspondences": int(got[_capi.SPLAT_ICP_COUNT]), "iterations": it,
+            "status": int(got[_capi.SPLAT_ICP_STATUS]), "history": got[ns:].reshape(rows, 4)[:it + 1].copy()}
+
+
+def align_vertices(rec_vertices, gt_vertices, align, gt_bounds=None):
+    """The protocol's registration step: ``align_icp`` of the reconstruction's vertices onto the ground truth's (``align``: True or a dict
+    of ``align_icp`` keywords), then the motion found applied to the reconstruction's vertices in double, rounded once (I1).  Returns
+    (aligned vertices, the ``align_icp`` dict plus ``translation_cm`` and ``rotation_deg``)."""
+    keywords = dict(align) if isinstance(align, dict) else {}
+    keywords.setdefault("target_bounds", gt_bounds)
+    found = align_icp(rec_vertices, gt_vertices, **keywords)
+    state = torch.from_numpy(np.concatenate((found["transformation"].reshape(-1), np.zeros(_capi.SPLAT_ICP_STATE - 16)))).to(rec_vertices.device)
+    found["translation_cm"], found["rotation_deg"] = motion_of(found["transformation"])
+    return apply_state(rec_vertices, state), found
 
 
 def _load(mesh, dev, transform, what):
@@ -247,7 +385,7 @@ def _transform(transform):
     return m
 
 
-def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cell=None):
+def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cell=None, align=False):
     """The reconstruction ``rec`` against the ground truth ``gt`` (each a ``Mesh`` tuple -- device tensors or host arrays -- or the path
     of a PLY): a dict of ``accuracy_cm`` (mean distance rec -> gt, cm), ``completion_cm`` (gt -> rec, cm), ``completion_ratio`` (percent
     of gt samples with a distance below ``threshold`` metres), ``precision`` / ``recall`` / ``fscore`` at ``threshold`` (fractions),
@@ -256,7 +394,11 @@ def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None,
 
     ``samples`` points are drawn on either surface with the same ``seed``; both directions are enqueued and the table of their rows is
     read with ONE host read (meshes given as device tensors cost one more read before, of their boxes).  No engine and no map is
-    touched: the inputs are meshes."""
+    touched: the inputs are meshes.
+
+    ``align`` (True, or a dict of ``align_icp`` keywords): the protocol's registration -- after ``transform``, the reconstruction's
+    VERTICES are registered to the ground truth's by point-to-point ICP and moved by what it finds before a point is sampled; the score
+    gains ``alignment``, the ``align_icp`` dict plus ``translation_cm`` and ``rotation_deg`` of that motion."""
     dev = _device(device)
     samples = int(samples)
     if samples <= 0 or not float(threshold) > 0:
@@ -266,6 +408,11 @@ def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None,
     if rb is None or gb is None:                                        # device meshes: both boxes with one read
         box = torch.stack((rv.min(dim=0).values, rv.max(dim=0).values, gv.min(dim=0).values, gv.max(dim=0).values)).double().cpu().numpy()
         rb, gb = (box[0], box[1]), (box[2], box[3])
+    alignment = None
+    if align:
+        rv, alignment = align_vertices(rv, gv, align, gt_bounds=gb)
+        box = torch.stack((rv.min(dim=0).values, rv.max(dim=0).values)).double().cpu().numpy()
+        rb = (box[0], box[1])
     table = torch.zeros(3, 4, dtype=torch.float64, device=dev)          # rec -> gt, gt -> rec, (area rec, area gt, 0, 0)
     partials = torch.empty(3 * _capi.SPLAT_NN_REDUCE_ROWS, dtype=torch.float64, device=dev)
     pts = []
@@ -281,9 +428,12 @@ def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None,
         raise ValueError(f"a mesh without surface area cannot be scored (areas {t[2, 0]}, {t[2, 1]})")
     n = float(samples)
     precision, recall = t[0, 1] / n, t[1, 1] / n
-    return {"accuracy_cm": 100.0 * t[0, 0] / n, "completion_cm": 100.0 * t[1, 0] / n, "completion_ratio": 100.0 * recall,
-            "precision": precision, "recall": recall, "fscore": 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0,
-            "max_rec_to_gt": float(t[0, 2]), "max_gt_to_rec": float(t[1, 2]), "samples": samples}
+    score = {"accuracy_cm": 100.0 * t[0, 0] / n, "completion_cm": 100.0 * t[1, 0] / n, "completion_ratio": 100.0 * recall,
+             "precision": precision, "recall": recall, "fscore": 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0,
+             "max_rec_to_gt": float(t[0, 2]), "max_gt_to_rec": float(t[1, 2]), "samples": samples}
+    if alignment is not None:
+        score["alignment"] = alignment
+    return score
 
 
 def score_culled_in_map_frame(rec, gt, w2c, intrinsics, size, gt_transform=None, device="cuda:0", **score):
@@ -314,8 +464,14 @@ def load_transform(path):
     return m.reshape(4, 4)
 
 
+def format_alignment(a):
+    return (f"Alignment: fitness {a['fitness']:.6f}, inlier RMSE {100.0 * a['inlier_rmse']:.4f} cm, {a['iterations']} iterations "
+            f"({ICP_STATUS[a['status']]}), translation {a['translation_cm']:.4f} cm, rotation {a['rotation_deg']:.4f} deg")
+
+
 def format_score(score):
-    text = (f"Accuracy: {score['accuracy_cm']:.4f} cm\nCompletion: {score['completion_cm']:.4f} cm\n"
+    text = format_alignment(score["alignment"]) + "\n" if score.get("alignment") is not None else ""
+    text += (f"Accuracy: {score['accuracy_cm']:.4f} cm\nCompletion: {score['completion_cm']:.4f} cm\n"
             f"Completion ratio: {score['completion_ratio']:.4f} %\nF-score: {score['fscore']:.6f} "
             f"(precision {score['precision']:.6f}, recall {score['recall']:.6f}; {score['samples']} samples)")
     if score.get("depth_l1_cm") is not None:                            # (only when mesh_render.depth_l1 was asked for)
@@ -329,21 +485,28 @@ CULL_SIZE, CULL_INTRINSICS = "1200x680", (600.0, 600.0, 599.5, 339.5)
 
 
 def score_with_views(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cull_w2c=None, intrinsics=CULL_INTRINSICS,
-                     size=(1200, 680), occlusion=False, depth_l1_views=0):
+                     size=(1200, 680), occlusion=False, depth_l1_views=0, align=False):
     """``score_mesh`` behind the protocol's preprocessing: with ``cull_w2c`` ([n, 4, 4] world-to-camera in the ground truth's frame) both
     meshes are culled to those views first (``mesh_render.cull_mesh``; ``occlusion``: each against renders of the ground truth), and
     ``depth_l1_views`` > 0 adds ``mesh_render.depth_l1`` at that many views from ``mesh_render.sample_views`` (same ``seed``).  Without
-    either this is ``score_mesh``."""
+    either this is ``score_mesh``.  ``align`` (``score_mesh``'s): the ICP runs on the CULLED meshes' vertices, and the samples, the
+    distances and the depth L1 are those of the aligned reconstruction."""
     from . import mesh_render as MR
     if cull_w2c is None and not depth_l1_views:
-        return score_mesh(rec, gt, samples=samples, threshold=threshold, seed=seed, transform=transform, device=device)
+        return score_mesh(rec, gt, samples=samples, threshold=threshold, seed=seed, transform=transform, device=device, align=align)
     r, g = MR.to_device_mesh(rec, device, _transform(transform)), MR.to_device_mesh(gt, device, None)
     if cull_w2c is not None:                                            # (occlusion: both against ONE set of renders of the ground truth)
         r, g = MR.cull_meshes([r, g], cull_w2c, intrinsics, size, occlusion=1 if occlusion else None, device=device)
         for m, what in ((r, "reconstruction"), (g, "ground truth")):
             if m.faces.shape[0] == 0:
                 raise ValueError(f"the views see nothing of the {what}: are the poses in the ground truth's frame (--transform)?")
+    alignment = None
+    if align:
+        aligned, alignment = align_vertices(r.vertices, g.vertices, align)
+        r = Mesh(aligned, r.faces, r.colors)
     score = score_mesh(r, g, samples=samples, threshold=threshold, seed=seed, device=device)
+    if alignment is not None:
+        score["alignment"] = alignment
     if depth_l1_views:
         views = MR.sample_views(g, depth_l1_views, intrinsics, size, seed=seed, device=device)
         score.update(MR.depth_l1(r, g, views, intrinsics, size, device=device))
@@ -368,9 +531,18 @@ def main(argv=None):
     parser.add_argument("--cull-intrinsics", type=float, nargs=4, default=CULL_INTRINSICS, metavar=("FX", "FY", "CX", "CY"))
     parser.add_argument("--occlusion", action="store_true", help="with --cull-poses: also cull what the ground truth hides in every frame")
     parser.add_argument("--depth-l1", type=int, default=0, metavar="N", help="add depth L1 over N virtual views rendered from both meshes")
+    parser.add_argument("--align", action="store_true",
+                        help="register the reconstruction's vertices to the ground truth's by point-to-point ICP before scoring")
+    parser.add_argument("--align-threshold", type=float, default=None, metavar="M", help="with --align: correspondence distance in metres (0.1)")
+    parser.add_argument("--align-iterations", type=int, default=None, metavar="N", help="with --align: at most N updates (30)")
     args = parser.parse_args(argv)
     if args.occlusion and not args.cull_poses:
         parser.error("--occlusion needs --cull-poses")
+    if (args.align_threshold is not None or args.align_iterations is not None) and not args.align:
+        parser.error("--align-threshold and --align-iterations need --align")
+    align = False
+    if args.align:
+        align = {k: v for k, v in (("threshold", args.align_threshold), ("max_iterations", args.align_iterations)) if v is not None} or True
     try:
         transform = load_transform(args.transform) if args.transform else None
         if args.cull_poses or args.depth_l1:
@@ -378,10 +550,10 @@ def main(argv=None):
             score = score_with_views(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
                                      device=args.device, cull_w2c=load_poses(args.cull_poses, args.cull_every) if args.cull_poses else None,
                                      intrinsics=tuple(args.cull_intrinsics), size=parse_size(args.cull_size), occlusion=args.occlusion,
-                                     depth_l1_views=args.depth_l1)
+                                     depth_l1_views=args.depth_l1, align=align)
         else:
             score = score_mesh(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
-                               device=args.device)
+                               device=args.device, align=align)
     except (ValueError, OSError) as e:
         raise SystemExit(str(e)) from None
     print(format_score(score), flush=True)

@@ -80,7 +80,7 @@ def check_supported(config):
 
 
 def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resume_exact=None, exact_checkpoints=False, mesh=False, gt_mesh=None,
-        gt_transform=None, cull=False):
+        gt_transform=None, cull=False, align=False):
     """Runs ``config`` (an experiment file's dict); returns ``(params, variables, stats, path of params.npz)``.  The reference's four
     checkpoint keys (``save_checkpoints``, ``checkpoint_interval``, ``load_checkpoint``, ``checkpoint_time_idx``) are honoured under
     ``workdir/run_name``; ``exact_checkpoints=True`` makes every checkpoint ``save_checkpoints`` writes an exact one (``session<t>.npz``
@@ -90,7 +90,9 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     against it, with ``gt_transform`` (a 4 x 4, or the path of a text file of one) applied to the reconstruction: the first frame's
     ABSOLUTE camera-to-world pose, which the loaders do not keep (Replica: the first line of ``traj.txt``).  ``cull`` (with ``gt_mesh``):
     both meshes are first culled to the frusta of the dataset's poses in the MAP's frame, where those poses live, the inverse of
-    ``gt_transform`` bringing the ground truth there (``mesh_score.score_culled_in_map_frame``)."""
+    ``gt_transform`` bringing the ground truth there (``mesh_score.score_culled_in_map_frame``).  ``align`` (with ``gt_mesh``; True or a
+    dict of ``mesh_score.align_icp`` keywords): the reconstruction is registered to the ground truth by ICP before it is measured, and
+    ``stats['mesh_score']['alignment']`` records what was found."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -148,11 +150,12 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
                     try:
                         stats['mesh_score'] = score_culled_in_map_frame(
                             stats['mesh'], gt_mesh, out['gt_w2c_all_frames'], out['intrinsics'],
-                            (data["desired_image_width"], data["desired_image_height"]), gt_transform=transform, device=device)
+                            (data["desired_image_width"], data["desired_image_height"]), gt_transform=transform, device=device,
+                            **({"align": align} if align else {}))
                     except ValueError as e:
                         raise SystemExit(f"--cull: {e}") from None
                 else:
-                    stats['mesh_score'] = score_mesh(stats['mesh'], gt_mesh, transform=transform, device=device)
+                    stats['mesh_score'] = score_mesh(stats['mesh'], gt_mesh, transform=transform, device=device, **({"align": align} if align else {}))
     finally:
         dataset.close()
     return params, variables, stats, path
@@ -176,7 +179,11 @@ def main(argv=None):
                              "(Replica: the first line of traj.txt)")
     parser.add_argument("--cull", action="store_true",
                         help="with --gt-mesh: cull both meshes to the frusta of the dataset's poses before scoring (splatam_amd.mesh_render)")
+    parser.add_argument("--align", action="store_true",
+                        help="with --gt-mesh: register the mesh to the ground truth by point-to-point ICP before scoring")
     args = parser.parse_args(argv)
+    if args.align and not args.gt_mesh:
+        parser.error("--align needs --gt-mesh")
     if args.gt_mesh and not args.mesh:
         parser.error("--gt-mesh needs --mesh")
     if args.cull and not args.gt_mesh:
@@ -186,7 +193,7 @@ def main(argv=None):
     print(f"Seed set to: {config['seed']}")
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
                             exact_checkpoints=args.exact_checkpoints, mesh=args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
-                            cull=args.cull)
+                            cull=args.cull, **({"align": True} if args.align else {}))
     ev = stats.get('eval')
     if ev is not None:
         print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"
