@@ -34,6 +34,7 @@ extern "C" {
                                       ADDED WITHIN 17 (no struct changed, no symbol removed, so the number stays and every binding built against
                                       17 keeps working): SplatLossConfigEx, SPLAT_LOSS_SPLATAM / SPLAT_LOSS_GS, splat_iter_loss_backward_ex,
                                       splat_iter_mapping_step_ex -- the mapping loss of the refinement script (get_loss_gs);
+                                      SPLAT_EVAL_LPIPS, SplatLpipsWorkspace, splat_lpips_* -- LPIPS from caller-supplied AlexNet weights (csrc/lpips.hip);
                                       16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
                                       15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
                                       14: frame ingest (splat_frame_ingest);
@@ -707,7 +708,8 @@ int splat_map_duplicate(SplatMapStore *store, const SplatDensifyArgs *args, void
  *   pixels with gt_depth > 0 && !(silhouette > sil_thres) -- the frame has depth where the map shows nothing; a NaN silhouette is a hole --,
  *   into row slot SPLAT_EVAL_HOLES.  The count does not depend on sil_mask or ms_ssim, costs no pass and no launch, and needs the silhouette.
  *   The reference counts a frame towards its novel-view averages unless holes / (H * W) * 100 > 0.1 in float32.
- * LPIPS is not computed (it needs network weights this library does not carry).
+ * LPIPS goes into row slot SPLAT_EVAL_LPIPS when the caller supplies AlexNet weights (splat_lpips_planes, "LPIPS" below); this library
+ *   carries none, and without them the slot stays 0.
  * ------------------------------------------------------------------------------------------------------------ */
 #define SPLAT_EVAL_ROW 8         /* doubles per output row */
 #define SPLAT_EVAL_PSNR 0
@@ -718,6 +720,7 @@ int splat_map_duplicate(SplatMapStore *store, const SplatDensifyArgs *args, void
 #define SPLAT_EVAL_FLAGGED 5     /* != 0: the render behind this row ran on truncated / unsorted lists (st.status OVERFLOW or STALE_HINT):
                                     re-size the lists and evaluate the frame again (splat_iter_eval only; 0 from splat_eval_metrics) */
 #define SPLAT_EVAL_HOLES 6       /* number of holes when cfg->holes is set, otherwise 0 */
+#define SPLAT_EVAL_LPIPS 7       /* (added within ABI 17) 0 from the entries above; splat_lpips_planes writes it when the caller asks */
 #define SPLAT_EVAL_LEVELS 5
 #define SPLAT_EVAL_SUMS 40       /* doubles per copy of SplatEvalWorkspace.sums: [0..2] squared error per channel, [3] depth term, [4] valid count, [5] hole count (cfg->holes),
                                     [8 + 6 level + 2 channel] sum of the contrast-structure term, [... + 1] sum of ssim over the level's window positions */
@@ -1038,6 +1041,58 @@ int splat_icp_accumulate(const float *source, const float *targets, int64_t num_
                          double threshold, const double *origin, const double *state, double *partials, void *stream);
 int splat_icp_solve(const double *partials, int64_t n, int32_t max_iterations, double relative_fitness, double relative_rmse,
                     const double *origin, double *state, double *history, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * LPIPS (added within ABI 17; csrc/lpips.hip, arithmetic in csrc/lpips_math.h): what the reference's eval() / eval_nvs() compute with
+ * torchmetrics' LearnedPerceptualImagePatchSimilarity(net_type='alex', normalize=True) on clamp(weighted_im, 0, 1) and
+ * clamp(weighted_gt_im, 0, 1), from weights THE CALLER SUPPLIES.  The definition is restated from the public implementation as recalled
+ * (DESIGN.md 4): x <- 2x - 1, (x - shift_c) / scale_c with shift (-0.030, -0.088, -0.188), scale (0.458, 0.448, 0.450); the five AlexNet
+ * `features` convolutions (3->64 11x11 stride 4 pad 2; maxpool 3x3 stride 2, 64->192 5x5 pad 2; maxpool, 192->384 3x3 pad 1; 384->256 3x3
+ * pad 1; 256->256 3x3 pad 1), each with bias and ReLU, tapped after the ReLU; per tap and pixel u = f / (sqrt(sum_c f_c^2) + 1e-10) for
+ * both images, d_l = mean over the tap's pixels of sum_c w_lc (u0_c - u1_c)^2; LPIPS = sum_l d_l.
+ * The convolutions are one implicit GEMM on the exact-f32 MFMA, k = (c KH + dy) KH + dx: per 32 consecutive k a k-ordered fmaf chain
+ * from zero, the blocks' sums added in order of k -- float32 as torch computes it, the same bits on every run, no atomics anywhere.  Both images go through every kernel as a batch of two, so an image
+ * scored against itself -- or a frame whose every pixel is masked -- gives exactly 0.0.  Nothing is read back.
+ *
+ * weights: splat_lpips_weight_floats() floats on the device, in the canonical order: per layer the weight [Cout][Cin][KH][KH] then the
+ * bias [Cout], conv1 .. conv5; then lin0 .. lin4 ([Cout] each, the non-negative 1x1 `lin` weights).
+ * splat_lpips_pack turns them, ONCE per network, into the packed network `net` (splat_lpips_pack_floats() floats) that every other entry
+ * reads: per layer the weights as [Kpad][Cout] (zero rows behind K: conv1's 363 -> 384), then the five biases, then the five lin vectors.
+ * It does not depend on the image size, so it lives beside the workspaces, not in them.
+ * The workspace (per image size; both extents >= SPLAT_LPIPS_MIN_SIZE, refused otherwise) holds the transformed input, the five taps,
+ * the two pooled maps and the distance's double partials: arrays "input", "tap0" .. "tap4", "pool1", "pool2", "partials" in the
+ * SplatArrayInfo convention.  It MUST come from splat_lpips_workspace_layout for the very size it is used at: the kernels write what the
+ * size implies.  splat_lpips_workspace_bind records the size, and splat_lpips_planes / _images refuse a workspace bound for another.
+ * ------------------------------------------------------------------------------------------------------------ */
+#define SPLAT_LPIPS_LAYERS 5
+#define SPLAT_LPIPS_MIN_SIZE 31
+typedef struct SplatLpipsWorkspace {
+    float *input;                        /* [2][3][H][W] */
+    float *taps[SPLAT_LPIPS_LAYERS];     /* tap l: [2][C_l][H_l][W_l], C = 64, 192, 384, 256, 256 */
+    float *pooled[2];                    /* what conv2 / conv3 read */
+    double *partials;
+    int32_t width, height;               /* the image size it was laid out and bound for (splat_lpips_workspace_bind) */
+} SplatLpipsWorkspace;
+size_t splat_lpips_weight_floats(void);
+size_t splat_lpips_pack_floats(void);
+/* extent of tap `layer` (0..4) along an image dimension of n pixels; 0 when there is none */
+int32_t splat_lpips_tap_size(int32_t n, int32_t layer);
+/* returns the number of arrays or -SPLAT_E_INVALID (an extent under SPLAT_LPIPS_MIN_SIZE) */
+int splat_lpips_workspace_layout(int32_t width, int32_t height, SplatArrayInfo *out, int32_t max_entries, size_t *total_bytes);
+/* width, height: what splat_lpips_workspace_layout was asked for */
+int splat_lpips_workspace_bind(SplatLpipsWorkspace *ws, void *slab, const SplatArrayInfo *arrays, int32_t n, int32_t width, int32_t height);
+int splat_lpips_pack(const float *weights, float *net, void *stream);
+/* One layer alone (tests, measurements): convolution `layer` + bias + ReLU of x [2][Cin][in_height][in_width] into
+ * y [2][Cout][out_h][out_w]; no pool. */
+int splat_lpips_conv(int32_t layer, int32_t in_width, int32_t in_height, const float *x, const float *net, float *y, void *stream);
+/* LPIPS of an evaluated frame: weighted_im / weighted_gt_im formed from rgb [3][H][W], silhouette [H][W] (may be NULL with sil_mask 0),
+ * gt_im [3][H][W], gt_depth [H][W] exactly as splat_eval_metrics forms them, clamped to 0..1; one double to out (a caller passes
+ * &row[SPLAT_EVAL_LPIPS], AFTER the call that writes the row). */
+int splat_lpips_planes(int32_t width, int32_t height, const float *rgb, const float *silhouette, const float *gt_im, const float *gt_depth,
+                       float sil_thres, int32_t sil_mask, const float *net, const SplatLpipsWorkspace *workspace, double *out, void *stream);
+/* ... of two plain images [3][H][W] in 0..1 (values outside are clamped) */
+int splat_lpips_images(int32_t width, int32_t height, const float *im0, const float *im1, const float *net,
+                       const SplatLpipsWorkspace *workspace, double *out, void *stream);
 
 /* Developer switches used by scripts/ (never by the product path): key 0 = skip the per-tile count atomics of K1 (timing
  * experiment; results are then invalid); key 4 = measurement builds of the fused backward composite (bits: 1 = per-workgroup

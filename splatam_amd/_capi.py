@@ -160,9 +160,13 @@ class SplatMeshView(C.Structure):          # (added within ABI 17: the mesh rend
                 ("near_z", C.c_float), ("w2c", _fp)]
 
 
+class SplatLpipsWorkspace(C.Structure):    # (added within ABI 17: LPIPS from caller-supplied weights, csrc/lpips.hip)
+    _fields_ = [("input", _fp), ("taps", _fp * 5), ("pooled", _fp * 2), ("partials", _fp), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
-                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView)
+                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView, SplatLpipsWorkspace)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -190,6 +194,7 @@ SPLAT_ICP_STATE, SPLAT_ICP_ROWS, SPLAT_ICP_SUMS = 24, 256, 17      # (added with
 SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS, SPLAT_ICP_FITNESS, SPLAT_ICP_RMSE = 16, 17, 18, 19
 SPLAT_ICP_PREV_FITNESS, SPLAT_ICP_PREV_RMSE, SPLAT_ICP_COUNT, SPLAT_ICP_POINTS = 20, 21, 22, 23
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
+SPLAT_EVAL_LPIPS, SPLAT_LPIPS_LAYERS, SPLAT_LPIPS_MIN_SIZE = 7, 5, 31      # (added within ABI 17: csrc/lpips.hip)
 
 
 def lists_sorted_by_composite(max_list_hint: int) -> bool:
@@ -219,6 +224,8 @@ EXPORTS = (
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
     "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
     "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
+    "splat_lpips_weight_floats", "splat_lpips_pack_floats", "splat_lpips_tap_size", "splat_lpips_workspace_layout", "splat_lpips_workspace_bind",
+    "splat_lpips_pack", "splat_lpips_conv", "splat_lpips_planes", "splat_lpips_images",
 )
 
 _lib = None
@@ -375,6 +382,24 @@ def lib():
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = args
+    lp = C.POINTER(SplatLpipsWorkspace)
+    for name in ("splat_lpips_weight_floats", "splat_lpips_pack_floats"):
+        f = getattr(L, name)
+        f.restype = C.c_size_t
+        f.argtypes = []
+    L.splat_lpips_tap_size.restype = C.c_int32
+    L.splat_lpips_tap_size.argtypes = [C.c_int32, C.c_int32]
+    for name, args in (
+        ("splat_lpips_workspace_layout", [C.c_int32, C.c_int32, info, C.c_int32, C.POINTER(C.c_size_t)]),
+        ("splat_lpips_workspace_bind", [lp, _fp, info, C.c_int32, C.c_int32, C.c_int32]),
+        ("splat_lpips_pack", [_fp, _fp, _fp]),
+        ("splat_lpips_conv", [C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
+        ("splat_lpips_planes", [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_float, C.c_int32, _fp, lp, _fp, _fp]),
+        ("splat_lpips_images", [C.c_int32, C.c_int32, _fp, _fp, _fp, lp, _fp, _fp]),
+    ):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = args
     L.splat_debug_option.restype = C.c_int
     L.splat_debug_option.argtypes = [C.c_int, C.c_int]
     L.splat_debug_stamps.restype = C.c_int
@@ -447,6 +472,18 @@ def eval_workspace_layout(width, height, ms_ssim=True):
     if n < 0 or n > 4:
         raise RuntimeError(f"splat_eval_workspace_layout({width}, {height}, ms_ssim={bool(ms_ssim)}) failed: "
                            f"{lib().splat_error_string(-n).decode()} (MS-SSIM needs min(width, height) > 160)")
+    return Layout(arrays, n, int(total.value))
+
+
+def lpips_workspace_layout(width, height):
+    """LPIPS' scratch for an image size (SplatLpipsWorkspace): the transformed input, the five taps, the two pooled maps and the
+    distance's partials (the packed network is size-independent and lives beside the workspaces).  Raises for an extent under SPLAT_LPIPS_MIN_SIZE."""
+    arrays = (SplatArrayInfo * 16)()
+    total = C.c_size_t(0)
+    n = lib().splat_lpips_workspace_layout(int(width), int(height), arrays, 16, C.byref(total))
+    if n < 0 or n > 16:
+        raise RuntimeError(f"splat_lpips_workspace_layout({width}, {height}) failed: LPIPS needs images of at least "
+                           f"{SPLAT_LPIPS_MIN_SIZE} x {SPLAT_LPIPS_MIN_SIZE} pixels")
     return Layout(arrays, n, int(total.value))
 
 

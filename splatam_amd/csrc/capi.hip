@@ -2,6 +2,7 @@
 #include <cstring>
 
 #include "splat_device.h"
+#include "lpips_math.h"
 
 using namespace splat;
 
@@ -61,6 +62,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
     SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid); SPLAT_SIZEOF_CASE(SplatMeshView);
+    SPLAT_SIZEOF_CASE(SplatLpipsWorkspace);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -814,6 +816,88 @@ int splat_eval_workspace_bind(SplatEvalWorkspace *ews, void *slab, const SplatAr
         if (strcmp(arrays[i].name, "sums") == 0) ews->sums = reinterpret_cast<double *>(base + arrays[i].offset);
     }
     return SPLAT_OK;
+}
+
+// the LPIPS layer (csrc/lpips.hip)
+static_assert(SPLAT_LPIPS_LAYERS == kLpipsLayers && SPLAT_LPIPS_MIN_SIZE == kLpipsMinSize, "include/splat_hip.h and lpips_math.h agree");
+
+size_t splat_lpips_weight_floats(void) { return lpips_weight_floats(); }
+size_t splat_lpips_pack_floats(void) { return lpips_pack_floats(); }
+int32_t splat_lpips_tap_size(int32_t n, int32_t layer) { return n <= 0 || layer < 0 || layer >= kLpipsLayers ? 0 : lpips_tap_size(n, layer); }
+
+static bool valid_lpips_size(int32_t width, int32_t height) {
+    return width >= kLpipsMinSize && height >= kLpipsMinSize && (long long)width * height <= 0x3ffffffLL;
+}
+
+int splat_lpips_workspace_layout(int32_t width, int32_t height, SplatArrayInfo *out, int32_t max_entries, size_t *total_bytes) {
+    if (!valid_lpips_size(width, height)) return -SPLAT_E_INVALID;
+    static const char *const tap_names[kLpipsLayers] = {"tap0", "tap1", "tap2", "tap3", "tap4"};
+    static const char *const pool_names[2] = {"pool1", "pool2"};
+    LayoutWriter w{out, max_entries};
+    w.add("input", 4 * 6 * (size_t)width * height, 0);
+    int pools = 0;
+    for (int l = 0; l < kLpipsLayers; ++l) {
+        const LpipsLayer L = lpips_layer(l);
+        if (L.pool) w.add(pool_names[pools++], 4 * 2 * (size_t)L.cin * lpips_layer_in(width, l) * lpips_layer_in(height, l), 0);
+        w.add(tap_names[l], 4 * 2 * (size_t)L.cout * lpips_tap_size(width, l) * lpips_tap_size(height, l), 0);
+    }
+    w.add("partials", 8 * lpips_partial_rows(width, height), 0);
+    if (total_bytes) *total_bytes = (w.offset + SPLAT_SLAB_ALIGN - 1) / SPLAT_SLAB_ALIGN * SPLAT_SLAB_ALIGN;
+    return w.n;
+}
+
+int splat_lpips_workspace_bind(SplatLpipsWorkspace *ws, void *slab, const SplatArrayInfo *arrays, int32_t n, int32_t width, int32_t height) {
+    if (!ws || !slab || !arrays || n < 0 || ((uintptr_t)slab % SPLAT_SLAB_ALIGN) != 0 || !valid_lpips_size(width, height)) return SPLAT_E_INVALID;
+    *ws = SplatLpipsWorkspace{};
+    char *base = static_cast<char *>(slab);
+    for (int32_t i = 0; i < n; ++i) {
+        const char *name = arrays[i].name;
+        if (!name) return SPLAT_E_INVALID;
+        float *p = reinterpret_cast<float *>(base + arrays[i].offset);
+        if (strcmp(name, "input") == 0) ws->input = p;
+        else if (strncmp(name, "tap", 3) == 0 && name[3] >= '0' && name[3] < '0' + kLpipsLayers && !name[4]) ws->taps[name[3] - '0'] = p;
+        else if (strcmp(name, "pool1") == 0) ws->pooled[0] = p;
+        else if (strcmp(name, "pool2") == 0) ws->pooled[1] = p;
+        else if (strcmp(name, "partials") == 0) ws->partials = reinterpret_cast<double *>(p);
+    }
+    ws->width = width;
+    ws->height = height;
+    return SPLAT_OK;
+}
+
+int splat_lpips_pack(const float *weights, float *net, void *stream) {
+    if (!weights || !net) return SPLAT_E_INVALID;
+    return check(launch_lpips_pack(weights, net, (hipStream_t)stream));
+}
+
+int splat_lpips_conv(int32_t layer, int32_t in_width, int32_t in_height, const float *x, const float *net, float *y, void *stream) {
+    if (layer < 0 || layer >= kLpipsLayers || !x || !net || !y || in_width <= 0 || in_height <= 0) return SPLAT_E_INVALID;
+    const LpipsLayer L = lpips_layer(layer);
+    if (lpips_conv_out(in_width, L.k, L.stride, L.pad) <= 0 || lpips_conv_out(in_height, L.k, L.stride, L.pad) <= 0) return SPLAT_E_INVALID;
+    if ((long long)in_width * in_height * L.cin > 0x1fffffffLL) return SPLAT_E_INVALID;
+    return check(launch_lpips_conv(layer, in_width, in_height, x, net, y, (hipStream_t)stream));
+}
+
+// laid out and bound for exactly this size: the kernels write what the size implies, a smaller slab would be overrun
+static bool valid_lpips_workspace(const SplatLpipsWorkspace *ws, int32_t width, int32_t height) {
+    if (!ws || ws->width != width || ws->height != height || !ws->input || !ws->pooled[0] || !ws->pooled[1] || !ws->partials) return false;
+    for (int l = 0; l < kLpipsLayers; ++l)
+        if (!ws->taps[l]) return false;
+    return true;
+}
+
+int splat_lpips_planes(int32_t width, int32_t height, const float *rgb, const float *silhouette, const float *gt_im, const float *gt_depth,
+                       float sil_thres, int32_t sil_mask, const float *net, const SplatLpipsWorkspace *workspace, double *out, void *stream) {
+    if (!valid_lpips_size(width, height) || !valid_lpips_workspace(workspace, width, height) || !rgb || !gt_im || !gt_depth || !net || !out ||
+        (sil_mask && !silhouette))
+        return SPLAT_E_INVALID;
+    return check(launch_lpips(width, height, rgb, gt_im, silhouette, gt_depth, sil_thres, sil_mask, net, *workspace, out, (hipStream_t)stream));
+}
+
+int splat_lpips_images(int32_t width, int32_t height, const float *im0, const float *im1, const float *net,
+                       const SplatLpipsWorkspace *workspace, double *out, void *stream) {
+    if (!valid_lpips_size(width, height) || !valid_lpips_workspace(workspace, width, height) || !im0 || !im1 || !net || !out) return SPLAT_E_INVALID;
+    return check(launch_lpips(width, height, im0, im1, nullptr, nullptr, 0.f, 0, net, *workspace, out, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -117,6 +117,13 @@ hipError_t launch_nn_cell_starts(const SplatNnGrid &g, const int32_t *sorted_key
 hipError_t launch_nn_query(const SplatNnGrid &g, const float *points, const int32_t *order, long long n, float *dist2, int32_t *index,
                            int32_t *account, hipStream_t s);
 hipError_t launch_nn_reduce(const float *dist2, long long n, double threshold, double *partials, double *row, hipStream_t s);
+// lpips.hip: LPIPS (AlexNet taps) from caller-supplied weights; the convolutions are an implicit GEMM on the f32-input MFMA
+size_t lpips_partial_rows(int W, int H);
+hipError_t launch_lpips_pack(const float *weights, float *net, hipStream_t s);
+hipError_t launch_lpips_conv(int l, int Win, int Hin, const float *x, const float *net, float *y, hipStream_t s);
+hipError_t launch_lpips(int W, int H, const float *im0, const float *im1, const float *sil, const float *gt_depth, float sil_thres, int sil_mask,
+                        const float *net, const SplatLpipsWorkspace &ws, double *out, hipStream_t s);
+
 // icp.hip: point-to-point ICP on the correspondences splat_nn_query finds
 hipError_t launch_icp_transform(const float *source, long long n, const double *state, float *moved, hipStream_t s);
 hipError_t launch_icp_accumulate(const float *source, const float *targets, long long num_targets, const float *dist2, const int32_t *index,

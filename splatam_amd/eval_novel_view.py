@@ -7,7 +7,8 @@ configs/replica_v2/eval_novel_view.py); this package ships none of them.  What h
 of ``python -m splatam_amd.run`` leaves), and
   * with ``use_train_split`` the training frames are scored by ``evaluation.evaluate`` into ``<workdir>/<run_name>/eval_train``,
   * otherwise the held-out frames by ``evaluation.evaluate_novel_views`` into ``<workdir>/<run_name>/eval_nvs``,
-with the pictures saved (``save_frames=True``), and the reference's five lines printed; LPIPS is "not computed".
+with the pictures saved (``save_frames=True``), and the reference's five lines printed; LPIPS is "not computed" unless
+``--lpips-weights PATH`` (or ``config['lpips_weights']``) names the AlexNet weights (``splatam_amd.lpips``).
 """
 from __future__ import annotations
 
@@ -62,6 +63,8 @@ def run(config, engine="fused", prefetch=4):
         mapping = config['mapping']
         opts = dict(eval_every=config['eval_every'], engine="mirror" if engine == "mirror" else None, ms_ssim=ms_ssim,
                     save_frames=engine != "mirror")        # (the pictures are formed on the device: the mirror writes the numbers only)
+        if config.get('lpips_weights') is not None:
+            opts['lpips_weights'] = config['lpips_weights']
         if data['use_train_split']:
             eval_dir = os.path.join(results_dir, "eval_train")
             out = evaluation.evaluate(dataset, params, n, mapping['sil_thres'], mapping['num_iters'], mapping['add_new_gaussians'],
@@ -80,12 +83,17 @@ def main(argv=None):
     parser.add_argument("experiment", help="path to an eval_novel_view experiment file (a Python file that defines `config`)")
     parser.add_argument("--engine", default="fused", choices=("fused", "mirror"),
                         help="fused: the HIP path (default); mirror: the torch form (slow; saves no pictures)")
+    parser.add_argument("--lpips-weights", default=None, metavar="PATH",
+                        help="AlexNet + LPIPS linear-layer weights (canonical .npz or a torch state dict): LPIPS is then computed")
     args = parser.parse_args(argv)
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
+    if args.lpips_weights is not None:
+        config = dict(config, lpips_weights=args.lpips_weights)        # (a copy: the experiment module's dict stays as written)
     out, eval_dir = run(config, engine=args.engine)
     print(f"Average PSNR: {out['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * out['avg_depth_rmse']:.2f} cm\n"
-          f"Average Depth L1: {100 * out['avg_depth_l1']:.2f} cm\nAverage MS-SSIM: {out['avg_ms_ssim']:.3f}\nAverage LPIPS: not computed")
+          f"Average Depth L1: {100 * out['avg_depth_l1']:.2f} cm\nAverage MS-SSIM: {out['avg_ms_ssim']:.3f}\n"
+          + (f"Average LPIPS: {out['avg_lpips']:.3f}" if out.get('lpips') is not None else "Average LPIPS: not computed"))
     if 'valid_nvs_frames' in out:
         print(f"{int(out['valid_nvs_frames'].sum())} of {len(out['frames'])} held-out frames are valid novel views (at most 0.1 % holes)")
     print(f"wrote {eval_dir}")

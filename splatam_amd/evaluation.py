@@ -13,8 +13,10 @@ Kept from the reference, quirks included (each is pinned by tests/golden/eval_re
 ``save_frames=True`` writes the reference's four picture directories (``rendered_rgb/gs_%04d.png``, ``rendered_depth/gs_%04d.png``,
 ``rgb/gt_%04d.png``, ``depth/gt_%04d.png``: eval_helpers.py:418-426, 509-528) from the planes the evaluation render left, through
 splat_view_finish (csrc/view.hip); the depth pictures carry matplotlib's jet, not ``cv2.COLORMAP_JET`` (``splatam_amd.view``).
-Not kept: the plots, and LPIPS -- it needs AlexNet weights that this package does not carry; the result says
-``lpips: None`` instead of a made-up number.  A failure in the trajectory error is raised, not replaced by 100.0.
+Not kept: the plots.  LPIPS is computed when the caller supplies the AlexNet weights (``lpips_weights``: a path or an
+``lpips.LpipsWeights``; csrc/lpips.hip writes slot 7 of the frame's row, still without a host read) -- this package carries none and
+downloads none, and without them the result says ``lpips: None`` instead of a made-up number.  A failure in the trajectory error is
+raised, not replaced by 100.0.
 
 ``evaluate_novel_views`` is the reference's ``eval_nvs`` (utils/eval_helpers.py:626-825) in the same manner: the finished map scored
 at HELD-OUT poses (a dataset's test split, whose item 0 is the first training frame), one ``FusedEngine.evaluate_view`` per frame,
@@ -76,17 +78,18 @@ def _read_table(table):
     return table.cpu().numpy()
 
 
-def _mirror_row(params, curr_data, t, sil_thres, sil_mask, ms_ssim):
+def _mirror_row(params, curr_data, t, sil_thres, sil_mask, ms_ssim, lpips_weights=None):
     """One frame by the torch mirror: the reference's two renders through ``slam.Renderer`` + ``slam.eval_frame_metrics``."""
     with torch.no_grad():
         p = {k: v.detach() for k, v in params.items()}
         tg = slam.transform_to_frame(p, t, gaussians_grad=False, camera_grad=False)
         depth_sil, _, _ = slam.Renderer(raster_settings=curr_data['cam'])(**slam.transformed_params2depthplussilhouette(p, curr_data['w2c'], tg))
         im, _, _ = slam.Renderer(raster_settings=curr_data['cam'])(**slam.transformed_params2rendervar(p, tg))
-        m = slam.eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=ms_ssim)
+        m = slam.eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=ms_ssim, lpips_weights=lpips_weights)
     nan = torch.full((), float("nan"))
-    vals = [m['psnr'], m['depth_rmse'], m['depth_l1'], m['ms_ssim'] if ms_ssim else nan, m['valid']]
-    return torch.stack([v.detach().double().cpu() for v in vals] + [torch.zeros((), dtype=torch.float64)] * 3)
+    zero = torch.zeros((), dtype=torch.float64)
+    vals = [m['psnr'], m['depth_rmse'], m['depth_l1'], m['ms_ssim'] if ms_ssim else nan, m['valid'], zero, zero, m.get('lpips', zero)]
+    return torch.stack([v.detach().double().cpu() for v in vals])
 
 
 class _FrameSaver:
@@ -156,14 +159,30 @@ class _FrameSaver:
             self.pool.shutdown(wait=True)                                      # (the evaluation failed: its own error is the one to raise)
 
 
+def _lpips_arguments(lpips_weights, dev, mirror):
+    """(weights or None, keyword arguments for evaluate_frame / evaluate_view): without weights NOTHING is passed on, so the calls are
+    the ones they were."""
+    from . import lpips as lp
+    if isinstance(lpips_weights, lp.Lpips):                 # (a caller that evaluates often keeps the packed network)
+        if mirror:
+            raise ValueError("the mirror engine takes the weights (a path or LpipsWeights), not a device network")
+        return lpips_weights, {'lpips': lpips_weights}
+    weights = lp.as_weights(lpips_weights)
+    if weights is None or mirror:
+        return weights, {}
+    return weights, {'lpips': lp.Lpips(weights, dev)}
+
+
 def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every=1, engine=None, eval_dir=None,
-             ms_ssim=True, save_frames=False):
+             ms_ssim=True, save_frames=False, lpips_weights=None):
     """Evaluates ``params`` (the final map and trajectory of a run over ``dataset``) on frames ``eval_frame_indices(num_frames,
     eval_every)``.  Returns a dict: per-frame float64 arrays ``psnr``, ``depth_rmse``, ``depth_l1``, ``ms_ssim`` (NaN when
-    ``ms_ssim=False``), their means ``avg_psnr`` ..., ``ate_rmse``, ``frames`` (the evaluated indices), ``lpips`` (None: not computed),
+    ``ms_ssim=False``), their means ``avg_psnr`` ..., ``ate_rmse``, ``frames`` (the evaluated indices), ``lpips`` / ``avg_lpips``
+    (with ``lpips_weights`` -- a path ``lpips.load_weights`` reads, an ``lpips.LpipsWeights``, or an ``lpips.Lpips`` already on the device --: the per-frame array and its mean;
+    without: ``lpips`` is None, there is no ``avg_lpips``, and nothing more is launched),
     ``repeated`` (frames evaluated twice because their render outgrew the learnt list buckets), ``eval_s`` / ``eval_ms_per_frame`` (wall
     time from the call to the table read, dataset access and list learning included).  With ``eval_dir`` the reference's text
-    files psnr.txt, rmse.txt, l1.txt, ssim.txt are written there; ``save_frames`` (needs ``eval_dir`` and an engine) also writes the
+    files psnr.txt, rmse.txt, l1.txt, ssim.txt (and lpips.txt with ``lpips_weights``) are written there; ``save_frames`` (needs ``eval_dir`` and an engine) also writes the
     evaluated frames as PNGs (``_FrameSaver``) -- the metrics and their single table read are the same with and without it.
 
     ``engine``: a ``FusedEngine`` that holds ``params`` (it evaluates on its own map), ``None`` (a throw-away engine is built
@@ -194,6 +213,7 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
         cam = engine.cam_settings
     if ms_ssim and min(color0.shape[1:]) <= 160:
         raise ValueError(f"MS-SSIM needs frames with min(H, W) > 160 (got {tuple(color0.shape[1:])}); pass ms_ssim=False")
+    lpips_w, lpips_kw = _lpips_arguments(lpips_weights, dev, mirror)
 
     def curr(t, color, depth):
         return {'cam': cam, 'im': color, 'depth': depth, 'id': t, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
@@ -212,7 +232,7 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
                 color, depth, _, pose = _frame(dataset, t)
                 poses.append(pose)
                 if t in frames:
-                    rows.append(_mirror_row(params, curr(t, color, depth), t, sil_thres, sil_mask, ms_ssim))
+                    rows.append(_mirror_row(params, curr(t, color, depth), t, sil_thres, sil_mask, ms_ssim, lpips_w))
             host = torch.stack(rows).numpy()
         else:
             engine.relearn_lists(curr(0, color0, depth0), 0)                      # (one read: sizes the list buckets for the map as it is)
@@ -222,7 +242,7 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
                 color, depth, _, pose = _frame(dataset, t)
                 poses.append(pose)                                               # (every frame's pose feeds the trajectory error)
                 if t in row_of:
-                    engine.evaluate_frame(curr(t, color, depth), t, table[row_of[t]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
+                    engine.evaluate_frame(curr(t, color, depth), t, table[row_of[t]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, **lpips_kw)
                     if saver is not None:
                         saver.save(t, engine.buf['out6'], color, depth)
             host = _read_table(table)
@@ -237,7 +257,7 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
                     engine.buf[k].zero_()
                 engine.relearn_lists(curr(t, color, depth), t)
                 again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
-                engine.evaluate_frame(curr(t, color, depth), t, again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim)
+                engine.evaluate_frame(curr(t, color, depth), t, again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, **lpips_kw)
                 host[i] = _read_table(again)
                 if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
                     raise RuntimeError(f"frame {t}: the per-tile lists could not be sized for its evaluation render")
@@ -249,11 +269,16 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
            'valid_pixels': host[:, _capi.SPLAT_EVAL_VALID].copy(), 'lpips': None, 'repeated': repeated, 'sil_mask': bool(sil_mask)}
     for k in ('psnr', 'depth_rmse', 'depth_l1', 'ms_ssim'):
         out['avg_' + k] = float(out[k].mean())
+    if lpips_w is not None:
+        out['lpips'] = host[:, _capi.SPLAT_EVAL_LPIPS].copy()
+        out['avg_lpips'] = float(out['lpips'].mean())
     out['ate_rmse'] = trajectory_error(params, first_frame_w2c, torch.stack([p.detach().to(dev).float() for p in poses]), num_frames)
     if eval_dir is not None:
         os.makedirs(eval_dir, exist_ok=True)
         for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')):
             np.savetxt(os.path.join(eval_dir, name), out[k])
+        if lpips_w is not None:
+            np.savetxt(os.path.join(eval_dir, "lpips.txt"), out['lpips'])
     return out
 
 
@@ -275,7 +300,7 @@ def _rigid_inverse(m):
     return torch.cat([torch.cat([rt, -(rt @ m[:3, 3:4])], dim=1), m[3:4]], dim=0)        # (the last row of a rigid matrix is its own)
 
 
-def _mirror_nvs_row(params, curr_data, gt_w2c, sil_thres, sil_mask, ms_ssim):
+def _mirror_nvs_row(params, curr_data, gt_w2c, sil_thres, sil_mask, ms_ssim, lpips_weights=None):
     """One held-out frame by the torch mirror, rendered the way eval_nvs renders it: the centres are moved by ``gt_w2c`` (and for an
     anisotropic map the rotations composed with its quaternion), then seen through the first frame's camera and depth row.  Returns
     (row, planes [5, H, W]: r, g, b, depth, silhouette)."""
@@ -291,16 +316,16 @@ def _mirror_nvs_row(params, curr_data, gt_w2c, sil_thres, sil_mask, ms_ssim):
             tg['unnorm_rotations'] = slam.quat_mult(q, F.normalize(p['unnorm_rotations']))
         depth_sil, _, _ = slam.Renderer(raster_settings=curr_data['cam'])(**slam.transformed_params2depthplussilhouette(p, curr_data['w2c'], tg))
         im, _, _ = slam.Renderer(raster_settings=curr_data['cam'])(**slam.transformed_params2rendervar(p, tg))
-        m = slam.eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=ms_ssim)
+        m = slam.eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=ms_ssim, lpips_weights=lpips_weights)
         holes = (~((depth_sil[1] > sil_thres) | ~(curr_data['depth'][0] > 0))).sum()
     nan = torch.full((), float("nan"))
     zero = torch.zeros((), dtype=torch.float64)
-    vals = [m['psnr'], m['depth_rmse'], m['depth_l1'], m['ms_ssim'] if ms_ssim else nan, m['valid'], zero, holes, zero]
+    vals = [m['psnr'], m['depth_rmse'], m['depth_l1'], m['ms_ssim'] if ms_ssim else nan, m['valid'], zero, holes, m.get('lpips', zero)]
     return torch.stack([v.detach().double().cpu() for v in vals]), torch.cat([im, depth_sil[0:2]]).contiguous()
 
 
 def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every=1, engine=None, eval_dir=None,
-                         ms_ssim=True, save_frames=False):
+                         ms_ssim=True, save_frames=False, lpips_weights=None):
     """Novel-view synthesis of a finished map, with the semantics of the reference's ``eval_nvs``.  ``dataset`` is a held-out split:
     item 0 is the first training frame -- it only supplies ``first_frame_w2c = inv(pose_0)`` and the camera, and is not scored --,
     items 1 .. num_frames - 1 are the held-out frames; index k = t - 1 is scored when ``k == 0 or (k + 1) % eval_every == 0``.  The
@@ -311,8 +336,9 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
     A frame is VALID unless ``holes / (H W) * 100 > 0.1`` (in float32, as torch evaluates it), holes = pixels with depth > 0 whose
     silhouette is not above ``sil_thres``.  Returns the dict of ``evaluate`` without ``ate_rmse`` -- ``frames`` are the scored k,
     the per-frame arrays hold ALL scored frames, the four averages run over the VALID frames only (NaN when there is none) -- and
-    ``holes`` (int64 per frame), ``percent_holes`` (float32), ``valid_nvs_frames`` (bool), ``lpips: None``.  With ``eval_dir``:
-    psnr.txt, rmse.txt, l1.txt, ssim.txt and valid_nvs_frames.npy; with ``save_frames`` also the four picture directories with
+    ``holes`` (int64 per frame), ``percent_holes`` (float32), ``valid_nvs_frames`` (bool), ``lpips: None`` -- or, with
+    ``lpips_weights`` (as in ``evaluate``), ``lpips`` per scored frame and ``avg_lpips`` over the VALID frames.  With ``eval_dir``:
+    psnr.txt, rmse.txt, l1.txt, ssim.txt (lpips.txt with weights) and valid_nvs_frames.npy; with ``save_frames`` also the four picture directories with
     ``splatam_%04d.png`` (rendered) and ``gt_%04d.png``, numbered by k.
 
     ``engine``: a ``FusedEngine`` that holds the map, ``None`` (a throw-away one) or ``"mirror"`` (torch, runs without a GPU: the
@@ -344,6 +370,7 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
         cam = slam.setup_camera(W, H, intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
     if engine is None:
         engine = FusedEngine({k: v.detach().float().contiguous() for k, v in params.items()}, cam)
+    lpips_w, lpips_kw = _lpips_arguments(lpips_weights, dev, mirror)
     k_host = _intrinsics4(intrinsics)                                     # (on the host once: a device matrix would be read per view)
 
     def curr(t, color, depth):
@@ -359,7 +386,7 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
                 if t - 1 not in row_of:
                     continue
                 color, depth, _, pose = _frame(dataset, t)
-                row, planes = _mirror_nvs_row(params, curr(t, color, depth), torch.linalg.inv(pose), sil_thres, sil_mask, ms_ssim)
+                row, planes = _mirror_nvs_row(params, curr(t, color, depth), torch.linalg.inv(pose), sil_thres, sil_mask, ms_ssim, lpips_w)
                 rows.append(row)
                 if saver is not None:
                     saver.save(t - 1, planes, color, depth)
@@ -377,7 +404,7 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
                     engine.relearn_lists(curr(t, color, depth), 0, view=view, w2c=w2c, intrinsics=k_host)
                     learnt = True
                 engine.evaluate_view(view, w2c, curr(t, color, depth), table[row_of[t - 1]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim,
-                                     holes=True, intrinsics=k_host)
+                                     holes=True, intrinsics=k_host, **lpips_kw)
                 if saver is not None:
                     saver.save(t - 1, view.camera.buf['out6'], color, depth)
             host = _read_table(table)
@@ -393,7 +420,7 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
                 engine.relearn_lists(curr(k + 1, color, depth), 0, view=view, w2c=w2c, intrinsics=k_host)
                 again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
                 engine.evaluate_view(view, w2c, curr(k + 1, color, depth), again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=True,
-                                     intrinsics=k_host)
+                                     intrinsics=k_host, **lpips_kw)
                 host[i] = _read_table(again)
                 if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
                     raise RuntimeError(f"held-out frame {k}: the per-tile lists could not be sized for its evaluation render")
@@ -409,9 +436,14 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
            'repeated': repeated, 'sil_mask': bool(sil_mask), 'holes': holes, 'percent_holes': percent, 'valid_nvs_frames': valid}
     for k in ('psnr', 'depth_rmse', 'depth_l1', 'ms_ssim'):
         out['avg_' + k] = float(out[k][valid].mean()) if valid.any() else float("nan")       # (numpy's mean of nothing, without its warning)
+    if lpips_w is not None:                                                                    # (eval_nvs: the valid frames only)
+        out['lpips'] = host[:, _capi.SPLAT_EVAL_LPIPS].copy()
+        out['avg_lpips'] = float(out['lpips'][valid].mean()) if valid.any() else float("nan")
     if eval_dir is not None:
         os.makedirs(eval_dir, exist_ok=True)
         for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')):
             np.savetxt(os.path.join(eval_dir, name), out[k])
+        if lpips_w is not None:
+            np.savetxt(os.path.join(eval_dir, "lpips.txt"), out['lpips'])
         np.save(os.path.join(eval_dir, "valid_nvs_frames.npy"), valid)
     return out

@@ -555,11 +555,12 @@ class FusedEngine:
         return self.rendered()
 
     # ------------------------------------------------------------------ evaluation (csrc/evalmetrics.hip; nothing is read here)
-    def evaluate_frame(self, curr_data, time_idx, out_row, sil_thres, sil_mask=False, ms_ssim=True):
+    def evaluate_frame(self, curr_data, time_idx, out_row, sil_thres, sil_mask=False, ms_ssim=True, lpips=None):
         """Render the map from pose ``time_idx`` and write the frame's metrics against ``curr_data['im']`` / ``['depth']`` into
         ``out_row`` (8 float64 on the device: psnr, depth_rmse, depth_l1, ms_ssim -- NaN when off --, valid count, != 0 when the
-        render ran on truncated lists, 2 spare; include/splat_hip.h SPLAT_EVAL_*).  Enqueues only: rows are read by the caller, as a
-        table, when it pleases.  The planes stay in ``rendered()``."""
+        render ran on truncated lists, the hole count (0 here: ``evaluate_view`` counts), LPIPS (0 without ``lpips``); include/splat_hip.h SPLAT_EVAL_*).  Enqueues only: rows are read by the caller, as a
+        table, when it pleases.  The planes stay in ``rendered()``.  ``lpips``: an ``lpips.Lpips`` on this device -- the frame's LPIPS
+        goes into slot SPLAT_EVAL_LPIPS (``evaluate_lpips`` on the planes the render left); None: the slot stays 0, nothing more is launched."""
         self._check_cam(curr_data)
         _check_eval_row(out_row, self.dev)
         cam = self._camera
@@ -574,12 +575,15 @@ class FusedEngine:
         with torch.cuda.device(self.dev):
             _capi.check(self.L.splat_iter_eval(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(cfg), C.byref(ws), C.byref(ews),
                                                out_row.data_ptr(), self._stream()), "splat_iter_eval")
+        if lpips is not None:
+            o = self.buf['out6']
+            evaluate_lpips(lpips, o[0:3], o[4], curr_data, out_row, sil_thres, sil_mask=sil_mask)      # (after the finish kernel, which leaves 0 there)
 
     def evaluate_metrics(self, rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True, holes=False):
         """``evaluate_metrics`` of this module (the metric kernels alone, on caller-supplied planes of any size)."""
         return evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=holes)
 
-    def evaluate_view(self, view, w2c, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True, holes=True, intrinsics=None):
+    def evaluate_view(self, view, w2c, curr_data, out_row, sil_thres, sil_mask=False, ms_ssim=True, holes=True, intrinsics=None, lpips=None):
         """A held-out frame scored at ITS pose (the per-frame part of the reference's eval_nvs()): ``render_view(view, w2c=w2c,
         rgb8=False)`` -- the view camera moves to ``w2c`` (float32 [4, 4] on the device: the frame's effective world-to-camera), the
         unchanged splat_iter_render composites the map there -- followed by ``evaluate_metrics`` of the view's planes against
@@ -587,7 +591,7 @@ class FusedEngine:
         SPLAT_EVAL_HOLES and the view's truncation status in slot SPLAT_EVAL_FLAGGED.  ``intrinsics``: the view's (default
         ``curr_data['intrinsics']``, which must then be on the host).  Nothing is read on the host and nothing is allocated after the
         view's first call; the current camera, the map, its Adam state and ``variables`` stay untouched (``render_view``).  Returns the
-        ``ViewImage`` (its ``out6`` holds the planes the row was formed from)."""
+        ``ViewImage`` (its ``out6`` holds the planes the row was formed from).  ``lpips``: as in ``evaluate_frame``."""
         _check_eval_row(out_row, self.dev)
         for name, t, c in (("im", curr_data['im'], 3), ("depth", curr_data['depth'], 1)):
             if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, view.H, view.W)):
@@ -596,6 +600,8 @@ class FusedEngine:
         o = img.out6
         evaluate_metrics(o[0:3], o[3], o[4], curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=holes)
         out_row[_capi.SPLAT_EVAL_FLAGGED:_capi.SPLAT_EVAL_FLAGGED + 1].copy_(img.truncated)     # (after the finish kernel, which leaves 0 there)
+        if lpips is not None:
+            evaluate_lpips(lpips, o[0:3], o[4], curr_data, out_row, sil_thres, sil_mask=sil_mask)
         return img
 
     def lists_known(self, curr_data=None):
@@ -1603,3 +1609,13 @@ def evaluate_metrics(rgb, depth, sil, curr_data, out_row, sil_thres, sil_mask=Fa
                                                    planes[3].data_ptr(), planes[4].data_ptr(), C.byref(cfg), C.byref(ews),
                                                    out_row.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "splat_eval_metrics")
     return sums
+
+
+def evaluate_lpips(lpips, rgb, sil, curr_data, out_row, sil_thres, sil_mask=False):
+    """LPIPS of an evaluated frame into slot SPLAT_EVAL_LPIPS of ``out_row`` (csrc/lpips.hip, splat_lpips_planes): ``lpips`` an
+    ``lpips.Lpips`` on the planes' device, ``rgb`` [3,H,W] and ``sil`` [H,W] the render, ``curr_data['im']`` / ``['depth']`` the frame.
+    The images are weighted as ``evaluate_metrics`` weighs them and clamped to 0..1, as the reference hands them to its network.  Call it
+    AFTER the call that writes the row (the finish kernel of the metrics leaves 0 in the slot).  Enqueues only."""
+    _check_eval_row(out_row, rgb.device)
+    lpips.planes(rgb, sil, curr_data['im'], curr_data['depth'], sil_thres, sil_mask=sil_mask,
+                 out=out_row[_capi.SPLAT_EVAL_LPIPS:_capi.SPLAT_EVAL_LPIPS + 1])

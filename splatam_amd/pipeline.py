@@ -391,9 +391,9 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
       * after every edit of the map (densification, pruning) the row counts of the replicas are compared (all-reduce of min / max).
 
     ``evaluate``: ``None`` (default) -- the loop ends where it always did; a dict with any of ``eval_every`` (1), ``eval_dir`` (None),
-    ``ms_ssim`` (True) -- the run's last act is the reference's (scripts/splatam.py:961-971): ``evaluation.evaluate`` on the final
+    ``ms_ssim`` (True), ``save_frames``, ``lpips_weights`` (None; default ``config['lpips_weights']`` where the config has it) -- the run's last act is the reference's (scripts/splatam.py:961-971): ``evaluation.evaluate`` on the final
     parameters with the mapping configuration's ``sil_thres`` / ``num_iters`` / ``add_new_gaussians``, returned as ``stats['eval']``
-    (PSNR, depth L1, MS-SSIM per evaluated frame, ATE; LPIPS is not computed).  The fused engine evaluates on its own map, the other
+    (PSNR, depth L1, MS-SSIM per evaluated frame, ATE; LPIPS with ``lpips_weights``: ``evaluation.evaluate``).  The fused engine evaluates on its own map, the other
     engines' parameters get a throw-away ``FusedEngine``; with several ranks rank 0 evaluates and the dict is broadcast.
 
     Checkpoints (splatam_amd/checkpoint.py; engines "fused" and "dropin", one rank).  With ``checkpoint_dir`` -- default
@@ -457,9 +457,11 @@ def rgbd_slam(dataset, config, engine="fused", num_frames=None, gaussian_capacit
     if evaluate is not None:
         from . import evaluation
         opts = dict(evaluate)
-        unknown = set(opts) - {'eval_every', 'eval_dir', 'ms_ssim', 'save_frames'}
+        unknown = set(opts) - {'eval_every', 'eval_dir', 'ms_ssim', 'save_frames', 'lpips_weights'}
         if unknown:
-            raise ValueError(f"evaluate: unknown keys {sorted(unknown)} (eval_every, eval_dir, ms_ssim, save_frames)")
+            raise ValueError(f"evaluate: unknown keys {sorted(unknown)} (eval_every, eval_dir, ms_ssim, save_frames, lpips_weights)")
+        if opts.get('lpips_weights') is None and config.get('lpips_weights') is not None:
+            opts['lpips_weights'] = config['lpips_weights']
         box = [None]
         if rank == 0:
             with torch.no_grad():

@@ -33,7 +33,8 @@ its counts on its own schedule, and the capacity flag is read there, before each
 iterations the device skipped because a view's lists outgrew their buckets are run again on re-learnt lists (plain iterations at
 the rate of the check's iteration, on frames drawn anew), as the frame loop does.
 
-``use_wandb`` and ``report_iter_progress`` are refused.  Not covered: ``scripts/gaussian_splatting.py``, multi-rank runs, LPIPS.
+``use_wandb`` and ``report_iter_progress`` are refused.  LPIPS is part of both evaluations with ``config['lpips_weights']`` (``--lpips-weights``).
+Not covered: ``scripts/gaussian_splatting.py``, multi-rank runs.
 """
 from __future__ import annotations
 
@@ -171,7 +172,8 @@ def post_splatam_opt(config, engine="fused", dataset=None, eval_dataset=None, nu
             if not ms_ssim:
                 print("frames with min(H, W) <= 160: MS-SSIM is not computed")
             return evaluation.evaluate(eval_dataset, params_now, eval_num_frames, sil_thres, mapping_iters=train['num_iters_mapping'],
-                                       add_new_gaussians=True, engine=eng, eval_dir=os.path.join(out_dir, name), ms_ssim=ms_ssim)
+                                       add_new_gaussians=True, engine=eng, eval_dir=os.path.join(out_dir, name), ms_ssim=ms_ssim,
+                                       **({'lpips_weights': config['lpips_weights']} if config.get('lpips_weights') is not None else {}))
 
         t_loop = time.perf_counter()
         if engine == "fused":
@@ -309,9 +311,13 @@ def main(argv=None):
     parser.add_argument("--engine", default="fused", choices=("fused", "dropin", "mirror"))
     parser.add_argument("--num-iters", type=int, default=None, help="overrides config['train']['num_iters_mapping']")
     parser.add_argument("--no-eval", action="store_true", help="skip the evaluations (at 7000 iterations and of the final map)")
+    parser.add_argument("--lpips-weights", default=None, metavar="PATH",
+                        help="AlexNet + LPIPS linear-layer weights (canonical .npz or a torch state dict): the evaluations also report LPIPS")
     args = parser.parse_args(argv)
     config = load_experiment(args.experiment)
     check_supported(config)
+    if args.lpips_weights is not None:
+        config = dict(config, lpips_weights=args.lpips_weights)        # (a copy: the experiment module's dict stays as written)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
     results_dir = os.path.join(config["workdir"], config["run_name"])
@@ -323,6 +329,8 @@ def main(argv=None):
         if ev is not None:
             print(f"[{name}] Average PSNR: {ev['avg_psnr']:.2f}  Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm  "
                   f"Depth L1: {100 * ev['avg_depth_l1']:.2f} cm  MS-SSIM: {ev['avg_ms_ssim']:.3f}")
+            if ev.get('lpips') is not None:
+                print(f"[{name}] Average LPIPS: {ev['avg_lpips']:.3f}")
     print(f"{stats['iterations']} iterations, {params['means3D'].shape[0]} Gaussians: "
           f"{stats['iterations'] / max(stats['loop_s'], 1e-9):.1f} iterations/s in the loop")
     print(f"saved {path}")

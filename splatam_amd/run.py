@@ -167,6 +167,9 @@ def main(argv=None):
     parser.add_argument("--engine", default="fused", choices=("fused", "dropin", "plugin", "plugin_map_edits"))
     parser.add_argument("--num-frames", type=int, default=None, help="overrides config['data']['num_frames'] (-1 = all)")
     parser.add_argument("--no-eval", action="store_true", help="skip the evaluation of the final map")
+    parser.add_argument("--lpips-weights", default=None, metavar="PATH",
+                        help="AlexNet + LPIPS linear-layer weights (canonical .npz or a torch state dict: splatam_amd.lpips): the evaluation "
+                             "then also reports LPIPS; sets config['lpips_weights']")
     parser.add_argument("--resume-exact", type=int, default=None, metavar="T",
                         help="continue at frame T + 1 from the exact checkpoint (session<T>.npz) under workdir/run_name")
     parser.add_argument("--exact-checkpoints", action="store_true",
@@ -191,14 +194,18 @@ def main(argv=None):
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
+    if args.lpips_weights is not None:
+        config = dict(config, lpips_weights=args.lpips_weights)        # (a copy: the experiment module's dict stays as written)
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
                             exact_checkpoints=args.exact_checkpoints, mesh=args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
                             cull=args.cull, **({"align": True} if args.align else {}))
     ev = stats.get('eval')
     if ev is not None:
         print(f"Average PSNR: {ev['avg_psnr']:.2f}\nAverage Depth RMSE: {100 * ev['avg_depth_rmse']:.2f} cm\n"
-              f"Average Depth L1: {100 * ev['avg_depth_l1']:.2f} cm\nAverage MS-SSIM: {ev['avg_ms_ssim']:.3f}\n"
-              f"Final Average ATE RMSE: {100 * ev['ate_rmse']:.2f} cm")
+              f"Average Depth L1: {100 * ev['avg_depth_l1']:.2f} cm\nAverage MS-SSIM: {ev['avg_ms_ssim']:.3f}")
+        if ev.get('lpips') is not None:          # (right after MS-SSIM, three decimals, as the reference prints it)
+            print(f"Average LPIPS: {ev['avg_lpips']:.3f}")
+        print(f"Final Average ATE RMSE: {100 * ev['ate_rmse']:.2f} cm")
     if stats.get('mesh_score') is not None:
         from .mesh_score import format_score
         print(format_score(stats['mesh_score']))

@@ -743,11 +743,42 @@ def calc_psnr(img1, img2):
     return 20 * torch.log10(1.0 / torch.sqrt(mse))
 
 
-def eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=True):
+def lpips_taps(x, weights):
+    """The five AlexNet taps of ``x`` [B, 3, H, W] in 0..1 (clamped here), in ``x``'s dtype on ``x``'s device: the input transform,
+    the convolutions with bias and ReLU, the two max-pools (splatam_amd/lpips.py states the definition)."""
+    from . import lpips as lp
+    x = torch.clamp(x, 0, 1)
+    x = 2 * x - 1
+    x = (x - torch.tensor(lp.SHIFT, dtype=x.dtype, device=x.device).view(1, 3, 1, 1)) / torch.tensor(lp.SCALE, dtype=x.dtype, device=x.device).view(1, 3, 1, 1)
+    taps = []
+    for l, (stride, pad, pool) in enumerate(lp.CONV_GEOMETRY):
+        if pool:
+            x = F.max_pool2d(x, kernel_size=3, stride=2)
+        x = F.relu(F.conv2d(x, weights.conv_weight[l].to(x), weights.conv_bias[l].to(x), stride=stride, padding=pad))
+        taps.append(x)
+    return taps
+
+
+def lpips(im0, im1, weights, return_taps=False):
+    """LPIPS (AlexNet) of two images [3, H, W] in 0..1 with ``weights`` (an ``lpips.LpipsWeights``): the torch form of csrc/lpips.hip, for
+    the ``mirror`` engine and ``device="cpu"``.  A 0-dim tensor of the images' dtype; with ``return_taps`` also the five taps [2, C, H_l, W_l]."""
+    from . import lpips as lp
+    if min(im0.shape[-2:]) < lp.MIN_SIZE:
+        raise ValueError(f"LPIPS needs images of at least {lp.MIN_SIZE} x {lp.MIN_SIZE} pixels (got {int(im0.shape[-1])} x {int(im0.shape[-2])})")
+    taps = lpips_taps(torch.stack([im0, im1]), weights)
+    total = torch.zeros((), dtype=im0.dtype, device=im0.device)
+    for f, w in zip(taps, weights.lin):
+        u = f / (torch.sqrt((f ** 2).sum(dim=1, keepdim=True)) + 1e-10)
+        total = total + (w.to(f).view(1, -1, 1, 1) * (u[0:1] - u[1:2]) ** 2).sum(dim=1).mean()
+    return (total, taps) if return_taps else total
+
+
+def eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ssim=True, lpips_weights=None):
     """The numbers the reference's ``eval`` forms for one frame from its two renders: ``im`` [3,H,W] (colour render),
     ``depth_sil`` [>=2,H,W] (depth, silhouette).  ``sil_mask``: the reference's ``mapping_iters == 0 and not add_new_gaussians``
     branch -- images weighted by presence * valid, depth difference by presence; otherwise images by valid.
-    Returns a dict of 0-d tensors: psnr, depth_rmse, depth_l1, ms_ssim (None when not asked for), valid.
+    Returns a dict of 0-d tensors: psnr, depth_rmse, depth_l1, ms_ssim (None when not asked for), valid, and -- with
+    ``lpips_weights`` (an ``lpips.LpipsWeights``) -- lpips.
 
     ``depth_rmse`` keeps the reference's quirk: it takes the square root PER PIXEL (sqrt(d^2) = |d|) before summing, so the
     number it reports as depth RMSE equals ``depth_l1`` by construction."""
@@ -765,6 +796,8 @@ def eval_frame_metrics(im, depth_sil, curr_data, sil_thres, sil_mask, with_ms_ss
            'depth_l1': (torch.abs(diff) * valid).sum() / valid.sum(),
            'ms_ssim': ms_ssim(weighted_im.unsqueeze(0), weighted_gt.unsqueeze(0)) if with_ms_ssim else None,
            'valid': valid.sum()}
+    if lpips_weights is not None:        # (eval_helpers.py:484-485: the network sees the weighted images, clamped)
+        out['lpips'] = lpips(torch.clamp(weighted_im, 0, 1), torch.clamp(weighted_gt, 0, 1), lpips_weights)
     return out
 
 
