@@ -892,6 +892,47 @@ int splat_tsdf_integrate(const SplatTsdfVolume *volume, const SplatTsdfView *vie
 int splat_tsdf_triangles(const SplatTsdfVolume *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
 int splat_tsdf_vertices(const SplatTsdfVolume *volume, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream);
 
+/* The mesh layer on a SPARSE volume (csrc/tsdf_sparse.hip; added within ABI 17): the same virtual grid, of which only BRICKS near
+ * observed surfaces are stored.  A brick is brick[0] x brick[1] x brick[2] = 2048 grid points, x fastest inside it, 8 KiB contiguous per
+ * array in a POOL of `slots` bricks (tsdf, weight, r, g, b: [slots][2048] float32 each, 16-byte aligned); `directory`
+ * ([ceil(nx / brick[0]) ceil(ny / brick[1]) ceil(nz / brick[2])] int32, x fastest) holds the slot of every brick of the grid or -1,
+ * `brick_of_slot` ([slots] int32) the brick of every slot.  splat_tsdf_sparse_brick_shape(n, shape): the n-th brick shape the library
+ * accepts (0: the default), returns how many there are.  splat_tsdf_sparse_bytes: pool + directory + brick_of_slot for the struct's
+ * grid, shape and `slots` (0 for a volume that would be refused; the pointers are not looked at).
+ *
+ * splat_tsdf_sparse_mark: one launch per view, one lane per pixel.  A pixel that passes splat_tsdf_integrate's gates (the depth limit
+ * widened to depth_max + trunc) stores 1 into flags[brick] (int32 [bricks], the caller zeroes it once) for every brick that meets a
+ * conservative index box around the grid points that pixel can update with f < 0, their 3 x 3 x 3 neighbourhood included: the eight
+ * corners of the frustum segment of (u +- 0.5, v +- 0.5) between depths d and d + trunc, in world space, half a voxel and one index
+ * wider.  Every cell that can emit a triangle has all eight corners in a marked brick.  `skip` / `skipped` as in splat_tsdf_integrate.
+ * Allocation is the caller's: slots for the marked bricks that have none (any deterministic order), then splat_tsdf_sparse_reset_slots
+ * over the new slot range [first, first + count): tsdf = 1, the rest 0.
+ *
+ * splat_tsdf_sparse_integrate: splat_tsdf_integrate's update, the same float32 operations in the same order, on every grid point of
+ * every allocated brick: a brick allocated before the first view and given every view holds the dense volume's bits.
+ * splat_tsdf_sparse_triangles / _vertices: splat_tsdf_triangles / _vertices with the same keys (they name edges of the virtual grid);
+ * a cell belongs to the brick of its corner 0 and emits nothing when a brick of one of its corners is not allocated.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for what splat_tsdf_* refuse, a brick shape that
+ * is not listed, slots < 0, 2^31 bricks or more, and NULL pointers where they are used. */
+typedef struct SplatTsdfSparse {
+    int32_t nx, ny, nz;
+    float origin[3];
+    float voxel, trunc;
+    int32_t brick[3];
+    int32_t slots;
+    int32_t *directory;
+    int32_t *brick_of_slot;
+    float *tsdf, *weight, *r, *g, *b;
+} SplatTsdfSparse;
+int splat_tsdf_sparse_brick_shape(int index, int32_t *shape);
+size_t splat_tsdf_sparse_bytes(const SplatTsdfSparse *volume);
+int splat_tsdf_sparse_mark(const SplatTsdfSparse *volume, const SplatTsdfView *view, int32_t *flags, void *stream);
+int splat_tsdf_sparse_reset_slots(const SplatTsdfSparse *volume, int64_t first, int64_t count, void *stream);
+int splat_tsdf_sparse_integrate(const SplatTsdfSparse *volume, const SplatTsdfView *view, void *stream);
+int splat_tsdf_sparse_triangles(const SplatTsdfSparse *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
+int splat_tsdf_sparse_vertices(const SplatTsdfSparse *volume, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream);
+
 /* The mesh score layer (csrc/meshscore.hip, arithmetic in csrc/meshscore_math.h; added within ABI 17): points sampled uniformly by area
  * on a triangle mesh, and the exact nearest target of every query through a uniform grid -- what accuracy, completion and completion
  * ratio of a reconstruction against a ground-truth mesh are made of.

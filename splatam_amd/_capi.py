@@ -151,6 +151,12 @@ class SplatTsdfView(C.Structure):
                 ("out6", _fp), ("w2c", _fp), ("skip", _fp), ("skipped", _fp)]
 
 
+class SplatTsdfSparse(C.Structure):        # (added within ABI 17: the sparse volume, csrc/tsdf_sparse.hip)
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("origin", C.c_float * 3), ("voxel", C.c_float), ("trunc", C.c_float),
+                ("brick", C.c_int32 * 3), ("slots", C.c_int32), ("directory", _fp), ("brick_of_slot", _fp),
+                ("tsdf", _fp), ("weight", _fp), ("r", _fp), ("g", _fp), ("b", _fp)]
+
+
 class SplatNnGrid(C.Structure):            # (added within ABI 17: the mesh score layer, csrc/meshscore.hip)
     _fields_ = [("lo", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int32 * 3), ("count", C.c_int32), ("records", _fp), ("start", _fp)]
 
@@ -166,7 +172,8 @@ class SplatLpipsWorkspace(C.Structure):    # (added within ABI 17: LPIPS from ca
 
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
-                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView, SplatLpipsWorkspace)
+                    SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView, SplatLpipsWorkspace,
+                    SplatTsdfSparse)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -221,6 +228,8 @@ EXPORTS = (
     "splat_view_camera", "splat_view_finish",
     "splat_iter_loss_backward_ex", "splat_iter_mapping_step_ex",
     "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
+    "splat_tsdf_sparse_brick_shape", "splat_tsdf_sparse_bytes", "splat_tsdf_sparse_mark", "splat_tsdf_sparse_reset_slots",
+    "splat_tsdf_sparse_integrate", "splat_tsdf_sparse_triangles", "splat_tsdf_sparse_vertices",
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
     "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
     "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
@@ -354,6 +363,18 @@ def lib():
     L.splat_tsdf_triangles.argtypes = [vol, C.c_float, _fp, C.c_int64, _fp, _fp]
     L.splat_tsdf_vertices.restype = C.c_int
     L.splat_tsdf_vertices.argtypes = [vol, _fp, C.c_int64, _fp, _fp, _fp]
+    sparse = C.POINTER(SplatTsdfSparse)
+    L.splat_tsdf_sparse_brick_shape.restype = C.c_int
+    L.splat_tsdf_sparse_brick_shape.argtypes = [C.c_int, C.POINTER(C.c_int32)]
+    L.splat_tsdf_sparse_bytes.restype = C.c_size_t
+    L.splat_tsdf_sparse_bytes.argtypes = [sparse]
+    for name, args in (("splat_tsdf_sparse_mark", [sparse, C.POINTER(SplatTsdfView), _fp, _fp]),
+                       ("splat_tsdf_sparse_reset_slots", [sparse, C.c_int64, C.c_int64, _fp]),
+                       ("splat_tsdf_sparse_integrate", [sparse, C.POINTER(SplatTsdfView), _fp]),
+                       ("splat_tsdf_sparse_triangles", [sparse, C.c_float, _fp, C.c_int64, _fp, _fp]),
+                       ("splat_tsdf_sparse_vertices", [sparse, _fp, C.c_int64, _fp, _fp, _fp])):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = args
     nn = C.POINTER(SplatNnGrid)
     for name, args in (
         ("splat_mesh_areas", [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp]),

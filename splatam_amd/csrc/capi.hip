@@ -62,7 +62,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
     SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid); SPLAT_SIZEOF_CASE(SplatMeshView);
-    SPLAT_SIZEOF_CASE(SplatLpipsWorkspace);
+    SPLAT_SIZEOF_CASE(SplatLpipsWorkspace); SPLAT_SIZEOF_CASE(SplatTsdfSparse);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -457,6 +457,64 @@ int splat_tsdf_triangles(const SplatTsdfVolume *v, float min_weight, int64_t *ke
 int splat_tsdf_vertices(const SplatTsdfVolume *v, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream) {
     if (!valid_tsdf_volume(v) || n < 0 || (n > 0 && (!keys || !vertices))) return SPLAT_E_INVALID;
     return check(launch_tsdf_vertices(*v, keys, (long long)n, vertices, colors, (hipStream_t)stream));
+}
+
+// the mesh layer on a sparse volume (csrc/tsdf_sparse.hip)
+static const int32_t kSparseBrickShapes[2][3] = {{16, 16, 8}, {64, 4, 8}};     // (the first is the default: profiles/mesh_sparse.md 1)
+
+int splat_tsdf_sparse_brick_shape(int index, int32_t *shape) {
+    if (shape && index >= 0 && index < 2)
+        for (int a = 0; a < 3; ++a) shape[a] = kSparseBrickShapes[index][a];
+    return 2;
+}
+
+static long long sparse_bricks(const SplatTsdfSparse *v) {
+    return (long long)((v->nx + v->brick[0] - 1) / v->brick[0]) * ((v->ny + v->brick[1] - 1) / v->brick[1]) * ((v->nz + v->brick[2] - 1) / v->brick[2]);
+}
+static bool valid_sparse_grid(const SplatTsdfSparse *v) {
+    if (!v || v->nx <= 0 || v->ny <= 0 || v->nz <= 0 || !(v->voxel > 0.f) || !(v->trunc > 0.f) || v->slots < 0) return false;
+    if (!((long long)v->nx * v->ny < (1ll << 40) && (long long)v->nx * v->ny * (long long)v->nz < (1ll << 40))) return false;
+    bool listed = false;
+    for (int n = 0; n < 2; ++n)
+        listed |= v->brick[0] == kSparseBrickShapes[n][0] && v->brick[1] == kSparseBrickShapes[n][1] && v->brick[2] == kSparseBrickShapes[n][2];
+    return listed && sparse_bricks(v) < (1ll << 31);
+}
+static bool valid_sparse_volume(const SplatTsdfSparse *v) {
+    return valid_sparse_grid(v) && v->directory && (v->slots == 0 || (v->brick_of_slot && v->tsdf && v->weight && v->r && v->g && v->b));
+}
+static bool valid_tsdf_view(const SplatTsdfView *w) {
+    if (!w || w->width <= 0 || w->height <= 0 || (long long)w->width * w->height > 0x3fffffffLL) return false;
+    return w->out6 && w->w2c && !(w->skip && !w->skipped);
+}
+
+size_t splat_tsdf_sparse_bytes(const SplatTsdfSparse *v) {
+    if (!valid_sparse_grid(v)) return 0;
+    return (5 * sizeof(float) * 2048 + sizeof(int32_t)) * (size_t)v->slots + sizeof(int32_t) * (size_t)sparse_bricks(v);
+}
+
+int splat_tsdf_sparse_mark(const SplatTsdfSparse *v, const SplatTsdfView *w, int32_t *flags, void *stream) {
+    if (!valid_sparse_grid(v) || !valid_tsdf_view(w) || !flags) return SPLAT_E_INVALID;
+    return check(launch_tsdf_sparse_mark(*v, *w, flags, (hipStream_t)stream));
+}
+
+int splat_tsdf_sparse_reset_slots(const SplatTsdfSparse *v, int64_t first, int64_t count, void *stream) {
+    if (!valid_sparse_volume(v) || first < 0 || count < 0 || first + count > v->slots) return SPLAT_E_INVALID;
+    return check(launch_tsdf_sparse_reset_slots(*v, (long long)first, (long long)count, (hipStream_t)stream));
+}
+
+int splat_tsdf_sparse_integrate(const SplatTsdfSparse *v, const SplatTsdfView *w, void *stream) {
+    if (!valid_sparse_volume(v) || !valid_tsdf_view(w)) return SPLAT_E_INVALID;
+    return check(launch_tsdf_sparse_integrate(*v, *w, (hipStream_t)stream));
+}
+
+int splat_tsdf_sparse_triangles(const SplatTsdfSparse *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
+    if (!valid_sparse_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    return check(launch_tsdf_sparse_triangles(*v, min_weight, keys, (long long)capacity, count, (hipStream_t)stream));
+}
+
+int splat_tsdf_sparse_vertices(const SplatTsdfSparse *v, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream) {
+    if (!valid_sparse_volume(v) || n < 0 || (n > 0 && (!keys || !vertices))) return SPLAT_E_INVALID;
+    return check(launch_tsdf_sparse_vertices(*v, keys, (long long)n, vertices, colors, (hipStream_t)stream));
 }
 
 // the mesh score layer (csrc/meshscore.hip)

@@ -1,6 +1,7 @@
 // tsdf_math.h -- arithmetic of the mesh layer (tsdf.hip), written once as host/device inline functions: the kernels call them per lane,
 // tests/test_tsdf_math_cpu.py compiles the very same header with g++ (tests/tsdf_math_shim.cpp, -ffp-contract=off) and checks it
-// against the float64 numpy form of the same definitions (tests/tsdf_ref.py).
+// against the float64 numpy form of the same definitions (tests/tsdf_ref.py).  The sparse volume's part (bricks, the mark; at the end)
+// is held to the dense part of this same header by tests/test_tsdf_sparse_cpu.py through tests/tsdf_sparse_shim.cpp.
 //
 //   VOLUME   grid points p(i, j, k) = origin + voxel (i, j, k), nx ny nz of them, x fastest; five float32 arrays of that many:
 //            tsdf (reset 1), weight (reset 0), r, g, b (reset 0).
@@ -216,7 +217,22 @@ SPLAT_HD int tsdf_cell_emit(const TsdfGrid &g, int i, int j, int k, int cell_mas
     return n;
 }
 
-// position and colour of the vertex a key names; the five arrays are the volume's
+// position and colour of the vertex a key names, from the values of its edge's two grid points: va, vb = tsdf, weight, r, g, b (the
+// volume's array order; the weight is not used) at corner a and at corner a + dir
+SPLAT_HD void tsdf_vertex_values(const TsdfGrid &g, int64_t key, const float *va, const float *vb, float *pos, float *col) {
+    const int dir = (int)(key & 7);
+    int i, j, k;
+    tsdf_unlinear(g, key >> 3, i, j, k);
+    const float fa = va[0], fb = vb[0];
+    const float t = tsdf_div(fa, tsdf_sub(fa, fb));
+    float pa[3], pb[3];
+    tsdf_point(g, i, j, k, pa);
+    tsdf_point(g, i + (dir & 1), j + ((dir >> 1) & 1), k + ((dir >> 2) & 1), pb);
+    for (int c = 0; c < 3; ++c) pos[c] = tsdf_add(pa[c], tsdf_mul(t, tsdf_sub(pb[c], pa[c])));
+    for (int c = 0; c < 3; ++c) col[c] = tsdf_add(va[2 + c], tsdf_mul(t, tsdf_sub(vb[2 + c], va[2 + c])));
+}
+
+// ... and with the two grid points read from the volume's five arrays
 SPLAT_HD void tsdf_vertex(const TsdfGrid &g, int64_t key, const float *tsdf, const float *r, const float *gr, const float *b, float *pos,
                           float *col) {
     const int64_t la = key >> 3;
@@ -224,15 +240,90 @@ SPLAT_HD void tsdf_vertex(const TsdfGrid &g, int64_t key, const float *tsdf, con
     int i, j, k;
     tsdf_unlinear(g, la, i, j, k);
     const int64_t lb = tsdf_linear(g, i + (dir & 1), j + ((dir >> 1) & 1), k + ((dir >> 2) & 1));
-    const float fa = tsdf[la], fb = tsdf[lb];
-    const float t = tsdf_div(fa, tsdf_sub(fa, fb));
-    float pa[3], pb[3];
-    tsdf_point(g, i, j, k, pa);
-    tsdf_point(g, i + (dir & 1), j + ((dir >> 1) & 1), k + ((dir >> 2) & 1), pb);
-    for (int c = 0; c < 3; ++c) pos[c] = tsdf_add(pa[c], tsdf_mul(t, tsdf_sub(pb[c], pa[c])));
-    col[0] = tsdf_add(r[la], tsdf_mul(t, tsdf_sub(r[lb], r[la])));
-    col[1] = tsdf_add(gr[la], tsdf_mul(t, tsdf_sub(gr[lb], gr[la])));
-    col[2] = tsdf_add(b[la], tsdf_mul(t, tsdf_sub(b[lb], b[la])));
+    const float va[5] = {tsdf[la], 0.f, r[la], gr[la], b[la]}, vb[5] = {tsdf[lb], 0.f, r[lb], gr[lb], b[lb]};
+    tsdf_vertex_values(g, key, va, vb, pos, col);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- sparse volume
+// A SPARSE volume (tsdf_sparse.hip) keeps the same virtual grid and stores only BRICKS of it: boxes of 2^lx x 2^ly x 2^lz = 2048 grid
+// points, x fastest inside the brick, each 8 KiB contiguous per array in a pool; a directory over all bricks of the grid (x fastest)
+// holds a brick's slot in the pool or -1.  Which bricks: a grid point's tsdf is a running convex mean, from 1, of the f it received,
+// so tsdf < 0 needs one update with f < 0 -- the point lay in the band d < z <= d + trunc behind the surface of some view --, and a
+// cell emits triangles only with a negative corner and all eight seen: every emitting cell lies in the 3 x 3 x 3 index neighbourhood
+// of a grid point some view updated with f < 0.  tsdf_mark_box is a conservative index box around the grid points ONE PIXEL of one
+// view can update so, neighbourhood included; the bricks meeting the boxes of every pixel of every view are allocated, and when each
+// of them then receives every update of every view, every corner of every emitting cell holds the dense volume's bits.
+constexpr int kTsdfBrickPoints = 2048, kTsdfBrickLog2 = 11;
+
+struct TsdfBricks {
+    int lx, ly, lz;                 // log2 of the brick's points per axis; lx + ly + lz = 11, lx >= 2 (a row is a multiple of 4 points)
+    int bx, by, bz;                 // bricks per axis: the grid's points, rounded up
+};
+SPLAT_HD TsdfBricks tsdf_bricks(const TsdfGrid &g, int lx, int ly, int lz) {
+    TsdfBricks b;
+    b.lx = lx; b.ly = ly; b.lz = lz;
+    b.bx = (g.nx + (1 << lx) - 1) >> lx; b.by = (g.ny + (1 << ly) - 1) >> ly; b.bz = (g.nz + (1 << lz) - 1) >> lz;
+    return b;
+}
+SPLAT_HD int64_t tsdf_brick_count(const TsdfBricks &b) { return (int64_t)b.bx * b.by * b.bz; }
+// the brick of grid point (i, j, k), and the point's offset inside it
+SPLAT_HD int64_t tsdf_brick_of(const TsdfBricks &b, int i, int j, int k) { return ((int64_t)(k >> b.lz) * b.by + (j >> b.ly)) * b.bx + (i >> b.lx); }
+SPLAT_HD int tsdf_brick_local(const TsdfBricks &b, int i, int j, int k) {
+    return ((((k & ((1 << b.lz) - 1)) << b.ly) | (j & ((1 << b.ly) - 1))) << b.lx) | (i & ((1 << b.lx) - 1));
+}
+// ... and back: the first grid point of a brick, and the grid point at a local offset from it
+SPLAT_HD void tsdf_brick_origin(const TsdfBricks &b, int64_t brick, int &i0, int &j0, int &k0) {
+    i0 = (int)(brick % b.bx) << b.lx;
+    const int64_t r = brick / b.bx;
+    j0 = (int)(r % b.by) << b.ly;
+    k0 = (int)(r / b.by) << b.lz;
+}
+SPLAT_HD void tsdf_brick_unlocal(const TsdfBricks &b, int local, int &li, int &lj, int &lk) {
+    li = local & ((1 << b.lx) - 1);
+    lj = (local >> b.lx) & ((1 << b.ly) - 1);
+    lk = local >> (b.lx + b.ly);
+}
+
+// lower / upper clipped index of a box coordinate; written so that a NaN (a depth beyond float range) gives the whole axis
+SPLAT_HD int tsdf_index_lo(float a, int n) { return !(a > 0.f) ? 0 : (a < (float)n ? (int)a : n); }
+SPLAT_HD int tsdf_index_hi(float a, int n) { return !(a < (float)(n - 1)) ? n - 1 : (a >= 0.f ? (int)a : -1); }
+
+// The index box [lo, hi] (inclusive, clipped to the grid; empty when lo > hi on an axis) of pixel (u, v) of a view whose silhouette
+// and depth-plane value there are s and depth: false when the pixel can give no grid point an f < 0.  The gates are tsdf_measure's,
+// the depth limit widened to depth_max + trunc.  A grid point the pixel updates with f < 0 projects into [u - 0.5, u + 0.5) x
+// [v - 0.5, v + 0.5) at a depth in (d, d + trunc]: inside the frustum segment whose eight corners are the rays through
+// (u +- 0.5, v +- 0.5) at depths d and d + trunc.  The corners go to world space by the rigid inverse of w2c (R^T (pc - t)); their
+// axis-aligned box, widened by half a voxel against the rounding of all this (float32 at 100 m: 1e-5 m; a voxel is a millimetre at
+// least) and by one index for the cell neighbourhood, is [ceil((lo - o) / voxel - 0.5) - 1, floor((hi - o) / voxel + 0.5) + 1].
+SPLAT_HD bool tsdf_mark_box(const TsdfGrid &g, const TsdfCamera &c, int u, int v, float s, float depth, int *lo, int *hi) {
+    if (!(s > c.sil_thres)) return false;
+    const float d = tsdf_div(depth, s);
+    if (!(d > 0.f) || !(d <= 3.0e38f)) return false;                 // (an infinite d gives sdf = inf and f = 1 wherever it is seen)
+    if (c.depth_max > 0.f && !(d <= tsdf_add(c.depth_max, c.trunc))) return false;
+    float wlo[3] = {INFINITY, INFINITY, INFINITY}, whi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool finite = true;
+    for (int q = 0; q < 8; ++q) {
+        const float z = (q & 4) ? tsdf_add(d, c.trunc) : d;
+        const float uf = tsdf_add((float)u, (q & 1) ? 0.5f : -0.5f), vf = tsdf_add((float)v, (q & 2) ? 0.5f : -0.5f);
+        // the camera-space corner less the translation
+        const float pc[3] = {tsdf_sub(tsdf_mul(tsdf_div(tsdf_sub(uf, c.cx), c.fx), z), c.m[3]),
+                             tsdf_sub(tsdf_mul(tsdf_div(tsdf_sub(vf, c.cy), c.fy), z), c.m[7]), tsdf_sub(z, c.m[11])};
+        for (int a = 0; a < 3; ++a) {
+            const float w = tsdf_add(tsdf_add(tsdf_mul(c.m[a], pc[0]), tsdf_mul(c.m[4 + a], pc[1])), tsdf_mul(c.m[8 + a], pc[2]));
+            finite = finite && w >= -3.0e38f && w <= 3.0e38f;
+            wlo[a] = fminf(wlo[a], w);
+            whi[a] = fmaxf(whi[a], w);
+        }
+    }
+    const float o[3] = {g.ox, g.oy, g.oz};
+    const int n[3] = {g.nx, g.ny, g.nz};
+    for (int a = 0; a < 3; ++a) {
+        const float fl = finite ? tsdf_sub(ceilf(tsdf_sub(tsdf_div(tsdf_sub(wlo[a], o[a]), g.voxel), 0.5f)), 1.f) : NAN;
+        const float fh = finite ? tsdf_add(floorf(tsdf_add(tsdf_div(tsdf_sub(whi[a], o[a]), g.voxel), 0.5f)), 1.f) : NAN;
+        lo[a] = tsdf_index_lo(fl, n[a]);
+        hi[a] = tsdf_index_hi(fh, n[a]);
+    }
+    return lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2];
 }
 
 }  // namespace splat

@@ -1,5 +1,5 @@
 """A triangle mesh of the map: ``python -m splatam_amd.mesh PARAMS.npz --out mesh.ply [--voxel M] [--trunc M] [--every N] [--size WxH]
-[--sil-thres S] [--depth-max M] [--bounds X0 Y0 Z0 X1 Y1 Z1]``.
+[--sil-thres S] [--depth-max M] [--bounds X0 Y0 Z0 X1 Y1 Z1] [--sparse]``.
 
 Depth rendered at the estimated poses is fused into a truncated signed distance volume and the volume's zero surface is extracted,
 all on the device (csrc/tsdf.hip, arithmetic in csrc/tsdf_math.h): the usual deliverable of a dense RGB-D SLAM system, and what the
@@ -10,6 +10,10 @@ The surface is marching tetrahedra on Kuhn's split of every cell (six tetrahedra
 on their shared faces and the mesh is closed wherever the volume was seen); vertices are named by the grid edge they lie on, so
 welding is a ``torch.unique`` over integer keys and the result is canonical: vertices sorted by key, faces lexicographically -- the
 same volume always gives the same bytes.
+
+The dense ``TsdfVolume`` holds five floats for every grid point of the box and is refused beyond ``max_bytes``; ``--sparse``
+(``SparseTsdfVolume``, csrc/tsdf_sparse.hip) stores only the bricks of 2048 grid points within the truncation band of a surface some
+view saw and gives the same mesh bit for bit: an apartment at 1 cm, a room at 5 mm, a walk down a corridor.
 
 The command loads a ``params.npz`` as ``python -m splatam_amd.run`` writes it; poses come from the map, frames from
 ``keyframe_time_indices`` when present (otherwise every ``--every``-th), size and intrinsics from ``org_width`` / ``org_height`` /
@@ -54,22 +58,78 @@ def default_bounds(means3D, logit_opacities, pad):
     return tuple(float(v) - pad for v in box[0]), tuple(float(v) + pad for v in box[1])
 
 
-def plan_volume(bounds, voxel_size, max_bytes=DEFAULT_MAX_BYTES):
+def plan_volume(bounds, voxel_size, max_bytes=DEFAULT_MAX_BYTES, sparse=False):
     """(origin, dims) of the grid that covers ``bounds`` at ``voxel_size``: grid points from the lower corner, one past the upper.
-    ValueError, with the size it would need, for a volume beyond ``max_bytes`` (or beyond the library's 2^40 grid points)."""
+    ValueError, with the size it would need, for a volume beyond ``max_bytes`` (or beyond the library's 2^40 grid points).
+    ``sparse``: the grid is a ``SparseTsdfVolume``'s virtual one, whose bytes ``allocate`` checks; only the 2^40 points hold here."""
     lo, hi = (tuple(float(v) for v in b) for b in bounds)
     voxel_size = float(voxel_size)
     if not voxel_size > 0 or len(lo) != 3 or len(hi) != 3 or not all(h > l for l, h in zip(lo, hi)):
         raise ValueError(f"a volume needs a positive voxel size and bounds with a positive extent (got {voxel_size}, {lo} .. {hi})")
     dims = tuple(int(math.ceil((h - l) / voxel_size - 1e-9)) + 1 for l, h in zip(lo, hi))      # (an extent of n voxels is n + 1 points)
     need = volume_bytes(dims)
-    if need > max_bytes or dims[0] * dims[1] * dims[2] >= MAX_POINTS:
+    if (need > max_bytes and not sparse) or dims[0] * dims[1] * dims[2] >= MAX_POINTS:
         raise ValueError(f"a {dims[0]} x {dims[1]} x {dims[2]} volume at voxel size {voxel_size} needs {need} bytes ({need / 2 ** 30:.2f} GiB), "
                          f"beyond max_bytes = {max_bytes}: raise the voxel size, pass tighter bounds or a larger max_bytes")
     return lo, dims
 
 
-class TsdfVolume:
+class _Surface:
+    """``extract`` of a volume class that has ``_triangles(min_weight, keys, count)``, ``_vertices(uniq, vertices, colors)`` and
+    ``_default_capacity()``."""
+
+    def extract(self, min_weight=1.0, capacity=None):
+        """The zero surface over the cells whose eight corners have ``weight >= min_weight`` as a ``Mesh`` on the device.  One pass over
+        the cells into ``capacity`` triangle slots (default: a guess from the grid's size), ONE host read of the count, a second pass
+        at the reported size if they did not fit; vertices welded by ``torch.unique`` over their keys, positions and colours by one
+        launch.  Canonical: vertices sorted by key, faces lexicographically."""
+        if capacity is None:
+            capacity = self._default_capacity()
+        capacity = max(int(capacity), 0)
+        count = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        keys = torch.empty(capacity, 3, dtype=torch.int64, device=self.dev) if capacity else None
+        self._triangles(min_weight, keys, count)
+        n = int(count.item())
+        if n > capacity:
+            keys = torch.empty(n, 3, dtype=torch.int64, device=self.dev)
+            self._triangles(min_weight, keys, count)
+        self.last_triangle_count = n
+        if n == 0:
+            z = torch.zeros(0, 3, dtype=torch.float32, device=self.dev)
+            return Mesh(z, torch.zeros(0, 3, dtype=torch.int32, device=self.dev), z.clone())
+        uniq, inverse = torch.unique(keys[:n].reshape(-1), return_inverse=True)
+        if uniq.numel() >= 2 ** 31:
+            raise RuntimeError(f"{uniq.numel()} vertices do not fit int32 faces: extract a smaller volume")
+        faces = inverse.view(n, 3)
+        for col in (2, 1, 0):                               # lexicographic rows: three stable sorts, last column first
+            faces = faces[torch.sort(faces[:, col], stable=True).indices]
+        vertices = torch.empty(uniq.numel(), 3, dtype=torch.float32, device=self.dev)
+        colors = torch.empty_like(vertices)
+        self._vertices(uniq, vertices, colors)
+        self.last_keys = uniq
+        return Mesh(vertices, faces.to(torch.int32).contiguous(), colors)
+
+
+def _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, weight_max, skip, skipped, dev):
+    """(``_capi.SplatTsdfView`` of one view's planes, the tensors it points into)."""
+    from .fused import _device_mat4, _intrinsics4
+    if not (isinstance(out6, torch.Tensor) and out6.dtype == torch.float32 and out6.device == dev and out6.dim() == 3
+            and out6.shape[0] >= 5 and out6.is_contiguous()):
+        raise RuntimeError(f"out6 must be a contiguous float32 tensor [>= 5, H, W] on {dev}")
+    if skip is not None and not (isinstance(skip, torch.Tensor) and skip.dtype == torch.int32 and skip.device == dev and skip.numel() >= 1):
+        raise RuntimeError(f"skip must be an int32 tensor on {dev}")
+    keep = [out6, skip]
+    w = _capi.SplatTsdfView()
+    w.height, w.width = int(out6.shape[1]), int(out6.shape[2])
+    w.fx, w.fy, w.cx, w.cy = _intrinsics4(intrinsics)
+    w.sil_thres, w.depth_max, w.weight_max = float(sil_thres), float(depth_max), float(weight_max)
+    w.out6, w.w2c = out6.data_ptr(), _device_mat4(w2c, "w2c", dev, keep).data_ptr()
+    w.skip = skip.data_ptr() if skip is not None else None
+    w.skipped = skipped.data_ptr()
+    return w, keep
+
+
+class TsdfVolume(_Surface):
     """A truncated signed distance volume on the device: grid points ``origin + voxel_size (i, j, k)``, ``dims = (nx, ny, nz)`` of them,
     x fastest; ``tsdf``, ``weight``, ``r``, ``g``, ``b`` are [nz, ny, nx] float32 views of one allocation.  Every method enqueues on the
     current stream; only ``extract`` reads (one count)."""
@@ -117,20 +177,7 @@ class TsdfVolume:
         them: depth is sum w z, divided by the silhouette here; a view into a larger buffer is fine), ``w2c`` float32 [4, 4] on the
         device, ``intrinsics`` a 3 x 3 or (fx, fy, cx, cy) on the host.  ``skip``: int32 [1] on the device (a ``ViewImage.truncated``);
         non-zero when the launch runs: the volume stays as it is and ``skipped`` counts one.  One launch, nothing read."""
-        from .fused import _device_mat4, _intrinsics4
-        if not (isinstance(out6, torch.Tensor) and out6.dtype == torch.float32 and out6.device == self.dev and out6.dim() == 3
-                and out6.shape[0] >= 5 and out6.is_contiguous()):
-            raise RuntimeError(f"out6 must be a contiguous float32 tensor [>= 5, H, W] on {self.dev}")
-        if skip is not None and not (isinstance(skip, torch.Tensor) and skip.dtype == torch.int32 and skip.device == self.dev and skip.numel() >= 1):
-            raise RuntimeError(f"skip must be an int32 tensor on {self.dev}")
-        keep = [out6, skip]
-        w = _capi.SplatTsdfView()
-        w.height, w.width = int(out6.shape[1]), int(out6.shape[2])
-        w.fx, w.fy, w.cx, w.cy = _intrinsics4(intrinsics)
-        w.sil_thres, w.depth_max, w.weight_max = float(sil_thres), float(depth_max), float(weight_max)
-        w.out6, w.w2c = out6.data_ptr(), _device_mat4(w2c, "w2c", self.dev, keep).data_ptr()
-        w.skip = skip.data_ptr() if skip is not None else None
-        w.skipped = self.skipped.data_ptr()
+        w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, weight_max, skip, self.skipped, self.dev)
         with torch.cuda.device(self.dev):
             _capi.check(self.L.splat_tsdf_integrate(C.byref(self.struct), C.byref(w), self._stream()), "splat_tsdf_integrate")
         self._keep = keep
@@ -151,39 +198,217 @@ class TsdfVolume:
             _capi.check(self.L.splat_tsdf_triangles(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
                                                     count.data_ptr(), self._stream()), "splat_tsdf_triangles")
 
-    def extract(self, min_weight=1.0, capacity=None):
-        """The zero surface over the cells whose eight corners have ``weight >= min_weight`` as a ``Mesh`` on the device.  One pass over
-        the cells into ``capacity`` triangle slots (default: a guess from the grid's size), ONE host read of the count, a second pass
-        at the reported size if they did not fit; vertices welded by ``torch.unique`` over their keys, positions and colours by one
-        launch.  Canonical: vertices sorted by key, faces lexicographically."""
+    def _default_capacity(self):                            # a closed surface crosses O(n^2) of n^3 cells, ~4 triangles each
         nx, ny, nz = self.dims
-        if capacity is None:                                # a closed surface crosses O(n^2) of n^3 cells, ~4 triangles each
-            capacity = 16 * (nx * ny + ny * nz + nz * nx) + 4096
-        capacity = max(int(capacity), 0)
-        count = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        keys = torch.empty(capacity, 3, dtype=torch.int64, device=self.dev) if capacity else None
-        self._triangles(min_weight, keys, count)
-        n = int(count.item())
-        if n > capacity:
-            keys = torch.empty(n, 3, dtype=torch.int64, device=self.dev)
-            self._triangles(min_weight, keys, count)
-        self.last_triangle_count = n
-        if n == 0:
-            z = torch.zeros(0, 3, dtype=torch.float32, device=self.dev)
-            return Mesh(z, torch.zeros(0, 3, dtype=torch.int32, device=self.dev), z.clone())
-        uniq, inverse = torch.unique(keys[:n].reshape(-1), return_inverse=True)
-        if uniq.numel() >= 2 ** 31:
-            raise RuntimeError(f"{uniq.numel()} vertices do not fit int32 faces: extract a smaller volume")
-        faces = inverse.view(n, 3)
-        for col in (2, 1, 0):                               # lexicographic rows: three stable sorts, last column first
-            faces = faces[torch.sort(faces[:, col], stable=True).indices]
-        vertices = torch.empty(uniq.numel(), 3, dtype=torch.float32, device=self.dev)
-        colors = torch.empty_like(vertices)
+        return 16 * (nx * ny + ny * nz + nz * nx) + 4096
+
+    def _vertices(self, uniq, vertices, colors):
         with torch.cuda.device(self.dev):
             _capi.check(self.L.splat_tsdf_vertices(C.byref(self.struct), uniq.data_ptr(), uniq.numel(), vertices.data_ptr(), colors.data_ptr(),
                                                    self._stream()), "splat_tsdf_vertices")
-        self.last_keys = uniq
-        return Mesh(vertices, faces.to(torch.int32).contiguous(), colors)
+
+
+BRICK_POINTS = 2048                  # (csrc/tsdf_math.h kTsdfBrickPoints)
+
+
+def brick_shapes():
+    """The brick shapes the library accepts, each (x, y, z) grid points; the first is the default."""
+    L = _capi.lib()
+    shape = (C.c_int32 * 3)()
+    return [tuple(shape) for n in range(L.splat_tsdf_sparse_brick_shape(0, shape)) if L.splat_tsdf_sparse_brick_shape(n, shape)]
+
+
+class SparseTsdfVolume(_Surface):
+    """``TsdfVolume``'s grid, of which only BRICKS near observed surfaces are stored (csrc/tsdf_sparse.hip): a brick is 2048 grid points
+    (``brick`` = its shape, default ``brick_shapes()[0]``), 8 KiB per array in a pool; ``directory`` (int32, one entry per brick of the
+    grid, x fastest) holds a brick's slot in the pool or -1, ``brick_of_slot`` the reverse.  ``dims`` may be far beyond what a dense
+    volume could hold: memory follows the surfaces, not the box.
+
+    The order that gives the dense volume's mesh BIT FOR BIT: ``mark`` every view, ``allocate`` once, ``integrate`` every view,
+    ``extract`` (``extract_mesh(..., sparse=True)`` does that).  ``mark`` flags every brick that meets the 3 x 3 x 3 neighbourhood of a
+    grid point the view can update with a negative value -- every cell that can emit a triangle has its eight corners there -- and a
+    brick that then receives every view holds the dense volume's bits.  ``allocate`` may also be called again and again (mark,
+    allocate, integrate view by view: the pool grows); a brick allocated late has missed the earlier views' free-space updates, so the
+    result may then differ from the dense one.
+
+    Every method enqueues on the current stream; ``marked_count`` and ``extract`` read one number each.  ``capacity_bricks``: room in
+    the pool from the start (it grows by reallocation otherwise)."""
+
+    def __init__(self, origin, dims, voxel_size, trunc=None, capacity_bricks=0, device="cuda:0", brick=None):
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise RuntimeError("SparseTsdfVolume needs a CUDA/HIP device; the HIP library has no CPU path")
+        self.origin = tuple(float(v) for v in origin)
+        self.dims = tuple(int(d) for d in dims)
+        self.voxel_size = float(voxel_size)
+        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
+        self.L = _capi.lib()
+        self.brick = tuple(int(b) for b in (brick or brick_shapes()[0]))
+        v = self.struct = _capi.SplatTsdfSparse()
+        if len(self.origin) != 3 or len(self.dims) != 3 or len(self.brick) != 3:
+            raise ValueError(f"a volume needs three dims, an origin and a brick shape (got {self.dims}, {self.origin}, {self.brick})")
+        v.nx, v.ny, v.nz = self.dims
+        v.origin[:] = self.origin
+        v.voxel, v.trunc = self.voxel_size, self.trunc
+        v.brick[:] = self.brick
+        v.slots = 0
+        if int(self.L.splat_tsdf_sparse_bytes(C.byref(v))) == 0:
+            raise ValueError(f"a sparse volume needs positive dims (fewer than 2^40 grid points, 2^31 bricks), voxel size and trunc and a brick shape "
+                             f"of {brick_shapes()} (got {self.dims}, {self.voxel_size}, {self.trunc}, {self.brick})")
+        self.bricks_per_axis = tuple(-(-d // b) for d, b in zip(self.dims, self.brick))
+        self.num_bricks = self.bricks_per_axis[0] * self.bricks_per_axis[1] * self.bricks_per_axis[2]
+        self.directory = torch.full((self.num_bricks,), -1, dtype=torch.int32, device=self.dev)
+        self.flags = torch.zeros(self.num_bricks, dtype=torch.int32, device=self.dev)
+        self.slots = 0
+        self.pool = self.brick_of_slot = None
+        self._capacity = 0
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)          # ``integrate`` launches a non-zero ``skip`` turned away
+        self.mark_skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)     # ... and ``mark`` launches
+        self._keep = None
+        v.directory = self.directory.data_ptr()
+        if capacity_bricks:
+            self._reserve(int(capacity_bricks))
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _bind(self):
+        v = self.struct
+        v.slots = self.slots
+        v.directory = self.directory.data_ptr()
+        if self.pool is not None:
+            v.brick_of_slot = self.brick_of_slot.data_ptr()
+            v.tsdf, v.weight, v.r, v.g, v.b = (t.data_ptr() for t in self.pool.unbind(0))
+
+    def _reserve(self, capacity):
+        """Room for ``capacity`` bricks in the pool; what is there is kept."""
+        if capacity <= self._capacity:
+            return
+        pool = torch.empty(5, capacity, BRICK_POINTS, dtype=torch.float32, device=self.dev)
+        table = torch.empty(capacity + 1, dtype=torch.int32, device=self.dev)      # (one entry more: where ``allocate`` drops the bricks it skips)
+        if self.slots:
+            pool[:, :self.slots].copy_(self.pool[:, :self.slots])
+            table[:self.slots].copy_(self.brick_of_slot[:self.slots])
+        self.pool, self.brick_of_slot, self._capacity = pool, table, capacity
+        self._bind()
+
+    def bytes_for(self, slots):
+        """Device bytes of this volume with ``slots`` bricks in the pool: the pool, ``brick_of_slot``, the directory and the flags."""
+        return (20 * BRICK_POINTS + 4) * int(slots) + 8 * self.num_bricks
+
+    def bytes(self):
+        return self.bytes_for(self.slots)
+
+    def arrays(self):
+        """tsdf, weight, r, g, b of the pool: each [slots, 2048]."""
+        if self.pool is None:
+            return {k: torch.zeros(0, BRICK_POINTS, device=self.dev) for k in VOLUME_ARRAYS}
+        return dict(zip(VOLUME_ARRAYS, self.pool[:, :self.slots].unbind(0)))
+
+    def mark(self, out6, w2c, intrinsics, sil_thres=0.99, depth_max=0.0, skip=None):
+        """Flags the bricks one view needs (``integrate``'s arguments; ``weight_max`` plays no part).  A non-zero ``skip`` leaves the
+        flags as they are and ``mark_skipped`` counts one.  One launch, nothing read."""
+        w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, 0.0, skip, self.mark_skipped, self.dev)
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_tsdf_sparse_mark(C.byref(self.struct), C.byref(w), self.flags.data_ptr(), self._stream()), "splat_tsdf_sparse_mark")
+        self._keep = keep
+        return self
+
+    def mark_view(self, engine, view, time_idx=None, w2c=None, intrinsics=None, first_w2c=None, near=0.01, far=100, weight_max=0.0, **kw):
+        """``integrate_view`` with ``mark`` in place of ``integrate``.  Returns the ``ViewImage``."""
+        with torch.no_grad():
+            img = engine.render_view(view, w2c=w2c, time_idx=time_idx, intrinsics=intrinsics, first_w2c=first_w2c, near=near, far=far, rgb8=False)
+        self.mark(img.out6, view.w2c, intrinsics, skip=img.truncated, **kw)
+        return img
+
+    def _new(self):
+        return (self.flags != 0) & (self.directory < 0)
+
+    def marked_count_tensor(self):
+        """int64 [1] on the device: marked bricks that have no slot yet."""
+        return self._new().sum().reshape(1)
+
+    def marked_count(self):
+        """Marked bricks that have no slot yet.  One host read."""
+        return int(self.marked_count_tensor().item())
+
+    def allocate(self, max_bytes=DEFAULT_MAX_BYTES, count=None):
+        """Slots for the marked bricks that have none, in brick order, reset to tsdf = 1, weight = r = g = b = 0.  ``count``: their
+        number when the caller has read it already (``marked_count()`` otherwise: the one read).  ValueError, with the bytes it would
+        need, when the volume would grow beyond ``max_bytes``.  Returns the number of new slots."""
+        count = self.marked_count() if count is None else int(count)
+        total = self.slots + count
+        need = self.bytes_for(total)
+        if need > max_bytes or total >= 2 ** 31:
+            nx, ny, nz = self.dims
+            raise ValueError(f"a sparse {nx} x {ny} x {nz} volume at voxel size {self.voxel_size} with {total} bricks of {BRICK_POINTS} grid points needs "
+                             f"{need} bytes ({need / 2 ** 30:.2f} GiB), beyond max_bytes = {max_bytes}: raise the voxel size, pass tighter bounds "
+                             f"or a larger max_bytes")
+        if count == 0:
+            return 0
+        self._reserve(max(total, self._capacity))
+        new = self._new()
+        slot = (self.slots - 1 + torch.cumsum(new, 0)).to(torch.int32)             # (of the new bricks; deterministic: brick order)
+        self.directory.copy_(torch.where(new, slot, self.directory))
+        # brick_of_slot without a host read: every brick writes its number at its new slot, the others into the spare last entry
+        where = torch.where(new, slot.long(), torch.full_like(slot, self._capacity, dtype=torch.int64))
+        self.brick_of_slot.scatter_(0, where, torch.arange(self.num_bricks, dtype=torch.int32, device=self.dev))
+        first, self.slots = self.slots, total
+        self._bind()
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_tsdf_sparse_reset_slots(C.byref(self.struct), first, count, self._stream()), "splat_tsdf_sparse_reset_slots")
+        return count
+
+    def integrate(self, out6, w2c, intrinsics, sil_thres=0.99, depth_max=0.0, weight_max=0.0, skip=None):
+        """``TsdfVolume.integrate`` on every allocated brick: the same arithmetic, the same bits.  One launch, nothing read."""
+        w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, weight_max, skip, self.skipped, self.dev)
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_tsdf_sparse_integrate(C.byref(self.struct), C.byref(w), self._stream()), "splat_tsdf_sparse_integrate")
+        self._keep = keep
+        return self
+
+    integrate_view = TsdfVolume.integrate_view
+
+    def _triangles(self, min_weight, keys, count):
+        cap = 0 if keys is None else int(keys.shape[0])
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_tsdf_sparse_triangles(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
+                                                           count.data_ptr(), self._stream()), "splat_tsdf_sparse_triangles")
+
+    def _default_capacity(self):                            # the band is several bricks thick and the surface crosses some of them
+        return 768 * self.slots + 4096
+
+    def _vertices(self, uniq, vertices, colors):
+        with torch.cuda.device(self.dev):
+            _capi.check(self.L.splat_tsdf_sparse_vertices(C.byref(self.struct), uniq.data_ptr(), uniq.numel(), vertices.data_ptr(),
+                                                          colors.data_ptr(), self._stream()), "splat_tsdf_sparse_vertices")
+
+    def point_offsets(self):
+        """int64 [nz, ny, nx]: every grid point's offset in the pool's arrays (slot 2048 + local), -1 where its brick is not allocated.
+        For tests and small volumes."""
+        bx, by, bz = self.brick
+        i, j, k = (torch.arange(d, device=self.dev) for d in self.dims)
+        brick = ((k // bz)[:, None, None] * self.bricks_per_axis[1] + (j // by)[None, :, None]) * self.bricks_per_axis[0] + (i // bx)[None, None, :]
+        local = ((k % bz)[:, None, None] * by + (j % by)[None, :, None]) * bx + (i % bx)[None, None, :]
+        slot = self.directory[brick].long()
+        return torch.where(slot >= 0, slot * BRICK_POINTS + local, torch.full_like(slot, -1))
+
+    def to_dense(self, max_bytes=DEFAULT_MAX_BYTES):
+        """A ``TsdfVolume`` of the same grid with this volume's values, the reset values where no brick is allocated.  For tests and
+        small volumes: ValueError beyond ``max_bytes``, like ``plan_volume``."""
+        need = volume_bytes(self.dims)
+        if need > max_bytes:
+            nx, ny, nz = self.dims
+            raise ValueError(f"a {nx} x {ny} x {nz} volume at voxel size {self.voxel_size} needs {need} bytes ({need / 2 ** 30:.2f} GiB), "
+                             f"beyond max_bytes = {max_bytes}")
+        dense = TsdfVolume(self.origin, self.dims, self.voxel_size, self.trunc, self.dev)
+        if self.slots:
+            at = self.point_offsets()
+            have = at >= 0
+            flat = self.pool.view(5, -1)
+            for n, t in enumerate(dense.data.unbind(0)):
+                t[have] = flat[n][at[have]]
+        return dense
 
 
 def _scaled_intrinsics(intrinsics, size, org_size):
@@ -193,8 +418,37 @@ def _scaled_intrinsics(intrinsics, size, org_size):
     return fx * sx, fy * sy, cx * sx, cy * sy
 
 
+def _views_pass(frames, run, skipped, view, extra=None):
+    """``run(frame)`` (a render and what follows it; returns the ``ViewImage``) for every frame, each view's truncation status kept in a
+    device table that is read ONCE at the end, with the ``skipped`` counter and ``extra`` (an int64 [1] tensor made after the loop, or
+    None) behind it; the views whose lists did not fit -- turned away on the device -- then get ``view.check_overflow()`` and go
+    again.  Returns (the frames repeated, ``extra``'s value or None)."""
+    dev = skipped.device
+    table = torch.zeros(len(frames) + 2, dtype=torch.int64, device=dev)       # a flag per frame, the skipped counter, ``extra``
+    for n, fr in enumerate(frames):
+        img = run(fr)
+        table[n:n + 1].copy_(img.truncated)
+    table[len(frames):len(frames) + 1].copy_(skipped)
+    if extra is not None:
+        table[len(frames) + 1:].copy_(extra())
+    table = table.cpu().tolist()                            # the one read
+    flagged = [n for n in range(len(frames)) if table[n]]
+    if table[len(frames)] != len(flagged):
+        raise RuntimeError(f"{table[len(frames)]} views were turned away on the device but {len(flagged)} are flagged")
+    if flagged:
+        view.check_overflow()                               # (digests the latest render; clears the camera's status either way)
+    for n in flagged:
+        for _ in range(3):
+            run(frames[n])
+            if not view.check_overflow():                   # (True: the lists are grown, the view goes again)
+                break
+        else:
+            raise RuntimeError(f"frame {frames[n]}: the per-tile lists could not be sized for its view")
+    return [frames[n] for n in flagged], (table[-1] if extra is not None else None)
+
+
 def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, bounds=None, max_bytes=DEFAULT_MAX_BYTES, sil_thres=0.99,
-                 depth_max=0.0, weight_max=0.0, min_weight=1.0, first_w2c=None, view=None, return_volume=False):
+                 depth_max=0.0, weight_max=0.0, min_weight=1.0, first_w2c=None, view=None, return_volume=False, sparse=False):
     """A ``Mesh`` of ``engine``'s map from renders at ``frames``: each a time index of the map (seen through ``first_w2c``, default the
     identity) or a float32 [4, 4] ``w2c`` on the device.  ``size`` = (width, height) of the renders, ``intrinsics`` theirs (host).
     ``bounds`` = ((x0, y0, z0), (x1, y1, z1)); default ``default_bounds`` of the map padded by ``trunc + voxel_size`` (one host read).
@@ -203,48 +457,39 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
     One view camera (``view``, or a new one) moves from pose to pose; every frame is enqueued -- render, integrate, its truncation
     status kept in a device table -- and the table is read ONCE at the end.  Views whose lists did not fit were turned away on the
     device; they get ``view.check_overflow()`` and are integrated again.  The map, its Adam state, ``variables`` and the current camera
-    are left as they were (``render_view``'s contract).  Between iterations, like every view render."""
+    are left as they were (``render_view``'s contract).  Between iterations, like every view render.
+
+    ``sparse=True``: the same mesh, bit for bit, from a ``SparseTsdfVolume``, whose memory follows the surfaces instead of the box --
+    ``max_bytes`` then bounds its pool and tables, and a box far beyond what a dense volume could hold is fine.  Two passes over the
+    frames: render + ``mark`` (one read: the table, with the number of bricks marked), ``allocate``, then render + ``integrate`` as
+    above.  A render costs less than the dense volume's integration of it."""
     trunc = 4.0 * float(voxel_size) if trunc is None else float(trunc)
     if bounds is None:
         bounds = default_bounds(engine.params['means3D'][:engine.P], engine.params['logit_opacities'][:engine.P], trunc + float(voxel_size))
-    origin, dims = plan_volume(bounds, voxel_size, max_bytes)
+    origin, dims = plan_volume(bounds, voxel_size, max_bytes, sparse=sparse)
     frames = list(frames)
     W, H = int(size[0]), int(size[1])
     if view is None:
         view = engine.view_camera(W, H)
     elif (view.W, view.H) != (W, H):
         raise ValueError(f"the view camera is {view.W} x {view.H}, not {W} x {H}")
-    volume = TsdfVolume(origin, dims, voxel_size, trunc, engine.dev)
+    volume = (SparseTsdfVolume if sparse else TsdfVolume)(origin, dims, voxel_size, trunc, device=engine.dev)
     kw = dict(intrinsics=intrinsics, sil_thres=sil_thres, depth_max=depth_max, weight_max=weight_max)
 
     def pose(fr):
         return dict(w2c=fr) if isinstance(fr, torch.Tensor) else dict(time_idx=int(fr), first_w2c=first_w2c)
 
-    table = torch.zeros(len(frames) + 1, dtype=torch.int32, device=engine.dev)          # a flag per frame, then the skipped counter
-    for n, fr in enumerate(frames):
-        img = volume.integrate_view(engine, view, **pose(fr), **kw)
-        table[n:n + 1].copy_(img.truncated)
-    table[len(frames):].copy_(volume.skipped)
-    table = table.cpu().tolist()                            # the one read
-    flagged = [n for n in range(len(frames)) if table[n]]
-    if table[-1] != len(flagged):
-        raise RuntimeError(f"{table[-1]} views were turned away on the device but {len(flagged)} are flagged")
-    if flagged:
-        view.check_overflow()                               # (digests the latest render; clears the camera's status either way)
-    for n in flagged:
-        for _ in range(3):
-            volume.integrate_view(engine, view, **pose(frames[n]), **kw)
-            if not view.check_overflow():                   # (True: the lists are grown, the view goes again)
-                break
-        else:
-            raise RuntimeError(f"frame {frames[n]}: the per-tile lists could not be sized for its view")
-    volume.repeated = [frames[n] for n in flagged]
+    if sparse:
+        volume.repeated_marks, count = _views_pass(frames, lambda fr: volume.mark_view(engine, view, **pose(fr), **kw), volume.mark_skipped, view,
+                                                   extra=volume.marked_count_tensor)
+        volume.allocate(max_bytes, count=None if volume.repeated_marks else count)      # (views marked again: the count is read again)
+    volume.repeated, _ = _views_pass(frames, lambda fr: volume.integrate_view(engine, view, **pose(fr), **kw), volume.skipped, view)
     mesh = volume.extract(min_weight)
     return (mesh, volume) if return_volume else mesh
 
 
 def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None, sil_thres=0.99, depth_max=0.0, bounds=None,
-                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True):
+                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False):
     """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``."""
     from . import slam
     from .export import save_mesh_ply
@@ -260,7 +505,7 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
         engine = FusedEngine(params, cam, variables=variables)
         frames = keyframes or list(range(0, engine.num_frames, max(int(every), 1)))
         mesh = extract_mesh(engine, frames, (W, H), _scaled_intrinsics(k, (W, H), (W0, H0)), voxel_size=voxel_size, trunc=trunc, bounds=bounds,
-                            max_bytes=max_bytes, sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous())
+                            max_bytes=max_bytes, sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse)
     save_mesh_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), mesh.colors.cpu().numpy())
     if verbose:
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces from {len(frames)} views", flush=True)
@@ -281,12 +526,14 @@ def main(argv=None):
     parser.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                         help="the volume's box in metres (default: the opaque Gaussians' box)")
     parser.add_argument("--max-bytes", type=int, default=DEFAULT_MAX_BYTES)
+    parser.add_argument("--sparse", action="store_true", help="a sparse volume: the same mesh, memory only near surfaces (for boxes a dense volume cannot hold)")
     parser.add_argument("--device", default="cuda:0")
     args = parser.parse_args(argv)
     bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds else None
     try:
         mesh_from_params(args.params, args.out, voxel_size=args.voxel, trunc=args.trunc, every=args.every, size=args.size,
-                         sil_thres=args.sil_thres, depth_max=args.depth_max, bounds=bounds, max_bytes=args.max_bytes, device=args.device)
+                         sil_thres=args.sil_thres, depth_max=args.depth_max, bounds=bounds, max_bytes=args.max_bytes, device=args.device,
+                         sparse=args.sparse)
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return 0

@@ -85,7 +85,8 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     checkpoint keys (``save_checkpoints``, ``checkpoint_interval``, ``load_checkpoint``, ``checkpoint_time_idx``) are honoured under
     ``workdir/run_name``; ``exact_checkpoints=True`` makes every checkpoint ``save_checkpoints`` writes an exact one (``session<t>.npz``
     beside the pair) and ``resume_exact=t`` continues from the exact checkpoint of frame ``t`` there (``pipeline.rgbd_slam``).
-    ``mesh=True`` (or a dict of ``mesh.mesh_from_params`` keywords): ``mesh.ply`` next to ``params.npz``, from the saved map.
+    ``mesh=True`` (or a dict of ``mesh.mesh_from_params`` keywords, ``dict(sparse=True)`` for a sparse volume): ``mesh.ply`` next to
+    ``params.npz``, from the saved map.
     ``gt_mesh`` (with ``mesh``): the path of a ground-truth PLY; ``stats['mesh_score']`` is ``mesh_score.score_mesh`` of the written mesh
     against it, with ``gt_transform`` (a 4 x 4, or the path of a text file of one) applied to the reconstruction: the first frame's
     ABSOLUTE camera-to-world pose, which the loaders do not keep (Replica: the first line of ``traj.txt``).  ``cull`` (with ``gt_mesh``):
@@ -175,6 +176,8 @@ def main(argv=None):
     parser.add_argument("--exact-checkpoints", action="store_true",
                         help="with config['save_checkpoints']: also write session<t>.npz, the state --resume-exact continues from")
     parser.add_argument("--mesh", action="store_true", help="write mesh.ply next to params.npz (python -m splatam_amd.mesh on the saved map)")
+    parser.add_argument("--mesh-sparse", action="store_true",
+                        help="with --mesh: fuse into a sparse volume (python -m splatam_amd.mesh --sparse): the same mesh, memory only near surfaces")
     parser.add_argument("--gt-mesh", default=None, metavar="GT.ply",
                         help="with --mesh: score mesh.ply against this ground-truth mesh (python -m splatam_amd.mesh_score)")
     parser.add_argument("--gt-transform", default=None, metavar="FILE",
@@ -189,6 +192,8 @@ def main(argv=None):
         parser.error("--align needs --gt-mesh")
     if args.gt_mesh and not args.mesh:
         parser.error("--gt-mesh needs --mesh")
+    if args.mesh_sparse and not args.mesh:
+        parser.error("--mesh-sparse needs --mesh")
     if args.cull and not args.gt_mesh:
         parser.error("--cull needs --gt-mesh")
     config = load_experiment(args.experiment)
@@ -197,7 +202,7 @@ def main(argv=None):
     if args.lpips_weights is not None:
         config = dict(config, lpips_weights=args.lpips_weights)        # (a copy: the experiment module's dict stays as written)
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
-                            exact_checkpoints=args.exact_checkpoints, mesh=args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
+                            exact_checkpoints=args.exact_checkpoints, mesh=dict(sparse=True) if args.mesh_sparse else args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
                             cull=args.cull, **({"align": True} if args.align else {}))
     ev = stats.get('eval')
     if ev is not None:
