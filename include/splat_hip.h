@@ -35,6 +35,7 @@ extern "C" {
                                       17 keeps working): SplatLossConfigEx, SPLAT_LOSS_SPLATAM / SPLAT_LOSS_GS, splat_iter_loss_backward_ex,
                                       splat_iter_mapping_step_ex -- the mapping loss of the refinement script (get_loss_gs);
                                       SPLAT_EVAL_LPIPS, SplatLpipsWorkspace, splat_lpips_* -- LPIPS from caller-supplied AlexNet weights (csrc/lpips.hip);
+                                      splat_mesh_components, splat_mesh_component_stats -- connected components of a mesh (csrc/meshclean.hip);
                                       16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
                                       15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
                                       14: frame ingest (splat_frame_ingest);
@@ -1082,6 +1083,38 @@ int splat_icp_accumulate(const float *source, const float *targets, int64_t num_
                          double threshold, const double *origin, const double *state, double *partials, void *stream);
 int splat_icp_solve(const double *partials, int64_t n, int32_t max_iterations, double relative_fitness, double relative_rmse,
                     const double *origin, double *state, double *history, void *stream);
+
+/* The mesh cleaning layer (csrc/meshclean.hip, loop bodies in csrc/meshclean_math.h; added within ABI 17): connected components of a
+ * triangle mesh and per-component statistics -- what removing the floaters of a fused mesh (every component below a size) is made of.
+ *
+ * Two vertices belong to one component when a chain of faces that share a vertex INDEX joins them; coincident vertices with different
+ * indices do not connect.  A face with an index outside 0..num_vertices-1 links nothing and counts for nothing; a face with a repeated
+ * index links the vertices it names and counts as a face of area 0; a vertex no face names is a component of its own, with 0 faces.
+ *
+ * splat_mesh_components: labels [num_vertices] int32, labels[v] = the SMALLEST vertex index of v's component: canonical, the same bits
+ * on every run and for every order of the faces.  A concurrent union-find over `labels` itself (one lane per face: find with path
+ * halving, the larger root hooked under the smaller by a compare-and-swap; every access an agent-scope atomic; bounded because a word
+ * never holds more than its own index), then a launch that flattens.  num_faces == 0: labels[v] = v.
+ *
+ * splat_mesh_component_stats: five arrays indexed by ROOT LABEL, all of length num_vertices (lo / hi: [num_vertices][3]), which the call
+ * initialises itself; entries of indices that are no root keep their initial value (0; SPLAT_MESH_KEY_HIGHEST in lo, _LOWEST in hi).
+ * num_v / num_f: the component's vertices / faces (a face counts for the label of its first vertex).  area_q: the sum over its faces of
+ * rint(area 2^SPLAT_MESH_AREA_BITS), area being splat_mesh_areas' double: a 64-bit integer sum of quanta of 2^-40 m^2, exact in the
+ * quanta and independent of order; it holds 2^23 m^2 (about 8.4e6 m^2) per component and wraps beyond; a face whose area is not below
+ * 2^22 m^2 (an infinite one included) adds SPLAT_MESH_AREA_BAD quanta instead.  lo / hi: the component's box as KEYS of the float32
+ * coordinates, key = bits >= 0 ? bits : bits ^ 0x7fffffff on the bits as int32 (-0 taken as +0): signed integer order is the floats'
+ * order for both signs, and the same expression maps a key back.  Only integer atomics: the same bits on every run.  `labels` is what
+ * splat_mesh_components gave (an entry outside 0..num_vertices-1 counts for nothing).
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for negative sizes and NULL pointers where
+ * something would be read or written; num_vertices == 0 succeeds without a launch. */
+#define SPLAT_MESH_AREA_BITS 40
+#define SPLAT_MESH_AREA_BAD (1LL << 62)
+#define SPLAT_MESH_KEY_HIGHEST 2147483647
+#define SPLAT_MESH_KEY_LOWEST (-2147483647 - 1)
+int splat_mesh_components(const int32_t *faces, int32_t num_faces, int32_t num_vertices, int32_t *labels, void *stream);
+int splat_mesh_component_stats(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const int32_t *labels,
+                               int32_t *num_v, int32_t *num_f, int64_t *area_q, int32_t *lo, int32_t *hi, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LPIPS (added within ABI 17; csrc/lpips.hip, arithmetic in csrc/lpips_math.h): what the reference's eval() / eval_nvs() compute with

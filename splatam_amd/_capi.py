@@ -198,6 +198,8 @@ SPLAT_EVAL_ROW, SPLAT_EVAL_LEVELS, SPLAT_EVAL_SUMS, SPLAT_EVAL_LAYOUT_MS_SSIM = 
 SPLAT_NN_MAX_CELLS, SPLAT_NN_REDUCE_ROWS = 1 << 21, 256
 SPLAT_MESH_COMPARE_ROWS, SPLAT_MESH_COMPARE_PARTIALS = 256, 6 * 256
 SPLAT_ICP_STATE, SPLAT_ICP_ROWS, SPLAT_ICP_SUMS = 24, 256, 17      # (added within ABI 17: the ICP layer, csrc/icp.hip)
+SPLAT_MESH_AREA_BITS, SPLAT_MESH_AREA_BAD = 40, 1 << 62            # (added within ABI 17: the mesh cleaning layer, csrc/meshclean.hip)
+SPLAT_MESH_KEY_HIGHEST, SPLAT_MESH_KEY_LOWEST = 2 ** 31 - 1, -2 ** 31
 SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS, SPLAT_ICP_FITNESS, SPLAT_ICP_RMSE = 16, 17, 18, 19
 SPLAT_ICP_PREV_FITNESS, SPLAT_ICP_PREV_RMSE, SPLAT_ICP_COUNT, SPLAT_ICP_POINTS = 20, 21, 22, 23
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
@@ -233,6 +235,7 @@ EXPORTS = (
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
     "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
     "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
+    "splat_mesh_components", "splat_mesh_component_stats",
     "splat_lpips_weight_floats", "splat_lpips_pack_floats", "splat_lpips_tap_size", "splat_lpips_workspace_layout", "splat_lpips_workspace_bind",
     "splat_lpips_pack", "splat_lpips_conv", "splat_lpips_planes", "splat_lpips_images",
 )
@@ -391,6 +394,13 @@ def lib():
         ("splat_mesh_depth", [_fp, C.c_int32, _fp, C.c_int32, C.POINTER(SplatMeshView), _fp, _fp]),
         ("splat_mesh_seen", [_fp, C.c_int32, C.POINTER(SplatMeshView), _fp, C.c_int32, C.c_int32, _fp, C.c_float, _fp, _fp]),
         ("splat_mesh_depth_compare", [_fp, _fp, C.c_int64, _fp, _fp, _fp]),
+    ):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = args
+    for name, args in (
+        ("splat_mesh_components", [_fp, C.c_int32, C.c_int32, _fp, _fp]),
+        ("splat_mesh_component_stats", [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     ):
         f = getattr(L, name)
         f.restype = C.c_int

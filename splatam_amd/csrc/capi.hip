@@ -584,6 +584,19 @@ int splat_icp_solve(const double *partials, int64_t n, int32_t max_iterations, d
                                   (hipStream_t)stream));
 }
 
+// the mesh cleaning layer (csrc/meshclean.hip)
+int splat_mesh_components(const int32_t *faces, int32_t num_faces, int32_t num_vertices, int32_t *labels, void *stream) {
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !labels)) return SPLAT_E_INVALID;
+    return check(launch_mesh_components(faces, num_faces, num_vertices, labels, (hipStream_t)stream));
+}
+
+int splat_mesh_component_stats(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const int32_t *labels,
+                               int32_t *num_v, int32_t *num_f, int64_t *area_q, int32_t *lo, int32_t *hi, void *stream) {
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces)) return SPLAT_E_INVALID;
+    if (num_vertices > 0 && (!vertices || !labels || !num_v || !num_f || !area_q || !lo || !hi)) return SPLAT_E_INVALID;
+    return check(launch_mesh_component_stats(vertices, num_vertices, faces, num_faces, labels, num_v, num_f, area_q, lo, hi, (hipStream_t)stream));
+}
+
 // the mesh render layer (csrc/meshrender.hip)
 static bool finite_f(float x) { return x >= -3.0e38f && x <= 3.0e38f; }
 static bool valid_mesh_view(const SplatMeshView *v) {

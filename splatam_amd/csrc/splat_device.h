@@ -136,6 +136,10 @@ hipError_t launch_icp_accumulate(const float *source, const float *targets, long
                                  long long n, double threshold, const double *origin, const double *state, double *partials, hipStream_t s);
 hipError_t launch_icp_solve(const double *partials, long long n, int32_t max_iterations, double relative_fitness, double relative_rmse,
                             const double *origin, double *state, double *history, hipStream_t s);
+// meshclean.hip: connected components of a mesh given by its faces (concurrent union-find), and per-component statistics
+hipError_t launch_mesh_components(const int32_t *faces, int32_t F, int32_t V, int32_t *labels, hipStream_t s);
+hipError_t launch_mesh_component_stats(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const int32_t *labels, int32_t *num_v,
+                                       int32_t *num_f, int64_t *area_q, int32_t *lo, int32_t *hi, hipStream_t s);
 // meshrender.hip: the depth image of a triangle mesh (z-buffer), views that see each vertex, and the sums of a depth comparison
 hipError_t launch_mesh_depth(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const SplatMeshView &view, float *depth,
                              hipStream_t s);

@@ -1,5 +1,5 @@
 """A triangle mesh of the map: ``python -m splatam_amd.mesh PARAMS.npz --out mesh.ply [--voxel M] [--trunc M] [--every N] [--size WxH]
-[--sil-thres S] [--depth-max M] [--bounds X0 Y0 Z0 X1 Y1 Z1] [--sparse]``.
+[--sil-thres S] [--depth-max M] [--bounds X0 Y0 Z0 X1 Y1 Z1] [--sparse] [--clean [--min-vertices N] [--min-area M2] [--keep-largest K]]``.
 
 Depth rendered at the estimated poses is fused into a truncated signed distance volume and the volume's zero surface is extracted,
 all on the device (csrc/tsdf.hip, arithmetic in csrc/tsdf_math.h): the usual deliverable of a dense RGB-D SLAM system, and what the
@@ -14,6 +14,9 @@ same volume always gives the same bytes.
 The dense ``TsdfVolume`` holds five floats for every grid point of the box and is refused beyond ``max_bytes``; ``--sparse``
 (``SparseTsdfVolume``, csrc/tsdf_sparse.hip) stores only the bricks of 2048 grid points within the truncation band of a surface some
 view saw and gives the same mesh bit for bit: an apartment at 1 cm, a room at 5 mm, a walk down a corridor.
+
+``--clean`` (``extract_mesh(..., clean=True)`` or a dict of ``mesh_clean.clean_mesh`` keywords) removes the mesh's small connected
+components -- the floaters of rendered depth -- on the device before it is returned or written.  Off by default.
 
 The command loads a ``params.npz`` as ``python -m splatam_amd.run`` writes it; poses come from the map, frames from
 ``keyframe_time_indices`` when present (otherwise every ``--every``-th), size and intrinsics from ``org_width`` / ``org_height`` /
@@ -448,7 +451,7 @@ def _views_pass(frames, run, skipped, view, extra=None):
 
 
 def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, bounds=None, max_bytes=DEFAULT_MAX_BYTES, sil_thres=0.99,
-                 depth_max=0.0, weight_max=0.0, min_weight=1.0, first_w2c=None, view=None, return_volume=False, sparse=False):
+                 depth_max=0.0, weight_max=0.0, min_weight=1.0, first_w2c=None, view=None, return_volume=False, sparse=False, clean=None):
     """A ``Mesh`` of ``engine``'s map from renders at ``frames``: each a time index of the map (seen through ``first_w2c``, default the
     identity) or a float32 [4, 4] ``w2c`` on the device.  ``size`` = (width, height) of the renders, ``intrinsics`` theirs (host).
     ``bounds`` = ((x0, y0, z0), (x1, y1, z1)); default ``default_bounds`` of the map padded by ``trunc + voxel_size`` (one host read).
@@ -462,7 +465,12 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
     ``sparse=True``: the same mesh, bit for bit, from a ``SparseTsdfVolume``, whose memory follows the surfaces instead of the box --
     ``max_bytes`` then bounds its pool and tables, and a box far beyond what a dense volume could hold is fine.  Two passes over the
     frames: render + ``mark`` (one read: the table, with the number of bricks marked), ``allocate``, then render + ``integrate`` as
-    above.  A render costs less than the dense volume's integration of it."""
+    above.  A render costs less than the dense volume's integration of it.
+
+    ``clean`` (True, or a dict of ``mesh_clean.clean_mesh`` keywords): the mesh is ``clean_mesh`` of what was extracted -- its small
+    connected components are removed on the device, with one more host read.  ``None``: the mesh as extracted."""
+    from .mesh_clean import clean_options
+    clean = clean_options(clean)
     trunc = 4.0 * float(voxel_size) if trunc is None else float(trunc)
     if bounds is None:
         bounds = default_bounds(engine.params['means3D'][:engine.P], engine.params['logit_opacities'][:engine.P], trunc + float(voxel_size))
@@ -485,16 +493,22 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
         volume.allocate(max_bytes, count=None if volume.repeated_marks else count)      # (views marked again: the count is read again)
     volume.repeated, _ = _views_pass(frames, lambda fr: volume.integrate_view(engine, view, **pose(fr), **kw), volume.skipped, view)
     mesh = volume.extract(min_weight)
+    if clean is not None:
+        from .mesh_clean import clean_mesh
+        mesh = clean_mesh(mesh, device=engine.dev, **clean)
     return (mesh, volume) if return_volume else mesh
 
 
 def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None, sil_thres=0.99, depth_max=0.0, bounds=None,
-                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False):
-    """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``."""
+                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False, clean=None, cleaning=None):
+    """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``.  ``clean`` (True or a dict of
+    ``mesh_clean.clean_mesh`` keywords): the mesh is cleaned before it is written; ``cleaning``, a dict, then receives the report."""
     from . import slam
     from .export import save_mesh_ply
     from .fused import FusedEngine
+    from .mesh_clean import clean_mesh, clean_options, format_cleaning
     from .view import load_map
+    clean = clean_options(clean)
     dev = torch.device(device)
     params, variables, k, first_w2c, (W0, H0) = load_map(path, dev)
     with np.load(path) as z:
@@ -506,9 +520,15 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
         frames = keyframes or list(range(0, engine.num_frames, max(int(every), 1)))
         mesh = extract_mesh(engine, frames, (W, H), _scaled_intrinsics(k, (W, H), (W0, H0)), voxel_size=voxel_size, trunc=trunc, bounds=bounds,
                             max_bytes=max_bytes, sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse)
+        if clean is not None:
+            mesh, found = clean_mesh(mesh, device=dev, report=True, **clean)
+            if cleaning is not None:
+                cleaning.update(found)
     save_mesh_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), mesh.colors.cpu().numpy())
     if verbose:
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces from {len(frames)} views", flush=True)
+        if clean is not None:
+            print(format_cleaning(found), flush=True)
     return mesh
 
 
@@ -527,13 +547,20 @@ def main(argv=None):
                         help="the volume's box in metres (default: the opaque Gaussians' box)")
     parser.add_argument("--max-bytes", type=int, default=DEFAULT_MAX_BYTES)
     parser.add_argument("--sparse", action="store_true", help="a sparse volume: the same mesh, memory only near surfaces (for boxes a dense volume cannot hold)")
+    parser.add_argument("--clean", action="store_true", help="remove the mesh's small connected components before it is written")
+    parser.add_argument("--min-vertices", type=int, default=None, metavar="N", help="with --clean: components with fewer vertices go (200)")
+    parser.add_argument("--min-area", type=float, default=None, metavar="M2", help="with --clean: components with less area in m^2 go (0)")
+    parser.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --clean: keep at most the K components with the most faces")
     parser.add_argument("--device", default="cuda:0")
     args = parser.parse_args(argv)
+    options = {k: v for k, v in (("min_vertices", args.min_vertices), ("min_area", args.min_area), ("keep_largest", args.keep_largest)) if v is not None}
+    if options and not args.clean:
+        parser.error("--min-vertices, --min-area and --keep-largest need --clean")
     bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds else None
     try:
         mesh_from_params(args.params, args.out, voxel_size=args.voxel, trunc=args.trunc, every=args.every, size=args.size,
                          sil_thres=args.sil_thres, depth_max=args.depth_max, bounds=bounds, max_bytes=args.max_bytes, device=args.device,
-                         sparse=args.sparse)
+                         sparse=args.sparse, **({"clean": options or True} if args.clean else {}))
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return 0

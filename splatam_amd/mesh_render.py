@@ -278,13 +278,26 @@ def _keep_seen(mesh, seen, rule):
     idx = f.clamp(0, V - 1).long()
     fv = (seen > 0)[idx]
     keep = (fv.all(dim=1) if rule == "all" else fv.any(dim=1)) & valid
+    return _keep_faces(mesh, idx, keep)
+
+
+def _keep_faces(mesh, idx, keep, extra=None):
+    """The faces of ``mesh`` flagged in ``keep`` [F] (``idx``: its faces as int64 indices inside the vertices), compacted: surviving faces
+    keep their order, the vertices they name are renumbered densely in their order and colours travel with them.  ONE host read, of the
+    surviving sizes, with ``extra`` (int64 values on the device, or None) behind them; with ``extra`` the result is (the ``Mesh``, those
+    values on the host).  ``cull_mesh`` and ``mesh_clean.clean_mesh`` share it."""
+    v, f, c = mesh
+    V, F = int(v.shape[0]), int(f.shape[0])
     named = torch.zeros(V, dtype=torch.int32, device=v.device)
     named.index_add_(0, idx.reshape(-1), keep[:, None].expand(F, 3).reshape(-1).to(torch.int32))
     used = named > 0
-    nF, nV = (int(x) for x in torch.stack((keep.sum(), used.sum())).cpu())       # the one read
+    sizes = torch.stack((keep.sum(), used.sum()))
+    got = (sizes if extra is None else torch.cat((sizes, extra.to(torch.int64).reshape(-1)))).cpu()      # the one read
+    nF, nV = int(got[0]), int(got[1])
     fi, vi = _compact(keep, nF), _compact(used, nV)
     renumber = torch.cumsum(used, 0) - 1
-    return Mesh(v[vi].contiguous(), renumber[idx[fi]].to(torch.int32).contiguous(), None if c is None else c[vi].contiguous())
+    out = Mesh(v[vi].contiguous(), renumber[idx[fi]].to(torch.int32).contiguous(), None if c is None else c[vi].contiguous())
+    return out if extra is None else (out, got[2:])
 
 
 # ---------------------------------------------------------------------------------------------------------------- depth L1

@@ -1,6 +1,6 @@
 """A reconstructed mesh against a ground-truth mesh: ``python -m splatam_amd.mesh_score REC.ply GT.ply [--samples N] [--threshold M]
 [--seed S] [--transform FILE] [--device DEV] [--cull-poses TRAJ.txt [--cull-every N] [--cull-size WxH] [--cull-intrinsics FX FY CX CY]
-[--occlusion]] [--depth-l1 N] [--align [--align-threshold M] [--align-iterations N]]``.
+[--occlusion]] [--depth-l1 N] [--align [--align-threshold M] [--align-iterations N]] [--clean [--min-vertices N]]``.
 
 The three figures of the NICE-SLAM evaluation protocol, which SplaTAM's comparison tables use: ACCURACY, the mean distance in cm from
 the reconstruction to the ground truth; COMPLETION, the mean distance in cm from the ground truth to the reconstruction; COMPLETION
@@ -24,6 +24,10 @@ and ``--depth-l1 N`` adds the depth L1 between the two meshes rendered at ``N`` 
 The protocol's registration step is ``align_icp`` (csrc/icp.hip, arithmetic in csrc/icp_math.h): ``--align`` registers the
 reconstruction's vertices to the ground truth's by point-to-point ICP -- after ``--transform`` and the culling, before a point is sampled
 -- and prints an ``Alignment:`` line in front of the figures.  Off unless asked for.
+
+Floaters: ``--clean`` (``score_with_views(..., clean=True)`` or a dict of ``mesh_clean.clean_mesh`` keywords) removes the small connected
+components of the RECONSTRUCTION alone (csrc/meshclean.hip) -- after ``--transform``, before the culling, the ICP and the samples -- and
+prints a ``Cleaning:`` line ahead of ``Alignment:``; the score gains ``cleaning``.  Off unless asked for.
 
 Not here: marching cubes; point-to-plane or coloured ICP, scale, a global registration in front of the ICP.
 """
@@ -398,13 +402,32 @@ def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None,
 
     ``align`` (True, or a dict of ``align_icp`` keywords): the protocol's registration -- after ``transform``, the reconstruction's
     VERTICES are registered to the ground truth's by point-to-point ICP and moved by what it finds before a point is sampled; the score
-    gains ``alignment``, the ``align_icp`` dict plus ``translation_cm`` and ``rotation_deg`` of that motion."""
+    gains ``alignment``, the ``align_icp`` dict plus ``translation_cm`` and ``rotation_deg`` of that motion.
+
+    Cleaning the reconstruction first: ``score_with_views(..., clean=True)``; this function's signature is as it was."""
+    return _score_mesh(rec, gt, samples, threshold, seed, transform, device, cell, align, None)
+
+
+def _score_mesh(rec, gt, samples, threshold, seed, transform, device, cell, align, clean):
+    """``score_mesh`` with ``clean`` (None, True, or a dict of ``mesh_clean.clean_mesh`` keywords): the RECONSTRUCTION alone loses its
+    small connected components after ``transform`` and before everything else (one more host read); the score gains ``cleaning``,
+    ``clean_mesh``'s report.  A reconstruction given as host arrays or a path keeps the box of the uncleaned mesh for its search grid,
+    which changes no figure."""
+    from .mesh_clean import clean_options
+    clean = clean_options(clean)
     dev = _device(device)
     samples = int(samples)
     if samples <= 0 or not float(threshold) > 0:
         raise ValueError("score_mesh needs samples > 0 and threshold > 0")
     rv, rf, rb = _load(rec, dev, _transform(transform), "the reconstruction")
     gv, gf, gb = _load(gt, dev, None, "the ground truth")
+    cleaning = None
+    if clean is not None:
+        from .mesh_clean import clean_mesh
+        cleaned, cleaning = clean_mesh(Mesh(rv, rf, None), device=dev, report=True, **clean)
+        rv, rf = cleaned.vertices, cleaned.faces
+        if rf.shape[0] == 0:
+            raise ValueError("the reconstruction: cleaning removed every component")
     if rb is None or gb is None:                                        # device meshes: both boxes with one read
         box = torch.stack((rv.min(dim=0).values, rv.max(dim=0).values, gv.min(dim=0).values, gv.max(dim=0).values)).double().cpu().numpy()
         rb, gb = (box[0], box[1]), (box[2], box[3])
@@ -431,6 +454,8 @@ def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None,
     score = {"accuracy_cm": 100.0 * t[0, 0] / n, "completion_cm": 100.0 * t[1, 0] / n, "completion_ratio": 100.0 * recall,
              "precision": precision, "recall": recall, "fscore": 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0,
              "max_rec_to_gt": float(t[0, 2]), "max_gt_to_rec": float(t[1, 2]), "samples": samples}
+    if cleaning is not None:
+        score["cleaning"] = cleaning
     if alignment is not None:
         score["alignment"] = alignment
     return score
@@ -440,15 +465,23 @@ def score_culled_in_map_frame(rec, gt, w2c, intrinsics, size, gt_transform=None,
     """``score_mesh`` of a reconstruction in the MAP's frame against a ground truth in the world frame, both culled first to the frusta of
     ``w2c`` ([n, 4, 4] world-to-camera poses in the map's frame: a run's own).  ``gt_transform`` is what ``score_mesh`` would apply to the
     reconstruction, the first frame's absolute camera-to-world pose; its INVERSE brings the ground truth into the map's frame, where
-    both are culled and scored -- distances do not change under a rigid motion.  Further keywords go to ``score_mesh``."""
+    both are culled and scored -- distances do not change under a rigid motion.  Further keywords go to ``score_mesh``; ``clean``
+    among them cleans the reconstruction BEFORE it is culled."""
+    from .mesh_clean import clean_mesh, clean_options
     from .mesh_render import cull_mesh
     to_map = None if gt_transform is None else np.linalg.inv(_transform(gt_transform))
+    clean, cleaning = clean_options(score.pop("clean", None)), None
+    if clean is not None:
+        rec, cleaning = clean_mesh(rec, device=device, report=True, **clean)
     rec_c = cull_mesh(rec, w2c, intrinsics, size, device=device)
     gt_c = cull_mesh(gt, w2c, intrinsics, size, transform=to_map, device=device)
     for m, what in ((rec_c, "reconstruction"), (gt_c, "ground truth")):
         if m.faces.shape[0] == 0:
             raise ValueError(f"the run's views see nothing of the {what}: is the transform the first frame's camera-to-world pose?")
-    return score_mesh(rec_c, gt_c, device=device, **score)
+    result = score_mesh(rec_c, gt_c, device=device, **score)
+    if cleaning is not None:
+        result["cleaning"] = cleaning
+    return result
 
 
 def load_transform(path):
@@ -470,7 +503,12 @@ def format_alignment(a):
 
 
 def format_score(score):
-    text = format_alignment(score["alignment"]) + "\n" if score.get("alignment") is not None else ""
+    text = ""
+    if score.get("cleaning") is not None:
+        from .mesh_clean import format_cleaning
+        text += format_cleaning(score["cleaning"]) + "\n"
+    if score.get("alignment") is not None:
+        text += format_alignment(score["alignment"]) + "\n"
     text += (f"Accuracy: {score['accuracy_cm']:.4f} cm\nCompletion: {score['completion_cm']:.4f} cm\n"
             f"Completion ratio: {score['completion_ratio']:.4f} %\nF-score: {score['fscore']:.6f} "
             f"(precision {score['precision']:.6f}, recall {score['recall']:.6f}; {score['samples']} samples)")
@@ -485,16 +523,23 @@ CULL_SIZE, CULL_INTRINSICS = "1200x680", (600.0, 600.0, 599.5, 339.5)
 
 
 def score_with_views(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cull_w2c=None, intrinsics=CULL_INTRINSICS,
-                     size=(1200, 680), occlusion=False, depth_l1_views=0, align=False):
+                     size=(1200, 680), occlusion=False, depth_l1_views=0, clean=None, align=False):
     """``score_mesh`` behind the protocol's preprocessing: with ``cull_w2c`` ([n, 4, 4] world-to-camera in the ground truth's frame) both
     meshes are culled to those views first (``mesh_render.cull_mesh``; ``occlusion``: each against renders of the ground truth), and
     ``depth_l1_views`` > 0 adds ``mesh_render.depth_l1`` at that many views from ``mesh_render.sample_views`` (same ``seed``).  Without
     either this is ``score_mesh``.  ``align`` (``score_mesh``'s): the ICP runs on the CULLED meshes' vertices, and the samples, the
-    distances and the depth L1 are those of the aligned reconstruction."""
+    distances and the depth L1 are those of the aligned reconstruction.  ``clean`` (``score_mesh``'s): the reconstruction is cleaned
+    after ``transform`` and before it is culled -- the order is ``transform``, clean, cull, ICP, samples."""
     from . import mesh_render as MR
+    from .mesh_clean import clean_mesh, clean_options
     if cull_w2c is None and not depth_l1_views:
-        return score_mesh(rec, gt, samples=samples, threshold=threshold, seed=seed, transform=transform, device=device, align=align)
+        return _score_mesh(rec, gt, samples, threshold, seed, transform, device, None, align, clean)
+    clean, cleaning = clean_options(clean), None
     r, g = MR.to_device_mesh(rec, device, _transform(transform)), MR.to_device_mesh(gt, device, None)
+    if clean is not None:
+        r, cleaning = clean_mesh(r, device=device, report=True, **clean)
+        if r.faces.shape[0] == 0:
+            raise ValueError("the reconstruction: cleaning removed every component")
     if cull_w2c is not None:                                            # (occlusion: both against ONE set of renders of the ground truth)
         r, g = MR.cull_meshes([r, g], cull_w2c, intrinsics, size, occlusion=1 if occlusion else None, device=device)
         for m, what in ((r, "reconstruction"), (g, "ground truth")):
@@ -505,6 +550,8 @@ def score_with_views(rec, gt, samples=200_000, threshold=0.05, seed=0, transform
         aligned, alignment = align_vertices(r.vertices, g.vertices, align)
         r = Mesh(aligned, r.faces, r.colors)
     score = score_mesh(r, g, samples=samples, threshold=threshold, seed=seed, device=device)
+    if cleaning is not None:
+        score["cleaning"] = cleaning
     if alignment is not None:
         score["alignment"] = alignment
     if depth_l1_views:
@@ -535,7 +582,15 @@ def main(argv=None):
                         help="register the reconstruction's vertices to the ground truth's by point-to-point ICP before scoring")
     parser.add_argument("--align-threshold", type=float, default=None, metavar="M", help="with --align: correspondence distance in metres (0.1)")
     parser.add_argument("--align-iterations", type=int, default=None, metavar="N", help="with --align: at most N updates (30)")
+    parser.add_argument("--clean", action="store_true",
+                        help="remove the reconstruction's small connected components first (splatam_amd.mesh_clean); prints a Cleaning: line")
+    parser.add_argument("--min-vertices", type=int, default=None, metavar="N", help="with --clean: components with fewer vertices go (200)")
     args = parser.parse_args(argv)
+    if args.min_vertices is not None and not args.clean:
+        parser.error("--min-vertices needs --clean")
+    cleaning = {}
+    if args.clean:
+        cleaning = {"clean": {"min_vertices": args.min_vertices} if args.min_vertices is not None else True}
     if args.occlusion and not args.cull_poses:
         parser.error("--occlusion needs --cull-poses")
     if (args.align_threshold is not None or args.align_iterations is not None) and not args.align:
@@ -550,7 +605,10 @@ def main(argv=None):
             score = score_with_views(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
                                      device=args.device, cull_w2c=load_poses(args.cull_poses, args.cull_every) if args.cull_poses else None,
                                      intrinsics=tuple(args.cull_intrinsics), size=parse_size(args.cull_size), occlusion=args.occlusion,
-                                     depth_l1_views=args.depth_l1, align=align)
+                                     depth_l1_views=args.depth_l1, align=align, **cleaning)
+        elif cleaning:
+            score = score_with_views(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
+                                     device=args.device, align=align, **cleaning)
         else:
             score = score_mesh(args.rec, args.gt, samples=args.samples, threshold=args.threshold, seed=args.seed, transform=transform,
                                device=args.device, align=align)

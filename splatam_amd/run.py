@@ -93,7 +93,9 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     both meshes are first culled to the frusta of the dataset's poses in the MAP's frame, where those poses live, the inverse of
     ``gt_transform`` bringing the ground truth there (``mesh_score.score_culled_in_map_frame``).  ``align`` (with ``gt_mesh``; True or a
     dict of ``mesh_score.align_icp`` keywords): the reconstruction is registered to the ground truth by ICP before it is measured, and
-    ``stats['mesh_score']['alignment']`` records what was found."""
+    ``stats['mesh_score']['alignment']`` records what was found.  ``mesh=dict(clean=True)`` (or ``clean=`` a dict of
+    ``mesh_clean.clean_mesh`` keywords): the mesh's small connected components are removed before it is written and scored;
+    ``stats['mesh_cleaning']`` is the report, and with ``gt_mesh`` it is ``stats['mesh_score']['cleaning']`` too."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -143,7 +145,11 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
         if mesh:
             from .mesh import mesh_from_params
             stats['mesh'] = os.path.join(os.path.dirname(path), "mesh.ply")
-            mesh_from_params(path, stats['mesh'], device=device, **(mesh if isinstance(mesh, dict) else {}))
+            mesh_options = dict(mesh) if isinstance(mesh, dict) else {}
+            cleaning = {} if mesh_options.get("clean") else None
+            mesh_from_params(path, stats['mesh'], device=device, **mesh_options, **({"cleaning": cleaning} if cleaning is not None else {}))
+            if cleaning is not None:
+                stats['mesh_cleaning'] = cleaning
             if gt_mesh is not None:
                 from .mesh_score import load_transform, score_culled_in_map_frame, score_mesh
                 transform = load_transform(gt_transform) if isinstance(gt_transform, (str, os.PathLike)) else gt_transform
@@ -157,6 +163,8 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
                         raise SystemExit(f"--cull: {e}") from None
                 else:
                     stats['mesh_score'] = score_mesh(stats['mesh'], gt_mesh, transform=transform, device=device, **({"align": align} if align else {}))
+                if cleaning is not None:
+                    stats['mesh_score']['cleaning'] = cleaning
     finally:
         dataset.close()
     return params, variables, stats, path
@@ -178,6 +186,8 @@ def main(argv=None):
     parser.add_argument("--mesh", action="store_true", help="write mesh.ply next to params.npz (python -m splatam_amd.mesh on the saved map)")
     parser.add_argument("--mesh-sparse", action="store_true",
                         help="with --mesh: fuse into a sparse volume (python -m splatam_amd.mesh --sparse): the same mesh, memory only near surfaces")
+    parser.add_argument("--clean-mesh", action="store_true",
+                        help="with --mesh: remove the mesh's small connected components before it is written and scored (splatam_amd.mesh_clean)")
     parser.add_argument("--gt-mesh", default=None, metavar="GT.ply",
                         help="with --mesh: score mesh.ply against this ground-truth mesh (python -m splatam_amd.mesh_score)")
     parser.add_argument("--gt-transform", default=None, metavar="FILE",
@@ -196,13 +206,18 @@ def main(argv=None):
         parser.error("--mesh-sparse needs --mesh")
     if args.cull and not args.gt_mesh:
         parser.error("--cull needs --gt-mesh")
+    if args.clean_mesh and not args.mesh:
+        parser.error("--clean-mesh needs --mesh")
+    mesh = args.mesh
+    if args.mesh_sparse or args.clean_mesh:
+        mesh = dict(**({"sparse": True} if args.mesh_sparse else {}), **({"clean": True} if args.clean_mesh else {}))
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")
     if args.lpips_weights is not None:
         config = dict(config, lpips_weights=args.lpips_weights)        # (a copy: the experiment module's dict stays as written)
     _, _, stats, path = run(config, engine=args.engine, num_frames=args.num_frames, evaluate=not args.no_eval, resume_exact=args.resume_exact,
-                            exact_checkpoints=args.exact_checkpoints, mesh=dict(sparse=True) if args.mesh_sparse else args.mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
+                            exact_checkpoints=args.exact_checkpoints, mesh=mesh, gt_mesh=args.gt_mesh, gt_transform=args.gt_transform,
                             cull=args.cull, **({"align": True} if args.align else {}))
     ev = stats.get('eval')
     if ev is not None:

@@ -559,7 +559,8 @@ class SlamSession:
         """A triangle mesh of the map as it is now: ``mesh.extract_mesh`` at the estimated poses of ``frames`` (time indices; default
         the keyframes so far), rendered at ``size`` = (height, width) (default the loop's) with the loop's intrinsics scaled to it.
         Further keywords (``voxel_size``, ``trunc``, ``bounds``, ``max_bytes``, ``sil_thres``, ``depth_max``, ``weight_max``,
-        ``min_weight``, ``sparse``) go to ``mesh.extract_mesh``.  ``path``: also written there as a PLY.  Returns the ``Mesh`` (on the device).
+        ``min_weight``, ``sparse``, ``clean``) go to ``mesh.extract_mesh``; ``clean=True`` (or a dict of ``mesh_clean.clean_mesh``
+        keywords) removes the mesh's small connected components.  ``path``: also written there as a PLY.  Returns the ``Mesh`` (on the device).
         Between frames and after ``finish()``; engine "fused" only.  The map, the optimiser state and the loop's cameras are left
         as they were."""
         if not self.fused:
