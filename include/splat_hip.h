@@ -867,6 +867,16 @@ int splat_view_finish(const SplatViewArgs *view, void *stream);
  * towards positive tsdf (by the sign pattern alone; zero-area triangles at corners that are exactly zero are kept: the surface stays
  * closed).  keys: [capacity][3] int64; count: one device int64 that receives the number of triangles the volume asks for, whether or
  * not they fit (the call zeroes it first); nothing is written at or beyond `capacity`, in no particular order below it.
+ * splat_tsdf_cubes: the same pass by MARCHING CUBES -- same arguments, same cells, same keys, same count and capacity rules --: vertices
+ * on the twelve axis edges of a cell only (keys with dx + 2 dy + 4 dz in {1, 2, 4}: the keys, positions and colours the tetrahedra give
+ * on those edges), at most 5 triangles per cell against 12, a third of the triangles and a third to a half of the vertices.  The case table follows from
+ * one rule on sign patterns (csrc/tsdf_math.h "SURFACE, cubes"): on every face of a cell, walked counter-clockwise seen from outside,
+ * each run of inside corners gives one directed segment, so two diagonal inside corners are cut off one by one; the segments chain
+ * into loops, fanned from their lowest edge.  Neighbouring cells put reversed segments on their shared face, so the mesh is a closed
+ * oriented cycle wherever the volume was seen.  Not the asymptotic decider / MC33, not any library's table, no dual contouring; on
+ * adversarial sign noise a few edges can be shared by four triangles (each direction as often as its reverse).
+ * splat_tsdf_cubes_table: a host copy of that table, out[256][16] int8: row = inside mask (bit c: corner dx + 2 dy + 4 dz), the
+ * number of triangles, then three edge numbers each (edge = 4 axis + n: from the n-th corner, ascending, whose bit `axis` is clear).
  * splat_tsdf_vertices: vertices [n][3] (and colors [n][3], or NULL) of n keys: p(a) + t (p(b) - p(a)) with t = f_a / (f_a - f_b), the
  * colour interpolated alike.
  *
@@ -891,6 +901,8 @@ size_t splat_tsdf_bytes(const SplatTsdfVolume *volume);
 int splat_tsdf_reset(const SplatTsdfVolume *volume, void *stream);
 int splat_tsdf_integrate(const SplatTsdfVolume *volume, const SplatTsdfView *view, void *stream);
 int splat_tsdf_triangles(const SplatTsdfVolume *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
+int splat_tsdf_cubes(const SplatTsdfVolume *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
+int splat_tsdf_cubes_table(int8_t *out /* [256][16] */);
 int splat_tsdf_vertices(const SplatTsdfVolume *volume, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream);
 
 /* The mesh layer on a SPARSE volume (csrc/tsdf_sparse.hip; added within ABI 17): the same virtual grid, of which only BRICKS near
@@ -913,6 +925,7 @@ int splat_tsdf_vertices(const SplatTsdfVolume *volume, const int64_t *keys, int6
  * every allocated brick: a brick allocated before the first view and given every view holds the dense volume's bits.
  * splat_tsdf_sparse_triangles / _vertices: splat_tsdf_triangles / _vertices with the same keys (they name edges of the virtual grid);
  * a cell belongs to the brick of its corner 0 and emits nothing when a brick of one of its corners is not allocated.
+ * splat_tsdf_sparse_cubes: splat_tsdf_cubes on the sparse volume, with splat_tsdf_sparse_triangles' arguments and cell rule.
  *
  * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for what splat_tsdf_* refuse, a brick shape that
  * is not listed, slots < 0, 2^31 bricks or more, and NULL pointers where they are used. */
@@ -932,6 +945,7 @@ int splat_tsdf_sparse_mark(const SplatTsdfSparse *volume, const SplatTsdfView *v
 int splat_tsdf_sparse_reset_slots(const SplatTsdfSparse *volume, int64_t first, int64_t count, void *stream);
 int splat_tsdf_sparse_integrate(const SplatTsdfSparse *volume, const SplatTsdfView *view, void *stream);
 int splat_tsdf_sparse_triangles(const SplatTsdfSparse *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
+int splat_tsdf_sparse_cubes(const SplatTsdfSparse *volume, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream);
 int splat_tsdf_sparse_vertices(const SplatTsdfSparse *volume, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream);
 
 /* The mesh score layer (csrc/meshscore.hip, arithmetic in csrc/meshscore_math.h; added within ABI 17): points sampled uniformly by area

@@ -232,6 +232,7 @@ EXPORTS = (
     "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
     "splat_tsdf_sparse_brick_shape", "splat_tsdf_sparse_bytes", "splat_tsdf_sparse_mark", "splat_tsdf_sparse_reset_slots",
     "splat_tsdf_sparse_integrate", "splat_tsdf_sparse_triangles", "splat_tsdf_sparse_vertices",
+    "splat_tsdf_cubes", "splat_tsdf_sparse_cubes", "splat_tsdf_cubes_table",
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
     "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
     "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
@@ -364,6 +365,10 @@ def lib():
     L.splat_tsdf_integrate.argtypes = [vol, C.POINTER(SplatTsdfView), _fp]
     L.splat_tsdf_triangles.restype = C.c_int
     L.splat_tsdf_triangles.argtypes = [vol, C.c_float, _fp, C.c_int64, _fp, _fp]
+    L.splat_tsdf_cubes.restype = C.c_int
+    L.splat_tsdf_cubes.argtypes = [vol, C.c_float, _fp, C.c_int64, _fp, _fp]
+    L.splat_tsdf_cubes_table.restype = C.c_int
+    L.splat_tsdf_cubes_table.argtypes = [_fp]
     L.splat_tsdf_vertices.restype = C.c_int
     L.splat_tsdf_vertices.argtypes = [vol, _fp, C.c_int64, _fp, _fp, _fp]
     sparse = C.POINTER(SplatTsdfSparse)
@@ -375,6 +380,7 @@ def lib():
                        ("splat_tsdf_sparse_reset_slots", [sparse, C.c_int64, C.c_int64, _fp]),
                        ("splat_tsdf_sparse_integrate", [sparse, C.POINTER(SplatTsdfView), _fp]),
                        ("splat_tsdf_sparse_triangles", [sparse, C.c_float, _fp, C.c_int64, _fp, _fp]),
+                       ("splat_tsdf_sparse_cubes", [sparse, C.c_float, _fp, C.c_int64, _fp, _fp]),
                        ("splat_tsdf_sparse_vertices", [sparse, _fp, C.c_int64, _fp, _fp, _fp])):
         getattr(L, name).restype = C.c_int
         getattr(L, name).argtypes = args

@@ -3,6 +3,7 @@
 
 #include "splat_device.h"
 #include "lpips_math.h"
+#include "tsdf_math.h"
 
 using namespace splat;
 
@@ -451,7 +452,18 @@ int splat_tsdf_integrate(const SplatTsdfVolume *v, const SplatTsdfView *w, void 
 
 int splat_tsdf_triangles(const SplatTsdfVolume *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
     if (!valid_tsdf_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
-    return check(launch_tsdf_triangles(*v, min_weight, keys, (long long)capacity, count, (hipStream_t)stream));
+    return check(launch_tsdf_triangles(*v, min_weight, keys, (long long)capacity, count, false, (hipStream_t)stream));
+}
+
+int splat_tsdf_cubes(const SplatTsdfVolume *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
+    if (!valid_tsdf_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    return check(launch_tsdf_triangles(*v, min_weight, keys, (long long)capacity, count, true, (hipStream_t)stream));
+}
+
+int splat_tsdf_cubes_table(int8_t *out) {
+    if (!out) return SPLAT_E_INVALID;
+    memcpy(out, kTsdfCubesCases, sizeof(kTsdfCubesCases));
+    return SPLAT_OK;
 }
 
 int splat_tsdf_vertices(const SplatTsdfVolume *v, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream) {
@@ -509,7 +521,12 @@ int splat_tsdf_sparse_integrate(const SplatTsdfSparse *v, const SplatTsdfView *w
 
 int splat_tsdf_sparse_triangles(const SplatTsdfSparse *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
     if (!valid_sparse_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
-    return check(launch_tsdf_sparse_triangles(*v, min_weight, keys, (long long)capacity, count, (hipStream_t)stream));
+    return check(launch_tsdf_sparse_triangles(*v, min_weight, keys, (long long)capacity, count, false, (hipStream_t)stream));
+}
+
+int splat_tsdf_sparse_cubes(const SplatTsdfSparse *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
+    if (!valid_sparse_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    return check(launch_tsdf_sparse_triangles(*v, min_weight, keys, (long long)capacity, count, true, (hipStream_t)stream));
 }
 
 int splat_tsdf_sparse_vertices(const SplatTsdfSparse *v, const int64_t *keys, int64_t n, float *vertices, float *colors, void *stream) {

@@ -105,13 +105,16 @@ hipError_t launch_view_finish(const SplatViewArgs &v, hipStream_t s);
 // tsdf.hip: rendered depth fused into a truncated signed distance volume, and the volume's zero surface as vertex keys and vertices
 hipError_t launch_tsdf_reset(const SplatTsdfVolume &v, hipStream_t s);
 hipError_t launch_tsdf_integrate(const SplatTsdfVolume &v, const SplatTsdfView &w, hipStream_t s);
-hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, hipStream_t s);
+// (cubes: marching cubes instead of marching tetrahedra; the same contract)
+hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, bool cubes,
+                                 hipStream_t s);
 hipError_t launch_tsdf_vertices(const SplatTsdfVolume &v, const int64_t *keys, long long n, float *vertices, float *colors, hipStream_t s);
 // tsdf_sparse.hip: the same on a volume that stores only the bricks near observed surfaces
 hipError_t launch_tsdf_sparse_mark(const SplatTsdfSparse &v, const SplatTsdfView &w, int32_t *flags, hipStream_t s);
 hipError_t launch_tsdf_sparse_reset_slots(const SplatTsdfSparse &v, long long first, long long count, hipStream_t s);
 hipError_t launch_tsdf_sparse_integrate(const SplatTsdfSparse &v, const SplatTsdfView &w, hipStream_t s);
-hipError_t launch_tsdf_sparse_triangles(const SplatTsdfSparse &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, hipStream_t s);
+hipError_t launch_tsdf_sparse_triangles(const SplatTsdfSparse &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, bool cubes,
+                                        hipStream_t s);
 hipError_t launch_tsdf_sparse_vertices(const SplatTsdfSparse &v, const int64_t *keys, long long n, float *vertices, float *colors, hipStream_t s);
 // meshscore.hip: points sampled by area on a triangle mesh, and exact nearest neighbours through a uniform grid
 hipError_t launch_mesh_areas(const float *vertices, int32_t V, const int32_t *faces, int32_t F, double *area, hipStream_t s);

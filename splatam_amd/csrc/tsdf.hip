@@ -16,6 +16,9 @@
 //                                0..12 triangles as three keys each.  A wave reserves the slots of all its lanes with ONE returning atomic (prefix sum over the
 //                                lanes' counts, the last lane adds the total, every lane reads the base): the group-binning
 //                                reservation's idiom.  count[0] gets what is wanted; nothing is written at or beyond `capacity`.
+//      tsdf_triangles_kernel<true>   the same pass by marching cubes (tsdf_math.h "SURFACE, cubes"): the same mask, the same seen rule, the
+//                                same reservation; 0..5 triangles from the lane's 16-byte row of the case table, held in four
+//                                registers, the five slots unrolled and predicated on the count (no loop over a lane's own bound).
 //   T3 tsdf_vertices_kernel      one lane per unique key: position and colour.
 #include "splat_device.h"
 #include "tsdf_math.h"
@@ -185,6 +188,7 @@ struct TrianglesArgs {
     long long blocks;
 };
 
+template <bool kCubes>
 __global__ void __launch_bounds__(kBlock) tsdf_triangles_kernel(TrianglesArgs a) {
     const TsdfGrid &g = a.grid;
     const int lane = threadIdx.x & (kWave - 1);
@@ -204,7 +208,9 @@ __global__ void __launch_bounds__(kBlock) tsdf_triangles_kernel(TrianglesArgs a)
                 if (!seen) mask = 0;
             }
         }
-        const unsigned n = (unsigned)tsdf_cell_triangles(mask);
+        TsdfCubesRow cubes;                                                     // (row 0 of the table is empty: an idle lane's)
+        if constexpr (kCubes) cubes = tsdf_cubes_row(mask);
+        const unsigned n = kCubes ? (unsigned)tsdf_cubes_row_entry(cubes, 0) : (unsigned)tsdf_cell_triangles(mask);
         if (__builtin_amdgcn_ballot_w64(n != 0) == 0ull) continue;              // (wave-uniform)
         const unsigned incl = wave_scan_incl_u32(n);
         unsigned long long base = 0;
@@ -213,6 +219,10 @@ __global__ void __launch_bounds__(kBlock) tsdf_triangles_kernel(TrianglesArgs a)
                | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)base, kWave - 1);
         if (n == 0) continue;
         unsigned long long slot = base + (incl - n);
+        if constexpr (kCubes) {
+            tsdf_cubes_store(g, i, j, k, cubes, slot, (unsigned long long)a.capacity, a.keys);
+            continue;
+        }
 #pragma unroll 1
         for (int q = 0; q < 6; ++q) {
             const int8_t *row = kTsdfTetCases[tsdf_tet_mask(mask, q)];
@@ -273,7 +283,8 @@ hipError_t launch_tsdf_integrate(const SplatTsdfVolume &v, const SplatTsdfView &
     return hipGetLastError();
 }
 
-hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, hipStream_t s) {
+hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, bool cubes,
+                                 hipStream_t s) {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), s);
     if (e != hipSuccess) return e;
     if (v.nx < 2 || v.ny < 2 || v.nz < 2) return hipSuccess;        // no cell
@@ -283,7 +294,8 @@ hipError_t launch_tsdf_triangles(const SplatTsdfVolume &v, float min_weight, int
     a.keys = keys; a.capacity = capacity; a.count = reinterpret_cast<unsigned long long *>(count);
     a.bx = (v.nx - 1 + 63) / 64; a.by = (v.ny - 1 + 3) / 4;
     a.blocks = (long long)a.bx * a.by * (v.nz - 1);
-    hipLaunchKernelGGL(tsdf_triangles_kernel, dim3(grid_for(a.blocks)), dim3(kBlock), 0, s, a);
+    if (cubes) hipLaunchKernelGGL(tsdf_triangles_kernel<true>, dim3(grid_for(a.blocks)), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL(tsdf_triangles_kernel<false>, dim3(grid_for(a.blocks)), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -21,6 +21,25 @@
 //            at corners that are exactly zero; the zero-area triangles such corners give are kept (dropping them opens the mesh).
 //            Two corners inside, two outside: the quadrilateral (ac, ad, bd, bc) of inside a < b and outside c < d (positions along
 //            the path) is split along ac - bd.
+//   SURFACE, cubes   the second extractor: marching cubes, vertices on the twelve AXIS edges of a cell only (keys with dir in {1, 2, 4},
+//            the same keys, positions and colours the tetrahedra give there), at most 5 triangles per cell.  The case table
+//            (tsdf_cubes_table.h) follows from a rule that reads sign patterns alone.  Edge e = 0..11 is (c, c | 1 << a), axis-major
+//            (a = 0, 1, 2), c ascending within an axis.  Take each face of the cell with its four corners counter-clockwise seen from
+//            OUTSIDE the cell and walk that cycle: every maximal run of inside corners gives one directed SEGMENT, from the crossing
+//            where the walk enters the run to the crossing where it leaves.  A face with two crossings has one segment; a face whose
+//            inside corners are diagonal has two -- each inside corner is cut off on its own and the outside connects through the
+//            face: the one disambiguation, used everywhere.  Every crossed edge then has one outgoing and one incoming segment, so
+//            the segments chain into closed loops; a loop starts at its lowest edge, loops go by ascending start, and each is
+//            fan-triangulated from its start: (l0, li, li+1).  One corner inside: the loop x -> y -> z edge of that corner, normal
+//            away from it -- towards positive tsdf, like the tetrahedra.
+//            CLOSED: the segments on a face depend on that face's four signs only.  The neighbouring cell sees the same four signs on
+//            the same four grid points, walks them the other way round (its outside is this cell's inside of the face) and so puts
+//            the same segments there, reversed; inside a cell a fan's diagonals occur once in each direction.  Every directed edge
+//            of the mesh is therefore matched by its reverse wherever both cells are seen.
+//            NOT here: the asymptotic decider and interior ambiguity tests (MC33), parity with any library's table, dual contouring.
+//            KNOWN: a fan diagonal can join two crossings that lie on one ambiguous face, and the neighbour's fan can join the same
+//            two; on adversarial sign noise a few edges are then shared by four triangles (still a closed oriented cycle: each
+//            direction as often as its reverse).  Smooth surfaces do not do this.
 //
 // Every float32 step is an operation of its own (tsdf_add / _sub / _mul / _div: operators the device compiler may not contract, plain
 // operators under -ffp-contract=off on the host), so a decision does not depend on what a compiler contracts.
@@ -213,6 +232,58 @@ SPLAT_HD int tsdf_cell_emit(const TsdfGrid &g, int i, int j, int k, int cell_mas
     for (int q = 0; q < 6; ++q) {
         const int8_t *row = kTsdfTetCases[tsdf_tet_mask(cell_mask, q)];
         for (int t = 0; t < row[0]; ++t, ++n) tsdf_tet_triangle(g, i, j, k, q, row, t, out + 3 * n);
+    }
+    return n;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- surface, cubes
+#include "tsdf_cubes_table.h"
+
+// triangles a cell's sign pattern asks for (0..5)
+SPLAT_HD int tsdf_cubes_triangles(int cell_mask) { return kTsdfCubesCases[cell_mask][0]; }
+// lower corner of edge e = 4 a + n: n with a zero bit inserted at position a (the upper corner is that | 1 << a)
+SPLAT_HD int tsdf_cubes_edge_corner(int e) {
+    const int a = e >> 2, n = e & 3, low = (1 << a) - 1;
+    return (n & low) | ((n & ~low) << 1);
+}
+// key of the vertex on edge e of cell (i, j, k): an ordinary edge key with dir = 1 << axis
+SPLAT_HD int64_t tsdf_cubes_edge_key(const TsdfGrid &g, int i, int j, int k, int e) {
+    const int c = tsdf_cubes_edge_corner(e);
+    return tsdf_edge_key(g, i, j, k, c, c | (1 << (e >> 2)));
+}
+// triangle t of cell (i, j, k) under the table's row `row` (of the cell's mask): its three keys, wound
+SPLAT_HD void tsdf_cubes_triangle(const TsdfGrid &g, int i, int j, int k, const int8_t *row, int t, int64_t *key) {
+    for (int e = 0; e < 3; ++e) key[e] = tsdf_cubes_edge_key(g, i, j, k, row[1 + 3 * t + e]);
+}
+// the triangles of cell (i, j, k) with sign pattern cell_mask, three keys each, to out[3 n]; returns n (the host model's loop)
+SPLAT_HD int tsdf_cubes_emit(const TsdfGrid &g, int i, int j, int k, int cell_mask, int64_t *out) {
+    const int8_t *row = kTsdfCubesCases[cell_mask];
+    for (int t = 0; t < row[0]; ++t) tsdf_cubes_triangle(g, i, j, k, row, t, out + 3 * t);
+    return row[0];
+}
+
+// A row as the kernels hold it: four registers, fetched with one 16-byte load (each lane its own row: the table is 4 KiB and stays in
+// the vector cache), entries picked out by shifts at compile-time positions -- the triangle loop is unrolled over the row's five slots
+// and predicated on the count, so no lane indexes memory by a value it computed and the wave does not loop to its longest row.
+struct TsdfCubesRow {
+    uint32_t w[4];
+};
+SPLAT_HD TsdfCubesRow tsdf_cubes_row(int cell_mask) {
+    TsdfCubesRow r;
+    __builtin_memcpy(r.w, kTsdfCubesCases[cell_mask], 16);
+    return r;
+}
+SPLAT_HD int tsdf_cubes_row_entry(const TsdfCubesRow &r, int n) { return (int)((r.w[n >> 2] >> (8 * (n & 3))) & 0xffu); }
+// the row's triangles into keys[3 slot ...], those at or beyond `capacity` left out; returns their number
+SPLAT_HD int tsdf_cubes_store(const TsdfGrid &g, int i, int j, int k, const TsdfCubesRow &r, unsigned long long slot, unsigned long long capacity,
+                              int64_t *keys) {
+    const int n = tsdf_cubes_row_entry(r, 0);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int t = 0; t < 5; ++t) {
+        if (t >= n || slot + t >= capacity) continue;
+        for (int e = 0; e < 3; ++e) keys[3 * (slot + t) + e] = tsdf_cubes_edge_key(g, i, j, k, tsdf_cubes_row_entry(r, 1 + 3 * t + e));
     }
     return n;
 }

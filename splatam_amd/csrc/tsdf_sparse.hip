@@ -16,6 +16,8 @@
 //                                    in the +x, +y, +z neighbour bricks come through the directory (the eight slots a brick's cells
 //                                    can touch are looked up once per workgroup), a missing neighbour makes the cell unseen.  T2's
 //                                    reservation: scan, one returning atomic by the last lane, readlane.
+//      tsdf_sparse_triangles_kernel<true>  the same pass by marching cubes, as T2's (tsdf.hip): the lane's row of the case table in four
+//                                    registers, its five slots unrolled and predicated.
 //   S4 tsdf_sparse_vertices_kernel   one lane per unique key, the edge's two grid points through the directory.
 #include "splat_device.h"
 #include "tsdf_math.h"
@@ -196,6 +198,7 @@ struct SparseTrianglesArgs {
     unsigned long long *count;
 };
 
+template <bool kCubes>
 __global__ void __launch_bounds__(kBlock) tsdf_sparse_triangles_kernel(SparseTrianglesArgs a) {
     __shared__ int nb[8];                                           // slots of the brick and its +x, +y, +z neighbours (dx + 2 dy + 4 dz), -1 = none
     const TsdfGrid &g = a.grid;
@@ -244,7 +247,9 @@ __global__ void __launch_bounds__(kBlock) tsdf_sparse_triangles_kernel(SparseTri
                     }
                 }
             }
-            const unsigned n = (unsigned)tsdf_cell_triangles(mask);
+            TsdfCubesRow cubes;                                                 // (row 0 of the table is empty: an idle lane's)
+            if constexpr (kCubes) cubes = tsdf_cubes_row(mask);
+            const unsigned n = kCubes ? (unsigned)tsdf_cubes_row_entry(cubes, 0) : (unsigned)tsdf_cell_triangles(mask);
             if (__builtin_amdgcn_ballot_w64(n != 0) == 0ull) continue;          // (wave-uniform)
             const unsigned incl = wave_scan_incl_u32(n);
             unsigned long long base = 0;
@@ -253,6 +258,10 @@ __global__ void __launch_bounds__(kBlock) tsdf_sparse_triangles_kernel(SparseTri
                    | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)base, kWave - 1);
             if (n == 0) continue;
             unsigned long long out = base + (incl - n);
+            if constexpr (kCubes) {
+                tsdf_cubes_store(g, i, j, k, cubes, out, (unsigned long long)a.capacity, a.keys);
+                continue;
+            }
 #pragma unroll 1
             for (int q = 0; q < 6; ++q) {
                 const int8_t *row = kTsdfTetCases[tsdf_tet_mask(mask, q)];
@@ -342,7 +351,8 @@ hipError_t launch_tsdf_sparse_integrate(const SplatTsdfSparse &v, const SplatTsd
     return hipGetLastError();
 }
 
-hipError_t launch_tsdf_sparse_triangles(const SplatTsdfSparse &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, hipStream_t s) {
+hipError_t launch_tsdf_sparse_triangles(const SplatTsdfSparse &v, float min_weight, int64_t *keys, long long capacity, int64_t *count, bool cubes,
+                                        hipStream_t s) {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), s);
     if (e != hipSuccess) return e;
     if (v.nx < 2 || v.ny < 2 || v.nz < 2 || v.slots == 0) return hipSuccess;       // no cell
@@ -352,7 +362,8 @@ hipError_t launch_tsdf_sparse_triangles(const SplatTsdfSparse &v, float min_weig
     a.vol = arrays_of(v);
     a.min_weight = min_weight;
     a.keys = keys; a.capacity = capacity; a.count = reinterpret_cast<unsigned long long *>(count);
-    hipLaunchKernelGGL(tsdf_sparse_triangles_kernel, dim3(grid_for(v.slots)), dim3(kBlock), 0, s, a);
+    if (cubes) hipLaunchKernelGGL(tsdf_sparse_triangles_kernel<true>, dim3(grid_for(v.slots)), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL(tsdf_sparse_triangles_kernel<false>, dim3(grid_for(v.slots)), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

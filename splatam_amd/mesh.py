@@ -1,5 +1,5 @@
 """A triangle mesh of the map: ``python -m splatam_amd.mesh PARAMS.npz --out mesh.ply [--voxel M] [--trunc M] [--every N] [--size WxH]
-[--sil-thres S] [--depth-max M] [--bounds X0 Y0 Z0 X1 Y1 Z1] [--sparse] [--clean [--min-vertices N] [--min-area M2] [--keep-largest K]]``.
+[--sil-thres S] [--depth-max M] [--bounds X0 Y0 Z0 X1 Y1 Z1] [--sparse] [--method {tetrahedra,cubes}] [--clean [--min-vertices N] [--min-area M2] [--keep-largest K]]``.
 
 Depth rendered at the estimated poses is fused into a truncated signed distance volume and the volume's zero surface is extracted,
 all on the device (csrc/tsdf.hip, arithmetic in csrc/tsdf_math.h): the usual deliverable of a dense RGB-D SLAM system, and what the
@@ -9,7 +9,11 @@ methods SplaTAM is compared with are scored on.  ``FusedEngine.render_view(..., 
 The surface is marching tetrahedra on Kuhn's split of every cell (six tetrahedra, translation invariant, so neighbouring cells agree
 on their shared faces and the mesh is closed wherever the volume was seen); vertices are named by the grid edge they lie on, so
 welding is a ``torch.unique`` over integer keys and the result is canonical: vertices sorted by key, faces lexicographically -- the
-same volume always gives the same bytes.
+same volume always gives the same bytes.  ``--method cubes`` (``method="cubes"``) extracts the same surface by marching cubes
+instead: vertices on the grid's axis edges only -- the tetrahedra's own vertices there, bit for bit --, at most 5 triangles a cell
+against 12, a third of the triangles and a third to a half of the vertices, closed by the same kind of argument (csrc/tsdf_math.h "SURFACE, cubes": one
+rule on every face's four signs, which the neighbouring cell reads reversed).  No asymptotic decider (MC33), no parity with another
+library's table, no dual contouring.
 
 The dense ``TsdfVolume`` holds five floats for every grid point of the box and is refused beyond ``max_bytes``; ``--sparse``
 (``SparseTsdfVolume``, csrc/tsdf_sparse.hip) stores only the bricks of 2048 grid points within the truncation band of a surface some
@@ -77,25 +81,47 @@ def plan_volume(bounds, voxel_size, max_bytes=DEFAULT_MAX_BYTES, sparse=False):
     return lo, dims
 
 
+METHODS = ("tetrahedra", "cubes")
+
+
+def check_method(method):
+    """``method`` if it names a surface extractor; ValueError otherwise."""
+    if method not in METHODS:
+        raise ValueError(f"unknown surface method {method!r}: one of {', '.join(METHODS)}")
+    return method
+
+
+def cubes_table():
+    """The library's marching-cubes case table, [256, 16] int8 (include/splat_hip.h splat_tsdf_cubes_table)."""
+    table = np.zeros((256, 16), dtype=np.int8)
+    _capi.check(_capi.lib().splat_tsdf_cubes_table(table.ctypes.data), "splat_tsdf_cubes_table")
+    return table
+
+
 class _Surface:
-    """``extract`` of a volume class that has ``_triangles(min_weight, keys, count)``, ``_vertices(uniq, vertices, colors)`` and
+    """``extract`` of a volume class that has ``_triangles(min_weight, keys, count, method)``, ``_vertices(uniq, vertices, colors)`` and
     ``_default_capacity()``."""
 
-    def extract(self, min_weight=1.0, capacity=None):
+    def extract(self, min_weight=1.0, capacity=None, method="tetrahedra"):
         """The zero surface over the cells whose eight corners have ``weight >= min_weight`` as a ``Mesh`` on the device.  One pass over
         the cells into ``capacity`` triangle slots (default: a guess from the grid's size), ONE host read of the count, a second pass
         at the reported size if they did not fit; vertices welded by ``torch.unique`` over their keys, positions and colours by one
-        launch.  Canonical: vertices sorted by key, faces lexicographically."""
+        launch.  Canonical: vertices sorted by key, faces lexicographically.
+
+        ``method``: ``"tetrahedra"`` (marching tetrahedra on Kuhn's split: up to 12 triangles a cell, vertices on face and body
+        diagonals too) or ``"cubes"`` (marching cubes: at most 5 triangles a cell, vertices on axis edges only -- the subset of the
+        tetrahedra's vertices on those edges, bit for bit -- about a third of the triangles).  Anything else: ValueError."""
+        check_method(method)
         if capacity is None:
             capacity = self._default_capacity()
         capacity = max(int(capacity), 0)
         count = torch.zeros(1, dtype=torch.int64, device=self.dev)
         keys = torch.empty(capacity, 3, dtype=torch.int64, device=self.dev) if capacity else None
-        self._triangles(min_weight, keys, count)
+        self._triangles(min_weight, keys, count, method)
         n = int(count.item())
         if n > capacity:
             keys = torch.empty(n, 3, dtype=torch.int64, device=self.dev)
-            self._triangles(min_weight, keys, count)
+            self._triangles(min_weight, keys, count, method)
         self.last_triangle_count = n
         if n == 0:
             z = torch.zeros(0, 3, dtype=torch.float32, device=self.dev)
@@ -195,11 +221,12 @@ class TsdfVolume(_Surface):
         self.integrate(img.out6, view.w2c, intrinsics, skip=img.truncated, **kw)
         return img
 
-    def _triangles(self, min_weight, keys, count):
+    def _triangles(self, min_weight, keys, count, method="tetrahedra"):
         cap = 0 if keys is None else int(keys.shape[0])
+        name = "splat_tsdf_cubes" if method == "cubes" else "splat_tsdf_triangles"
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_triangles(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
-                                                    count.data_ptr(), self._stream()), "splat_tsdf_triangles")
+            _capi.check(getattr(self.L, name)(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
+                                              count.data_ptr(), self._stream()), name)
 
     def _default_capacity(self):                            # a closed surface crosses O(n^2) of n^3 cells, ~4 triangles each
         nx, ny, nz = self.dims
@@ -372,11 +399,12 @@ class SparseTsdfVolume(_Surface):
 
     integrate_view = TsdfVolume.integrate_view
 
-    def _triangles(self, min_weight, keys, count):
+    def _triangles(self, min_weight, keys, count, method="tetrahedra"):
         cap = 0 if keys is None else int(keys.shape[0])
+        name = "splat_tsdf_sparse_cubes" if method == "cubes" else "splat_tsdf_sparse_triangles"
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_sparse_triangles(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
-                                                           count.data_ptr(), self._stream()), "splat_tsdf_sparse_triangles")
+            _capi.check(getattr(self.L, name)(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
+                                              count.data_ptr(), self._stream()), name)
 
     def _default_capacity(self):                            # the band is several bricks thick and the surface crosses some of them
         return 768 * self.slots + 4096
@@ -451,7 +479,7 @@ def _views_pass(frames, run, skipped, view, extra=None):
 
 
 def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, bounds=None, max_bytes=DEFAULT_MAX_BYTES, sil_thres=0.99,
-                 depth_max=0.0, weight_max=0.0, min_weight=1.0, first_w2c=None, view=None, return_volume=False, sparse=False, clean=None):
+                 depth_max=0.0, weight_max=0.0, min_weight=1.0, first_w2c=None, view=None, return_volume=False, sparse=False, method="tetrahedra", clean=None):
     """A ``Mesh`` of ``engine``'s map from renders at ``frames``: each a time index of the map (seen through ``first_w2c``, default the
     identity) or a float32 [4, 4] ``w2c`` on the device.  ``size`` = (width, height) of the renders, ``intrinsics`` theirs (host).
     ``bounds`` = ((x0, y0, z0), (x1, y1, z1)); default ``default_bounds`` of the map padded by ``trunc + voxel_size`` (one host read).
@@ -467,9 +495,14 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
     frames: render + ``mark`` (one read: the table, with the number of bricks marked), ``allocate``, then render + ``integrate`` as
     above.  A render costs less than the dense volume's integration of it.
 
+    ``method``: the surface extractor, ``"tetrahedra"`` (default) or ``"cubes"`` (``_Surface.extract``): marching cubes gives a third
+    of the triangles and a third to a half of the vertices of the same surface, which everything downstream -- scoring, culling, alignment, cleaning,
+    the PLY -- then carries.  Dense and sparse volumes alike; an unknown name is a ValueError before anything is launched.
+
     ``clean`` (True, or a dict of ``mesh_clean.clean_mesh`` keywords): the mesh is ``clean_mesh`` of what was extracted -- its small
     connected components are removed on the device, with one more host read.  ``None``: the mesh as extracted."""
     from .mesh_clean import clean_options
+    check_method(method)
     clean = clean_options(clean)
     trunc = 4.0 * float(voxel_size) if trunc is None else float(trunc)
     if bounds is None:
@@ -492,7 +525,7 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
                                                    extra=volume.marked_count_tensor)
         volume.allocate(max_bytes, count=None if volume.repeated_marks else count)      # (views marked again: the count is read again)
     volume.repeated, _ = _views_pass(frames, lambda fr: volume.integrate_view(engine, view, **pose(fr), **kw), volume.skipped, view)
-    mesh = volume.extract(min_weight)
+    mesh = volume.extract(min_weight, method=method)
     if clean is not None:
         from .mesh_clean import clean_mesh
         mesh = clean_mesh(mesh, device=engine.dev, **clean)
@@ -500,14 +533,15 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
 
 
 def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None, sil_thres=0.99, depth_max=0.0, bounds=None,
-                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False, clean=None, cleaning=None):
-    """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``.  ``clean`` (True or a dict of
+                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False, clean=None, cleaning=None, method="tetrahedra"):
+    """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``.  ``method``: ``extract_mesh``'s.  ``clean`` (True or a dict of
     ``mesh_clean.clean_mesh`` keywords): the mesh is cleaned before it is written; ``cleaning``, a dict, then receives the report."""
     from . import slam
     from .export import save_mesh_ply
     from .fused import FusedEngine
     from .mesh_clean import clean_mesh, clean_options, format_cleaning
     from .view import load_map
+    check_method(method)
     clean = clean_options(clean)
     dev = torch.device(device)
     params, variables, k, first_w2c, (W0, H0) = load_map(path, dev)
@@ -519,7 +553,7 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
         engine = FusedEngine(params, cam, variables=variables)
         frames = keyframes or list(range(0, engine.num_frames, max(int(every), 1)))
         mesh = extract_mesh(engine, frames, (W, H), _scaled_intrinsics(k, (W, H), (W0, H0)), voxel_size=voxel_size, trunc=trunc, bounds=bounds,
-                            max_bytes=max_bytes, sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse)
+                            max_bytes=max_bytes, sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse, method=method)
         if clean is not None:
             mesh, found = clean_mesh(mesh, device=dev, report=True, **clean)
             if cleaning is not None:
@@ -532,7 +566,7 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
     return mesh
 
 
-def main(argv=None):
+def _parser():
     from .view import _size
     parser = argparse.ArgumentParser(prog="python -m splatam_amd.mesh", description=__doc__.split("\n\n")[0])
     parser.add_argument("params", help="params.npz of a run")
@@ -547,11 +581,18 @@ def main(argv=None):
                         help="the volume's box in metres (default: the opaque Gaussians' box)")
     parser.add_argument("--max-bytes", type=int, default=DEFAULT_MAX_BYTES)
     parser.add_argument("--sparse", action="store_true", help="a sparse volume: the same mesh, memory only near surfaces (for boxes a dense volume cannot hold)")
+    parser.add_argument("--method", choices=METHODS, default="tetrahedra",
+                        help="the surface extractor: marching tetrahedra, or marching cubes (about a third of the triangles)")
     parser.add_argument("--clean", action="store_true", help="remove the mesh's small connected components before it is written")
     parser.add_argument("--min-vertices", type=int, default=None, metavar="N", help="with --clean: components with fewer vertices go (200)")
     parser.add_argument("--min-area", type=float, default=None, metavar="M2", help="with --clean: components with less area in m^2 go (0)")
     parser.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --clean: keep at most the K components with the most faces")
     parser.add_argument("--device", default="cuda:0")
+    return parser
+
+
+def main(argv=None):
+    parser = _parser()
     args = parser.parse_args(argv)
     options = {k: v for k, v in (("min_vertices", args.min_vertices), ("min_area", args.min_area), ("keep_largest", args.keep_largest)) if v is not None}
     if options and not args.clean:
@@ -560,7 +601,7 @@ def main(argv=None):
     try:
         mesh_from_params(args.params, args.out, voxel_size=args.voxel, trunc=args.trunc, every=args.every, size=args.size,
                          sil_thres=args.sil_thres, depth_max=args.depth_max, bounds=bounds, max_bytes=args.max_bytes, device=args.device,
-                         sparse=args.sparse, **({"clean": options or True} if args.clean else {}))
+                         sparse=args.sparse, method=args.method, **({"clean": options or True} if args.clean else {}))
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return 0

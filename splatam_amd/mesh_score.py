@@ -29,7 +29,7 @@ Floaters: ``--clean`` (``score_with_views(..., clean=True)`` or a dict of ``mesh
 components of the RECONSTRUCTION alone (csrc/meshclean.hip) -- after ``--transform``, before the culling, the ICP and the samples -- and
 prints a ``Cleaning:`` line ahead of ``Alignment:``; the score gains ``cleaning``.  Off unless asked for.
 
-Not here: marching cubes; point-to-plane or coloured ICP, scale, a global registration in front of the ICP.
+Not here: point-to-plane or coloured ICP, scale, a global registration in front of the ICP.
 """
 from __future__ import annotations
 

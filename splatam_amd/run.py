@@ -93,7 +93,8 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     both meshes are first culled to the frusta of the dataset's poses in the MAP's frame, where those poses live, the inverse of
     ``gt_transform`` bringing the ground truth there (``mesh_score.score_culled_in_map_frame``).  ``align`` (with ``gt_mesh``; True or a
     dict of ``mesh_score.align_icp`` keywords): the reconstruction is registered to the ground truth by ICP before it is measured, and
-    ``stats['mesh_score']['alignment']`` records what was found.  ``mesh=dict(clean=True)`` (or ``clean=`` a dict of
+    ``stats['mesh_score']['alignment']`` records what was found.  ``mesh=dict(method="cubes")``: the mesh is extracted by marching
+    cubes instead of marching tetrahedra (``mesh.extract_mesh``).  ``mesh=dict(clean=True)`` (or ``clean=`` a dict of
     ``mesh_clean.clean_mesh`` keywords): the mesh's small connected components are removed before it is written and scored;
     ``stats['mesh_cleaning']`` is the report, and with ``gt_mesh`` it is ``stats['mesh_score']['cleaning']`` too."""
     from . import datasets, pipeline
@@ -170,7 +171,7 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     return params, variables, stats, path
 
 
-def main(argv=None):
+def _parser():
     parser = argparse.ArgumentParser(prog="python -m splatam_amd.run", description=__doc__.split("\n\n")[0])
     parser.add_argument("experiment", help="path to a SplaTAM experiment file (a Python file that defines `config`)")
     parser.add_argument("--engine", default="fused", choices=("fused", "dropin", "plugin", "plugin_map_edits"))
@@ -186,6 +187,8 @@ def main(argv=None):
     parser.add_argument("--mesh", action="store_true", help="write mesh.ply next to params.npz (python -m splatam_amd.mesh on the saved map)")
     parser.add_argument("--mesh-sparse", action="store_true",
                         help="with --mesh: fuse into a sparse volume (python -m splatam_amd.mesh --sparse): the same mesh, memory only near surfaces")
+    parser.add_argument("--mesh-method", choices=("tetrahedra", "cubes"), default=None,
+                        help="with --mesh: the surface extractor (python -m splatam_amd.mesh --method); cubes: about a third of the triangles")
     parser.add_argument("--clean-mesh", action="store_true",
                         help="with --mesh: remove the mesh's small connected components before it is written and scored (splatam_amd.mesh_clean)")
     parser.add_argument("--gt-mesh", default=None, metavar="GT.ply",
@@ -197,6 +200,11 @@ def main(argv=None):
                         help="with --gt-mesh: cull both meshes to the frusta of the dataset's poses before scoring (splatam_amd.mesh_render)")
     parser.add_argument("--align", action="store_true",
                         help="with --gt-mesh: register the mesh to the ground truth by point-to-point ICP before scoring")
+    return parser
+
+
+def main(argv=None):
+    parser = _parser()
     args = parser.parse_args(argv)
     if args.align and not args.gt_mesh:
         parser.error("--align needs --gt-mesh")
@@ -208,9 +216,12 @@ def main(argv=None):
         parser.error("--cull needs --gt-mesh")
     if args.clean_mesh and not args.mesh:
         parser.error("--clean-mesh needs --mesh")
+    if args.mesh_method and not args.mesh:
+        parser.error("--mesh-method needs --mesh")
     mesh = args.mesh
-    if args.mesh_sparse or args.clean_mesh:
-        mesh = dict(**({"sparse": True} if args.mesh_sparse else {}), **({"clean": True} if args.clean_mesh else {}))
+    if args.mesh_sparse or args.clean_mesh or args.mesh_method:
+        mesh = dict(**({"sparse": True} if args.mesh_sparse else {}), **({"clean": True} if args.clean_mesh else {}),
+                    **({"method": args.mesh_method} if args.mesh_method else {}))
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")

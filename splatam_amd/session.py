@@ -555,19 +555,21 @@ class SlamSession:
         return self._step(time_idx, curr, tracking_curr, densify_curr, pose, owned=dev.type == "cuda")
 
     # ------------------------------------------------------------------ a mesh of the map (csrc/tsdf.hip)
-    def extract_mesh(self, frames=None, size=None, path=None, **kwargs):
+    def extract_mesh(self, frames=None, size=None, path=None, method="tetrahedra", **kwargs):
         """A triangle mesh of the map as it is now: ``mesh.extract_mesh`` at the estimated poses of ``frames`` (time indices; default
         the keyframes so far), rendered at ``size`` = (height, width) (default the loop's) with the loop's intrinsics scaled to it.
         Further keywords (``voxel_size``, ``trunc``, ``bounds``, ``max_bytes``, ``sil_thres``, ``depth_max``, ``weight_max``,
-        ``min_weight``, ``sparse``, ``clean``) go to ``mesh.extract_mesh``; ``clean=True`` (or a dict of ``mesh_clean.clean_mesh``
+        ``min_weight``, ``sparse``, ``clean``) go to ``mesh.extract_mesh``, as does ``method`` (``"tetrahedra"``, or ``"cubes"`` for
+        marching cubes: about a third of the triangles; anything else is a ValueError); ``clean=True`` (or a dict of ``mesh_clean.clean_mesh``
         keywords) removes the mesh's small connected components.  ``path``: also written there as a PLY.  Returns the ``Mesh`` (on the device).
         Between frames and after ``finish()``; engine "fused" only.  The map, the optimiser state and the loop's cameras are left
         as they were."""
+        from . import mesh as mesh_mod
+        mesh_mod.check_method(method)
         if not self.fused:
             raise NotImplementedError("extract_mesh needs engine='fused'")
         if self.engine is None:
             raise RuntimeError("extract_mesh before the first frame: there is no map")
-        from . import mesh as mesh_mod
         H, W = (self.cam.image_height, self.cam.image_width) if size is None else (int(size[0]), int(size[1]))
         k = self.intrinsics.detach().cpu().double().numpy()
         k_view = (float(k[0][0]) * W / self.cam.image_width, float(k[1][1]) * H / self.cam.image_height,
@@ -575,7 +577,7 @@ class SlamSession:
         if frames is None:
             frames = list(self.keyframe_time_indices) or list(range(self.frames_seen))
         with torch.no_grad():
-            result = mesh_mod.extract_mesh(self.engine, frames, (W, H), k_view, first_w2c=self.first_frame_w2c.contiguous(), **kwargs)
+            result = mesh_mod.extract_mesh(self.engine, frames, (W, H), k_view, first_w2c=self.first_frame_w2c.contiguous(), method=method, **kwargs)
         if path is not None:
             from .export import save_mesh_ply
             save_mesh_ply(path, result.vertices.cpu().numpy(), result.faces.cpu().numpy(), result.colors.cpu().numpy())
