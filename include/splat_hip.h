@@ -36,6 +36,7 @@ extern "C" {
                                       splat_iter_mapping_step_ex -- the mapping loss of the refinement script (get_loss_gs);
                                       SPLAT_EVAL_LPIPS, SplatLpipsWorkspace, splat_lpips_* -- LPIPS from caller-supplied AlexNet weights (csrc/lpips.hip);
                                       splat_mesh_components, splat_mesh_component_stats -- connected components of a mesh (csrc/meshclean.hip);
+                                      SplatMeshShade, SPLAT_MESH_SHADE_*, splat_mesh_vertex_normals, splat_mesh_visibility, splat_mesh_shade -- pictures of a mesh (csrc/meshshade.hip);
                                       16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
                                       15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
                                       14: frame ingest (splat_frame_ingest);
@@ -1051,6 +1052,69 @@ int splat_mesh_depth(const float *vertices, int32_t num_vertices, const int32_t 
 int splat_mesh_seen(const float *vertices, int32_t num_vertices, const SplatMeshView *view, const float *w2c, int32_t n, int32_t edge,
                     const float *depth, float eps, int32_t *seen, void *stream);
 int splat_mesh_depth_compare(const float *a, const float *b, int64_t n, double *partials, double *row, void *stream);
+
+/* The mesh shade layer (csrc/meshshade.hip, arithmetic in csrc/meshshade_math.h; added within ABI 17): pictures of a triangle mesh --
+ * vertex normals, a z-buffer that remembers which triangle won each pixel, and a shading pass from that buffer to display bytes.  The
+ * camera, the edge planes, the coverage test and the hit are the mesh render layer's, unchanged.
+ *
+ * splat_mesh_vertex_normals: normals [num_vertices][3] float32, area-weighted, the same bits on every run and for every order of the
+ * faces.  accum [num_vertices][3] int64 is scratch, which the call clears.  A face adds n = (b - a) x (c - a), formed in double from
+ * the float32 vertices, to its three vertices as quanta rint(n_k 2^SPLAT_MESH_AREA_BITS) by 64-bit integer atomics (exact, independent
+ * of order; a vertex holds 2^23 m^2 per component and wraps beyond).  A face with an index out of range, a non-finite vertex or a
+ * component |n_k| >= 2^22 m^2 adds nothing; a repeated index gives n = 0.  Per vertex s = sqrt((x^2 + y^2) + z^2) on the sums converted
+ * to double, each component divided and rounded once to float32; s == 0 -- a vertex no face names, faces that cancel -- gives (0, 0, 0).
+ * Three launches (clear, faces, vertices); num_vertices == 0 succeeds without one.
+ *
+ * splat_mesh_visibility: keys [height][width] uint64: splat_mesh_depth's raster (the same setup, boxes, split and hit) with a hit
+ * entering the plane by a 64-bit unsigned atomic min of ((uint64)bits(z) << 32) | face index.  The plane is cleared to all ones, which
+ * stays where no triangle is met.  The high word of every other key is exactly what splat_mesh_depth holds at that pixel; among faces
+ * that hit at the same z bits (every pixel on a shared edge) the LOWEST face index wins: the same keys on every run.
+ *
+ * splat_mesh_shade: rgb8 [H][W][3] bytes from a key plane.  `view` describes the KEY plane, which holds samples x samples sub-pixels
+ * per output pixel: width = W samples, height = H samples, fx samples, fy samples, cx' = (cx + 0.5) samples - 0.5, cy' alike.  One lane
+ * per output pixel (i, j) loops over the sub-pixels (i samples + a, j samples + b) in row order.  A key of all ones, a face index
+ * >= num_faces and a face the raster's setup turns away are background and contribute bg.  Otherwise the winning face is set up again
+ * and its edge planes at the sub-pixel's ray d give the barycentrics l_a = E_bc / S, l_b = E_ca / S, l_c = E_ab / S,
+ * S = (E_ab + E_bc) + E_ca (homogeneous in camera space: perspective-correct without a division by w; S == 0: thirds).  An attribute is
+ * (l_a x_a + l_b x_b) + l_c x_c.  colour: of colors [num_vertices][3] in 0..1; albedo where colors is NULL.  normal: of normals
+ * [num_vertices][3], divided by its length; where that is 0, smooth == 0 or normals is NULL, the face's own (b - a) x (c - a) from the
+ * world-frame vertices in float32, normalised ((0, 0, 0) without area).  The depth is the key's high word, not recomputed.
+ *   SPLAT_MESH_SHADE_COLOR         colour
+ *   SPLAT_MESH_SHADE_SHADED        albedo L, L = ambient + (1 - ambient) |n . w| / |w|, w = R^T d: a head light, two-sided
+ *   SPLAT_MESH_SHADE_SHADED_COLOR  colour L
+ *   SPLAT_MESH_SHADE_NORMAL        (n + 1) / 2; normal_frame 0: n in the mesh's frame; 1: in the camera's, negated where it looks away
+ *   SPLAT_MESH_SHADE_DEPTH         row trunc(clip((z - vmin) / (vmax - vmin), 0, 1) 255) of lut (device, [256][3] bytes), as
+ *                                  SPLAT_VIEW_DEPTH; background pixels hold bg here too
+ * The sub-pixels' channel values are summed in float32 in loop order, multiplied by 1 / samples^2, clamped to 0..1 and rounded to
+ * nearest (ties to even) as splat_view_finish rounds.  depth [H][W] float32 (0 = none; bit for bit splat_mesh_depth's plane), face
+ * [H][W] int32 (-1 = none) and normal [H][W][3] float32 (the shading normal in the mesh's frame, zeros = none) are written where given,
+ * with samples == 1 only.  One launch.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for what splat_mesh_depth refuses (more than
+ * 2^30 - 1 pixels in the key plane among it), NULL keys, args or rgb8, samples outside 1..4 or not dividing the key plane's size, an
+ * unknown mode, SPLAT_MESH_SHADE_DEPTH without lut, and depth, face or normal with samples > 1.  Empty meshes succeed: a picture of bg. */
+#define SPLAT_MESH_SHADE_COLOR 0
+#define SPLAT_MESH_SHADE_SHADED 1
+#define SPLAT_MESH_SHADE_SHADED_COLOR 2
+#define SPLAT_MESH_SHADE_NORMAL 3
+#define SPLAT_MESH_SHADE_DEPTH 4
+typedef struct SplatMeshShade {
+    int32_t mode;                /* SPLAT_MESH_SHADE_* */
+    int32_t samples;             /* sub-pixels per axis, 1..4 */
+    int32_t smooth;              /* 0: every face its own normal */
+    int32_t normal_frame;        /* SPLAT_MESH_SHADE_NORMAL: 0 = the mesh's frame, 1 = the camera's */
+    float bg[3], albedo[3];
+    float ambient;
+    float vmin, vmax;            /* SPLAT_MESH_SHADE_DEPTH */
+    const uint8_t *lut;
+} SplatMeshShade;
+int splat_mesh_vertex_normals(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, int64_t *accum, float *normals,
+                              void *stream);
+int splat_mesh_visibility(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const SplatMeshView *view,
+                          uint64_t *keys, void *stream);
+int splat_mesh_shade(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const float *colors, const float *normals,
+                     const SplatMeshView *view, const uint64_t *keys, const SplatMeshShade *args, uint8_t *rgb8, float *depth, int32_t *face,
+                     float *normal, void *stream);
 
 /* The ICP layer (csrc/icp.hip, arithmetic in csrc/icp_math.h; added within ABI 17): point-to-point registration of a source cloud onto
  * the targets of a SplatNnGrid -- the alignment the NICE-SLAM mesh protocol runs before it measures (threshold 0.1 m, identity start, at

@@ -166,6 +166,11 @@ class SplatMeshView(C.Structure):          # (added within ABI 17: the mesh rend
                 ("near_z", C.c_float), ("w2c", _fp)]
 
 
+class SplatMeshShade(C.Structure):         # (added within ABI 17: the mesh shade layer, csrc/meshshade.hip)
+    _fields_ = [("mode", C.c_int32), ("samples", C.c_int32), ("smooth", C.c_int32), ("normal_frame", C.c_int32), ("bg", C.c_float * 3),
+                ("albedo", C.c_float * 3), ("ambient", C.c_float), ("vmin", C.c_float), ("vmax", C.c_float), ("lut", _fp)]
+
+
 class SplatLpipsWorkspace(C.Structure):    # (added within ABI 17: LPIPS from caller-supplied weights, csrc/lpips.hip)
     _fields_ = [("input", _fp), ("taps", _fp * 5), ("pooled", _fp * 2), ("partials", _fp), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -173,7 +178,7 @@ class SplatLpipsWorkspace(C.Structure):    # (added within ABI 17: LPIPS from ca
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
                     SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView, SplatLpipsWorkspace,
-                    SplatTsdfSparse)
+                    SplatTsdfSparse, SplatMeshShade)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -200,6 +205,7 @@ SPLAT_MESH_COMPARE_ROWS, SPLAT_MESH_COMPARE_PARTIALS = 256, 6 * 256
 SPLAT_ICP_STATE, SPLAT_ICP_ROWS, SPLAT_ICP_SUMS = 24, 256, 17      # (added within ABI 17: the ICP layer, csrc/icp.hip)
 SPLAT_MESH_AREA_BITS, SPLAT_MESH_AREA_BAD = 40, 1 << 62            # (added within ABI 17: the mesh cleaning layer, csrc/meshclean.hip)
 SPLAT_MESH_KEY_HIGHEST, SPLAT_MESH_KEY_LOWEST = 2 ** 31 - 1, -2 ** 31
+SPLAT_MESH_SHADE_COLOR, SPLAT_MESH_SHADE_SHADED, SPLAT_MESH_SHADE_SHADED_COLOR, SPLAT_MESH_SHADE_NORMAL, SPLAT_MESH_SHADE_DEPTH = 0, 1, 2, 3, 4
 SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS, SPLAT_ICP_FITNESS, SPLAT_ICP_RMSE = 16, 17, 18, 19
 SPLAT_ICP_PREV_FITNESS, SPLAT_ICP_PREV_RMSE, SPLAT_ICP_COUNT, SPLAT_ICP_POINTS = 20, 21, 22, 23
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
@@ -235,6 +241,7 @@ EXPORTS = (
     "splat_tsdf_cubes", "splat_tsdf_sparse_cubes", "splat_tsdf_cubes_table",
     "splat_mesh_areas", "splat_mesh_sample", "splat_nn_cell_keys", "splat_nn_cell_starts", "splat_nn_query", "splat_nn_reduce",
     "splat_mesh_depth", "splat_mesh_seen", "splat_mesh_depth_compare",
+    "splat_mesh_vertex_normals", "splat_mesh_visibility", "splat_mesh_shade",
     "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
     "splat_mesh_components", "splat_mesh_component_stats",
     "splat_lpips_weight_floats", "splat_lpips_pack_floats", "splat_lpips_tap_size", "splat_lpips_workspace_layout", "splat_lpips_workspace_bind",
@@ -400,6 +407,10 @@ def lib():
         ("splat_mesh_depth", [_fp, C.c_int32, _fp, C.c_int32, C.POINTER(SplatMeshView), _fp, _fp]),
         ("splat_mesh_seen", [_fp, C.c_int32, C.POINTER(SplatMeshView), _fp, C.c_int32, C.c_int32, _fp, C.c_float, _fp, _fp]),
         ("splat_mesh_depth_compare", [_fp, _fp, C.c_int64, _fp, _fp, _fp]),
+        ("splat_mesh_vertex_normals", [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp]),
+        ("splat_mesh_visibility", [_fp, C.c_int32, _fp, C.c_int32, C.POINTER(SplatMeshView), _fp, _fp]),
+        ("splat_mesh_shade", [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp, C.POINTER(SplatMeshView), _fp, C.POINTER(SplatMeshShade), _fp, _fp, _fp,
+                              _fp, _fp]),
     ):
         f = getattr(L, name)
         f.restype = C.c_int

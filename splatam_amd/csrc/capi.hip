@@ -63,7 +63,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatPruneArgs); SPLAT_SIZEOF_CASE(SplatDensifyArgs); SPLAT_SIZEOF_CASE(SplatArrayInfo);
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
     SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid); SPLAT_SIZEOF_CASE(SplatMeshView);
-    SPLAT_SIZEOF_CASE(SplatLpipsWorkspace); SPLAT_SIZEOF_CASE(SplatTsdfSparse);
+    SPLAT_SIZEOF_CASE(SplatLpipsWorkspace); SPLAT_SIZEOF_CASE(SplatTsdfSparse); SPLAT_SIZEOF_CASE(SplatMeshShade);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -638,6 +638,34 @@ int splat_mesh_seen(const float *vertices, int32_t num_vertices, const SplatMesh
 int splat_mesh_depth_compare(const float *a, const float *b, int64_t n, double *partials, double *row, void *stream) {
     if (n < 0 || (n > 0 && (!a || !b)) || !partials || !row) return SPLAT_E_INVALID;
     return check(launch_mesh_depth_compare(a, b, (long long)n, partials, row, (hipStream_t)stream));
+}
+
+// the mesh shade layer (csrc/meshshade.hip)
+int splat_mesh_vertex_normals(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, int64_t *accum, float *normals,
+                              void *stream) {
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces)) return SPLAT_E_INVALID;
+    if (num_vertices > 0 && (!vertices || !accum || !normals)) return SPLAT_E_INVALID;
+    return check(launch_mesh_vertex_normals(vertices, num_vertices, faces, num_faces, accum, normals, (hipStream_t)stream));
+}
+
+int splat_mesh_visibility(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const SplatMeshView *view,
+                          uint64_t *keys, void *stream) {
+    if (!valid_mesh_view(view) || !view->w2c || !(view->near_z > 0.f) || !finite_f(view->near_z) || !keys) return SPLAT_E_INVALID;
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    return check(launch_mesh_visibility(vertices, num_vertices, faces, num_faces, *view, keys, (hipStream_t)stream));
+}
+
+int splat_mesh_shade(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const float *colors, const float *normals,
+                     const SplatMeshView *view, const uint64_t *keys, const SplatMeshShade *args, uint8_t *rgb8, float *depth, int32_t *face,
+                     float *normal, void *stream) {
+    if (!valid_mesh_view(view) || !view->w2c || !(view->near_z > 0.f) || !finite_f(view->near_z) || !keys || !args || !rgb8) return SPLAT_E_INVALID;
+    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (args->samples < 1 || args->samples > 4 || view->width % args->samples != 0 || view->height % args->samples != 0) return SPLAT_E_INVALID;
+    if (args->mode < SPLAT_MESH_SHADE_COLOR || args->mode > SPLAT_MESH_SHADE_DEPTH) return SPLAT_E_INVALID;
+    if (args->mode == SPLAT_MESH_SHADE_DEPTH && !args->lut) return SPLAT_E_INVALID;
+    if (args->samples > 1 && (depth || face || normal)) return SPLAT_E_INVALID;
+    return check(launch_mesh_shade(vertices, num_vertices, faces, num_faces, colors, normals, *view, keys, *args, rgb8, depth, face, normal,
+                                   (hipStream_t)stream));
 }
 
 size_t splat_map_scratch_words(int64_t n) { return map_scratch_words(n < 0 ? 0 : n); }

@@ -149,6 +149,14 @@ hipError_t launch_mesh_depth(const float *vertices, int32_t V, const int32_t *fa
 hipError_t launch_mesh_seen(const float *vertices, int32_t V, const SplatMeshView &view, const float *w2c, int32_t n, int32_t edge,
                             const float *depth, float eps, int32_t *seen, hipStream_t s);
 hipError_t launch_mesh_depth_compare(const float *a, const float *b, long long n, double *partials, double *row, hipStream_t s);
+// meshshade.hip: pictures of a triangle mesh (vertex normals, a z-buffer of (depth, face) keys, shading to display bytes)
+hipError_t launch_mesh_vertex_normals(const float *vertices, int32_t V, const int32_t *faces, int32_t F, int64_t *accum, float *normals,
+                                      hipStream_t s);
+hipError_t launch_mesh_visibility(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const SplatMeshView &view, uint64_t *keys,
+                                  hipStream_t s);
+hipError_t launch_mesh_shade(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const float *colors, const float *normals,
+                             const SplatMeshView &view, const uint64_t *keys, const SplatMeshShade &a, uint8_t *rgb8, float *depth, int32_t *face,
+                             float *normal, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

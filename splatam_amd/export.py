@@ -42,8 +42,9 @@ def export_params_ply(params, path):
     return save_ply(path, a('means3D'), a('log_scales'), a('unnorm_rotations'), a('rgb_colors'), a('logit_opacities'))
 
 
-def save_mesh_ply(path, vertices, faces, colors=None):
-    """A triangle mesh as binary little-endian PLY: ``vertices`` [V, 3] as float x, y, z, ``colors`` [V, 3] in 0..1 as uchar red, green,
+def save_mesh_ply(path, vertices, faces, colors=None, normals=None):
+    """A triangle mesh as binary little-endian PLY: ``vertices`` [V, 3] as float x, y, z, ``normals`` [V, 3] as float nx, ny, nz (left
+    out when None: the file is then byte for byte what it was without the parameter), ``colors`` [V, 3] in 0..1 as uchar red, green,
     blue (rounded to nearest; left out when None), ``faces`` [F, 3] as ``list uchar int vertex_indices``.  What MeshLab, Open3D and
     trimesh open; written without the ``plyfile`` package, the tables in one piece each."""
     vertices = np.ascontiguousarray(np.asarray(vertices, dtype='<f4').reshape(-1, 3))
@@ -52,6 +53,12 @@ def save_mesh_ply(path, vertices, faces, colors=None):
         raise ValueError("faces index vertices that do not exist")
     fields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
     header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % vertices.shape[0]
+    if normals is not None:
+        normals = np.asarray(normals, dtype='<f4').reshape(-1, 3)
+        if normals.shape[0] != vertices.shape[0]:
+            raise ValueError(f"{normals.shape[0]} normals for {vertices.shape[0]} vertices")
+        fields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+        header += "property float nx\nproperty float ny\nproperty float nz\n"
     if colors is not None:
         colors = np.asarray(colors, dtype=np.float32).reshape(-1, 3)
         if colors.shape[0] != vertices.shape[0]:
@@ -61,6 +68,8 @@ def save_mesh_ply(path, vertices, faces, colors=None):
     header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % faces.shape[0]
     vt = np.zeros(vertices.shape[0], dtype=fields)
     vt['x'], vt['y'], vt['z'] = vertices[:, 0], vertices[:, 1], vertices[:, 2]
+    if normals is not None:
+        vt['nx'], vt['ny'], vt['nz'] = normals[:, 0], normals[:, 1], normals[:, 2]
     if colors is not None:
         bytes3 = np.rint(np.clip(np.nan_to_num(colors), 0.0, 1.0) * 255.0).astype(np.uint8)
         vt['red'], vt['green'], vt['blue'] = bytes3[:, 0], bytes3[:, 1], bytes3[:, 2]

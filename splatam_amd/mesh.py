@@ -533,9 +533,12 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
 
 
 def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None, sil_thres=0.99, depth_max=0.0, bounds=None,
-                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False, clean=None, cleaning=None, method="tetrahedra"):
+                     max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False, clean=None, cleaning=None, method="tetrahedra", views=None,
+                     views_mode="shaded"):
     """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``.  ``method``: ``extract_mesh``'s.  ``clean`` (True or a dict of
-    ``mesh_clean.clean_mesh`` keywords): the mesh is cleaned before it is written; ``cleaning``, a dict, then receives the report."""
+    ``mesh_clean.clean_mesh`` keywords): the mesh is cleaned before it is written; ``cleaning``, a dict, then receives the report.
+    ``views`` (a directory): pictures ``mesh_%04d.png`` of the mesh that was written, in ``views_mode``, at every ``every``-th estimated
+    pose of the run (``mesh_view.render_trajectory``)."""
     from . import slam
     from .export import save_mesh_ply
     from .fused import FusedEngine
@@ -563,6 +566,13 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces from {len(frames)} views", flush=True)
         if clean is not None:
             print(format_cleaning(found), flush=True)
+    if views is not None:
+        from . import mesh_view
+        poses, _, _ = mesh_view.params_poses(path)
+        written = mesh_view.render_trajectory(mesh, poses, views, _scaled_intrinsics(k, (W, H), (W0, H0)), (W, H), every=max(int(every), 1), device=dev,
+                                              mode=views_mode)
+        if verbose:
+            print(f"{views}: {len(written)} pictures of the mesh ({views_mode})", flush=True)
     return mesh
 
 
@@ -587,6 +597,9 @@ def _parser():
     parser.add_argument("--min-vertices", type=int, default=None, metavar="N", help="with --clean: components with fewer vertices go (200)")
     parser.add_argument("--min-area", type=float, default=None, metavar="M2", help="with --clean: components with less area in m^2 go (0)")
     parser.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --clean: keep at most the K components with the most faces")
+    parser.add_argument("--views", default=None, metavar="DIR",
+                        help="also write pictures mesh_%%04d.png of the mesh at every --every-th estimated pose (python -m splatam_amd.mesh_view)")
+    parser.add_argument("--views-mode", default=None, choices=("shaded", "shaded-color", "color", "normal", "depth"), help="with --views (default shaded)")
     parser.add_argument("--device", default="cuda:0")
     return parser
 
@@ -597,11 +610,14 @@ def main(argv=None):
     options = {k: v for k, v in (("min_vertices", args.min_vertices), ("min_area", args.min_area), ("keep_largest", args.keep_largest)) if v is not None}
     if options and not args.clean:
         parser.error("--min-vertices, --min-area and --keep-largest need --clean")
+    if args.views_mode and not args.views:
+        parser.error("--views-mode needs --views")
     bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds else None
     try:
         mesh_from_params(args.params, args.out, voxel_size=args.voxel, trunc=args.trunc, every=args.every, size=args.size,
                          sil_thres=args.sil_thres, depth_max=args.depth_max, bounds=bounds, max_bytes=args.max_bytes, device=args.device,
-                         sparse=args.sparse, method=args.method, **({"clean": options or True} if args.clean else {}))
+                         sparse=args.sparse, method=args.method, **({"clean": options or True} if args.clean else {}),
+                         **({"views": args.views, "views_mode": args.views_mode or "shaded"} if args.views else {}))
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return 0

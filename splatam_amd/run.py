@@ -149,6 +149,8 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
             mesh_options = dict(mesh) if isinstance(mesh, dict) else {}
             cleaning = {} if mesh_options.get("clean") else None
             mesh_from_params(path, stats['mesh'], device=device, **mesh_options, **({"cleaning": cleaning} if cleaning is not None else {}))
+            if mesh_options.get("views"):
+                stats['mesh_views'] = mesh_options["views"]
             if cleaning is not None:
                 stats['mesh_cleaning'] = cleaning
             if gt_mesh is not None:
@@ -191,6 +193,8 @@ def _parser():
                         help="with --mesh: the surface extractor (python -m splatam_amd.mesh --method); cubes: about a third of the triangles")
     parser.add_argument("--clean-mesh", action="store_true",
                         help="with --mesh: remove the mesh's small connected components before it is written and scored (splatam_amd.mesh_clean)")
+    parser.add_argument("--mesh-views", default=None, metavar="DIR",
+                        help="with --mesh: pictures of the mesh along the estimated trajectory into DIR (python -m splatam_amd.mesh --views)")
     parser.add_argument("--gt-mesh", default=None, metavar="GT.ply",
                         help="with --mesh: score mesh.ply against this ground-truth mesh (python -m splatam_amd.mesh_score)")
     parser.add_argument("--gt-transform", default=None, metavar="FILE",
@@ -218,10 +222,12 @@ def main(argv=None):
         parser.error("--clean-mesh needs --mesh")
     if args.mesh_method and not args.mesh:
         parser.error("--mesh-method needs --mesh")
+    if args.mesh_views and not args.mesh:
+        parser.error("--mesh-views needs --mesh")
     mesh = args.mesh
-    if args.mesh_sparse or args.clean_mesh or args.mesh_method:
+    if args.mesh_sparse or args.clean_mesh or args.mesh_method or args.mesh_views:
         mesh = dict(**({"sparse": True} if args.mesh_sparse else {}), **({"clean": True} if args.clean_mesh else {}),
-                    **({"method": args.mesh_method} if args.mesh_method else {}))
+                    **({"method": args.mesh_method} if args.mesh_method else {}), **({"views": args.mesh_views} if args.mesh_views else {}))
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])
     print(f"Seed set to: {config['seed']}")

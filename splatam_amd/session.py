@@ -555,13 +555,15 @@ class SlamSession:
         return self._step(time_idx, curr, tracking_curr, densify_curr, pose, owned=dev.type == "cuda")
 
     # ------------------------------------------------------------------ a mesh of the map (csrc/tsdf.hip)
-    def extract_mesh(self, frames=None, size=None, path=None, method="tetrahedra", **kwargs):
+    def extract_mesh(self, frames=None, size=None, path=None, method="tetrahedra", views=None, views_mode="shaded", **kwargs):
         """A triangle mesh of the map as it is now: ``mesh.extract_mesh`` at the estimated poses of ``frames`` (time indices; default
         the keyframes so far), rendered at ``size`` = (height, width) (default the loop's) with the loop's intrinsics scaled to it.
         Further keywords (``voxel_size``, ``trunc``, ``bounds``, ``max_bytes``, ``sil_thres``, ``depth_max``, ``weight_max``,
         ``min_weight``, ``sparse``, ``clean``) go to ``mesh.extract_mesh``, as does ``method`` (``"tetrahedra"``, or ``"cubes"`` for
         marching cubes: about a third of the triangles; anything else is a ValueError); ``clean=True`` (or a dict of ``mesh_clean.clean_mesh``
-        keywords) removes the mesh's small connected components.  ``path``: also written there as a PLY.  Returns the ``Mesh`` (on the device).
+        keywords) removes the mesh's small connected components.  ``path``: also written there as a PLY.  ``views`` (a directory): pictures
+        ``mesh_%04d.png`` of the mesh in ``views_mode`` at the estimated poses of ``frames``, numbered by time index
+        (``mesh_view.render_trajectory``).  Returns the ``Mesh`` (on the device).
         Between frames and after ``finish()``; engine "fused" only.  The map, the optimiser state and the loop's cameras are left
         as they were."""
         from . import mesh as mesh_mod
@@ -581,6 +583,15 @@ class SlamSession:
         if path is not None:
             from .export import save_mesh_ply
             save_mesh_ply(path, result.vertices.cpu().numpy(), result.faces.cpu().numpy(), result.colors.cpu().numpy())
+        if views is not None:
+            from . import mesh_view
+            from .post_opt import estimated_w2c
+            first = self.first_frame_w2c.detach().double().cpu().numpy().reshape(4, 4)
+            frames = list(frames)
+            numbers = [n if isinstance(fr, torch.Tensor) else int(fr) for n, fr in enumerate(frames)]          # (a w2c: its place in the list)
+            poses = np.stack([fr.detach().double().cpu().numpy().reshape(4, 4) if isinstance(fr, torch.Tensor)
+                              else estimated_w2c(self.engine.params, int(fr)).double().cpu().numpy() @ first for fr in frames])
+            mesh_view.render_trajectory(result, poses, views, k_view, (W, H), device=self.engine.dev, numbers=numbers, mode=views_mode)
         return result
 
     # ------------------------------------------------------------------ a picture of the map (csrc/view.hip)
