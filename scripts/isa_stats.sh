@@ -15,7 +15,7 @@ for m in re.finditer(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", txt, re.S
         continue
     body = m.group(2)
     g = lambda k: (re.search(r"\." + k + r"\s+(\S+)", body) or [None, "?"])[1]
-    short = re.sub(r"\(.*", "", name)[:110]
+    short = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", ""))[:110]
     print(f"{short:110s} vgpr {g('amdhsa_next_free_vgpr'):>4} sgpr {g('amdhsa_next_free_sgpr'):>4} lds {g('amdhsa_group_segment_fixed_size'):>6} scratch {g('amdhsa_private_segment_fixed_size'):>5}")
 # instruction counts per kernel body are in the text too: lines between the kernel's label and its s_endpgm
 PY

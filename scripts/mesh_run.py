@@ -12,6 +12,10 @@
              0.5), a map SLAM has built is opaque nearly everywhere, and the share of the grid a view updates is what T1's traffic scales with.
   whole      ``extract_mesh`` over the views end to end (render + integrate per view, one read, extract), wall clock.
 
+``integrate`` also gives a SHA-256 of the volume's five arrays after the first view into a fresh volume, ``whole`` one of the mesh's three
+tensors: run against two builds of the library (``SPLAT_HIP_LIB``), the lines say whether they compute the same bits.  The volume's
+digest copies one array at a time to the host, once and outside every timed loop: about 0.5 GB of host memory at the default 1 cm.
+
     python scripts/mesh_run.py [--parts integrate,extract,whole] [--voxel 0.01] [--sil-thres 0.5] [--views 4] [--launches 20] [--repeats 3]
 """
 import argparse
@@ -37,6 +41,15 @@ def timed(fn, launches):
     stop.record()
     stop.synchronize()
     return 1e3 * start.elapsed_time(stop) / launches          # microseconds per call
+
+
+def digest(tensors):
+    """SHA-256 over the bytes of ``tensors``, in order: two builds of the library give the same volume or mesh when their lines agree."""
+    import hashlib
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
 
 
 def scene(views):
@@ -87,6 +100,8 @@ def part_integrate(args, eng, view):
             volume.reset()
             volume.integrate(planes, w2c, intr, sil_thres=args.sil_thres)
             updated = int((volume.weight > 0).sum().item())
+            if t == 0:
+                out["volume_sha256_after_view0"] = digest(volume.arrays().values())
             nbytes = 40 * updated + 20 * W * H
             vals = [timed(lambda: volume.integrate(planes, w2c, intr, sil_thres=args.sil_thres), args.launches) for _ in range(args.repeats)]
             med = float(np.median(vals))
@@ -149,7 +164,7 @@ def part_whole(args, eng, view):
         torch.cuda.synchronize()
         vals.append(1e3 * (time.perf_counter() - t0))
     return {"part": "whole", "voxel": args.voxel, "views": args.views, "extract_mesh_wall_ms": [round(v, 1) for v in vals],
-            "vertices": int(m.vertices.shape[0]), "faces": int(m.faces.shape[0])}
+            "vertices": int(m.vertices.shape[0]), "faces": int(m.faces.shape[0]), "mesh_sha256": digest(m)}
 
 
 def main():

@@ -5,8 +5,10 @@ on ``scripts/mesh_run.py``'s map (workload B: 300 000 Gaussians, 1200 x 680), vi
            (from the dense volume: the bricks that meet the 3 x 3 x 3 dilation of ``tsdf < 0``), pool + tables bytes against the dense
            volume's, and the pool's occupancy (share of its points with weight > 0).  The default shape is the one that needs fewer bytes.
   kernels  microseconds per launch of S1 (mark) and S2 (integrate) per view against T1, S3 (triangles) against T2 and S4 (vertices)
-           against T3, hipEvents around ``--launches`` back-to-back launches, ``--repeats`` times; the slot reset against T0.
-  whole    ``extract_mesh`` end to end, dense and sparse, wall clock; the two meshes are compared tensor for tensor.
+           against T3, hipEvents around ``--launches`` back-to-back launches, ``--repeats`` times; the slot reset against T0; S2 per
+           view on either brick shape; a SHA-256 of either volume's arrays after the first view into fresh ones.
+  whole    ``extract_mesh`` end to end, dense and sparse, wall clock; the two meshes are compared tensor for tensor, and a SHA-256 of
+           each mesh's three tensors says whether another build of the library (``SPLAT_HIP_LIB``) gives the same bits.
   fine     the same map at ``--fine-voxel`` (default 0.005): the dense volume ``plan_volume`` refuses under the default 8 GiB, the sparse
            volume's bytes and ``extract_mesh(..., sparse=True)`` wall clock.
 
@@ -23,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
-from mesh_run import FX, FY, CX, CY, H, W, scene, timed  # noqa: E402
+from mesh_run import FX, FY, CX, CY, H, W, digest, scene, timed  # noqa: E402
 
 INTR = (FX, FY, CX, CY)
 
@@ -133,11 +135,14 @@ def part_kernels(args, eng, view):
             L.splat_tsdf_sparse_reset_slots(C.byref(sparse.struct), 0, sparse.slots, stream)
         volume.integrate(planes, w2c, INTR, sil_thres=args.sil_thres)
         out[f"view0_updated_points_{name}"] = int((volume.arrays()["weight"] > 0).sum().item())
+        out[f"volume_sha256_after_view0_{name}"] = digest(volume.arrays().values())
     out["sparse_pool_points"] = sparse.slots * mesh.BRICK_POINTS
     out["S2_view0_us_by_shape"] = {}
     for brick in mesh.brick_shapes():
         other, _ = fuse_sparse(args, eng, views, args.voxel, brick)
-        out["S2_view0_us_by_shape"]["x".join(map(str, brick))] = {"slots": other.slots, "us": rep(lambda: other.integrate(planes, w2c, INTR, sil_thres=args.sil_thres))}
+        out["S2_view0_us_by_shape"]["x".join(map(str, brick))] = {
+            "slots": other.slots, "us": rep(lambda: other.integrate(planes, w2c, INTR, sil_thres=args.sil_thres)),
+            "us_per_view": [rep(lambda: other.integrate(p, m, INTR, sil_thres=args.sil_thres)) for p, m in views]}
         del other
     out["T0_us"] = rep(dense.reset)
     out["reset_slots_us"] = rep(lambda: L.splat_tsdf_sparse_reset_slots(C.byref(sparse.struct), 0, sparse.slots, stream))
@@ -186,7 +191,7 @@ def part_whole(args, eng, view):
     sparse_ms, got, volume = whole(args, eng, view, args.voxel, True)
     return {"part": "whole", "voxel": args.voxel, "views": args.views, "extract_mesh_dense_wall_ms": dense_ms, "extract_mesh_sparse_wall_ms": sparse_ms,
             "vertices": int(got.vertices.shape[0]), "faces": int(got.faces.shape[0]), "sparse_bytes": volume.bytes(),
-            "mesh_equals_dense": all(torch.equal(a, b) for a, b in zip(got, want))}
+            "mesh_equals_dense": all(torch.equal(a, b) for a, b in zip(got, want)), "mesh_sha256_dense": digest(want), "mesh_sha256_sparse": digest(got)}
 
 
 def part_fine(args, eng, view):

@@ -427,13 +427,21 @@ int splat_view_finish(const SplatViewArgs *v, void *stream) {
 }
 
 // the mesh layer (csrc/tsdf.hip)
-static bool valid_tsdf_grid(const SplatTsdfVolume *v) {
-    if (!v || v->nx <= 0 || v->ny <= 0 || v->nz <= 0 || !(v->voxel > 0.f) || !(v->trunc > 0.f)) return false;
-    return (long long)v->nx * v->ny < (1ll << 40) && (long long)v->nx * v->ny * (long long)v->nz < (1ll << 40);
+// the grid of either volume struct: positive dims, voxel and trunc, fewer than 2^40 grid points (tsdf_math.h kTsdfMaxPoints)
+static bool valid_tsdf_dims(int nx, int ny, int nz, float voxel, float trunc) {
+    if (nx <= 0 || ny <= 0 || nz <= 0 || !(voxel > 0.f) || !(trunc > 0.f)) return false;
+    return (long long)nx * ny < kTsdfMaxPoints && (long long)nx * ny * (long long)nz < kTsdfMaxPoints;
 }
+static bool valid_tsdf_grid(const SplatTsdfVolume *v) { return v && valid_tsdf_dims(v->nx, v->ny, v->nz, v->voxel, v->trunc); }
 static bool valid_tsdf_volume(const SplatTsdfVolume *v) {
     return valid_tsdf_grid(v) && v->tsdf && v->weight && v->r && v->g && v->b;
 }
+static bool valid_tsdf_view(const SplatTsdfView *w) {
+    if (!w || w->width <= 0 || w->height <= 0 || (long long)w->width * w->height > 0x3fffffffLL) return false;
+    return w->out6 && w->w2c && !(w->skip && !w->skipped);
+}
+// room for `capacity` triangles' keys (none needed at capacity 0) and somewhere to put the count
+static bool valid_tsdf_keys(const int64_t *keys, int64_t capacity, const int64_t *count) { return capacity >= 0 && (capacity == 0 || keys) && count; }
 
 size_t splat_tsdf_bytes(const SplatTsdfVolume *v) {
     return valid_tsdf_grid(v) ? 5 * sizeof(float) * (size_t)v->nx * (size_t)v->ny * (size_t)v->nz : 0;
@@ -445,18 +453,17 @@ int splat_tsdf_reset(const SplatTsdfVolume *v, void *stream) {
 }
 
 int splat_tsdf_integrate(const SplatTsdfVolume *v, const SplatTsdfView *w, void *stream) {
-    if (!valid_tsdf_volume(v) || !w || w->width <= 0 || w->height <= 0 || (long long)w->width * w->height > 0x3fffffffLL) return SPLAT_E_INVALID;
-    if (!w->out6 || !w->w2c || (w->skip && !w->skipped)) return SPLAT_E_INVALID;
+    if (!valid_tsdf_volume(v) || !valid_tsdf_view(w)) return SPLAT_E_INVALID;
     return check(launch_tsdf_integrate(*v, *w, (hipStream_t)stream));
 }
 
 int splat_tsdf_triangles(const SplatTsdfVolume *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
-    if (!valid_tsdf_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    if (!valid_tsdf_volume(v) || !valid_tsdf_keys(keys, capacity, count)) return SPLAT_E_INVALID;
     return check(launch_tsdf_triangles(*v, min_weight, keys, (long long)capacity, count, false, (hipStream_t)stream));
 }
 
 int splat_tsdf_cubes(const SplatTsdfVolume *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
-    if (!valid_tsdf_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    if (!valid_tsdf_volume(v) || !valid_tsdf_keys(keys, capacity, count)) return SPLAT_E_INVALID;
     return check(launch_tsdf_triangles(*v, min_weight, keys, (long long)capacity, count, true, (hipStream_t)stream));
 }
 
@@ -484,8 +491,7 @@ static long long sparse_bricks(const SplatTsdfSparse *v) {
     return (long long)((v->nx + v->brick[0] - 1) / v->brick[0]) * ((v->ny + v->brick[1] - 1) / v->brick[1]) * ((v->nz + v->brick[2] - 1) / v->brick[2]);
 }
 static bool valid_sparse_grid(const SplatTsdfSparse *v) {
-    if (!v || v->nx <= 0 || v->ny <= 0 || v->nz <= 0 || !(v->voxel > 0.f) || !(v->trunc > 0.f) || v->slots < 0) return false;
-    if (!((long long)v->nx * v->ny < (1ll << 40) && (long long)v->nx * v->ny * (long long)v->nz < (1ll << 40))) return false;
+    if (!v || !valid_tsdf_dims(v->nx, v->ny, v->nz, v->voxel, v->trunc) || v->slots < 0) return false;
     bool listed = false;
     for (int n = 0; n < 2; ++n)
         listed |= v->brick[0] == kSparseBrickShapes[n][0] && v->brick[1] == kSparseBrickShapes[n][1] && v->brick[2] == kSparseBrickShapes[n][2];
@@ -493,10 +499,6 @@ static bool valid_sparse_grid(const SplatTsdfSparse *v) {
 }
 static bool valid_sparse_volume(const SplatTsdfSparse *v) {
     return valid_sparse_grid(v) && v->directory && (v->slots == 0 || (v->brick_of_slot && v->tsdf && v->weight && v->r && v->g && v->b));
-}
-static bool valid_tsdf_view(const SplatTsdfView *w) {
-    if (!w || w->width <= 0 || w->height <= 0 || (long long)w->width * w->height > 0x3fffffffLL) return false;
-    return w->out6 && w->w2c && !(w->skip && !w->skipped);
 }
 
 size_t splat_tsdf_sparse_bytes(const SplatTsdfSparse *v) {
@@ -520,12 +522,12 @@ int splat_tsdf_sparse_integrate(const SplatTsdfSparse *v, const SplatTsdfView *w
 }
 
 int splat_tsdf_sparse_triangles(const SplatTsdfSparse *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
-    if (!valid_sparse_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    if (!valid_sparse_volume(v) || !valid_tsdf_keys(keys, capacity, count)) return SPLAT_E_INVALID;
     return check(launch_tsdf_sparse_triangles(*v, min_weight, keys, (long long)capacity, count, false, (hipStream_t)stream));
 }
 
 int splat_tsdf_sparse_cubes(const SplatTsdfSparse *v, float min_weight, int64_t *keys, int64_t capacity, int64_t *count, void *stream) {
-    if (!valid_sparse_volume(v) || capacity < 0 || (capacity > 0 && !keys) || !count) return SPLAT_E_INVALID;
+    if (!valid_sparse_volume(v) || !valid_tsdf_keys(keys, capacity, count)) return SPLAT_E_INVALID;
     return check(launch_tsdf_sparse_triangles(*v, min_weight, keys, (long long)capacity, count, true, (hipStream_t)stream));
 }
 

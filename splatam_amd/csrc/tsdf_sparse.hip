@@ -1,61 +1,41 @@
 // tsdf_sparse.hip -- the mesh layer on a SPARSE volume: the virtual grid of tsdf.hip, of which only the bricks near observed surfaces
 // are stored (tsdf_math.h, "sparse volume": 2048 grid points per brick, 8 KiB contiguous per array in a pool, a directory of slots
-// over all bricks).  The arithmetic per grid point, cell and vertex is the dense kernels', call for call, so a sparse volume whose
-// bricks cover tsdf_mark_box of every pixel of every view, and that was then given every view, yields the dense volume's mesh bit
-// for bit.
+// over all bricks).  The arithmetic per grid point, cell and vertex is the dense kernels' -- tsdf_math.h's, through the very functions
+// of tsdf_device.h that tsdf.hip calls --, so a sparse volume whose bricks cover tsdf_mark_box of every pixel of every view, and that
+// was then given every view, yields the dense volume's mesh bit for bit.
 //
 //   S1 tsdf_mark_kernel              one lane per pixel: tsdf_mark_box, then a plain store of 1 into the flag of every brick the box
-//                                    meets (every writer stores the same value: no atomics).  Gated by `skip` as T1 is.
+//                                    meets (every writer stores the same value: no atomics).  Gated by `skip` (tsdf_view_skipped).
 //      allocation                    is the caller's (a prefix sum over the flags on the device); new slots are reset by T0 over the
 //                                    slot range (launch_tsdf_sparse_reset_slots).
-//   S2 tsdf_sparse_integrate_kernel  one workgroup per allocated brick (brick_of_slot): T1's eight-corner frustum test on the brick's
-//                                    box, then T1's per-point body on the brick's 2048 points, four per lane (a brick row is a
-//                                    multiple of four points and a brick starts on 8 KiB: always 16-byte accesses), points at or
-//                                    beyond nx, ny, nz masked.
+//   S2 tsdf_sparse_integrate_kernel  one workgroup per allocated brick (brick_of_slot): tsdf_brick_outside on the brick's box, then
+//                                    tsdf_integrate_lane<4> on the brick's 2048 points, four per lane (a brick row is a multiple of
+//                                    four points and a brick starts on 8 KiB: always 16-byte accesses), points at or beyond nx, ny,
+//                                    nz masked.
 //   S3 tsdf_sparse_triangles_kernel  one workgroup per allocated brick, lanes over the cells whose corner 0 is in the brick; corners
 //                                    in the +x, +y, +z neighbour bricks come through the directory (the eight slots a brick's cells
-//                                    can touch are looked up once per workgroup), a missing neighbour makes the cell unseen.  T2's
-//                                    reservation: scan, one returning atomic by the last lane, readlane.
-//      tsdf_sparse_triangles_kernel<true>  the same pass by marching cubes, as T2's (tsdf.hip): the lane's row of the case table in four
-//                                    registers, its five slots unrolled and predicated.
+//                                    can touch are looked up once per workgroup), a missing neighbour makes the cell unseen.  Then
+//                                    tsdf_emit_cell, by marching tetrahedra or (<true>) marching cubes.
 //   S4 tsdf_sparse_vertices_kernel   one lane per unique key, the edge's two grid points through the directory.
-#include "splat_device.h"
-#include "tsdf_math.h"
+#include "tsdf_device.h"
 
 namespace splat {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr long long kMaxGrid = 1ll << 30;
 
-struct SparseArrays {
-    float *tsdf, *weight, *r, *g, *b;
+struct SparseArrays : TsdfArrays {                          // (the pool's five arrays)
     const int32_t *directory, *brick_of_slot;
     int slots;
 };
 
-TsdfGrid grid_of(const SplatTsdfSparse &v) {
-    TsdfGrid g;
-    g.nx = v.nx; g.ny = v.ny; g.nz = v.nz;
-    g.ox = v.origin[0]; g.oy = v.origin[1]; g.oz = v.origin[2]; g.voxel = v.voxel;
-    return g;
-}
 int log2_of(int v) {
     int l = 0;
     while ((1 << l) < v) ++l;
     return l;
 }
-TsdfBricks bricks_of(const SplatTsdfSparse &v) { return tsdf_bricks(grid_of(v), log2_of(v.brick[0]), log2_of(v.brick[1]), log2_of(v.brick[2])); }
-SparseArrays arrays_of(const SplatTsdfSparse &v) { return SparseArrays{v.tsdf, v.weight, v.r, v.g, v.b, v.directory, v.brick_of_slot, v.slots}; }
-TsdfCamera camera_of(const SplatTsdfSparse &v, const SplatTsdfView &w) {
-    TsdfCamera c;
-    c.W = w.width; c.H = w.height;
-    c.fx = w.fx; c.fy = w.fy; c.cx = w.cx; c.cy = w.cy;
-    c.trunc = v.trunc; c.sil_thres = w.sil_thres; c.depth_max = w.depth_max; c.weight_max = w.weight_max;
-    for (int q = 0; q < 12; ++q) c.m[q] = 0.f;              // (filled in the kernel, from w2c)
-    return c;
-}
-unsigned grid_for(long long blocks) { return (unsigned)(blocks < 1 ? 1 : (blocks > kMaxGrid ? kMaxGrid : blocks)); }
+TsdfBricks bricks_of(const SplatTsdfSparse &v) { return tsdf_bricks(tsdf_grid_of(v), log2_of(v.brick[0]), log2_of(v.brick[1]), log2_of(v.brick[2])); }
+SparseArrays arrays_of(const SplatTsdfSparse &v) { return SparseArrays{tsdf_arrays_of(v), v.directory, v.brick_of_slot, v.slots}; }
 
 // ---------------------------------------------------------------------------------------------------------------- S1
 struct MarkArgs {
@@ -69,13 +49,8 @@ struct MarkArgs {
 };
 
 __global__ void __launch_bounds__(kBlock) tsdf_mark_kernel(MarkArgs a) {
-    if (a.skip && *a.skip != 0) {                                   // the view's lists did not fit: its planes are incomplete
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.skipped, 1);
-        return;
-    }
-    TsdfCamera cam = a.cam;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) cam.m[q] = a.w2c[q];
+    if (tsdf_view_skipped(a.skip, a.skipped)) return;
+    const TsdfCamera cam = tsdf_view_camera(a.cam, a.w2c);
     const size_t plane = (size_t)cam.W * cam.H;
     const TsdfBricks &b = a.bricks;
     for (size_t px = (size_t)blockIdx.x * kBlock + threadIdx.x; px < plane; px += (size_t)gridDim.x * kBlock) {
@@ -99,44 +74,16 @@ struct SparseIntegrateArgs {
     int32_t *skipped;
 };
 
-// T1's test (tsdf.hip brick_outside) on a brick of this file's shape: the brick's box, pushed out by half a voxel, against the planes
-// every updated point satisfies; lane l of a wave projects corner l mod 8 and six ballots combine them.
-__device__ __forceinline__ bool sparse_brick_outside(const TsdfGrid &g, const TsdfBricks &b, const TsdfCamera &cam, int i0, int j0, int k0) {
-    const int c = threadIdx.x & 7;
-    const int i1 = min(i0 + (1 << b.lx), g.nx) - 1, j1 = min(j0 + (1 << b.ly), g.ny) - 1, k1 = min(k0 + (1 << b.lz), g.nz) - 1;
-    const float p[3] = {g.ox + g.voxel * ((c & 1) ? (float)i1 + 0.5f : (float)i0 - 0.5f),
-                        g.oy + g.voxel * ((c & 2) ? (float)j1 + 0.5f : (float)j0 - 0.5f),
-                        g.oz + g.voxel * ((c & 4) ? (float)k1 + 0.5f : (float)k0 - 0.5f)};
-    const float *m = cam.m;
-    const float ax = cam.cx + 0.5f, ay = cam.cy + 0.5f, far_z = cam.depth_max + cam.trunc;
-    const float x = m[0] * p[0] + m[1] * p[1] + m[2] * p[2] + m[3];
-    const float y = m[4] * p[0] + m[5] * p[1] + m[6] * p[2] + m[7];
-    const float z = m[8] * p[0] + m[9] * p[1] + m[10] * p[2] + m[11];
-    bool outside = (__builtin_amdgcn_ballot_w64(!(z > 0.f)) & 0xffull) == 0xffull;
-    outside |= (__builtin_amdgcn_ballot_w64(!(cam.fx * x + ax * z >= 0.f)) & 0xffull) == 0xffull;
-    outside |= (__builtin_amdgcn_ballot_w64(!(cam.fx * x + (ax - (float)cam.W) * z < 0.f)) & 0xffull) == 0xffull;
-    outside |= (__builtin_amdgcn_ballot_w64(!(cam.fy * y + ay * z >= 0.f)) & 0xffull) == 0xffull;
-    outside |= (__builtin_amdgcn_ballot_w64(!(cam.fy * y + (ay - (float)cam.H) * z < 0.f)) & 0xffull) == 0xffull;
-    outside |= (__builtin_amdgcn_ballot_w64(cam.depth_max > 0.f && z > far_z) & 0xffull) == 0xffull;
-    return outside;
-}
-
 __global__ void __launch_bounds__(kBlock) tsdf_sparse_integrate_kernel(SparseIntegrateArgs a) {
-    if (a.skip && *a.skip != 0) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.skipped, 1);
-        return;
-    }
-    TsdfCamera cam = a.cam;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) cam.m[q] = a.w2c[q];
+    if (tsdf_view_skipped(a.skip, a.skipped)) return;
+    const TsdfCamera cam = tsdf_view_camera(a.cam, a.w2c);
     constexpr int V = 4, kPasses = kTsdfBrickPoints / (kBlock * V);
     const TsdfGrid &g = a.grid;
     const TsdfBricks &b = a.bricks;
-    const size_t plane = (size_t)cam.W * cam.H;
-    for (int slot = blockIdx.x; slot < a.vol.slots; slot += gridDim.x) {
+    for (int slot = blockIdx.x; slot < a.vol.slots; slot += gridDim.x) {       // (uniform bounds: tsdf_brick_outside)
         int i0, j0, k0;
         tsdf_brick_origin(b, a.vol.brick_of_slot[slot], i0, j0, k0);
-        if (sparse_brick_outside(g, b, cam, i0, j0, k0)) continue;
+        if (tsdf_brick_outside(g, cam, i0, min(i0 + (1 << b.lx), g.nx) - 1, j0, min(j0 + (1 << b.ly), g.ny) - 1, k0, min(k0 + (1 << b.lz), g.nz) - 1)) continue;
 #pragma unroll
         for (int pass = 0; pass < kPasses; ++pass) {
             const int local = (pass * kBlock + (int)threadIdx.x) * V;
@@ -144,45 +91,7 @@ __global__ void __launch_bounds__(kBlock) tsdf_sparse_integrate_kernel(SparseInt
             tsdf_brick_unlocal(b, local, li, lj, lk);
             const int i = i0 + li, j = j0 + lj, k = k0 + lk;
             if (i >= g.nx || j >= g.ny || k >= g.nz) continue;
-            // T1's three rounds of independent loads; a point at or beyond nx is never hit
-            float z[V], s[V], dep[V], f[V], rgb[V][3];
-            size_t px[V];
-            bool hit[V], any = false;
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                float p[3];
-                tsdf_point(g, i + v, j, k, p);
-                hit[v] = i + v < g.nx && tsdf_project(cam, p, z[v], px[v]);
-                if (!hit[v]) px[v] = 0;
-            }
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                s[v] = hit[v] ? a.out6[4 * plane + px[v]] : 0.f;
-                dep[v] = hit[v] ? a.out6[3 * plane + px[v]] : 0.f;
-            }
-#pragma unroll
-            for (int v = 0; v < V; ++v) {
-                hit[v] = hit[v] && tsdf_measure(cam, s[v], dep[v], z[v], f[v]);
-                any |= hit[v];
-            }
-            if (!any) continue;
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) rgb[v][c] = hit[v] ? tsdf_colour(a.out6[c * plane + px[v]], s[v]) : 0.f;
-            const size_t o = (size_t)slot * kTsdfBrickPoints + local;
-            float4 q[5] = {*reinterpret_cast<const float4 *>(a.vol.tsdf + o), *reinterpret_cast<const float4 *>(a.vol.weight + o),
-                           *reinterpret_cast<const float4 *>(a.vol.r + o), *reinterpret_cast<const float4 *>(a.vol.g + o),
-                           *reinterpret_cast<const float4 *>(a.vol.b + o)};
-            float *t = &q[0].x, *w = &q[1].x, *r = &q[2].x, *gg = &q[3].x, *bb = &q[4].x;
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-                if (hit[v]) tsdf_blend(f[v], rgb[v], cam.weight_max, t[v], w[v], r[v], gg[v], bb[v]);
-            *reinterpret_cast<float4 *>(a.vol.tsdf + o) = q[0];
-            *reinterpret_cast<float4 *>(a.vol.weight + o) = q[1];
-            *reinterpret_cast<float4 *>(a.vol.r + o) = q[2];
-            *reinterpret_cast<float4 *>(a.vol.g + o) = q[3];
-            *reinterpret_cast<float4 *>(a.vol.b + o) = q[4];
+            tsdf_integrate_lane<V>(g, cam, a.out6, a.vol, i, j, k, (size_t)slot * kTsdfBrickPoints + local);
         }
     }
 }
@@ -203,9 +112,8 @@ __global__ void __launch_bounds__(kBlock) tsdf_sparse_triangles_kernel(SparseTri
     __shared__ int nb[8];                                           // slots of the brick and its +x, +y, +z neighbours (dx + 2 dy + 4 dz), -1 = none
     const TsdfGrid &g = a.grid;
     const TsdfBricks &b = a.bricks;
-    const int lane = threadIdx.x & (kWave - 1);
     const int mx = (1 << b.lx) - 1, my = (1 << b.ly) - 1, mz = (1 << b.lz) - 1;
-    for (int slot = blockIdx.x; slot < a.vol.slots; slot += gridDim.x) {       // (uniform bounds: every lane of a wave reaches the scan)
+    for (int slot = blockIdx.x; slot < a.vol.slots; slot += gridDim.x) {       // (uniform bounds: tsdf_emit_cell)
         const long long brick = a.vol.brick_of_slot[slot];
         if (brick < 0 || brick >= tsdf_brick_count(b)) continue;    // (not a brick of this grid; uniform over the workgroup)
         int i0, j0, k0;
@@ -247,33 +155,7 @@ __global__ void __launch_bounds__(kBlock) tsdf_sparse_triangles_kernel(SparseTri
                     }
                 }
             }
-            TsdfCubesRow cubes;                                                 // (row 0 of the table is empty: an idle lane's)
-            if constexpr (kCubes) cubes = tsdf_cubes_row(mask);
-            const unsigned n = kCubes ? (unsigned)tsdf_cubes_row_entry(cubes, 0) : (unsigned)tsdf_cell_triangles(mask);
-            if (__builtin_amdgcn_ballot_w64(n != 0) == 0ull) continue;          // (wave-uniform)
-            const unsigned incl = wave_scan_incl_u32(n);
-            unsigned long long base = 0;
-            if (lane == kWave - 1) base = atomicAdd(a.count, (unsigned long long)incl);
-            base = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(base >> 32), kWave - 1) << 32)
-                   | (unsigned)__builtin_amdgcn_readlane((int)(unsigned)base, kWave - 1);
-            if (n == 0) continue;
-            unsigned long long out = base + (incl - n);
-            if constexpr (kCubes) {
-                tsdf_cubes_store(g, i, j, k, cubes, out, (unsigned long long)a.capacity, a.keys);
-                continue;
-            }
-#pragma unroll 1
-            for (int q = 0; q < 6; ++q) {
-                const int8_t *row = kTsdfTetCases[tsdf_tet_mask(mask, q)];
-                for (int t = 0; t < row[0]; ++t, ++out) {
-                    if (out >= (unsigned long long)a.capacity) continue;
-                    int64_t key[3];
-                    tsdf_tet_triangle(g, i, j, k, q, row, t, key);
-                    a.keys[3 * out] = key[0];
-                    a.keys[3 * out + 1] = key[1];
-                    a.keys[3 * out + 2] = key[2];
-                }
-            }
+            tsdf_emit_cell<kCubes>(g, i, j, k, mask, a.keys, (unsigned long long)a.capacity, a.count);
         }
     }
 }
@@ -319,12 +201,12 @@ __global__ void __launch_bounds__(kBlock) tsdf_sparse_vertices_kernel(TsdfGrid g
 
 hipError_t launch_tsdf_sparse_mark(const SplatTsdfSparse &v, const SplatTsdfView &w, int32_t *flags, hipStream_t s) {
     MarkArgs a;
-    a.grid = grid_of(v);
+    a.grid = tsdf_grid_of(v);
     a.bricks = bricks_of(v);
-    a.cam = camera_of(v, w);
+    a.cam = tsdf_camera_of(v, w);
     a.out6 = w.out6; a.w2c = w.w2c; a.skip = w.skip; a.skipped = w.skipped; a.flags = flags;
     const long long pixels = (long long)w.width * w.height;
-    hipLaunchKernelGGL(tsdf_mark_kernel, dim3(grid_for((pixels + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL(tsdf_mark_kernel, dim3(tsdf_grid_for((pixels + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 
@@ -342,12 +224,12 @@ hipError_t launch_tsdf_sparse_reset_slots(const SplatTsdfSparse &v, long long fi
 
 hipError_t launch_tsdf_sparse_integrate(const SplatTsdfSparse &v, const SplatTsdfView &w, hipStream_t s) {
     SparseIntegrateArgs a;
-    a.grid = grid_of(v);
+    a.grid = tsdf_grid_of(v);
     a.bricks = bricks_of(v);
     a.vol = arrays_of(v);
-    a.cam = camera_of(v, w);
+    a.cam = tsdf_camera_of(v, w);
     a.out6 = w.out6; a.w2c = w.w2c; a.skip = w.skip; a.skipped = w.skipped;
-    hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3(grid_for(v.slots)), dim3(kBlock), 0, s, a);      // (one block even without slots: `skip` is counted)
+    hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3(tsdf_grid_for(v.slots)), dim3(kBlock), 0, s, a);      // (one block even without slots: `skip` is counted)
     return hipGetLastError();
 }
 
@@ -357,19 +239,19 @@ hipError_t launch_tsdf_sparse_triangles(const SplatTsdfSparse &v, float min_weig
     if (e != hipSuccess) return e;
     if (v.nx < 2 || v.ny < 2 || v.nz < 2 || v.slots == 0) return hipSuccess;       // no cell
     SparseTrianglesArgs a;
-    a.grid = grid_of(v);
+    a.grid = tsdf_grid_of(v);
     a.bricks = bricks_of(v);
     a.vol = arrays_of(v);
     a.min_weight = min_weight;
     a.keys = keys; a.capacity = capacity; a.count = reinterpret_cast<unsigned long long *>(count);
-    if (cubes) hipLaunchKernelGGL(tsdf_sparse_triangles_kernel<true>, dim3(grid_for(v.slots)), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL(tsdf_sparse_triangles_kernel<false>, dim3(grid_for(v.slots)), dim3(kBlock), 0, s, a);
+    if (cubes) hipLaunchKernelGGL(tsdf_sparse_triangles_kernel<true>, dim3(tsdf_grid_for(v.slots)), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL(tsdf_sparse_triangles_kernel<false>, dim3(tsdf_grid_for(v.slots)), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_tsdf_sparse_vertices(const SplatTsdfSparse &v, const int64_t *keys, long long n, float *vertices, float *colors, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(tsdf_sparse_vertices_kernel, dim3(grid_for((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, grid_of(v), bricks_of(v),
+    hipLaunchKernelGGL(tsdf_sparse_vertices_kernel, dim3(tsdf_grid_for((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, tsdf_grid_of(v), bricks_of(v),
                        arrays_of(v), keys, n, (long long)v.nx * v.ny * v.nz, vertices, colors);
     return hipGetLastError();
 }

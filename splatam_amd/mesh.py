@@ -44,6 +44,7 @@ Mesh.__doc__ = """``vertices`` [V, 3] float32, ``faces`` [F, 3] int32 (wound wit
 0..1, on the volume's device."""
 
 MAX_POINTS = 1 << 40                 # (csrc/tsdf_math.h kTsdfMaxPoints)
+BRICK_POINTS = 2048                  # (csrc/tsdf_math.h kTsdfBrickPoints)
 DEFAULT_MAX_BYTES = 8 << 30
 VOLUME_ARRAYS = ("tsdf", "weight", "r", "g", "b")
 
@@ -65,6 +66,15 @@ def default_bounds(means3D, logit_opacities, pad):
     return tuple(float(v) - pad for v in box[0]), tuple(float(v) + pad for v in box[1])
 
 
+def _beyond_max_bytes(dims, voxel_size, need, max_bytes, bricks=None, advice=True):
+    """The ValueError for a volume of ``dims`` grid points (a sparse one with ``bricks`` bricks) that needs ``need`` bytes."""
+    nx, ny, nz = dims
+    what = f"a {nx} x {ny} x {nz} volume at voxel size {voxel_size}" if bricks is None else \
+        f"a sparse {nx} x {ny} x {nz} volume at voxel size {voxel_size} with {bricks} bricks of {BRICK_POINTS} grid points"
+    return ValueError(f"{what} needs {need} bytes ({need / 2 ** 30:.2f} GiB), beyond max_bytes = {max_bytes}"
+                      + (": raise the voxel size, pass tighter bounds or a larger max_bytes" if advice else ""))
+
+
 def plan_volume(bounds, voxel_size, max_bytes=DEFAULT_MAX_BYTES, sparse=False):
     """(origin, dims) of the grid that covers ``bounds`` at ``voxel_size``: grid points from the lower corner, one past the upper.
     ValueError, with the size it would need, for a volume beyond ``max_bytes`` (or beyond the library's 2^40 grid points).
@@ -76,8 +86,7 @@ def plan_volume(bounds, voxel_size, max_bytes=DEFAULT_MAX_BYTES, sparse=False):
     dims = tuple(int(math.ceil((h - l) / voxel_size - 1e-9)) + 1 for l, h in zip(lo, hi))      # (an extent of n voxels is n + 1 points)
     need = volume_bytes(dims)
     if (need > max_bytes and not sparse) or dims[0] * dims[1] * dims[2] >= MAX_POINTS:
-        raise ValueError(f"a {dims[0]} x {dims[1]} x {dims[2]} volume at voxel size {voxel_size} needs {need} bytes ({need / 2 ** 30:.2f} GiB), "
-                         f"beyond max_bytes = {max_bytes}: raise the voxel size, pass tighter bounds or a larger max_bytes")
+        raise _beyond_max_bytes(dims, voxel_size, need, max_bytes)
     return lo, dims
 
 
@@ -99,8 +108,71 @@ def cubes_table():
 
 
 class _Surface:
-    """``extract`` of a volume class that has ``_triangles(min_weight, keys, count, method)``, ``_vertices(uniq, vertices, colors)`` and
-    ``_default_capacity()``."""
+    """What ``TsdfVolume`` and ``SparseTsdfVolume`` share: the grid's parameters, the launches, fusing a view and ``extract``.  A volume
+    class names its entry points (``_prefix``: ``_launch("reset")`` calls ``splat_tsdf_reset`` or ``splat_tsdf_sparse_reset``), gives
+    ``_Surface.__init__`` its C struct and has ``_default_capacity()``."""
+
+    _prefix = None
+
+    def __init__(self, struct, origin, dims, voxel_size, trunc, device):
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} needs a CUDA/HIP device; the HIP library has no CPU path")
+        self.origin = tuple(float(v) for v in origin)
+        self.dims = tuple(int(d) for d in dims)
+        self.voxel_size = float(voxel_size)
+        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
+        self.struct = struct
+        self.L = _capi.lib()
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)          # ``integrate`` launches a non-zero ``skip`` turned away
+        self._keep = None
+
+    def _grid_to_struct(self):
+        v = self.struct
+        v.nx, v.ny, v.nz = self.dims
+        v.origin[:] = self.origin
+        v.voxel, v.trunc = self.voxel_size, self.trunc
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _launch(self, name, *args):
+        """The entry point ``_prefix + name`` on this volume's struct, ``args`` and the current stream; an error status raises."""
+        name = self._prefix + name
+        with torch.cuda.device(self.dev):
+            _capi.check(getattr(self.L, name)(C.byref(self.struct), *args, self._stream()), name)
+
+    def integrate(self, out6, w2c, intrinsics, sil_thres=0.99, depth_max=0.0, weight_max=0.0, skip=None):
+        """One view into the volume (a sparse volume: into every allocated brick, the same arithmetic, the same bits): ``out6``
+        [>= 5, H, W] float32 on the device (r, g, b, depth, silhouette as the composite leaves them: depth is sum w z, divided by the
+        silhouette here; a view into a larger buffer is fine), ``w2c`` float32 [4, 4] on the device, ``intrinsics`` a 3 x 3 or
+        (fx, fy, cx, cy) on the host.  ``skip``: int32 [1] on the device (a ``ViewImage.truncated``); non-zero when the launch runs: the
+        volume stays as it is and ``skipped`` counts one.  One launch, nothing read."""
+        w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, weight_max, skip, self.skipped, self.dev)
+        self._launch("integrate", C.byref(w))
+        self._keep = keep
+        return self
+
+    def _render_then(self, step, engine, view, time_idx, w2c, intrinsics, first_w2c, near, far, **kw):
+        """``engine.render_view(view, ..., rgb8=False)``, then ``step`` (``integrate`` or ``mark``) of the view's planes at the view's own
+        ``w2c`` buffer with its truncation status as ``skip``.  Returns the ``ViewImage``."""
+        with torch.no_grad():
+            img = engine.render_view(view, w2c=w2c, time_idx=time_idx, intrinsics=intrinsics, first_w2c=first_w2c, near=near, far=far, rgb8=False)
+        step(img.out6, view.w2c, intrinsics, skip=img.truncated, **kw)
+        return img
+
+    def integrate_view(self, engine, view, time_idx=None, w2c=None, intrinsics=None, first_w2c=None, near=0.01, far=100, **kw):
+        """``engine.render_view(view, ..., rgb8=False)`` at a pose of the map (``time_idx``, with ``first_w2c``) or at ``w2c``, then
+        ``integrate`` of the view's planes at the view's own ``w2c`` buffer with its truncation status as ``skip``: four launches,
+        nothing read on the host.  Returns the ``ViewImage``."""
+        return self._render_then(self.integrate, engine, view, time_idx, w2c, intrinsics, first_w2c, near, far, **kw)
+
+    def _triangles(self, min_weight, keys, count, method="tetrahedra"):
+        cap = 0 if keys is None else int(keys.shape[0])
+        self._launch("cubes" if method == "cubes" else "triangles", float(min_weight), keys.data_ptr() if cap else None, cap, count.data_ptr())
+
+    def _vertices(self, uniq, vertices, colors):
+        self._launch("vertices", uniq.data_ptr(), uniq.numel(), vertices.data_ptr(), colors.data_ptr())
 
     def extract(self, min_weight=1.0, capacity=None, method="tetrahedra"):
         """The zero surface over the cells whose eight corners have ``weight >= min_weight`` as a ``Mesh`` on the device.  One pass over
@@ -163,82 +235,34 @@ class TsdfVolume(_Surface):
     x fastest; ``tsdf``, ``weight``, ``r``, ``g``, ``b`` are [nz, ny, nx] float32 views of one allocation.  Every method enqueues on the
     current stream; only ``extract`` reads (one count)."""
 
+    _prefix = "splat_tsdf_"
+
     def __init__(self, origin, dims, voxel_size, trunc=None, device="cuda:0"):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise RuntimeError("TsdfVolume needs a CUDA/HIP device; the HIP library has no CPU path")
-        self.origin = tuple(float(v) for v in origin)
-        self.dims = tuple(int(d) for d in dims)
-        self.voxel_size = float(voxel_size)
-        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
-        v = self.struct = _capi.SplatTsdfVolume()
-        v.nx, v.ny, v.nz = self.dims
-        v.origin[:] = self.origin
-        v.voxel, v.trunc = self.voxel_size, self.trunc
-        self.L = _capi.lib()
-        need = int(self.L.splat_tsdf_bytes(C.byref(v)))
+        super().__init__(_capi.SplatTsdfVolume(), origin, dims, voxel_size, trunc, device)
+        self._grid_to_struct()
+        need = int(self.L.splat_tsdf_bytes(C.byref(self.struct)))
         if len(self.origin) != 3 or len(self.dims) != 3 or need == 0:
             raise ValueError(f"a volume needs positive dims (fewer than 2^40 grid points), voxel size and trunc (got {self.dims}, {self.voxel_size}, {self.trunc})")
         nx, ny, nz = self.dims
         self.data = torch.empty(5, nz, ny, nx, dtype=torch.float32, device=self.dev)
         assert self.data.numel() * 4 == need
         self.tsdf, self.weight, self.r, self.g, self.b = self.data.unbind(0)
+        v = self.struct
         v.tsdf, v.weight, v.r, v.g, v.b = (t.data_ptr() for t in self.data.unbind(0))
-        self.skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)          # launches a non-zero ``skip`` turned away
-        self._keep = None
         self.reset()
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream
 
     def arrays(self):
         return dict(zip(VOLUME_ARRAYS, self.data.unbind(0)))
 
     def reset(self):
         """tsdf = 1, weight and colours 0, the skipped counter 0."""
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_reset(C.byref(self.struct), self._stream()), "splat_tsdf_reset")
+        self._launch("reset")
         self.skipped.zero_()
         return self
-
-    def integrate(self, out6, w2c, intrinsics, sil_thres=0.99, depth_max=0.0, weight_max=0.0, skip=None):
-        """One view into the volume: ``out6`` [>= 5, H, W] float32 on the device (r, g, b, depth, silhouette as the composite leaves
-        them: depth is sum w z, divided by the silhouette here; a view into a larger buffer is fine), ``w2c`` float32 [4, 4] on the
-        device, ``intrinsics`` a 3 x 3 or (fx, fy, cx, cy) on the host.  ``skip``: int32 [1] on the device (a ``ViewImage.truncated``);
-        non-zero when the launch runs: the volume stays as it is and ``skipped`` counts one.  One launch, nothing read."""
-        w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, weight_max, skip, self.skipped, self.dev)
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_integrate(C.byref(self.struct), C.byref(w), self._stream()), "splat_tsdf_integrate")
-        self._keep = keep
-        return self
-
-    def integrate_view(self, engine, view, time_idx=None, w2c=None, intrinsics=None, first_w2c=None, near=0.01, far=100, **kw):
-        """``engine.render_view(view, ..., rgb8=False)`` at a pose of the map (``time_idx``, with ``first_w2c``) or at ``w2c``, then
-        ``integrate`` of the view's planes at the view's own ``w2c`` buffer with its truncation status as ``skip``: four launches,
-        nothing read on the host.  Returns the ``ViewImage``."""
-        with torch.no_grad():
-            img = engine.render_view(view, w2c=w2c, time_idx=time_idx, intrinsics=intrinsics, first_w2c=first_w2c, near=near, far=far, rgb8=False)
-        self.integrate(img.out6, view.w2c, intrinsics, skip=img.truncated, **kw)
-        return img
-
-    def _triangles(self, min_weight, keys, count, method="tetrahedra"):
-        cap = 0 if keys is None else int(keys.shape[0])
-        name = "splat_tsdf_cubes" if method == "cubes" else "splat_tsdf_triangles"
-        with torch.cuda.device(self.dev):
-            _capi.check(getattr(self.L, name)(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
-                                              count.data_ptr(), self._stream()), name)
 
     def _default_capacity(self):                            # a closed surface crosses O(n^2) of n^3 cells, ~4 triangles each
         nx, ny, nz = self.dims
         return 16 * (nx * ny + ny * nz + nz * nx) + 4096
-
-    def _vertices(self, uniq, vertices, colors):
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_vertices(C.byref(self.struct), uniq.data_ptr(), uniq.numel(), vertices.data_ptr(), colors.data_ptr(),
-                                                   self._stream()), "splat_tsdf_vertices")
-
-
-BRICK_POINTS = 2048                  # (csrc/tsdf_math.h kTsdfBrickPoints)
 
 
 def brick_shapes():
@@ -264,22 +288,15 @@ class SparseTsdfVolume(_Surface):
     Every method enqueues on the current stream; ``marked_count`` and ``extract`` read one number each.  ``capacity_bricks``: room in
     the pool from the start (it grows by reallocation otherwise)."""
 
+    _prefix = "splat_tsdf_sparse_"
+
     def __init__(self, origin, dims, voxel_size, trunc=None, capacity_bricks=0, device="cuda:0", brick=None):
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise RuntimeError("SparseTsdfVolume needs a CUDA/HIP device; the HIP library has no CPU path")
-        self.origin = tuple(float(v) for v in origin)
-        self.dims = tuple(int(d) for d in dims)
-        self.voxel_size = float(voxel_size)
-        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
-        self.L = _capi.lib()
+        super().__init__(_capi.SplatTsdfSparse(), origin, dims, voxel_size, trunc, device)
         self.brick = tuple(int(b) for b in (brick or brick_shapes()[0]))
-        v = self.struct = _capi.SplatTsdfSparse()
         if len(self.origin) != 3 or len(self.dims) != 3 or len(self.brick) != 3:
             raise ValueError(f"a volume needs three dims, an origin and a brick shape (got {self.dims}, {self.origin}, {self.brick})")
-        v.nx, v.ny, v.nz = self.dims
-        v.origin[:] = self.origin
-        v.voxel, v.trunc = self.voxel_size, self.trunc
+        self._grid_to_struct()
+        v = self.struct
         v.brick[:] = self.brick
         v.slots = 0
         if int(self.L.splat_tsdf_sparse_bytes(C.byref(v))) == 0:
@@ -292,15 +309,10 @@ class SparseTsdfVolume(_Surface):
         self.slots = 0
         self.pool = self.brick_of_slot = None
         self._capacity = 0
-        self.skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)          # ``integrate`` launches a non-zero ``skip`` turned away
-        self.mark_skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)     # ... and ``mark`` launches
-        self._keep = None
+        self.mark_skipped = torch.zeros(1, dtype=torch.int32, device=self.dev)     # ``mark`` launches a non-zero ``skip`` turned away
         v.directory = self.directory.data_ptr()
         if capacity_bricks:
             self._reserve(int(capacity_bricks))
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.dev).cuda_stream
 
     def _bind(self):
         v = self.struct
@@ -339,17 +351,13 @@ class SparseTsdfVolume(_Surface):
         """Flags the bricks one view needs (``integrate``'s arguments; ``weight_max`` plays no part).  A non-zero ``skip`` leaves the
         flags as they are and ``mark_skipped`` counts one.  One launch, nothing read."""
         w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, 0.0, skip, self.mark_skipped, self.dev)
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_sparse_mark(C.byref(self.struct), C.byref(w), self.flags.data_ptr(), self._stream()), "splat_tsdf_sparse_mark")
+        self._launch("mark", C.byref(w), self.flags.data_ptr())
         self._keep = keep
         return self
 
     def mark_view(self, engine, view, time_idx=None, w2c=None, intrinsics=None, first_w2c=None, near=0.01, far=100, weight_max=0.0, **kw):
         """``integrate_view`` with ``mark`` in place of ``integrate``.  Returns the ``ViewImage``."""
-        with torch.no_grad():
-            img = engine.render_view(view, w2c=w2c, time_idx=time_idx, intrinsics=intrinsics, first_w2c=first_w2c, near=near, far=far, rgb8=False)
-        self.mark(img.out6, view.w2c, intrinsics, skip=img.truncated, **kw)
-        return img
+        return self._render_then(self.mark, engine, view, time_idx, w2c, intrinsics, first_w2c, near, far, **kw)
 
     def _new(self):
         return (self.flags != 0) & (self.directory < 0)
@@ -370,10 +378,7 @@ class SparseTsdfVolume(_Surface):
         total = self.slots + count
         need = self.bytes_for(total)
         if need > max_bytes or total >= 2 ** 31:
-            nx, ny, nz = self.dims
-            raise ValueError(f"a sparse {nx} x {ny} x {nz} volume at voxel size {self.voxel_size} with {total} bricks of {BRICK_POINTS} grid points needs "
-                             f"{need} bytes ({need / 2 ** 30:.2f} GiB), beyond max_bytes = {max_bytes}: raise the voxel size, pass tighter bounds "
-                             f"or a larger max_bytes")
+            raise _beyond_max_bytes(self.dims, self.voxel_size, need, max_bytes, bricks=total)
         if count == 0:
             return 0
         self._reserve(max(total, self._capacity))
@@ -385,34 +390,11 @@ class SparseTsdfVolume(_Surface):
         self.brick_of_slot.scatter_(0, where, torch.arange(self.num_bricks, dtype=torch.int32, device=self.dev))
         first, self.slots = self.slots, total
         self._bind()
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_sparse_reset_slots(C.byref(self.struct), first, count, self._stream()), "splat_tsdf_sparse_reset_slots")
+        self._launch("reset_slots", first, count)
         return count
-
-    def integrate(self, out6, w2c, intrinsics, sil_thres=0.99, depth_max=0.0, weight_max=0.0, skip=None):
-        """``TsdfVolume.integrate`` on every allocated brick: the same arithmetic, the same bits.  One launch, nothing read."""
-        w, keep = _tsdf_view(out6, w2c, intrinsics, sil_thres, depth_max, weight_max, skip, self.skipped, self.dev)
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_sparse_integrate(C.byref(self.struct), C.byref(w), self._stream()), "splat_tsdf_sparse_integrate")
-        self._keep = keep
-        return self
-
-    integrate_view = TsdfVolume.integrate_view
-
-    def _triangles(self, min_weight, keys, count, method="tetrahedra"):
-        cap = 0 if keys is None else int(keys.shape[0])
-        name = "splat_tsdf_sparse_cubes" if method == "cubes" else "splat_tsdf_sparse_triangles"
-        with torch.cuda.device(self.dev):
-            _capi.check(getattr(self.L, name)(C.byref(self.struct), float(min_weight), keys.data_ptr() if cap else None, cap,
-                                              count.data_ptr(), self._stream()), name)
 
     def _default_capacity(self):                            # the band is several bricks thick and the surface crosses some of them
         return 768 * self.slots + 4096
-
-    def _vertices(self, uniq, vertices, colors):
-        with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_tsdf_sparse_vertices(C.byref(self.struct), uniq.data_ptr(), uniq.numel(), vertices.data_ptr(),
-                                                          colors.data_ptr(), self._stream()), "splat_tsdf_sparse_vertices")
 
     def point_offsets(self):
         """int64 [nz, ny, nx]: every grid point's offset in the pool's arrays (slot 2048 + local), -1 where its brick is not allocated.
@@ -429,9 +411,7 @@ class SparseTsdfVolume(_Surface):
         small volumes: ValueError beyond ``max_bytes``, like ``plan_volume``."""
         need = volume_bytes(self.dims)
         if need > max_bytes:
-            nx, ny, nz = self.dims
-            raise ValueError(f"a {nx} x {ny} x {nz} volume at voxel size {self.voxel_size} needs {need} bytes ({need / 2 ** 30:.2f} GiB), "
-                             f"beyond max_bytes = {max_bytes}")
+            raise _beyond_max_bytes(self.dims, self.voxel_size, need, max_bytes, advice=False)
         dense = TsdfVolume(self.origin, self.dims, self.voxel_size, self.trunc, self.dev)
         if self.slots:
             at = self.point_offsets()
@@ -525,11 +505,20 @@ def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, 
                                                    extra=volume.marked_count_tensor)
         volume.allocate(max_bytes, count=None if volume.repeated_marks else count)      # (views marked again: the count is read again)
     volume.repeated, _ = _views_pass(frames, lambda fr: volume.integrate_view(engine, view, **pose(fr), **kw), volume.skipped, view)
-    mesh = volume.extract(min_weight, method=method)
-    if clean is not None:
-        from .mesh_clean import clean_mesh
-        mesh = clean_mesh(mesh, device=engine.dev, **clean)
+    mesh = _cleaned(volume.extract(min_weight, method=method), clean, engine.dev)
     return (mesh, volume) if return_volume else mesh
+
+
+def _cleaned(mesh, clean, device, cleaning=None):
+    """``mesh`` as ``clean`` (what ``clean_options`` returned) asks for it: as it is (None), or ``clean_mesh`` of it with those
+    keywords; ``cleaning``, a dict, then receives the report."""
+    if clean is None:
+        return mesh
+    from .mesh_clean import clean_mesh
+    mesh, found = clean_mesh(mesh, device=device, report=True, **clean)
+    if cleaning is not None:
+        cleaning.update(found)
+    return mesh
 
 
 def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None, sil_thres=0.99, depth_max=0.0, bounds=None,
@@ -542,25 +531,24 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
     from . import slam
     from .export import save_mesh_ply
     from .fused import FusedEngine
-    from .mesh_clean import clean_mesh, clean_options, format_cleaning
+    from .mesh_clean import clean_options, format_cleaning
     from .view import load_map
     check_method(method)
     clean = clean_options(clean)
+    found = {} if cleaning is None else cleaning
     dev = torch.device(device)
     params, variables, k, first_w2c, (W0, H0) = load_map(path, dev)
     with np.load(path) as z:
         keyframes = [int(t) for t in z['keyframe_time_indices']] if 'keyframe_time_indices' in z else []
     W, H = size or (W0, H0)
+    intrinsics = _scaled_intrinsics(k, (W, H), (W0, H0))
     with torch.no_grad():
         cam = slam.setup_camera(W0, H0, k, first_w2c.cpu().numpy(), device=dev)
         engine = FusedEngine(params, cam, variables=variables)
         frames = keyframes or list(range(0, engine.num_frames, max(int(every), 1)))
-        mesh = extract_mesh(engine, frames, (W, H), _scaled_intrinsics(k, (W, H), (W0, H0)), voxel_size=voxel_size, trunc=trunc, bounds=bounds,
-                            max_bytes=max_bytes, sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse, method=method)
-        if clean is not None:
-            mesh, found = clean_mesh(mesh, device=dev, report=True, **clean)
-            if cleaning is not None:
-                cleaning.update(found)
+        mesh = extract_mesh(engine, frames, (W, H), intrinsics, voxel_size=voxel_size, trunc=trunc, bounds=bounds, max_bytes=max_bytes,
+                            sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse, method=method)
+        mesh = _cleaned(mesh, clean, dev, found)            # (not through extract_mesh: the report is wanted)
     save_mesh_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), mesh.colors.cpu().numpy())
     if verbose:
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces from {len(frames)} views", flush=True)
@@ -569,8 +557,7 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
     if views is not None:
         from . import mesh_view
         poses, _, _ = mesh_view.params_poses(path)
-        written = mesh_view.render_trajectory(mesh, poses, views, _scaled_intrinsics(k, (W, H), (W0, H0)), (W, H), every=max(int(every), 1), device=dev,
-                                              mode=views_mode)
+        written = mesh_view.render_trajectory(mesh, poses, views, intrinsics, (W, H), every=max(int(every), 1), device=dev, mode=views_mode)
         if verbose:
             print(f"{views}: {len(written)} pictures of the mesh ({views_mode})", flush=True)
     return mesh
