@@ -9,7 +9,8 @@ after a warm-up, ``--repeats`` times:
              as tests: an upper bound) and their share of the HBM peak (6.29 TB/s measured with a float4 copy); the clear and the finish
              alone; the same render with a load in front of the atomic min that filters the hits and with a plain store in its place
              (``splat_debug_option(6, .)``), which is what the z-buffer's atomic costs.  The thresholds go through
-             ``splat_debug_option(5, .)``.
+             ``splat_debug_option(5, .)``.  Per view the SHA-256 of the product's plane (``mesh_run.digest``), taken once and outside
+             every timed loop: two builds of the library render the same when these lines agree.
   seen       S (``splat_mesh_seen``) on the mesh's vertices x ``--poses`` ring poses, in chunks of ``--chunk`` views, without and with
              depth planes: vertex-views per second; the torch expression of the same predicate (batched matmul and masks) alongside,
              and whether both count the same.
@@ -101,6 +102,7 @@ def path_account(m, w2c, intr, size, near, split):
 
 
 def part_render(args, m, intr, size):
+    import mesh_run
     import numpy as np
     import torch
     from splatam_amd import mesh_render as MR
@@ -138,6 +140,7 @@ def part_render(args, m, intr, size):
                 row[f"zbuffer_{label}_us"] = rep(lambda: MR.render_depth(m.vertices, m.faces, dev_pose, intr, size, out=plane))
             L.splat_debug_option(6, 0)
             row["hits"] = hit_account(m, dev_pose, intr, size, plane)
+            row["sha256_depth"] = mesh_run.digest([plane])              # (the product's plane; outside every timed loop)
             out["views"][name] = row
     finally:
         L.splat_debug_option(5, 0)

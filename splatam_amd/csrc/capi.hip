@@ -545,14 +545,19 @@ static bool valid_nn_grid(const SplatNnGrid *g) {
     return (long long)g->dims[0] * g->dims[1] <= SPLAT_NN_MAX_CELLS && (long long)g->dims[0] * g->dims[1] * (long long)g->dims[2] <= SPLAT_NN_MAX_CELLS;
 }
 
+// the rule of every entry point that takes a mesh: counts that are not negative, and an array wherever its count is positive
+static bool valid_mesh_arrays(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces) {
+    return num_vertices >= 0 && num_faces >= 0 && (num_faces == 0 || faces) && (num_vertices == 0 || vertices);
+}
+
 int splat_mesh_areas(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, double *area, void *stream) {
-    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && (!faces || !area)) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (!valid_mesh_arrays(vertices, num_vertices, faces, num_faces) || (num_faces > 0 && !area)) return SPLAT_E_INVALID;
     return check(launch_mesh_areas(vertices, num_vertices, faces, num_faces, area, (hipStream_t)stream));
 }
 
 int splat_mesh_sample(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const double *prefix, uint64_t seed,
                       int64_t n, float *points, int32_t *face, void *stream) {
-    if (num_vertices < 0 || num_faces < 0 || n < 0 || (num_faces > 0 && (!faces || !prefix)) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (!valid_mesh_arrays(vertices, num_vertices, faces, num_faces) || n < 0 || (num_faces > 0 && !prefix)) return SPLAT_E_INVALID;
     if (n > 0 && (!points || !face)) return SPLAT_E_INVALID;
     return check(launch_mesh_sample(vertices, num_vertices, faces, num_faces, prefix, seed, (long long)n, points, face, (hipStream_t)stream));
 }
@@ -611,8 +616,8 @@ int splat_mesh_components(const int32_t *faces, int32_t num_faces, int32_t num_v
 
 int splat_mesh_component_stats(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const int32_t *labels,
                                int32_t *num_v, int32_t *num_f, int64_t *area_q, int32_t *lo, int32_t *hi, void *stream) {
-    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces)) return SPLAT_E_INVALID;
-    if (num_vertices > 0 && (!vertices || !labels || !num_v || !num_f || !area_q || !lo || !hi)) return SPLAT_E_INVALID;
+    if (!valid_mesh_arrays(vertices, num_vertices, faces, num_faces)) return SPLAT_E_INVALID;
+    if (num_vertices > 0 && (!labels || !num_v || !num_f || !area_q || !lo || !hi)) return SPLAT_E_INVALID;
     return check(launch_mesh_component_stats(vertices, num_vertices, faces, num_faces, labels, num_v, num_f, area_q, lo, hi, (hipStream_t)stream));
 }
 
@@ -622,11 +627,12 @@ static bool valid_mesh_view(const SplatMeshView *v) {
     if (!v || v->width <= 0 || v->height <= 0 || (long long)v->width * v->height > 0x3fffffffLL) return false;
     return finite_f(v->fx) && finite_f(v->fy) && v->fx != 0.f && v->fy != 0.f && finite_f(v->cx) && finite_f(v->cy);
 }
+// a view to render through: a valid view with a pose and a positive finite near plane
+static bool valid_mesh_camera(const SplatMeshView *v) { return valid_mesh_view(v) && v->w2c && v->near_z > 0.f && finite_f(v->near_z); }
 
 int splat_mesh_depth(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const SplatMeshView *view, float *depth,
                      void *stream) {
-    if (!valid_mesh_view(view) || !view->w2c || !(view->near_z > 0.f) || !finite_f(view->near_z) || !depth) return SPLAT_E_INVALID;
-    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (!valid_mesh_camera(view) || !valid_mesh_arrays(vertices, num_vertices, faces, num_faces) || !depth) return SPLAT_E_INVALID;
     return check(launch_mesh_depth(vertices, num_vertices, faces, num_faces, *view, depth, (hipStream_t)stream));
 }
 
@@ -645,23 +651,21 @@ int splat_mesh_depth_compare(const float *a, const float *b, int64_t n, double *
 // the mesh shade layer (csrc/meshshade.hip)
 int splat_mesh_vertex_normals(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, int64_t *accum, float *normals,
                               void *stream) {
-    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces)) return SPLAT_E_INVALID;
-    if (num_vertices > 0 && (!vertices || !accum || !normals)) return SPLAT_E_INVALID;
+    if (!valid_mesh_arrays(vertices, num_vertices, faces, num_faces)) return SPLAT_E_INVALID;
+    if (num_vertices > 0 && (!accum || !normals)) return SPLAT_E_INVALID;
     return check(launch_mesh_vertex_normals(vertices, num_vertices, faces, num_faces, accum, normals, (hipStream_t)stream));
 }
 
 int splat_mesh_visibility(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const SplatMeshView *view,
                           uint64_t *keys, void *stream) {
-    if (!valid_mesh_view(view) || !view->w2c || !(view->near_z > 0.f) || !finite_f(view->near_z) || !keys) return SPLAT_E_INVALID;
-    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (!valid_mesh_camera(view) || !valid_mesh_arrays(vertices, num_vertices, faces, num_faces) || !keys) return SPLAT_E_INVALID;
     return check(launch_mesh_visibility(vertices, num_vertices, faces, num_faces, *view, keys, (hipStream_t)stream));
 }
 
 int splat_mesh_shade(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const float *colors, const float *normals,
                      const SplatMeshView *view, const uint64_t *keys, const SplatMeshShade *args, uint8_t *rgb8, float *depth, int32_t *face,
                      float *normal, void *stream) {
-    if (!valid_mesh_view(view) || !view->w2c || !(view->near_z > 0.f) || !finite_f(view->near_z) || !keys || !args || !rgb8) return SPLAT_E_INVALID;
-    if (num_vertices < 0 || num_faces < 0 || (num_faces > 0 && !faces) || (num_vertices > 0 && !vertices)) return SPLAT_E_INVALID;
+    if (!valid_mesh_camera(view) || !valid_mesh_arrays(vertices, num_vertices, faces, num_faces) || !keys || !args || !rgb8) return SPLAT_E_INVALID;
     if (args->samples < 1 || args->samples > 4 || view->width % args->samples != 0 || view->height % args->samples != 0) return SPLAT_E_INVALID;
     if (args->mode < SPLAT_MESH_SHADE_COLOR || args->mode > SPLAT_MESH_SHADE_DEPTH) return SPLAT_E_INVALID;
     if (args->mode == SPLAT_MESH_SHADE_DEPTH && !args->lut) return SPLAT_E_INVALID;

@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(kBlock) lpips_finish_kernel(const double *part
     if (threadIdx.x == 0) *out = total;
 }
 
-unsigned blocks_for(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+unsigned blocks_for(long long n) { return splat::blocks_for(n, kBlock); }
 
 }  // namespace
 

@@ -23,7 +23,7 @@ namespace {
 
 constexpr int kBlock = 256;
 
-unsigned blocks_for(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+unsigned blocks_for(long long n) { return splat::blocks_for(n, kBlock); }
 
 __global__ void __launch_bounds__(kBlock) mc_init_kernel(int32_t *parent, int32_t V) {
     const long long v = (long long)blockIdx.x * kBlock + threadIdx.x;

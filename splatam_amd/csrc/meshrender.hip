@@ -2,12 +2,8 @@
 // vertex, and the sums depth L1 between two such images is made of.  The arithmetic is meshrender_math.h's.
 //
 //   R0 mr_clear_kernel    the plane, as uint32, to the bit pattern of +inf (16-byte stores where the plane allows).
-//   R1 mr_raster_kernel   one lane per triangle sets it up (camera-space vertices, the three edge planes, the normal, the box).  A lane
-//                         whose box holds at most 16 pixels (kMrSplit) walks it alone.  The others are taken one after the other by the whole
-//                         WAVE: the owner's lane broadcasts the 13 floats and the box, and lane l tests pixels l, l + 64, ... of the box
-//                         (a running row and column: no division per pixel),
-//                         so no lane's loop is proportional to a large triangle's pixel count while 63 idle.  Large faces are found by
-//                         a ballot, not a list: nothing is deferred, nothing can overflow.  Every loop is bounded by width x height.
+//   R1 mr_raster_kernel   the raster walk of mesh_device.h (mesh_raster_walk: one lane per triangle, boxes of at most kMrSplit = 16
+//                         pixels walked by their lane, the others by the whole wave), shared with meshshade.hip's V1.
 //                         A hit enters the plane by an integer atomic min on the float's bits (positive floats order as their bits).
 //                         A minimum does not depend on order: the same bits on every run.  (A plain load in front of the atomic, to
 //                         spare it where the pixel already holds something nearer, was measured and lost.)
@@ -16,18 +12,14 @@
 //                         no atomics.
 //   D  mr_compare_kernel  a workgroup per slice of the two planes, per lane running sums in double, a tree over the 256 lanes in LDS,
 //                         one row of partials per workgroup; mr_compare_finish_kernel adds the rows in workgroup order.  No atomics.
-#include "splat_device.h"
-#include "meshrender_math.h"
+#include "mesh_device.h"
 
 namespace splat {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kWave = 64;
 constexpr uint32_t kInfBits = 0x7f800000u;
 constexpr int kCmp = 6;                 // partial sums per workgroup of D
-
-unsigned blocks_for(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
 __global__ void __launch_bounds__(kBlock) mr_clear_kernel(uint32_t *plane, long long n, int vec) {
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -68,59 +60,12 @@ __device__ __forceinline__ void mr_put(uint32_t *plane, uint32_t o, float z) {
     else if (MODE == 0 || bits < plane[o]) atomicMin(plane + o, bits);
 }
 
-// Faces are [F][3] int32 and vertices [V][3] float32: rows of 12 bytes, which no 16-byte access fits without straddling rows, so a
-// lane reads its three indices and nine coordinates as 4-byte loads (consecutive lanes read consecutive rows: the wave's loads of the
-// faces are contiguous).  Pixel offsets fit 32 bits: the entry point refuses more than 2^30 - 1 pixels.
+// the walk is mesh_device.h's; a hit is mr_put<MODE>'s and needs no face index
 template <int MODE>
 __global__ void __launch_bounds__(kBlock) mr_raster_kernel(MrPinhole cam, float near_z, const float *__restrict__ w2c,
                                                            const float *__restrict__ vertices, int32_t V, const int32_t *__restrict__ faces,
                                                            int32_t F, int split, uint32_t *plane) {
-    const long long f = (long long)blockIdx.x * kBlock + threadIdx.x;
-    float m[12];
-    for (int k = 0; k < 12; ++k) m[k] = w2c[k];
-    MrFace face = {};                                                   // (kind 0: nothing)
-    if (f < F) {
-        const int32_t idx[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
-        mr_face_setup(cam, near_z, m, vertices, V, idx, split, face);
-    }
-    if (face.kind == kMrSmall) {
-        for (int j = face.j0; j <= face.j1; ++j) {
-            const float dy = mr_ray_y(cam, j);
-            for (int i = face.i0; i <= face.i1; ++i) {
-                float z;
-                if (mr_hit(face, near_z, mr_ray_x(cam, i), dy, z)) mr_put<MODE>(plane, (uint32_t)j * cam.W + i, z);
-            }
-        }
-    }
-    // (no lane has left: the ballot and the broadcasts below need the whole wave)
-    unsigned long long large = __ballot(face.kind == kMrLarge);
-    const int lane = threadIdx.x & (kWave - 1);
-    while (large) {
-        const int src = __ffsll((long long)large) - 1;
-        large &= large - 1;
-        MrFace g;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) g.e[a][b] = __shfl(face.e[a][b], src, kWave);
-        for (int a = 0; a < 3; ++a) g.n[a] = __shfl(face.n[a], src, kWave);
-        g.na = __shfl(face.na, src, kWave);
-        g.i0 = __shfl(face.i0, src, kWave); g.i1 = __shfl(face.i1, src, kWave);
-        g.j0 = __shfl(face.j0, src, kWave); g.j1 = __shfl(face.j1, src, kWave);
-        // lane l tests pixels l, l + 64, ... of the box in row order.  Two divisions per FACE (wave-uniform), none per pixel: a step of
-        // 64 pixels is `rows` rows and `cols` columns, with one carry when the column leaves the box.
-        const int bw = g.i1 - g.i0 + 1;
-        const int rows = kWave / bw, cols = kWave % bw;
-        int j = g.j0 + lane / bw, i = g.i0 + lane % bw;                 // (at most width x height / 64 trips: j grows every trip or two)
-        float dy = mr_ray_y(cam, j);
-        int row = j;
-        while (j <= g.j1) {
-            if (j != row) { dy = mr_ray_y(cam, j); row = j; }
-            float z;
-            if (mr_hit(g, near_z, mr_ray_x(cam, i), dy, z)) mr_put<MODE>(plane, (uint32_t)j * cam.W + i, z);
-            i += cols;
-            j += rows;
-            if (i > g.i1) { i -= bw; ++j; }
-        }
-    }
+    mesh_raster_walk<kBlock>(cam, near_z, w2c, vertices, V, faces, F, split, [=](uint32_t o, float z, uint32_t) { mr_put<MODE>(plane, o, z); });
 }
 
 __global__ void __launch_bounds__(kBlock) mr_seen_kernel(MrPinhole cam, const float *__restrict__ w2c, int32_t n,
@@ -178,13 +123,6 @@ __global__ void __launch_bounds__(kBlock) mr_compare_finish_kernel(const double 
     }
     row[0] = acc[0]; row[1] = acc[1]; row[2] = acc[2]; row[3] = acc[3]; row[4] = acc[4];
     row[5] = (double)n; row[6] = acc[5]; row[7] = 0.0;
-}
-
-MrPinhole pinhole_of(const SplatMeshView &v) {
-    MrPinhole c;
-    c.W = v.width; c.H = v.height;
-    c.fx = v.fx; c.fy = v.fy; c.cx = v.cx; c.cy = v.cy;
-    return c;
 }
 
 }  // namespace

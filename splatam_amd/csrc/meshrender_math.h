@@ -68,6 +68,14 @@ struct MrPinhole {
     float fx, fy, cx, cy;
 };
 
+// k4: (fx, fy, cx, cy)
+SPLAT_HD MrPinhole mr_pinhole(int W, int H, const float *k4) {
+    MrPinhole c;
+    c.W = W; c.H = H;
+    c.fx = k4[0]; c.fy = k4[1]; c.cx = k4[2]; c.cy = k4[3];
+    return c;
+}
+
 struct MrFace {
     float e[3][3];                      // edge planes ab, bc, ca
     float n[3], na;                     // normal and n . a
@@ -188,6 +196,23 @@ SPLAT_HD bool mr_hit(const MrFace &f, float near_z, float dx, float dy, float &z
     if (!((e0 >= 0.f && e1 >= 0.f && e2 >= 0.f) || (e0 <= 0.f && e1 <= 0.f && e2 <= 0.f))) return false;
     z = mr_div(f.na, mr_plane(f.n, dx, dy));
     return z >= near_z && z < INFINITY;
+}
+
+// One walker alone over a face's own box, row by row: sink(offset, z) for every pixel the face hits, offset = j W + i (it fits 32
+// bits: a view has fewer than 2^30 pixels).  Returns the pixel tests made: the box's area, at most width x height.  The one-lane
+// branch of the device walk (mesh_device.h) and the host models of the depth and the key plane are this loop.
+template <typename Sink>
+SPLAT_HD long long mr_walk_box(const MrPinhole &c, const MrFace &f, float near_z, Sink sink) {
+    long long tests = 0;
+    for (int j = f.j0; j <= f.j1; ++j) {
+        const float dy = mr_ray_y(c, j);
+        for (int i = f.i0; i <= f.i1; ++i) {
+            float z;
+            ++tests;
+            if (mr_hit(f, near_z, mr_ray_x(c, i), dy, z)) sink((uint32_t)j * c.W + i, z);
+        }
+    }
+    return tests;
 }
 
 // whether the view with w2c rows m[12] sees p; `depth` (or NULL): the view's plane

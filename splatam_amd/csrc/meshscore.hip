@@ -33,7 +33,6 @@ MsGrid grid_of(const SplatNnGrid &g) {
     m.count = g.count;
     return m;
 }
-unsigned blocks_for(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
 __global__ void __launch_bounds__(kBlock) ms_areas_kernel(const float *vertices, int32_t V, const int32_t *faces, int32_t F, double *area) {
     const int32_t f = blockIdx.x * kBlock + threadIdx.x;

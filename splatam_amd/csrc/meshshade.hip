@@ -7,23 +7,20 @@
 //                         are exact and do not depend on order: the same bits on every run and for every order of the faces.
 //   N2 ms_normal_vertices one lane per vertex: the three sums, normalised in double, rounded once.
 //   V0 ms_fill64_kernel   the key plane to all ones.
-//   V1 ms_raster_kernel   meshrender.hip's R1 with an identity attached: the same setup, the same box, the same one-lane / whole-wave
-//                         split at kMrSplit, the same mr_hit.  A hit enters the plane by a 64-bit unsigned atomic min of
-//                         (bits(z) << 32) | face, which returns nothing the lane waits for (a guarding load in front of it lost in
-//                         R1: profiles/mesh_render.md 2).  No lane leaves before the ballot; every loop is bounded by the box.
+//   V1 ms_raster_kernel   meshrender.hip's R1 with an identity attached: the SAME walk (mesh_device.h's mesh_raster_walk, one
+//                         definition for both), which hands every hit the index of its face.  A hit enters the plane by a 64-bit
+//                         unsigned atomic min of (bits(z) << 32) | face, which returns nothing the lane waits for (a guarding load in
+//                         front of it lost in R1: profiles/mesh_render.md 2).
 //   S  ms_shade_kernel    one lane per OUTPUT pixel: its samples x samples keys, each decoded (the face id is range-checked before any
 //                         load), set up again and shaded (msh_sample), summed and written as three bytes; with samples == 1 the depth,
 //                         face and normal planes too.  The only loop is bounded by samples^2 <= 16.
-#include "splat_device.h"
+#include "mesh_device.h"
 #include "meshshade_math.h"
 
 namespace splat {
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kWave = 64;
-
-unsigned blocks_for(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
 // n words of 8 bytes to `value`; vec: the buffer starts on 16 bytes and lane i stores words 2 i and 2 i + 1 at once
 __global__ void __launch_bounds__(kBlock) ms_fill64_kernel(uint64_t *p, long long n, uint64_t value, int vec) {
@@ -66,55 +63,11 @@ __device__ __forceinline__ void ms_put(uint64_t *keys, uint32_t o, float z, uint
     __hip_atomic_fetch_min((unsigned long long *)keys + o, (unsigned long long)msh_key(z, f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// meshrender.hip's mr_raster_kernel, hit for hit; pixel offsets fit 32 bits: the entry point refuses more than 2^30 - 1 pixels
+// the walk is mesh_device.h's, hit for hit meshrender.hip's mr_raster_kernel; a hit is ms_put's
 __global__ void __launch_bounds__(kBlock) ms_raster_kernel(MrPinhole cam, float near_z, const float *__restrict__ w2c,
                                                            const float *__restrict__ vertices, int32_t V, const int32_t *__restrict__ faces,
                                                            int32_t F, int split, uint64_t *keys) {
-    const long long f = (long long)blockIdx.x * kBlock + threadIdx.x;
-    float m[12];
-    for (int k = 0; k < 12; ++k) m[k] = w2c[k];
-    MrFace face = {};                                                   // (kind 0: nothing)
-    if (f < F) {
-        const int32_t idx[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
-        mr_face_setup(cam, near_z, m, vertices, V, idx, split, face);
-    }
-    if (face.kind == kMrSmall) {
-        for (int j = face.j0; j <= face.j1; ++j) {
-            const float dy = mr_ray_y(cam, j);
-            for (int i = face.i0; i <= face.i1; ++i) {
-                float z;
-                if (mr_hit(face, near_z, mr_ray_x(cam, i), dy, z)) ms_put(keys, (uint32_t)j * cam.W + i, z, (uint32_t)f);
-            }
-        }
-    }
-    // (no lane has left: the ballot and the broadcasts below need the whole wave)
-    unsigned long long large = __ballot(face.kind == kMrLarge);
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t first = (uint32_t)(f - lane);                        // the face of lane 0 of this wave
-    while (large) {
-        const int src = __ffsll((long long)large) - 1;
-        large &= large - 1;
-        MrFace g;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) g.e[a][b] = __shfl(face.e[a][b], src, kWave);
-        for (int a = 0; a < 3; ++a) g.n[a] = __shfl(face.n[a], src, kWave);
-        g.na = __shfl(face.na, src, kWave);
-        g.i0 = __shfl(face.i0, src, kWave); g.i1 = __shfl(face.i1, src, kWave);
-        g.j0 = __shfl(face.j0, src, kWave); g.j1 = __shfl(face.j1, src, kWave);
-        const int bw = g.i1 - g.i0 + 1;
-        const int rows = kWave / bw, cols = kWave % bw;
-        int j = g.j0 + lane / bw, i = g.i0 + lane % bw;                 // (at most width x height / 64 trips: j grows every trip or two)
-        float dy = mr_ray_y(cam, j);
-        int row = j;
-        while (j <= g.j1) {
-            if (j != row) { dy = mr_ray_y(cam, j); row = j; }
-            float z;
-            if (mr_hit(g, near_z, mr_ray_x(cam, i), dy, z)) ms_put(keys, (uint32_t)j * cam.W + i, z, first + (uint32_t)src);
-            i += cols;
-            j += rows;
-            if (i > g.i1) { i -= bw; ++j; }
-        }
-    }
+    mesh_raster_walk<kBlock>(cam, near_z, w2c, vertices, V, faces, F, split, [=](uint32_t o, float z, uint32_t f) { ms_put(keys, o, z, f); });
 }
 
 struct ShadeOut {
@@ -140,13 +93,6 @@ __global__ void __launch_bounds__(kBlock) ms_shade_kernel(MrPinhole cam, float n
     if (out.depth) out.depth[p] = last.z;                               // (samples == 1: `last` is the pixel's one sample)
     if (out.face) out.face[p] = last.face;
     if (out.normal) { out.normal[3 * p] = last.n[0]; out.normal[3 * p + 1] = last.n[1]; out.normal[3 * p + 2] = last.n[2]; }
-}
-
-MrPinhole pinhole_of(const SplatMeshView &v) {
-    MrPinhole c;
-    c.W = v.width; c.H = v.height;
-    c.fx = v.fx; c.fy = v.fy; c.cx = v.cx; c.cy = v.cy;
-    return c;
 }
 
 }  // namespace

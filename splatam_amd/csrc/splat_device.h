@@ -12,6 +12,9 @@ namespace splat {
 
 constexpr int kWave = 64;
 
+// workgroups of `block` lanes for n lanes, one element each
+inline unsigned blocks_for(long long n, int block) { return (unsigned)((n + block - 1) / block); }
+
 // ---------------------------------------------------------------------------
 // launchers (one per .hip file); every one returns hipGetLastError()
 // ---------------------------------------------------------------------------

@@ -22,21 +22,11 @@ from __future__ import annotations
 import torch
 
 from . import _capi
+from ._mesh_common import _device, _ptr, _stream, _tensor
 from .mesh import Mesh
 
 AREA_QUANTUM = 2.0 ** -_capi.SPLAT_MESH_AREA_BITS
 REPORT_KEYS = ("components", "components_kept", "faces", "faces_removed", "area_m2", "area_removed_m2")
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _device(device):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("mesh cleaning needs a CUDA/HIP device; the HIP library has no CPU path")
-    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
 
 
 def _faces(faces, what="faces"):
@@ -58,7 +48,7 @@ def label_components(num_vertices, faces):
     dev = faces.device
     labels = torch.empty(V, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_components(faces.data_ptr() if F else None, F, V, labels.data_ptr() if V else None, _stream(dev)),
+        _capi.check(_capi.lib().splat_mesh_components(_ptr(faces, F), F, V, _ptr(labels, V), _stream(dev)),
                     "splat_mesh_components")
     return labels
 
@@ -76,21 +66,15 @@ def component_stats(mesh, labels=None):
     ``label_components`` gave, computed when None.  Enqueued; nothing is read."""
     v, f = mesh[0], _faces(mesh[1])
     dev = f.device
-    if not (isinstance(v, torch.Tensor) and v.dtype == torch.float32 and v.device == dev and v.dim() == 2 and v.shape[1] == 3):
-        raise RuntimeError(f"vertices must be a float32 tensor [V, 3] on {dev}")
-    v = v.contiguous()
+    v = _tensor(v, "vertices", torch.float32, ("V", 3), dev).contiguous()
     V, F = int(v.shape[0]), int(f.shape[0])
-    if labels is None:
-        labels = label_components(V, f)
-    elif not (isinstance(labels, torch.Tensor) and labels.dtype == torch.int32 and labels.device == dev and tuple(labels.shape) == (V,)):
-        raise RuntimeError(f"labels must be an int32 tensor [{V}] on {dev}")
-    labels = labels.contiguous()
+    labels = (label_components(V, f) if labels is None else _tensor(labels, "labels", torch.int32, (V,), dev)).contiguous()
     num_v, num_f = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev)
     area_q = torch.empty(V, dtype=torch.int64, device=dev)
     lo, hi = torch.empty(V, 3, dtype=torch.int32, device=dev), torch.empty(V, 3, dtype=torch.int32, device=dev)
     p = (lambda t: t.data_ptr()) if V else (lambda t: None)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_component_stats(p(v), V, f.data_ptr() if F else None, F, p(labels), p(num_v), p(num_f), p(area_q),
+        _capi.check(_capi.lib().splat_mesh_component_stats(p(v), V, _ptr(f, F), F, p(labels), p(num_v), p(num_f), p(area_q),
                                                            p(lo), p(hi), _stream(dev)), "splat_mesh_component_stats")
     return {"num_vertices": num_v, "num_faces": num_f, "area": area_q.double() * AREA_QUANTUM, "lo": key_to_float(lo), "hi": key_to_float(hi),
             "is_root": labels == torch.arange(V, dtype=torch.int32, device=dev), "area_quanta": area_q}
@@ -132,7 +116,7 @@ def clean_mesh(mesh, min_vertices=200, min_faces=0, min_area=0.0, min_extent=0.0
 
     ``min_vertices`` = 200 is recalled from the evaluation scripts of the Point-SLAM family, which remove every component with fewer
     vertices right after extraction; those scripts are not part of this project, so no parity is claimed."""
-    dev = _device(device)
+    dev = _device(device, "mesh cleaning")
     if int(min_vertices) < 0 or int(min_faces) < 0 or not float(min_area) >= 0 or not float(min_extent) >= 0:
         raise ValueError("clean_mesh needs thresholds that are not negative")
     if keep_largest is not None and int(keep_largest) <= 0:

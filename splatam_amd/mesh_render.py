@@ -21,26 +21,14 @@ parameters match.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import _capi
+from ._mesh_common import _device, _loaded, _mesh_arrays, _on_device, _pose_tensor, _ptr, _stream, _tensor, _transform  # noqa: F401
 from .mesh import Mesh
 
 NEAR = 0.01
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _device(device):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("mesh rendering needs a CUDA/HIP device; the HIP library has no CPU path")
-    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
 
 
 def parse_size(text):
@@ -76,31 +64,17 @@ def _view(intrinsics, size, near=NEAR):
 
 def _poses(w2c, dev):
     """[n, 16] float32 on ``dev`` of one or many 4 x 4 world-to-camera matrices (host arrays are rounded once, from float64)."""
-    if isinstance(w2c, torch.Tensor):
-        t = w2c.detach().to(device=dev, dtype=torch.float32)
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(w2c, dtype=np.float64).astype(np.float32))).to(dev)
+    t = _pose_tensor(w2c).to(device=dev, dtype=torch.float32)
     if t.numel() % 16 != 0:
         raise ValueError("poses are 4 x 4 matrices")
     return t.reshape(-1, 16).contiguous()
 
 
-def _mesh_arrays(vertices, faces, dev):
-    if not (isinstance(vertices, torch.Tensor) and vertices.dtype == torch.float32 and vertices.device == dev and vertices.dim() == 2
-            and vertices.shape[1] == 3):
-        raise RuntimeError(f"vertices must be a float32 tensor [V, 3] on {dev}")
-    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.device == dev and faces.dim() == 2 and faces.shape[1] == 3):
-        raise RuntimeError(f"faces must be an int32 tensor [F, 3] on {dev}")
-    return vertices.contiguous(), faces.contiguous()
-
-
 def to_device_mesh(mesh, device="cuda:0", transform=None):
     """``mesh`` (a ``Mesh`` tuple of device tensors or host arrays, or the path of a PLY) as a ``Mesh`` of float32 / int32 tensors on
     ``device``; ``transform`` (4 x 4) is applied to the vertices in float64 and rounded once.  Colours stay ``None`` when there are none."""
-    dev = _device(device)
-    if isinstance(mesh, (str, os.PathLike)):
-        from .export import load_mesh_ply
-        mesh = load_mesh_ply(mesh)
+    dev = _device(device, "mesh rendering")
+    mesh = _loaded(mesh)
     vertices, faces = mesh[0], mesh[1]
     colors = mesh[2] if len(mesh) > 2 else None
 
@@ -111,10 +85,7 @@ def to_device_mesh(mesh, device="cuda:0", transform=None):
 
     v = tensor(vertices, np.float32).reshape(-1, 3)
     if transform is not None:
-        m = np.asarray(transform.detach().cpu() if isinstance(transform, torch.Tensor) else transform, dtype=np.float64)
-        if m.shape != (4, 4) or not np.isfinite(m).all():
-            raise ValueError("transform must be a finite 4 x 4 matrix")
-        m = torch.from_numpy(m).to(dev)
+        m = torch.from_numpy(_transform(transform)).to(dev)
         v = v.double() @ m[:3, :3].T + m[:3, 3]
     f = tensor(faces, np.int64).reshape(-1, 3)
     c = None if colors is None else tensor(colors, np.float32).reshape(-1, 3).float().contiguous()
@@ -129,8 +100,7 @@ def render_depth(vertices, faces, w2c, intrinsics, size, near=NEAR, out=None):
     zeros.  ``out``: a contiguous float32 [H, W] to render into (one plane of a [k, H, W] chunk, say).  Enqueued on the current stream; nothing
     is read."""
     dev = vertices.device
-    if dev.type != "cuda":
-        raise RuntimeError("render_depth needs a CUDA/HIP device; the HIP library has no CPU path")
+    _on_device(dev, "render_depth")
     vertices, faces = _mesh_arrays(vertices, faces, dev)
     view = _view(intrinsics, size, near)
     if not (float(near) > 0 and np.isfinite(float(near))):
@@ -139,16 +109,11 @@ def render_depth(vertices, faces, w2c, intrinsics, size, near=NEAR, out=None):
     if pose.shape[0] != 1:
         raise ValueError("render_depth renders one view: w2c is one 4 x 4 matrix")
     W, H = view.width, view.height
-    if out is None:
-        out = torch.empty(H, W, dtype=torch.float32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == (H, W)
-              and out.is_contiguous()):
-        raise RuntimeError(f"out must be a contiguous float32 tensor [{H}, {W}] on {dev}")
+    out = torch.empty(H, W, dtype=torch.float32, device=dev) if out is None else _tensor(out, "out", torch.float32, (H, W), dev, contiguous=True)
     view.w2c = pose.data_ptr()
     V, F = int(vertices.shape[0]), int(faces.shape[0])
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_depth(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F, view, out.data_ptr(),
-                                                 _stream(dev)), "splat_mesh_depth")
+        _capi.check(_capi.lib().splat_mesh_depth(_ptr(vertices, V), V, _ptr(faces, F), F, view, out.data_ptr(), _stream(dev)), "splat_mesh_depth")
     return out
 
 
@@ -157,28 +122,19 @@ def seen_counts(vertices, w2c, intrinsics, size, edge=0, depth=None, eps=0.0, ou
     pixels inside the image and -- with ``depth`` [n, H, W] float32 -- at a depth z <= d + ``eps`` of a pixel with d > 0.  ``out`` is
     INCREMENTED (a long sequence is fed in chunks).  Exact, no atomics.  Enqueued; nothing is read."""
     dev = vertices.device
-    if dev.type != "cuda":
-        raise RuntimeError("seen_counts needs a CUDA/HIP device; the HIP library has no CPU path")
-    if not (vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3):
-        raise RuntimeError(f"vertices must be a float32 tensor [V, 3] on {dev}")
-    vertices = vertices.contiguous()
+    _on_device(dev, "seen_counts")
+    vertices = _tensor(vertices, "vertices", torch.float32, ("V", 3), dev).contiguous()
     view = _view(intrinsics, size)
     poses = _poses(w2c, dev)
     n, V = int(poses.shape[0]), int(vertices.shape[0])
     if int(edge) < 0 or not float(eps) >= 0:
         raise ValueError("seen_counts needs edge >= 0 and eps >= 0")
     if depth is not None:
-        if not (isinstance(depth, torch.Tensor) and depth.dtype == torch.float32 and depth.device == dev
-                and tuple(depth.shape) == (n, view.height, view.width) and depth.is_contiguous()):
-            raise RuntimeError(f"depth must be a contiguous float32 tensor [{n}, {view.height}, {view.width}] on {dev}")
-    if out is None:
-        out = torch.zeros(V, dtype=torch.int32, device=dev)
-    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.device == dev and tuple(out.shape) == (V,) and out.is_contiguous()):
-        raise RuntimeError(f"out must be a contiguous int32 tensor [{V}] on {dev}")
+        _tensor(depth, "depth", torch.float32, (n, view.height, view.width), dev, contiguous=True)
+    out = torch.zeros(V, dtype=torch.int32, device=dev) if out is None else _tensor(out, "out", torch.int32, (V,), dev, contiguous=True)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_seen(vertices.data_ptr() if V else None, V, view, poses.data_ptr() if n else None, n, int(edge),
-                                                depth.data_ptr() if depth is not None and n else None, float(eps), out.data_ptr() if V else None,
-                                                _stream(dev)), "splat_mesh_seen")
+        _capi.check(_capi.lib().splat_mesh_seen(_ptr(vertices, V), V, view, _ptr(poses, n), n, int(edge), _ptr(depth, depth is not None and n),
+                                                float(eps), _ptr(out, V), _stream(dev)), "splat_mesh_seen")
     return out
 
 
@@ -190,14 +146,13 @@ def compare_depth(a, b, row, partials=None):
     for t in (a, b):
         if not (t.dtype == torch.float32 and t.device == dev and t.is_contiguous() and t.numel() == a.numel()):
             raise RuntimeError("the planes must be contiguous float32 tensors of one size on one device")
-    if not (row.dtype == torch.float64 and row.device == dev and row.numel() == 8 and row.is_contiguous()):
-        raise RuntimeError(f"row must be 8 contiguous float64 on {dev}")
+    _tensor(row, "row", torch.float64, 8, dev)
     if partials is None:
         partials = torch.empty(_capi.SPLAT_MESH_COMPARE_PARTIALS, dtype=torch.float64, device=dev)
     n = int(a.numel())
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_depth_compare(a.data_ptr() if n else None, b.data_ptr() if n else None, n, partials.data_ptr(),
-                                                         row.data_ptr(), _stream(dev)), "splat_mesh_depth_compare")
+        _capi.check(_capi.lib().splat_mesh_depth_compare(_ptr(a, n), _ptr(b, n), n, partials.data_ptr(), row.data_ptr(), _stream(dev)),
+                    "splat_mesh_depth_compare")
     return row
 
 
@@ -240,7 +195,7 @@ def cull_meshes(meshes, w2c, intrinsics, size, occlusion=None, eps=0.03, edge=0,
     if chunk <= 0:
         raise ValueError("chunk must be positive")
     meshes = [to_device_mesh(m, device, None) for m in meshes]
-    dev = _device(device)
+    dev = _device(device, "mesh rendering")
     poses = _poses(w2c, dev)
     n = int(poses.shape[0])
     view = _view(intrinsics, size, near)

@@ -36,13 +36,13 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import math
-import os
 import sys
 
 import numpy as np
 import torch
 
 from . import _capi
+from ._mesh_common import _device, _loaded, _on_device, _ptr, _stream, _tensor, _transform
 from .mesh import Mesh          # noqa: F401  (re-exported: what score_mesh takes)
 
 MAX_CELLS = _capi.SPLAT_NN_MAX_CELLS
@@ -83,20 +83,7 @@ def plan_grid(lo, hi, count, cell=None, per_cell=POINTS_PER_CELL):
 
 
 def _points(t, dev, what):
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and t.dim() == 2 and t.shape[1] == 3):
-        raise RuntimeError(f"{what} must be a float32 tensor [n, 3] on {dev}")
-    return t.contiguous()
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _device(device):
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError("the mesh score needs a CUDA/HIP device; the HIP library has no CPU path")
-    return torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+    return _tensor(t, what, torch.float32, ("n", 3), dev).contiguous()
 
 
 def surface_prefix(vertices, faces):
@@ -106,8 +93,7 @@ def surface_prefix(vertices, faces):
     V, F = int(vertices.shape[0]), int(faces.shape[0])
     area = torch.empty(F, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _capi.check(L.splat_mesh_areas(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F, area.data_ptr() if F else None,
-                                       _stream(dev)), "splat_mesh_areas")
+        _capi.check(L.splat_mesh_areas(_ptr(vertices, V), V, _ptr(faces, F), F, _ptr(area, F), _stream(dev)), "splat_mesh_areas")
     return area, torch.cumsum(area, 0)
 
 
@@ -116,12 +102,9 @@ def sample_surface(vertices, faces, n, seed=0, prefix=None):
     float32, face [n] int32)``.  Sample ``i`` depends on ``(seed, i)`` alone -- not on ``n``, not on the launch.  Zero-area triangles
     get no sample.  Enqueued on the current stream; nothing is read."""
     dev = vertices.device
-    if dev.type != "cuda":
-        raise RuntimeError("sample_surface needs a CUDA/HIP device; the HIP library has no CPU path")
+    _on_device(dev, "sample_surface")
     vertices = _points(vertices, dev, "vertices")
-    if not (isinstance(faces, torch.Tensor) and faces.dtype == torch.int32 and faces.device == dev and faces.dim() == 2 and faces.shape[1] == 3):
-        raise RuntimeError(f"faces must be an int32 tensor [F, 3] on {dev}")
-    faces = faces.contiguous()
+    faces = _tensor(faces, "faces", torch.int32, ("F", 3), dev).contiguous()
     V, F, n = int(vertices.shape[0]), int(faces.shape[0]), int(n)
     if F == 0 or n < 0:
         raise ValueError("sample_surface needs a mesh with faces and n >= 0")
@@ -130,9 +113,8 @@ def sample_surface(vertices, faces, n, seed=0, prefix=None):
     points = torch.empty(n, 3, dtype=torch.float32, device=dev)
     face = torch.empty(n, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_sample(vertices.data_ptr() if V else None, V, faces.data_ptr(), F, prefix.data_ptr(),
-                                                  int(seed) & (2 ** 64 - 1), n, points.data_ptr() if n else None, face.data_ptr() if n else None,
-                                                  _stream(dev)), "splat_mesh_sample")
+        _capi.check(_capi.lib().splat_mesh_sample(_ptr(vertices, V), V, faces.data_ptr(), F, prefix.data_ptr(), int(seed) & (2 ** 64 - 1), n,
+                                                  _ptr(points, n), _ptr(face, n), _stream(dev)), "splat_mesh_sample")
     return points, face
 
 
@@ -169,8 +151,8 @@ class NearestGrid:
         self.start = torch.empty(self.cells + 1, dtype=torch.int32, device=dev)
         key, order = self._sorted_keys(targets)
         with torch.cuda.device(dev):
-            _capi.check(self.L.splat_nn_cell_starts(C.byref(g), key.data_ptr() if M else None, order.data_ptr() if M else None,
-                                                    targets.data_ptr() if M else None, self.records.data_ptr(), self.start.data_ptr(),
+            _capi.check(self.L.splat_nn_cell_starts(C.byref(g), _ptr(key, M), _ptr(order, M),
+                                                    _ptr(targets, M), self.records.data_ptr(), self.start.data_ptr(),
                                                     _stream(dev)), "splat_nn_cell_starts")
         g.records, g.start = self.records.data_ptr(), self.start.data_ptr()
 
@@ -178,7 +160,7 @@ class NearestGrid:
         n = int(points.shape[0])
         key = torch.empty(n, dtype=torch.int32, device=self.dev)
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_nn_cell_keys(C.byref(self.struct), points.data_ptr() if n else None, n, key.data_ptr() if n else None,
+            _capi.check(self.L.splat_nn_cell_keys(C.byref(self.struct), _ptr(points, n), n, _ptr(key, n),
                                                   _stream(self.dev)), "splat_nn_cell_keys")
         key, order = torch.sort(key, stable=True)
         return key, order.to(torch.int32)
@@ -205,8 +187,8 @@ class NearestGrid:
         else:
             order = self._sorted_keys(points)[1] if sort and n else None
         with torch.cuda.device(self.dev):
-            _capi.check(self.L.splat_nn_query(C.byref(self.struct), points.data_ptr() if n else None, order.data_ptr() if order is not None else None,
-                                              n, dist2.data_ptr() if n else None, index.data_ptr() if n else None,
+            _capi.check(self.L.splat_nn_query(C.byref(self.struct), _ptr(points, n), order.data_ptr() if order is not None else None,
+                                              n, _ptr(dist2, n), _ptr(index, n),
                                               acc.data_ptr() if account and n else None, _stream(self.dev)), "splat_nn_query")
         return (dist2, index, acc) if account else (dist2, index)
 
@@ -217,13 +199,12 @@ def reduce_distances(dist2, threshold, row, partials=None):
     dev = dist2.device
     if not (dist2.dtype == torch.float32 and dist2.dim() == 1 and dist2.is_contiguous()):
         raise RuntimeError("dist2 must be a contiguous float32 vector")
-    if not (row.dtype == torch.float64 and row.device == dev and row.numel() == 4 and row.is_contiguous()):
-        raise RuntimeError(f"row must be 4 contiguous float64 on {dev}")
+    _tensor(row, "row", torch.float64, 4, dev)
     if partials is None:
         partials = torch.empty(3 * _capi.SPLAT_NN_REDUCE_ROWS, dtype=torch.float64, device=dev)
     n = int(dist2.shape[0])
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_nn_reduce(dist2.data_ptr() if n else None, n, float(threshold), partials.data_ptr(), row.data_ptr(),
+        _capi.check(_capi.lib().splat_nn_reduce(_ptr(dist2, n), n, float(threshold), partials.data_ptr(), row.data_ptr(),
                                                 _stream(dev)), "splat_nn_reduce")
     return row
 
@@ -258,7 +239,7 @@ def apply_state(source, state, out=None):
     n = int(source.shape[0])
     moved = torch.empty(n, 3, dtype=torch.float32, device=dev) if out is None else out
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_icp_transform(source.data_ptr() if n else None, n, state.data_ptr(), moved.data_ptr() if n else None,
+        _capi.check(_capi.lib().splat_icp_transform(_ptr(source, n), n, state.data_ptr(), _ptr(moved, n),
                                                     _stream(dev)), "splat_icp_transform")
     return moved
 
@@ -272,8 +253,8 @@ def accumulate_moments(source, targets, dist2, index, threshold, origin, state, 
         partials = torch.zeros(_capi.SPLAT_ICP_ROWS, _capi.SPLAT_ICP_SUMS, dtype=torch.float64, device=dev)
     c = (C.c_double * 3)(*[float(v) for v in origin])
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_icp_accumulate(source.data_ptr() if n else None, targets.data_ptr() if m else None, m,
-                                                     dist2.data_ptr() if n else None, index.data_ptr() if n else None, n, float(threshold), c,
+        _capi.check(_capi.lib().splat_icp_accumulate(_ptr(source, n), _ptr(targets, m), m,
+                                                     _ptr(dist2, n), _ptr(index, n), n, float(threshold), c,
                                                      state.data_ptr(), partials.data_ptr(), _stream(dev)), "splat_icp_accumulate")
     return partials
 
@@ -355,9 +336,7 @@ def align_vertices(rec_vertices, gt_vertices, align, gt_bounds=None):
 def _load(mesh, dev, transform, what):
     """(vertices float32 [V, 3] on dev, faces int32 [F, 3] on dev, bounds or None): a path or host arrays go through numpy (bounds known
     without a device read), device tensors stay there."""
-    if isinstance(mesh, (str, os.PathLike)):
-        from .export import load_mesh_ply
-        mesh = load_mesh_ply(mesh)
+    mesh = _loaded(mesh)
     vertices, faces = mesh[0], mesh[1]
     if isinstance(vertices, torch.Tensor) and vertices.device.type == "cuda":
         v = vertices.detach().to(dev).reshape(-1, 3)
@@ -378,15 +357,6 @@ def _load(mesh, dev, transform, what):
     if f.shape[0] == 0 or v.shape[0] == 0:
         raise ValueError(f"{what}: a mesh without faces cannot be sampled")
     return v, f, bounds
-
-
-def _transform(transform):
-    if transform is None:
-        return None
-    m = np.asarray(transform.detach().cpu() if isinstance(transform, torch.Tensor) else transform, dtype=np.float64)
-    if m.shape != (4, 4) or not np.isfinite(m).all():
-        raise ValueError("transform must be a finite 4 x 4 matrix")
-    return m
 
 
 def score_mesh(rec, gt, samples=200_000, threshold=0.05, seed=0, transform=None, device="cuda:0", cell=None, align=False):
@@ -415,7 +385,7 @@ def _score_mesh(rec, gt, samples, threshold, seed, transform, device, cell, alig
     which changes no figure."""
     from .mesh_clean import clean_options
     clean = clean_options(clean)
-    dev = _device(device)
+    dev = _device(device, "the mesh score")
     samples = int(samples)
     if samples <= 0 or not float(threshold) > 0:
         raise ValueError("score_mesh needs samples > 0 and threshold > 0")

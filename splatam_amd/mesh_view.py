@@ -34,7 +34,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from .mesh_render import NEAR, _intrinsics, _mesh_arrays, _stream, _view, load_poses, parse_size, to_device_mesh
+from ._mesh_common import _mesh_arrays, _on_device, _pose_tensor, _ptr, _stream, _tensor
+from .mesh_render import NEAR, _intrinsics, _view, load_poses, parse_size, to_device_mesh
 
 MODES = {"color": _capi.SPLAT_MESH_SHADE_COLOR, "shaded": _capi.SPLAT_MESH_SHADE_SHADED, "shaded-color": _capi.SPLAT_MESH_SHADE_SHADED_COLOR,
          "normal": _capi.SPLAT_MESH_SHADE_NORMAL, "depth": _capi.SPLAT_MESH_SHADE_DEPTH}
@@ -59,21 +60,13 @@ def vertex_normals(vertices, faces, out=None, accum=None):
     2^22 m^2 or more add nothing.  The same bits on every run and for every order of the faces.  ``accum``: int64 [V, 3] scratch.
     Enqueued on the current stream; nothing is read."""
     dev = vertices.device
-    if dev.type != "cuda":
-        raise RuntimeError("vertex_normals needs a CUDA/HIP device; the HIP library has no CPU path")
+    _on_device(dev, "vertex_normals")
     vertices, faces = _mesh_arrays(vertices, faces, dev)
     V, F = int(vertices.shape[0]), int(faces.shape[0])
-    if out is None:
-        out = torch.empty(V, 3, dtype=torch.float32, device=dev)
-    elif not (out.dtype == torch.float32 and out.device == dev and tuple(out.shape) == (V, 3) and out.is_contiguous()):
-        raise RuntimeError(f"out must be a contiguous float32 tensor [{V}, 3] on {dev}")
-    if accum is None:
-        accum = torch.empty(V, 3, dtype=torch.int64, device=dev)
-    elif not (accum.dtype == torch.int64 and accum.device == dev and tuple(accum.shape) == (V, 3) and accum.is_contiguous()):
-        raise RuntimeError(f"accum must be a contiguous int64 tensor [{V}, 3] on {dev}")
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev) if out is None else _tensor(out, "out", torch.float32, (V, 3), dev, contiguous=True)
+    accum = torch.empty(V, 3, dtype=torch.int64, device=dev) if accum is None else _tensor(accum, "accum", torch.int64, (V, 3), dev, contiguous=True)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_vertex_normals(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F,
-                                                          accum.data_ptr() if V else None, out.data_ptr() if V else None, _stream(dev)),
+        _capi.check(_capi.lib().splat_mesh_vertex_normals(_ptr(vertices, V), V, _ptr(faces, F), F, _ptr(accum, V), _ptr(out, V), _stream(dev)),
                     "splat_mesh_vertex_normals")
     return out
 
@@ -85,8 +78,8 @@ def render_keys(vertices, faces, w2c_ptr, view, keys):
     V, F = int(vertices.shape[0]), int(faces.shape[0])
     view.w2c = w2c_ptr
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().splat_mesh_visibility(vertices.data_ptr() if V else None, V, faces.data_ptr() if F else None, F, view, keys.data_ptr(),
-                                                      _stream(dev)), "splat_mesh_visibility")
+        _capi.check(_capi.lib().splat_mesh_visibility(_ptr(vertices, V), V, _ptr(faces, F), F, view, keys.data_ptr(), _stream(dev)),
+                    "splat_mesh_visibility")
     return keys
 
 
@@ -123,15 +116,10 @@ class MeshViewer:
         self.args = _capi.SplatMeshShade()
 
     def _set_pose(self, w2c):
-        if isinstance(w2c, torch.Tensor):
-            if w2c.numel() != 16:
-                raise ValueError("render renders one view: w2c is one 4 x 4 matrix")
-            self.pose.copy_(w2c.detach().reshape(16))
-        else:
-            m = np.ascontiguousarray(np.asarray(w2c, dtype=np.float64).astype(np.float32))
-            if m.size != 16:
-                raise ValueError("render renders one view: w2c is one 4 x 4 matrix")
-            self.pose.copy_(torch.from_numpy(m.reshape(16)))
+        t = _pose_tensor(w2c)
+        if t.numel() != 16:
+            raise ValueError("render renders one view: w2c is one 4 x 4 matrix")
+        self.pose.copy_(t.reshape(16))
 
     def _set_lut(self, lut):
         if lut is None:
@@ -179,8 +167,7 @@ class MeshViewer:
         render_keys(v, f, self.pose.data_ptr(), self.view, self.keys)
         p = self.planes if planes else None
         with torch.cuda.device(self.dev):
-            _capi.check(_capi.lib().splat_mesh_shade(v.data_ptr() if V else None, V, f.data_ptr() if F else None, F,
-                                                     c.data_ptr() if c is not None and V else None, self.normals.data_ptr() if V else None, self.view,
+            _capi.check(_capi.lib().splat_mesh_shade(_ptr(v, V), V, _ptr(f, F), F, _ptr(c, c is not None and V), _ptr(self.normals, V), self.view,
                                                      self.keys.data_ptr(), a, self.rgb8.data_ptr(), p['depth'].data_ptr() if p else None,
                                                      p['face'].data_ptr() if p else None, p['normal'].data_ptr() if p else None, _stream(self.dev)),
                         "splat_mesh_shade")

@@ -7,15 +7,6 @@
 
 using namespace splat;
 
-namespace {
-MrPinhole pinhole(int W, int H, const float *k) {
-    MrPinhole c;
-    c.W = W; c.H = H;
-    c.fx = k[0]; c.fy = k[1]; c.cx = k[2]; c.cy = k[3];
-    return c;
-}
-}  // namespace
-
 extern "C" {
 
 int mr_default_split(void) { return kMrSplit; }
@@ -25,7 +16,7 @@ int mr_default_split(void) { return kMrSplit; }
 int mr_render(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const float *w2c, const float *k4, int W, int H, float near_z,
               int split, float *depth, int32_t *kinds, long long *tested) {
     if (W <= 0 || H <= 0 || !(near_z > 0.f)) return -1;
-    const MrPinhole c = pinhole(W, H, k4);
+    const MrPinhole c = mr_pinhole(W, H, k4);
     const size_t n = (size_t)W * H;
     for (size_t o = 0; o < n; ++o) depth[o] = INFINITY;
     long long tests = 0;
@@ -34,14 +25,9 @@ int mr_render(const float *vertices, int32_t V, const int32_t *faces, int32_t F,
         mr_face_setup(c, near_z, w2c, vertices, V, faces + 3 * (int64_t)f, split > 0 ? split : kMrSplit, face);
         if (kinds) kinds[f] = face.kind;
         if (face.kind == kMrNothing) continue;
-        for (int j = face.j0; j <= face.j1; ++j) {
-            const float dy = mr_ray_y(c, j);
-            for (int i = face.i0; i <= face.i1; ++i) {
-                float z;
-                ++tests;
-                if (mr_hit(face, near_z, mr_ray_x(c, i), dy, z) && z < depth[(size_t)j * W + i]) depth[(size_t)j * W + i] = z;
-            }
-        }
+        tests += mr_walk_box(c, face, near_z, [&](uint32_t o, float z) {
+            if (z < depth[o]) depth[o] = z;
+        });
     }
     for (size_t o = 0; o < n; ++o)
         if (depth[o] == INFINITY) depth[o] = 0.f;
@@ -53,7 +39,7 @@ int mr_render(const float *vertices, int32_t V, const int32_t *faces, int32_t F,
 int mr_seen_counts(const float *vertices, int32_t V, const float *w2c, int32_t n, const float *k4, int W, int H, int edge, const float *depth,
                    float eps, int32_t *seen) {
     if (W <= 0 || H <= 0 || edge < 0 || n < 0) return -1;
-    const MrPinhole c = pinhole(W, H, k4);
+    const MrPinhole c = mr_pinhole(W, H, k4);
     for (int32_t v = 0; v < V; ++v) {
         int32_t count = 0;
         for (int32_t k = 0; k < n; ++k)

@@ -7,15 +7,6 @@
 
 using namespace splat;
 
-namespace {
-MrPinhole pinhole(int W, int H, const float *k) {
-    MrPinhole c;
-    c.W = W; c.H = H;
-    c.fx = k[0]; c.fy = k[1]; c.cx = k[2]; c.cy = k[3];
-    return c;
-}
-}  // namespace
-
 extern "C" {
 
 // N0 - N2: accum [V][3] is scratch, normals [V][3]
@@ -31,22 +22,17 @@ int msh_vertex_normals(const float *vertices, int32_t V, const int32_t *faces, i
 int msh_visibility(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const float *w2c, const float *k4, int W, int H,
                    float near_z, int split, uint64_t *keys) {
     if (W <= 0 || H <= 0 || !(near_z > 0.f)) return -1;
-    const MrPinhole c = pinhole(W, H, k4);
+    const MrPinhole c = mr_pinhole(W, H, k4);
     const size_t n = (size_t)W * H;
     for (size_t o = 0; o < n; ++o) keys[o] = kMshNoKey;
     for (int32_t f = 0; f < F && V > 0; ++f) {
         MrFace face;
         mr_face_setup(c, near_z, w2c, vertices, V, faces + 3 * (int64_t)f, split > 0 ? split : kMrSplit, face);
         if (face.kind == kMrNothing) continue;
-        for (int j = face.j0; j <= face.j1; ++j) {
-            const float dy = mr_ray_y(c, j);
-            for (int i = face.i0; i <= face.i1; ++i) {
-                float z;
-                if (!mr_hit(face, near_z, mr_ray_x(c, i), dy, z)) continue;
-                const uint64_t key = msh_key(z, (uint32_t)f);
-                if (key < keys[(size_t)j * W + i]) keys[(size_t)j * W + i] = key;
-            }
-        }
+        mr_walk_box(c, face, near_z, [&](uint32_t o, float z) {
+            const uint64_t key = msh_key(z, (uint32_t)f);
+            if (key < keys[o]) keys[o] = key;
+        });
     }
     return 0;
 }
@@ -63,7 +49,7 @@ int msh_shade(const float *vertices, int32_t V, const int32_t *faces, int32_t F,
     a.lut = lut;
     if (W <= 0 || H <= 0 || a.samples < 1 || a.samples > kMshMaxSamples || a.mode < kMshColor || a.mode > kMshDepth) return -1;
     if ((a.mode == kMshDepth && !lut) || (a.samples > 1 && (depth || face || normal))) return -1;
-    const MrPinhole c = pinhole(W * a.samples, H * a.samples, k4);
+    const MrPinhole c = mr_pinhole(W * a.samples, H * a.samples, k4);
     if (V <= 0) F = 0;
     for (int j = 0; j < H; ++j)
         for (int i = 0; i < W; ++i) {
@@ -93,7 +79,7 @@ void msh_view_bytes(const float *values, long long n, uint8_t *bytes) {
 // one barycentric evaluation, for the S == 0 test: l [3] of the face idx [3] at pixel (i, j)
 int msh_barycentrics_at(const float *vertices, int32_t V, const int32_t *idx, const float *w2c, const float *k4, int W, int H, float near_z, int i,
                         int j, float *l) {
-    const MrPinhole c = pinhole(W, H, k4);
+    const MrPinhole c = mr_pinhole(W, H, k4);
     MrFace g;
     mr_face_setup(c, near_z, w2c, vertices, V, idx, kMrSplit, g);
     if (g.kind == kMrNothing) return 1;

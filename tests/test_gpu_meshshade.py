@@ -76,6 +76,17 @@ def test_keys_equal_the_header_and_hold_the_depth_plane(shim, name):
     assert np.array_equal(keys, want)
     viewer.render(w2c)
     assert np.array_equal(_keys(viewer.keys), keys)
+    # at the default split only faces with a box beyond 16 pixels reach the wave's walk and its face index (the lane's own in the other)
+    from splatam_amd import _capi
+    L = _capi.lib()
+    try:
+        for split in (1, 1 << 30):                                       # every face by the wave; every face with a box by one lane
+            assert L.splat_debug_option(5, split) in (0, 1)
+            viewer.keys.fill_(0)
+            viewer.render(w2c)
+            assert np.array_equal(_keys(viewer.keys), want), split
+    finally:
+        L.splat_debug_option(5, 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. pictures
