@@ -845,6 +845,85 @@ typedef struct SplatViewArgs {
 int splat_view_camera(const SplatViewArgs *view, void *stream);
 int splat_view_finish(const SplatViewArgs *view, void *stream);
 
+/* The view overlay (csrc/viewoverlay.hip, arithmetic in csrc/viewoverlay_math.h; added within ABI 17): the cameras of a run, its
+ * trajectory and the centres of the map's Gaussians drawn into a view -- what the reference's viewers show besides the composite
+ * (/root/reference/viz_scripts/final_recon.py:194-223, online_recon.py:245-273 and its render_mode 'centers').  Caller's stream, caller's
+ * memory, no allocation, nothing read back.
+ *
+ * The KEY PLANE keys [height][width] uint64: splat_view_overlay_clear sets it to all ones; splat_view_points and splat_view_segments
+ * enter primitives by unsigned 64-bit atomic minimum of (bits(z) << 32) | id (device scope, as splat_mesh_visibility).  z: the float32
+ * camera-space depth (positive: its bits order like the floats).  id: bit 31 set = a segment, the other bits its index in the segment
+ * array; bit 31 clear = a row of the map.  Equal depth bits resolve to the lowest id, so points win over segments; the plane holds the
+ * same bits on every run and for every order of the launches.  The camera: w2c (16 device floats, row-major, as splat_view_camera
+ * writes them), pinhole fx, fy, cx, cy, near plane near_z > 0.
+ *
+ * splat_view_run_segments: one lane per frame t of [first, first + count) of a run of num_frames frames.  The pose is the map's,
+ * first_w2c . rel_w2c[t] exactly as splat_view_camera composes it (double), or, with w2c_all != NULL, row t of w2c_all [num_frames][16];
+ * c2w is its rigid inverse.  Written into segments [.][6] float32 (two world points) and colors [.][3] bytes:
+ *   trajectory  segment t - 1 (t > 0): camera centre t - 1 -> centre t, colour cool(0.5 (t - 1) / (num_frames - 1) + 0.5);
+ *   frustum     (frusta != 0) segments num_frames - 1 + 8 t ..: apex = the centre, corners c2w (K^-1 (u, v, 1) scale) for
+ *               (u, v) = (0, 0), (width - 1, 0), (width - 1, height - 1), (0, height - 1) with K of fx, fy, cx, cy; apex-corner x 4,
+ *               then the rectangle; colour cool(0.5 t / num_frames).  A stated definition: Open3D's create_camera_visualization as
+ *               recalled, with the viewers' scale 0.045 as the usual value; no parity with Open3D is claimed.
+ *   cool(x)     entry min(int(256 x), 255) of matplotlib's 256-entry `cool`, entry i = (i / 255, 1 - i / 255, 1), as the bytes
+ *               round(255 v) = (i, 255 - i, 255).  With fixed_color != 0 every segment gets `color` instead.
+ * A prefix of each part is "the run up to t".  Endpoints are evaluated in double and rounded once.
+ *
+ * splat_view_points: one lane per row of means3D [count][3]: pc = w2c p; skipped unless pc.z > near_z; the pixel is
+ * (floor(fx pc.x / pc.z + cx + 0.5), floor(fy pc.y / pc.z + cy + 0.5)) as for mesh vertices below; the footprint is the square of
+ * point_size (1..8) pixels from pixel - (point_size - 1) / 2, clipped to the image; id = row.  Non-finite centres write nothing.
+ *
+ * splat_view_segments: segments [first, first + count) of an array as splat_view_run_segments writes it, id = index in the array.
+ * Each is clipped in camera space to z >= near_z, projected, clipped to the pixels' rectangle (Liang-Barsky, double), and walked along
+ * its major axis from the end with the smaller major coordinate: one step per pixel centre the clipped span covers along that axis
+ * (a span that covers none, a zero-length segment among them: one step where it starts), the minor pixel floor(minor + 0.5), one stamp of
+ * line_width (1..4) pixels across the minor axis per step, at most max(width, height) + 1 steps; depth is interpolated perspective-correctly (1 / z linear on the screen) and rounded to float32 once
+ * per step.  A segment and its reverse give the same keys.  A non-finite endpoint or a segment wholly behind near_z writes nothing; a
+ * zero-length segment writes one stamp.  One wave per segment.
+ *
+ * splat_view_overlay_finish: one lane per pixel, after splat_view_finish wrote the scene's bytes.  Where the key is not all ones:
+ * z its high word, d = depth[pixel] (depth: out6's plane 3, or NULL = no scene); the primitive's bytes replace rgb8's iff occlude == 0
+ * or d <= 0 or z <= d.  A point's bytes: round(255 clamp01(rgb_colors[row][c])) as splat_view_finish rounds; a segment's: its
+ * segment_colors entry; ids outside num_rows / num_segments change nothing.  With fill != 0 every pixel nothing is drawn on gets bg
+ * (the `centers` picture: no composite runs).
+ *
+ * SPLAT_E_INVALID for a NULL struct or array that is needed, a non-positive size, a size outside its range, a negative range. */
+#define SPLAT_VIEW_MAX_POINT_SIZE 8
+#define SPLAT_VIEW_MAX_LINE_WIDTH 4
+#define SPLAT_VIEW_FRUSTUM_SEGMENTS 8
+typedef struct SplatViewOverlay {
+    int32_t width, height;
+    float fx, fy, cx, cy, near_z;
+    const float *w2c;
+    uint64_t *keys;
+} SplatViewOverlay;
+typedef struct SplatViewRun {
+    int32_t num_frames, first, count;
+    const float *w2c_all;                                   /* [num_frames][16], or NULL: */
+    const float *cam_unnorm_rots, *cam_trans, *first_w2c;   /* [1][4][num_frames], [1][3][num_frames], [16] */
+    int32_t width, height;
+    double fx, fy, cx, cy, scale;
+    int32_t frusta, fixed_color;
+    uint8_t color[4];                                       /* r, g, b (the fourth byte is not read) */
+    float *segments;
+    uint8_t *colors;
+} SplatViewRun;
+typedef struct SplatViewOverlayFinish {
+    const float *depth;
+    int32_t occlude, fill;
+    const float *rgb_colors;
+    int32_t num_rows;
+    const uint8_t *segment_colors;
+    int32_t num_segments;
+    float bg[3];
+    uint8_t *rgb8;
+} SplatViewOverlayFinish;
+int splat_view_run_segments(const SplatViewRun *run, void *stream);
+int splat_view_overlay_clear(const SplatViewOverlay *view, void *stream);
+int splat_view_points(const SplatViewOverlay *view, const float *means3D, int32_t count, int32_t point_size, void *stream);
+int splat_view_segments(const SplatViewOverlay *view, const float *segments, int32_t first, int32_t count, int32_t line_width, void *stream);
+int splat_view_overlay_finish(const SplatViewOverlay *view, const SplatViewOverlayFinish *finish, void *stream);
+
 /* The mesh layer (csrc/tsdf.hip, arithmetic in csrc/tsdf_math.h; added within ABI 17): composites of the map at known poses fused into
  * a truncated signed distance volume on the device, and the volume's zero surface as a triangle mesh.
  *

@@ -171,6 +171,23 @@ class SplatMeshShade(C.Structure):         # (added within ABI 17: the mesh shad
                 ("albedo", C.c_float * 3), ("ambient", C.c_float), ("vmin", C.c_float), ("vmax", C.c_float), ("lut", _fp)]
 
 
+class SplatViewOverlay(C.Structure):       # (added within ABI 17: the view overlay, csrc/viewoverlay.hip)
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near_z", C.c_float), ("w2c", _fp), ("keys", _fp)]
+
+
+class SplatViewRun(C.Structure):
+    _fields_ = [("num_frames", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("w2c_all", _fp),
+                ("cam_unnorm_rots", _fp), ("cam_trans", _fp), ("first_w2c", _fp), ("width", C.c_int32), ("height", C.c_int32),
+                ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("scale", C.c_double),
+                ("frusta", C.c_int32), ("fixed_color", C.c_int32), ("color", C.c_uint8 * 4), ("segments", _fp), ("colors", _fp)]
+
+
+class SplatViewOverlayFinish(C.Structure):
+    _fields_ = [("depth", _fp), ("occlude", C.c_int32), ("fill", C.c_int32), ("rgb_colors", _fp), ("num_rows", C.c_int32),
+                ("segment_colors", _fp), ("num_segments", C.c_int32), ("bg", C.c_float * 3), ("rgb8", _fp)]
+
+
 class SplatLpipsWorkspace(C.Structure):    # (added within ABI 17: LPIPS from caller-supplied weights, csrc/lpips.hip)
     _fields_ = [("input", _fp), ("taps", _fp * 5), ("pooled", _fp * 2), ("partials", _fp), ("width", C.c_int32), ("height", C.c_int32)]
 
@@ -178,7 +195,7 @@ class SplatLpipsWorkspace(C.Structure):    # (added within ABI 17: LPIPS from ca
 MIRRORED_STRUCTS = (SplatCamera, SplatGaussians, SplatState, SplatGrads, SplatMap, SplatFrameData, SplatLossConfig, SplatLossConfigEx,
                     SplatIterWorkspace, SplatAdamMap, SplatMapStore, SplatAddArgs, SplatPruneArgs, SplatDensifyArgs, SplatPoseAdam, SplatArrayInfo,
                     SplatEvalConfig, SplatEvalWorkspace, SplatViewArgs, SplatTsdfVolume, SplatTsdfView, SplatNnGrid, SplatMeshView, SplatLpipsWorkspace,
-                    SplatTsdfSparse, SplatMeshShade)
+                    SplatTsdfSparse, SplatMeshShade, SplatViewOverlay, SplatViewRun, SplatViewOverlayFinish)
 
 
 SPLAT_ADD_VALID_DEPTH = 0
@@ -209,6 +226,7 @@ SPLAT_MESH_SHADE_COLOR, SPLAT_MESH_SHADE_SHADED, SPLAT_MESH_SHADE_SHADED_COLOR, 
 SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS, SPLAT_ICP_FITNESS, SPLAT_ICP_RMSE = 16, 17, 18, 19
 SPLAT_ICP_PREV_FITNESS, SPLAT_ICP_PREV_RMSE, SPLAT_ICP_COUNT, SPLAT_ICP_POINTS = 20, 21, 22, 23
 SPLAT_EVAL_PSNR, SPLAT_EVAL_DEPTH_RMSE, SPLAT_EVAL_DEPTH_L1, SPLAT_EVAL_MS_SSIM, SPLAT_EVAL_VALID, SPLAT_EVAL_FLAGGED, SPLAT_EVAL_HOLES = 0, 1, 2, 3, 4, 5, 6
+SPLAT_VIEW_MAX_POINT_SIZE, SPLAT_VIEW_MAX_LINE_WIDTH, SPLAT_VIEW_FRUSTUM_SEGMENTS = 8, 4, 8      # (added within ABI 17: csrc/viewoverlay.hip)
 SPLAT_EVAL_LPIPS, SPLAT_LPIPS_LAYERS, SPLAT_LPIPS_MIN_SIZE = 7, 5, 31      # (added within ABI 17: csrc/lpips.hip)
 
 
@@ -234,6 +252,7 @@ EXPORTS = (
     "splat_eval_workspace_layout", "splat_eval_workspace_bind", "splat_eval_metrics", "splat_iter_eval",
     "splat_frame_prepare", "splat_frame_ingest", "splat_frame_ingest_planes",
     "splat_view_camera", "splat_view_finish",
+    "splat_view_run_segments", "splat_view_overlay_clear", "splat_view_points", "splat_view_segments", "splat_view_overlay_finish",
     "splat_iter_loss_backward_ex", "splat_iter_mapping_step_ex",
     "splat_tsdf_bytes", "splat_tsdf_reset", "splat_tsdf_integrate", "splat_tsdf_triangles", "splat_tsdf_vertices",
     "splat_tsdf_sparse_brick_shape", "splat_tsdf_sparse_bytes", "splat_tsdf_sparse_mark", "splat_tsdf_sparse_reset_slots",
@@ -363,7 +382,15 @@ def lib():
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = [C.POINTER(SplatViewArgs), _fp]
-    vol = C.POINTER(SplatTsdfVolume)
+    overlay = C.POINTER(SplatViewOverlay)
+    for name, args in (("splat_view_run_segments", [C.POINTER(SplatViewRun), _fp]), ("splat_view_overlay_clear", [overlay, _fp]),
+                       ("splat_view_points", [overlay, _fp, C.c_int32, C.c_int32, _fp]),
+                       ("splat_view_segments", [overlay, _fp, C.c_int32, C.c_int32, C.c_int32, _fp]),
+                       ("splat_view_overlay_finish", [overlay, C.POINTER(SplatViewOverlayFinish), _fp])):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = args
+    vol =C.POINTER(SplatTsdfVolume)
     L.splat_tsdf_bytes.restype = C.c_size_t
     L.splat_tsdf_bytes.argtypes = [vol]
     L.splat_tsdf_reset.restype = C.c_int

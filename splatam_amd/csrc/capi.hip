@@ -64,6 +64,7 @@ size_t splat_sizeof(const char *name) {
     SPLAT_SIZEOF_CASE(SplatEvalConfig); SPLAT_SIZEOF_CASE(SplatEvalWorkspace); SPLAT_SIZEOF_CASE(SplatViewArgs);
     SPLAT_SIZEOF_CASE(SplatTsdfVolume); SPLAT_SIZEOF_CASE(SplatTsdfView); SPLAT_SIZEOF_CASE(SplatNnGrid); SPLAT_SIZEOF_CASE(SplatMeshView);
     SPLAT_SIZEOF_CASE(SplatLpipsWorkspace); SPLAT_SIZEOF_CASE(SplatTsdfSparse); SPLAT_SIZEOF_CASE(SplatMeshShade);
+    SPLAT_SIZEOF_CASE(SplatViewOverlay); SPLAT_SIZEOF_CASE(SplatViewRun); SPLAT_SIZEOF_CASE(SplatViewOverlayFinish);
 #undef SPLAT_SIZEOF_CASE
     return 0;
 }
@@ -424,6 +425,50 @@ int splat_view_finish(const SplatViewArgs *v, void *stream) {
     if (v->points && (!v->w2c || !(v->fx > 0.0) || !(v->fy > 0.0))) return SPLAT_E_INVALID;
     if (!v->rgb8 && !v->points && !v->colors) return SPLAT_OK;
     return check(launch_view_finish(*v, (hipStream_t)stream));
+}
+
+// the view overlay (csrc/viewoverlay.hip)
+static bool valid_overlay(const SplatViewOverlay *v) {
+    return v && v->width > 0 && v->height > 0 && (long long)v->width * v->height <= 0x3fffffffLL && v->keys;
+}
+// ... as a camera to draw through: positive finite focal lengths and near plane, finite centre
+static bool valid_overlay_camera(const SplatViewOverlay *v) {
+    return valid_overlay(v) && v->w2c && v->fx > 0.f && v->fy > 0.f && v->near_z > 0.f && v->fx - v->fx == 0.f && v->fy - v->fy == 0.f
+           && v->cx - v->cx == 0.f && v->cy - v->cy == 0.f && v->near_z - v->near_z == 0.f;
+}
+
+int splat_view_run_segments(const SplatViewRun *r, void *stream) {
+    if (!r || r->num_frames <= 0 || r->first < 0 || r->count < 0 || r->count > r->num_frames - r->first || !r->segments || !r->colors)
+        return SPLAT_E_INVALID;
+    if (!r->w2c_all && (!r->cam_unnorm_rots || !r->cam_trans || !r->first_w2c)) return SPLAT_E_INVALID;
+    if (r->frusta && (r->width <= 0 || r->height <= 0 || !(r->fx > 0.0) || !(r->fy > 0.0) || !(r->scale > 0.0))) return SPLAT_E_INVALID;
+    if (r->num_frames > 0x7fffffff / (SPLAT_VIEW_FRUSTUM_SEGMENTS + 1)) return SPLAT_E_INVALID;
+    return check(launch_view_run_segments(*r, (hipStream_t)stream));
+}
+
+int splat_view_overlay_clear(const SplatViewOverlay *v, void *stream) {
+    if (!valid_overlay(v)) return SPLAT_E_INVALID;
+    return check(launch_view_overlay_clear(*v, (hipStream_t)stream));
+}
+
+int splat_view_points(const SplatViewOverlay *v, const float *means3D, int32_t count, int32_t point_size, void *stream) {
+    if (!valid_overlay_camera(v) || count < 0 || (count > 0 && !means3D) || point_size < 1 || point_size > SPLAT_VIEW_MAX_POINT_SIZE)
+        return SPLAT_E_INVALID;
+    return check(launch_view_points(*v, means3D, count, point_size, (hipStream_t)stream));
+}
+
+int splat_view_segments(const SplatViewOverlay *v, const float *segments, int32_t first, int32_t count, int32_t line_width, void *stream) {
+    if (!valid_overlay_camera(v) || first < 0 || count < 0 || count > 0x7fffffff - first || (count > 0 && !segments) || line_width < 1
+        || line_width > SPLAT_VIEW_MAX_LINE_WIDTH)
+        return SPLAT_E_INVALID;
+    return check(launch_view_segments(*v, segments, first, count, line_width, (hipStream_t)stream));
+}
+
+int splat_view_overlay_finish(const SplatViewOverlay *v, const SplatViewOverlayFinish *f, void *stream) {
+    if (!valid_overlay(v) || !f || !f->rgb8 || f->num_rows < 0 || f->num_segments < 0 || (f->num_rows > 0 && !f->rgb_colors)
+        || (f->num_segments > 0 && !f->segment_colors))
+        return SPLAT_E_INVALID;
+    return check(launch_view_overlay_finish(*v, *f, (hipStream_t)stream));
 }
 
 // the mesh layer (csrc/tsdf.hip)

@@ -34,12 +34,16 @@ __global__ void __launch_bounds__(kBlock) ms_fill64_kernel(uint64_t *p, long lon
     }
 }
 
+}  // namespace
+
 hipError_t fill64(void *p, long long n, uint64_t value, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const int vec = ((uintptr_t)p & 15) == 0 ? 1 : 0;
     hipLaunchKernelGGL(ms_fill64_kernel, dim3(blocks_for(vec ? (n + 1) / 2 : n, kBlock)), dim3(kBlock), 0, s, (uint64_t *)p, n, value, vec);
     return hipGetLastError();
 }
+
+namespace {
 
 __global__ void __launch_bounds__(kBlock) ms_normal_faces(const float *__restrict__ vertices, int32_t V, const int32_t *__restrict__ faces, int32_t F,
                                                           int64_t *accum) {

@@ -160,6 +160,15 @@ hipError_t launch_mesh_visibility(const float *vertices, int32_t V, const int32_
 hipError_t launch_mesh_shade(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const float *colors, const float *normals,
                              const SplatMeshView &view, const uint64_t *keys, const SplatMeshShade &a, uint8_t *rgb8, float *depth, int32_t *face,
                              float *normal, hipStream_t s);
+// n words of 8 bytes at p to `value` (meshshade.hip: the key planes of the mesh pictures and of the view overlay)
+hipError_t fill64(void *p, long long n, uint64_t value, hipStream_t s);
+// viewoverlay.hip: the cameras of a run as segments, Gaussian centres as points, one depth-tested key plane, its bytes into a picture
+hipError_t launch_view_run_segments(const SplatViewRun &run, hipStream_t s);
+hipError_t launch_view_overlay_clear(const SplatViewOverlay &v, hipStream_t s);
+hipError_t launch_view_points(const SplatViewOverlay &v, const float *means3D, int32_t count, int32_t point_size, hipStream_t s);
+hipError_t launch_view_segments(const SplatViewOverlay &v, const float *segments, int32_t first, int32_t count, int32_t line_width,
+                                hipStream_t s);
+hipError_t launch_view_overlay_finish(const SplatViewOverlay &v, const SplatViewOverlayFinish &f, hipStream_t s);
 hipError_t launch_map_add(const SplatMapStore &st, const SplatAddArgs &a, hipStream_t s);
 hipError_t launch_map_prune(const SplatMapStore &st, const SplatPruneArgs &a, hipStream_t s);
 hipError_t launch_map_densify_select(const SplatMapStore &st, const SplatDensifyArgs &a, hipStream_t s);

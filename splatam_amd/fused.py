@@ -885,7 +885,8 @@ class FusedEngine:
         return rows
 
     def render_view(self, view, w2c=None, time_idx=None, intrinsics=None, mode="color", background=(0.0, 0.0, 0.0), depth_range=(0.0, 6.0),
-                    lut=None, max_timestep=None, points=False, offset=None, near=0.01, far=100, first_w2c=None, rgb8=True):
+                    lut=None, max_timestep=None, points=False, offset=None, near=0.01, far=100, first_w2c=None, rgb8=True, point_size=1,
+                    overlay=None, overlay_upto=None, frusta="all", line_width=1, occlude=True, overlay_planes=False):
         """The map from any pose, as display bytes (and a point cloud): three launches on the current stream -- splat_view_camera moves
         ``view`` to the pose, splat_iter_render composites the map's own Gaussian arrays at it, splat_view_finish turns the six planes
         into ``rgb8`` [H, W, 3] uint8 (``mode`` "color" on ``background``, "depth" through ``lut`` over ``depth_range``, "sil": grey
@@ -911,18 +912,41 @@ class FusedEngine:
 
         Lists that did not fit do not stop the call: the picture is then incomplete and ``truncated`` (a device int32, != 0) says so,
         from the view camera's status.  ``view.check_overflow()`` is the digest for that camera (grows the lists, learns the buckets):
-        call it where the image is read anyway, then render again."""
+        call it where the image is read anyway, then render again.
+
+        The overlay (csrc/viewoverlay.hip): ``mode="centers"`` is the viewers' render mode of that name -- no composite; every Gaussian's
+        centre (of the rows ``max_timestep`` selects) as a square of ``point_size`` (1..8) pixels in the Gaussian's colour on
+        ``background``, the nearest centre winning each pixel.  ``overlay``: a ``view.RunOverlay`` -- the run's cameras drawn into the
+        picture of any mode as line segments ``line_width`` (1..4) pixels wide: the trajectory up to time step ``overlay_upto``
+        (default: the whole run) and, with ``frusta="all"``, every camera frustum up to it, with ``"current"`` that step's alone,
+        with ``None`` none; the overlay's ground-truth polyline, if it has one, up to the same step.  Segments (and centres) are
+        depth-tested among themselves and, unless ``occlude=False``, against the picture's depth plane (``out6[3]``: the cloud the
+        reference's viewers test against; in ``centers`` mode there is none).  ``overlay_planes=True`` adds ``key`` to the result: the
+        key plane as int64 [H, W] (include/splat_hip.h; -1 where nothing was drawn).  The view allocates that plane at its first call
+        with an overlay or in ``centers`` mode, and nothing after it; the launches are the clear, one per kind of primitive and
+        the resolve behind splat_view_finish.  An overlay without segments to draw leaves ``rgb8`` as the call without one gives it."""
         if (w2c is None) == (time_idx is None):
             raise ValueError("render_view takes a w2c or a time_idx")
         if view.engine is not self:
             raise RuntimeError("this view camera belongs to another FusedEngine")
         if intrinsics is None:
             raise ValueError("render_view needs the view's intrinsics")
+        centers = mode == "centers"
         try:
             view_mode = {"color": _capi.SPLAT_VIEW_COLOR, "depth": _capi.SPLAT_VIEW_DEPTH, "sil": _capi.SPLAT_VIEW_SILHOUETTE,
-                         "silhouette": _capi.SPLAT_VIEW_SILHOUETTE}[mode]
+                         "silhouette": _capi.SPLAT_VIEW_SILHOUETTE, "centers": _capi.SPLAT_VIEW_COLOR}[mode]
         except KeyError:
-            raise ValueError(f"mode must be 'color', 'depth' or 'sil' (got {mode!r})") from None
+            raise ValueError(f"mode must be 'color', 'depth', 'sil' or 'centers' (got {mode!r})") from None
+        ranges = ()
+        if centers or overlay is not None or overlay_planes:
+            if not rgb8 or (centers and points):
+                raise ValueError("an overlay is drawn into rgb8; the centers picture has no point cloud")
+            if not 1 <= int(point_size) <= _capi.SPLAT_VIEW_MAX_POINT_SIZE or not 1 <= int(line_width) <= _capi.SPLAT_VIEW_MAX_LINE_WIDTH:
+                raise ValueError(f"point_size is 1..{_capi.SPLAT_VIEW_MAX_POINT_SIZE}, line_width 1..{_capi.SPLAT_VIEW_MAX_LINE_WIDTH}")
+            if overlay is not None:
+                if overlay.dev != self.dev:
+                    raise RuntimeError(f"the overlay's arrays are on {overlay.dev}, the engine on {self.dev}")
+                ranges = overlay.ranges(overlay_upto, frusta)                      # (may raise: before anything is launched)
         fx, fy, cx, cy = _intrinsics4(intrinsics)
         a = view.args
         a.fx, a.fy, a.cx, a.cy, a.near_z, a.far_z = fx, fy, cx, cy, float(near), float(far)
@@ -977,15 +1001,41 @@ class FusedEngine:
             with torch.cuda.device(self.dev):
                 stream = self._stream()
                 _capi.check(self.L.splat_view_camera(C.byref(a), stream), "splat_view_camera")
-                _capi.check(self.L.splat_iter_render(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(ws), stream), "splat_iter_render")
-                _capi.check(self.L.splat_view_finish(C.byref(a), stream), "splat_view_finish")
-                status = cam.buf['status']
-                torch.bitwise_or(status[_STATUS_OVERFLOW:_STATUS_OVERFLOW + 1], status[_STATUS_STALE_HINT:_STATUS_STALE_HINT + 1], out=view.truncated)
+                if centers:                                  # (no composite: nothing of the lists is used, nothing can be truncated)
+                    view.truncated.zero_()
+                else:
+                    _capi.check(self.L.splat_iter_render(C.byref(cam.struct), C.byref(m), C.byref(fr), C.byref(ws), stream), "splat_iter_render")
+                    _capi.check(self.L.splat_view_finish(C.byref(a), stream), "splat_view_finish")
+                    status = cam.buf['status']
+                    torch.bitwise_or(status[_STATUS_OVERFLOW:_STATUS_OVERFLOW + 1], status[_STATUS_STALE_HINT:_STATUS_STALE_HINT + 1], out=view.truncated)
+                if centers or overlay is not None or overlay_planes:
+                    ov = view.overlay_args()
+                    ov.fx, ov.fy, ov.cx, ov.cy, ov.near_z = fx, fy, cx, cy, float(near)
+                    _capi.check(self.L.splat_view_overlay_clear(C.byref(ov), stream), "splat_view_overlay_clear")
+                    if centers and P > 0:
+                        _capi.check(self.L.splat_view_points(C.byref(ov), self.params['means3D'].data_ptr(), P, int(point_size), stream), "splat_view_points")
+                    for first, count in ranges:
+                        _capi.check(self.L.splat_view_segments(C.byref(ov), overlay.segments.data_ptr(), first, count, int(line_width), stream),
+                                    "splat_view_segments")
+                    f = _capi.SplatViewOverlayFinish()
+                    f.depth = None if centers else cam.buf['out6'][3].data_ptr()
+                    f.occlude, f.fill = int(bool(occlude)), int(centers)
+                    if centers and P > 0:
+                        f.rgb_colors, f.num_rows = self.params['rgb_colors'].data_ptr(), P
+                    if overlay is not None:
+                        f.segment_colors, f.num_segments = overlay.colors.data_ptr(), overlay.num_segments
+                        keep.append(overlay)
+                    f.bg[:] = a.bg[:]
+                    f.rgb8 = view.rgb8.data_ptr()
+                    _capi.check(self.L.splat_view_overlay_finish(C.byref(ov), C.byref(f), stream), "splat_view_overlay_finish")
         finally:
             self._use(current)
-        view._keep, view._rendered_P = keep, P
+        view._keep = keep
+        if not centers:
+            view._rendered_P = P
         o = cam.buf['out6']
-        return ViewImage(view.rgb8 if rgb8 else None, view.points if points else None, view.colors if points else None, view.truncated, o)
+        return ViewImage(view.rgb8 if rgb8 else None, view.points if points else None, view.colors if points else None, view.truncated, o,
+                         view.keys if overlay_planes else None)
 
     # ------------------------------------------------------------------ plumbing
     def _alloc_lists(self, capacity):
@@ -1426,10 +1476,11 @@ FusedEngine.cam_settings, FusedEngine._cam = _of_current_camera("settings"), _of
 
 
 # ---------------------------------------------------------------------- views (csrc/view.hip)
-ViewImage = namedtuple("ViewImage", "rgb8 points colors truncated out6")
+ViewImage = namedtuple("ViewImage", "rgb8 points colors truncated out6 key", defaults=(None,))
 ViewImage.__doc__ = """What ``FusedEngine.render_view`` returns, all on the device and all the VIEW's (overwritten by its next call): ``rgb8``
 [H, W, 3] uint8, ``points`` / ``colors`` [H W, 3] float32 (None unless asked for), ``truncated`` (int32 [1], != 0: the lists did not fit, the
-picture is incomplete), ``out6`` [6, H, W] (r, g, b, depth, silhouette, depth^2 on a zero background)."""
+picture is incomplete), ``out6`` [6, H, W] (r, g, b, depth, silhouette, depth^2 on a zero background; not written in ``centers`` mode),
+``key`` (None unless ``overlay_planes``): the overlay's key plane, int64 [H, W]."""
 
 
 def _intrinsics4(k):
@@ -1476,8 +1527,8 @@ class ViewCamera:
         self.camera = _Camera(dev, settings, engine.Pcap, int(capacity) if capacity else 4 * engine.P + 65536, 0)
         assert self.camera.struct.viewmatrix == self.viewmatrix.data_ptr() and self.camera.struct.projmatrix == self.projmatrix.data_ptr()
         self.rgb8 = torch.zeros(height, width, 3, dtype=torch.uint8, device=dev)
-        self.points = self.colors = None
-        self.truncated = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.points = self.colors = self.keys = None
+        self.truncated =torch.zeros(1, dtype=torch.int32, device=dev)
         from .view import jet_lut
         self._lut = torch.from_numpy(jet_lut()).to(dev).contiguous()     # depth mode's default table (768 bytes: made here, so that a later mode allocates nothing)
         self._offset = (C.c_double * 16)()
@@ -1493,6 +1544,14 @@ class ViewCamera:
 
     def default_lut(self):
         return self._lut
+
+    def overlay_args(self):
+        """The view as csrc/viewoverlay.hip draws through it; the key plane (8 bytes a pixel) is allocated at the first call."""
+        if self.keys is None:
+            self.keys = torch.full((self.H, self.W), -1, dtype=torch.int64, device=self.engine.dev)
+            o = self._overlay = _capi.SplatViewOverlay()
+            o.width, o.height, o.w2c, o.keys = self.W, self.H, self.w2c.data_ptr(), self.keys.data_ptr()
+        return self._overlay
 
     def check_overflow(self, grow=True):
         """``FusedEngine.check_overflow`` for THIS camera (two small host reads): True when its renders since the last call ran on lists

@@ -596,13 +596,19 @@ class SlamSession:
 
     # ------------------------------------------------------------------ a picture of the map (csrc/view.hip)
     def render_view(self, w2c=None, follow=False, time_idx=None, size=None, intrinsics=None, mode="color", background=(0.0, 0.0, 0.0),
-                    to_host=False, **kwargs):
+                    to_host=False, cameras=False, frusta="current", **kwargs):
         """The map as it is now, as display bytes: ``FusedEngine.render_view`` on a view camera the session creates on first use
         (``size`` = (height, width), default the loop's; fixed by the first call).  The pose is one of: ``w2c`` (float32 [4, 4] on the
         device), ``follow=True`` -- the latest estimated pose seen from 0.5 m behind it, ``offset . first_frame_w2c . rel_w2c[latest]``
         with the reference's online viewer's offset --, or ``time_idx``, the estimated pose of that frame.  ``intrinsics`` default
         to the loop's, scaled to ``size``.  Further keywords (``depth_range``, ``lut``, ``max_timestep``, ``points``, ``offset``,
-        ``near``, ``far``) go to the engine's method; nothing is read on the host for the picture.
+        ``near``, ``far``, ``point_size``, ``line_width``, ``occlude``, ``overlay_planes``; ``mode="centers"``) go to the engine's
+        method; nothing is read on the host for the picture.
+
+        ``cameras=True`` draws the session's own run so far into the picture (csrc/viewoverlay.hip): the estimated trajectory up to the
+        latest frame and, with ``frusta="current"`` (the online viewer's picture), the latest camera's frustum -- ``"all"``: every
+        camera's so far, ``None``: none.  The segments are rebuilt from the pose parameters on the loop's stream at every call (one
+        small launch, no host read); the ``view.RunOverlay`` behind it is made at the first such call.
 
         Returns the engine's ``ViewImage`` (tensors on the device, overwritten by the next call).  ``to_host=True``: returns a
         ``HostView(array, event, truncated)`` instead -- ``rgb8`` and the truncation flag copied on the loop's stream into one of two
@@ -635,6 +641,14 @@ class SlamSession:
             time_idx = self.frames_seen - 1
             kwargs.setdefault('offset', V['follow'])
         pose = dict(w2c=w2c) if w2c is not None else dict(time_idx=time_idx, first_w2c=self.first_frame_w2c)
+        if cameras:
+            if 'overlay' not in V:
+                from .view import RunOverlay
+                V['first_w2c'] = self.first_frame_w2c.contiguous()
+                V['overlay'] = RunOverlay(eng, eng.num_frames, first_w2c=V['first_w2c'], intrinsics=self.intrinsics.detach().cpu().double().numpy(),
+                                          size=(self.cam.image_width, self.cam.image_height))
+            latest = self.frames_seen - 1
+            kwargs.update(overlay=V['overlay'].refresh(latest), overlay_upto=latest, frusta=frusta)
         with torch.no_grad():
             image = eng.render_view(V['view'], intrinsics=V['k'] if intrinsics is None else intrinsics, mode=mode,
                                     background=background, **pose, **kwargs)

@@ -1,11 +1,14 @@
-"""Look at a map: ``python -m splatam_amd.view PARAMS.npz --out DIR [--mode color|depth|sil] [--replay] [--every N] [--size WxH] [--white]``.
+"""Look at a map: ``python -m splatam_amd.view PARAMS.npz --out DIR [--mode color|depth|sil|centers] [--replay] [--every N] [--size WxH]
+[--white] [--cameras] [--frusta all|current|none] [--gt-trajectory] [--frustum-size M] [--point-size K] [--line-width K] [--no-occlude]``.
 
 Loads a ``params.npz`` as ``python -m splatam_amd.run`` writes it (the reference's entries: the map, ``timestep``, ``intrinsics``,
 ``w2c``, ``org_width`` / ``org_height``), builds a ``FusedEngine`` around it and writes ``view_%04d.png`` along the estimated
 trajectory through ``FusedEngine.render_view`` (csrc/view.hip): the headless counterpart of the reference's viewers.  Without
 ``--replay`` it is ``viz_scripts/final_recon.py``'s camera on the finished map at every estimated pose; with ``--replay`` it is
 ``viz_scripts/online_recon.py``: the map as it stood at each time step (the Gaussians with ``timestep <= t``), seen from the follow
-camera half a metre behind the estimated pose.  ``--white`` composites on the viewers' white background.  No window is opened;
+camera half a metre behind the estimated pose.  ``--white`` composites on the viewers' white background.  ``--cameras`` draws what the
+viewers draw besides the map -- the estimated trajectory and the camera frusta, coloured along matplotlib's ``cool``, depth-tested
+against the picture (csrc/viewoverlay.hip, ``RunOverlay``); ``--mode centers`` is their render mode of that name.  No window is opened;
 INTEGRATION.md section 7 shows how to feed one.
 
 ``jet_lut()`` is the default colour table of depth mode: matplotlib's ``jet`` at 256 entries, rebuilt from its piecewise-linear
@@ -49,11 +52,126 @@ def jet_lut():
     return (table * 255).astype(np.uint8)
 
 
+def cool_lut():
+    """[256, 3] uint8: matplotlib's ``cool`` at 256 entries from its formula, entry i = (i / 255, 1 - i / 255, 1), as bytes rounded to
+    nearest like every colour of the view layer: (i, 255 - i, 255).  (``matplotlib.colormaps['cool'](i, bytes=True)`` truncates a
+    table that sits an ulp below i / 255 in places and is one lower in 62 of its bytes.)  The map the reference's viewers colour frusta
+    (its lower half) and trajectory (its upper half) with; the overlay kernels evaluate the same formula (csrc/viewoverlay_math.h
+    vo_cool), this table is for legends and tests."""
+    v = np.arange(256, dtype=np.float64) / 255.0
+    return np.rint(np.stack([v, 1.0 - v, np.ones(256)], axis=1) * 255).astype(np.uint8)
+
+
 def follow_offset(dz=FOLLOW_OFFSET_Z):
     """The 4 x 4 multiplied from the left of a pose by the follow camera: a translation along the view's z."""
     m = np.eye(4)
     m[2, 3] = dz
     return m
+
+
+FRUSTUM_SIZE = 0.045        # the viewers' frustum_size
+GT_COLOR = (255, 255, 0)    # the ground-truth polyline (this project's addition: the reference's viewers do not draw one)
+
+
+class RunOverlay:
+    """The cameras of a run as line segments on the device (csrc/viewoverlay.hip splat_view_run_segments), for ``render_view(overlay=...)``:
+    the estimated trajectory as a polyline through the camera centres and one frustum per frame, coloured along matplotlib's ``cool``
+    as the reference's viewers colour them (viz_scripts/final_recon.py:194-223).  The frustum is a stated construction -- apex at the
+    centre, the image's four corners at depth ``frustum_size`` -- after Open3D's ``create_camera_visualization`` as recalled; Open3D
+    is not available to compare with and no parity is claimed.
+
+    ``source``: a ``FusedEngine`` or a dict of parameters with ``cam_unnorm_rots`` [1, 4, n] / ``cam_trans`` [1, 3, n] on the device; the
+    poses are read by the kernel at every ``refresh``, never on the host.  ``first_w2c``: float32 [4, 4] on the device (default the
+    identity).  ``intrinsics`` / ``size`` = (width, height): the RUN's camera, whose image corners the frusta span.  ``gt_w2c``
+    ([n, 4, 4], e.g. a ``params.npz``'s ``gt_w2c_all_frames``): a second polyline through the ground-truth centres in ``GT_COLOR`` --
+    not in the reference's viewers, this project's addition.
+
+    Arrays: ``segments`` [S, 6] float32, ``colors`` [S, 3] uint8; trajectory segments [0, n - 1), eight per frame from n - 1, then the
+    ground-truth polyline's n - 1.  ``refresh(upto)`` rebuilds frames 0..upto in place (one launch, nothing allocated)."""
+
+    def __init__(self, source, num_frames, first_w2c=None, frustum_size=FRUSTUM_SIZE, intrinsics=None, size=None, gt_w2c=None):
+        import ctypes as C
+        import torch
+        from . import _capi
+        from .fused import _intrinsics4
+        if intrinsics is None or size is None:
+            raise ValueError("RunOverlay needs the run's intrinsics and size = (width, height)")
+        self._source = source
+        rots, _ = self._poses()
+        self.dev, n = rots.device, int(num_frames)
+        if n < 1 or n != rots.shape[-1]:
+            raise ValueError(f"num_frames {n} is not the number of poses the parameters hold ({rots.shape[-1]}): the run's length sets "
+                             "the colours and the layout (draw a part of it with overlay_upto)")
+        self.num_frames, self._stride = n, int(rots.shape[-1])
+        self.first_w2c = torch.eye(4, dtype=torch.float32, device=self.dev) if first_w2c is None else first_w2c
+        if not (self.first_w2c.dtype == torch.float32 and tuple(self.first_w2c.shape) == (4, 4) and self.first_w2c.is_contiguous()
+                and self.first_w2c.device == self.dev):
+            raise RuntimeError(f"first_w2c must be a contiguous float32 tensor of shape [4, 4] on {self.dev}")
+        self.gt_first = 9 * n - 1
+        self.num_segments = self.gt_first + (n - 1 if gt_w2c is not None else 0)
+        self.segments = torch.zeros(max(self.num_segments, 1), 6, dtype=torch.float32, device=self.dev)
+        self.colors = torch.zeros(max(self.num_segments, 1), 3, dtype=torch.uint8, device=self.dev)
+        r = self._run = _capi.SplatViewRun()
+        r.width, r.height = int(size[0]), int(size[1])
+        r.fx, r.fy, r.cx, r.cy = _intrinsics4(intrinsics)
+        r.scale, r.frusta = float(frustum_size), 1
+        r.segments, r.colors = self.segments.data_ptr(), self.colors.data_ptr()
+        self._C, self._capi, self._torch = C, _capi, torch
+        self.gt_w2c = None
+        if gt_w2c is not None:
+            gt = torch.as_tensor(np.ascontiguousarray(np.asarray(gt_w2c.cpu() if hasattr(gt_w2c, "cpu") else gt_w2c, dtype=np.float32)))
+            if tuple(gt.shape[1:]) != (4, 4) or gt.shape[0] < n:
+                raise ValueError(f"gt_w2c must be [>= {n}, 4, 4] (got {tuple(gt.shape)})")
+            self.gt_w2c = gt[:n].contiguous().to(self.dev)
+            g = _capi.SplatViewRun()
+            g.num_frames, g.first, g.count, g.w2c_all = n, 0, n, self.gt_w2c.data_ptr()
+            g.frusta, g.fixed_color = 0, 1
+            g.color[:3] = GT_COLOR
+            g.segments, g.colors = self.segments[self.gt_first:].data_ptr(), self.colors[self.gt_first:].data_ptr()
+            self._launch(g)
+        self.refresh()
+
+    def _poses(self):
+        p = self._source.params if hasattr(self._source, "params") else self._source
+        return p['cam_unnorm_rots'], p['cam_trans']
+
+    def _launch(self, run):
+        torch = self._torch
+        with torch.cuda.device(self.dev):
+            self._capi.check(self._capi.lib().splat_view_run_segments(self._C.byref(run), torch.cuda.current_stream(self.dev).cuda_stream),
+                             "splat_view_run_segments")
+
+    def refresh(self, upto=None):
+        """Rebuilds the segments of frames 0..``upto`` (default: all) from the CURRENT pose parameters, on the current stream."""
+        upto = self.num_frames - 1 if upto is None else int(upto)
+        if not 0 <= upto < self.num_frames:
+            raise ValueError(f"upto {upto} is outside the run's {self.num_frames} frames")
+        rots, trans = self._poses()
+        if rots.shape[-1] != self._stride or not (rots.is_contiguous() and trans.is_contiguous()) or rots.dtype != self._torch.float32:
+            raise RuntimeError("the pose parameters changed their shape or layout since the overlay was made")
+        r = self._run
+        r.num_frames, r.first, r.count = self._stride, 0, upto + 1
+        r.cam_unnorm_rots, r.cam_trans, r.first_w2c = rots.data_ptr(), trans.data_ptr(), self.first_w2c.data_ptr()
+        self._launch(r)
+        return self
+
+    def ranges(self, upto=None, frusta="all"):
+        """[(first, count)] of ``segments`` that show the run up to time step ``upto``: the trajectory so far, every frustum up to it
+        ("all"), its own ("current") or none (None / "none"), the ground-truth polyline so far."""
+        upto = self.num_frames - 1 if upto is None else int(upto)
+        if not 0 <= upto < self.num_frames:
+            raise ValueError(f"overlay_upto {upto} is outside the run's {self.num_frames} frames")
+        if frusta not in ("all", "current", "none", None):
+            raise ValueError(f"frusta must be 'all', 'current' or None (got {frusta!r})")
+        base = self._stride - 1
+        out = [(0, upto)]
+        if frusta == "all":
+            out.append((base, 8 * (upto + 1)))
+        elif frusta == "current":
+            out.append((base + 8 * upto, 8))
+        if self.gt_w2c is not None:
+            out.append((self.gt_first, upto))
+        return [(first, count) for first, count in out if count > 0]
 
 
 def load_map(path, device):
@@ -73,8 +191,12 @@ def load_map(path, device):
     return params, variables, k, w2c, size
 
 
-def render_trajectory(path, out_dir, mode="color", replay=False, every=1, size=None, white=False, device="cuda:0", verbose=True):
-    """Writes ``view_%04d.png`` for every ``every``-th estimated pose of ``path`` into ``out_dir``; returns the files' paths."""
+def render_trajectory(path, out_dir, mode="color", replay=False, every=1, size=None, white=False, device="cuda:0", verbose=True,
+                      cameras=False, frusta=None, gt_trajectory=False, frustum_size=FRUSTUM_SIZE, point_size=1, line_width=1, occlude=True):
+    """Writes ``view_%04d.png`` for every ``every``-th estimated pose of ``path`` into ``out_dir``; returns the files' paths.
+    ``cameras``: the run's cameras drawn in (``RunOverlay``) -- with ``replay`` the online viewer's picture by default (the trajectory so
+    far and the current frustum), without it the final viewer's (the whole trajectory, every frustum); ``frusta`` ("all", "current",
+    "none") overrides.  ``gt_trajectory``: the file's ``gt_w2c_all_frames`` as a second polyline."""
     import torch
     from PIL import Image
     from . import slam
@@ -87,19 +209,31 @@ def render_trajectory(path, out_dir, mode="color", replay=False, every=1, size=N
     os.makedirs(out_dir, exist_ok=True)
     with torch.no_grad():
         cam = slam.setup_camera(W0, H0, k, first_w2c.cpu().numpy(), device=dev)
-        k = k.copy()
+        k0, k = k, k.copy()
         k[0] *= W / W0                  # (fx, cx and fy, cy of the pictures' size: slam.scale_intrinsics)
         k[1] *= H / H0
         engine = FusedEngine(params, cam, variables=variables)
         view = engine.view_camera(W, H)
         bg = (1.0, 1.0, 1.0) if white else (0.0, 0.0, 0.0)
         offset = follow_offset() if replay else None
+        overlay = None
+        if cameras or gt_trajectory:
+            gt = None
+            if gt_trajectory:
+                with np.load(path) as z:
+                    if 'gt_w2c_all_frames' not in z:
+                        raise SystemExit(f"{path}: --gt-trajectory needs the file's `gt_w2c_all_frames` entry")
+                    gt = np.array(z['gt_w2c_all_frames'], dtype=np.float32)
+            overlay = RunOverlay(engine, engine.num_frames, first_w2c=first_w2c.contiguous(), frustum_size=frustum_size, intrinsics=k0, size=(W0, H0),
+                                 gt_w2c=gt)
+            frusta = (("current" if replay else "all") if cameras else "none") if frusta is None else frusta
         written = []
         for t in range(0, engine.num_frames, max(int(every), 1)):
             for _ in range(3):
                 image = engine.render_view(view, time_idx=t, first_w2c=first_w2c, intrinsics=k, mode=mode, background=bg,
-                                           max_timestep=t if replay else None, offset=offset)
-                if not view.check_overflow():       # (the picture is read right below: the digest's two small reads ride along)
+                                           max_timestep=t if replay else None, offset=offset, point_size=point_size, overlay=overlay,
+                                           overlay_upto=t if replay else None, frusta=frusta, line_width=line_width, occlude=occlude)
+                if mode == "centers" or not view.check_overflow():       # (the picture is read right below: the digest's two small reads ride along)
                     break
             else:
                 raise RuntimeError(f"frame {t}: the per-tile lists could not be sized for its view")
@@ -126,15 +260,28 @@ def main(argv=None):
     parser = argparse.ArgumentParser(prog="python -m splatam_amd.view", description=__doc__.split("\n\n")[0])
     parser.add_argument("params", help="params.npz of a run")
     parser.add_argument("--out", required=True, help="directory for view_%%04d.png")
-    parser.add_argument("--mode", default="color", choices=("color", "depth", "sil"))
+    parser.add_argument("--mode", default="color", choices=("color", "depth", "sil", "centers"),
+                        help="centers: every Gaussian's centre as a point in its colour (the viewers' render mode of that name)")
     parser.add_argument("--replay", action="store_true", help="the map as it stood at each time step, from the follow camera")
     parser.add_argument("--every", type=int, default=1, help="every N-th pose of the trajectory")
     parser.add_argument("--size", type=_size, default=None, help="WIDTHxHEIGHT of the pictures (default: the run's frame size)")
     parser.add_argument("--white", action="store_true", help="composite on a white background")
+    parser.add_argument("--cameras", action="store_true",
+                        help="draw the estimated trajectory and camera frusta (with --replay: the trajectory so far and the current frustum)")
+    parser.add_argument("--frusta", default=None, choices=("all", "current", "none"), help="which frusta --cameras draws")
+    parser.add_argument("--gt-trajectory", action="store_true", help="draw the ground-truth trajectory (gt_w2c_all_frames) as a second line")
+    parser.add_argument("--frustum-size", type=float, default=FRUSTUM_SIZE, metavar="M", help="depth of a frustum's base in metres")
+    parser.add_argument("--point-size", type=int, default=1, choices=range(1, 9), metavar="K", help="pixels across a centre (1..8)")
+    parser.add_argument("--line-width", type=int, default=1, choices=range(1, 5), metavar="K", help="pixels across a line (1..4)")
+    parser.add_argument("--no-occlude", action="store_true", help="draw cameras and trajectory over the map instead of depth-testing them")
     parser.add_argument("--device", default="cuda:0")
     args = parser.parse_args(argv)
+    if args.frusta is not None and not args.cameras:
+        parser.error("--frusta needs --cameras")
     written = render_trajectory(args.params, args.out, mode=args.mode, replay=args.replay, every=args.every, size=args.size,
-                                white=args.white, device=args.device)
+                                white=args.white, device=args.device, cameras=args.cameras, frusta=args.frusta,
+                                gt_trajectory=args.gt_trajectory, frustum_size=args.frustum_size, point_size=args.point_size,
+                                line_width=args.line_width, occlude=not args.no_occlude)
     print(f"wrote {len(written)} pictures to {args.out}")
     return 0
 
