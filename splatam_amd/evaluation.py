@@ -20,7 +20,8 @@ raised, not replaced by 100.0.
 
 ``evaluate_novel_views`` is the reference's ``eval_nvs`` (utils/eval_helpers.py:626-825) in the same manner: the finished map scored
 at HELD-OUT poses (a dataset's test split, whose item 0 is the first training frame), one ``FusedEngine.evaluate_view`` per frame,
-the table read once; frames with holes -- pixels that have depth where the map shows nothing -- stay out of the averages.
+the table read once; frames with holes -- pixels that have depth where the map shows nothing -- stay out of the averages.  Both are
+thin callers of ``_evaluate``, which enqueues, reads and repeats through ``map_pass.run_pass``.
 """
 from __future__ import annotations
 
@@ -173,6 +174,115 @@ def _lpips_arguments(lpips_weights, dev, mirror):
     return weights, {'lpips': lp.Lpips(weights, dev)}
 
 
+def _evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every, engine, eval_dir, ms_ssim, save_frames,
+              lpips_weights, *, indices, item_of, every_pose, steps, what, rendered_prefix="gs", validity=None):
+    """The body of ``evaluate`` and ``evaluate_novel_views`` (their arguments, then what differs between them).  ``indices(num_frames,
+    eval_every)``: the scored indices, ``item_of(index)`` the dataset item of one; ``every_pose``: every item of the dataset is visited
+    (its pose kept in ``env.poses``), not the scored ones alone.  ``steps(env)`` returns ``(locate, learn, score)``: ``locate(pose)``
+    forms, once per scored item, what the other two receive as ``at`` (None: the pose itself); ``learn(t, data, at, again)`` learns the
+    lists on item ``t`` (``again``: for a flagged item, after a reset of the camera's status; None on the mirror); ``score(t, data, at,
+    row)`` enqueues item ``t``'s metrics into ``row`` -- the mirror instead returns them as a host row -- and returns ``(host row or
+    None, the rendered planes or None)``.  ``validity(out, host, env)`` may add entries to the result and returns
+    the mask of the frames the averages run over (None: all).  ``what`` names a frame in the error of a row that stays flagged.
+    Returns ``(result, env)``; ``env`` carries what the set-up made (engine, mirror, dev, H, W, intrinsics, first_frame_w2c, sil_mask,
+    the LPIPS arguments) and ``poses``, the poses of the visited items."""
+    from types import SimpleNamespace
+    from .fused import FusedEngine
+    from .map_pass import run_pass
+    t_start = time.perf_counter()
+    num_frames = min(int(num_frames), len(dataset))
+    frames = indices(num_frames, eval_every)
+    sil_mask = uses_silhouette_mask(mapping_iters, add_new_gaussians)
+    color0, depth0, intrinsics, pose0 = _frame(dataset, 0)
+    dev = depth0.device
+    H, W = int(color0.shape[1]), int(color0.shape[2])
+    first_frame_w2c = torch.linalg.inv(pose0).to(dev).float().contiguous()
+    mirror = isinstance(engine, str)
+    if mirror and engine != "mirror":
+        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {engine!r})")
+    if not mirror and engine is not None and not isinstance(engine, FusedEngine):
+        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {type(engine).__name__})")
+    if ms_ssim and min(H, W) <= 160:
+        raise ValueError(f"MS-SSIM needs frames with min(H, W) > 160 (got {(H, W)}); pass ms_ssim=False")
+    if save_frames and eval_dir is None:
+        raise ValueError("save_frames needs eval_dir")
+    if mirror or engine is None:
+        cam = slam.setup_camera(W, H, intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
+        if engine is None:
+            engine = FusedEngine({k: v.detach().float().contiguous() for k, v in params.items()}, cam)
+    else:
+        cam = engine.cam_settings
+    lpips_w, lpips_kw = _lpips_arguments(lpips_weights, dev, mirror)
+    env = SimpleNamespace(engine=engine, mirror=mirror, dev=dev, H=H, W=W, intrinsics=intrinsics, first_frame_w2c=first_frame_w2c,
+                          sil_mask=sil_mask, lpips_w=lpips_w, lpips_kw=lpips_kw, poses=[], host=None)
+    locate, learn, score = steps(env)
+    row_of = {item_of(k): i for i, k in enumerate(frames)}
+    items = list(range(num_frames)) if every_pose else list(row_of)
+    table = torch.zeros(max(len(frames), 1), _capi.SPLAT_EVAL_ROW, dtype=torch.float64, device="cpu" if mirror else dev)[:len(frames)]
+
+    def item(t):
+        color, depth, _, pose = _frame(dataset, t)
+        return {'cam': cam, 'im': color, 'depth': depth, 'id': t, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}, pose
+
+    def put(t, data, at, row):
+        values, planes = score(t, data, at, row)
+        if values is not None:
+            row.copy_(values)
+        return planes
+
+    def save(t, data, planes):
+        if saver is not None:
+            saver.save(frames[row_of[t]], planes, data['im'], data['depth'])
+
+    def enqueue(n, t):
+        data, pose = item(t)
+        env.poses.append(pose)
+        if t not in row_of:
+            return
+        at = pose if locate is None else locate(pose)
+        if learn is not None and n == first:              # (one read: sizes the list buckets for the map as it is)
+            learn(t, data, at, False)
+        save(t, data, put(t, data, at, table[row_of[t]]))
+
+    def read():
+        env.host = _read_table(table)
+        return [n for n, t in enumerate(items) if t in row_of and env.host[row_of[t], _capi.SPLAT_EVAL_FLAGGED] != 0]
+
+    def redo(n, t):
+        # this view's lists outgrew the buckets learnt on the first scored one: its row was formed on truncated lists.  Re-learn on this
+        # view (exact lists, capacity grown as needed) and evaluate it again
+        data, pose = item(t)
+        at = pose if locate is None else locate(pose)
+        learn(t, data, at, True)
+        again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
+        planes = put(t, data, at, again)
+        env.host[row_of[t]] = _read_table(again)
+        if env.host[row_of[t], _capi.SPLAT_EVAL_FLAGGED] != 0:
+            raise RuntimeError(f"{what} {frames[row_of[t]]}: the per-tile lists could not be sized for its evaluation render")
+        save(t, data, planes)                                  # (its pictures again, from the complete lists)
+
+    first = min((n for n, t in enumerate(items) if t in row_of), default=None)
+    saver = _FrameSaver(eval_dir, dev, H, W, rendered_prefix) if save_frames else None
+    with saver if saver is not None else contextlib.nullcontext():       # (leaving it: every PNG is on disk, the pool shut down)
+        repeated = [frames[row_of[t]] for t in run_pass(items, enqueue, read, redo)]
+    t_metrics = time.perf_counter() - t_start          # (the table read above waited for the device)
+    host = env.host
+    out = {'frames': list(frames), 'eval_s': t_metrics, 'eval_ms_per_frame': 1e3 * t_metrics / max(len(frames), 1), 'psnr': host[:, _capi.SPLAT_EVAL_PSNR].copy(),
+           'depth_rmse': host[:, _capi.SPLAT_EVAL_DEPTH_RMSE].copy(), 'depth_l1': host[:, _capi.SPLAT_EVAL_DEPTH_L1].copy(),
+           'ms_ssim': host[:, _capi.SPLAT_EVAL_MS_SSIM].copy(), 'valid_pixels': host[:, _capi.SPLAT_EVAL_VALID].copy(), 'lpips': None,
+           'repeated': repeated, 'sil_mask': bool(sil_mask)}
+    valid = validity(out, host, env) if validity is not None else np.ones(len(frames), dtype=bool)
+    if lpips_w is not None:
+        out['lpips'] = host[:, _capi.SPLAT_EVAL_LPIPS].copy()
+    for k in ('psnr', 'depth_rmse', 'depth_l1', 'ms_ssim') + (('lpips',) if lpips_w is not None else ()):
+        out['avg_' + k] = float(out[k][valid].mean()) if valid.any() else float("nan")       # (numpy's mean of nothing, without its warning)
+    if eval_dir is not None:
+        os.makedirs(eval_dir, exist_ok=True)
+        for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')) + ((("lpips.txt", 'lpips'),) if lpips_w is not None else ()):
+            np.savetxt(os.path.join(eval_dir, name), out[k])
+    return out, env
+
+
 def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every=1, engine=None, eval_dir=None,
              ms_ssim=True, save_frames=False, lpips_weights=None):
     """Evaluates ``params`` (the final map and trajectory of a run over ``dataset``) on frames ``eval_frame_indices(num_frames,
@@ -191,94 +301,28 @@ def evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaus
 
     Host synchronisation on an engine: one read to learn the list statistics (``relearn_lists``) before the first frame; then every
     frame is enqueued; one read fetches the table; flagged rows (rare) are evaluated again on re-learnt lists."""
-    from .fused import FusedEngine
-    t_start = time.perf_counter()
-    num_frames = min(int(num_frames), len(dataset))
-    frames = eval_frame_indices(num_frames, eval_every)
-    sil_mask = uses_silhouette_mask(mapping_iters, add_new_gaussians)
-    color0, depth0, intrinsics, pose0 = _frame(dataset, 0)
-    dev = depth0.device
-    first_frame_w2c = torch.linalg.inv(pose0).to(dev).float().contiguous()
-    mirror = isinstance(engine, str)
-    if mirror and engine != "mirror":
-        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {engine!r})")
-    if engine is None:
-        cam = slam.setup_camera(color0.shape[2], color0.shape[1], intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
-        engine = FusedEngine({k: v.detach().float().contiguous() for k, v in params.items()}, cam)
-    elif mirror:
-        cam = slam.setup_camera(color0.shape[2], color0.shape[1], intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
-    else:
-        if not isinstance(engine, FusedEngine):
-            raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {type(engine).__name__})")
-        cam = engine.cam_settings
-    if ms_ssim and min(color0.shape[1:]) <= 160:
-        raise ValueError(f"MS-SSIM needs frames with min(H, W) > 160 (got {tuple(color0.shape[1:])}); pass ms_ssim=False")
-    lpips_w, lpips_kw = _lpips_arguments(lpips_weights, dev, mirror)
+    if save_frames and (eval_dir is None or isinstance(engine, str)):
+        raise ValueError("save_frames needs eval_dir and an engine (the pictures are formed on the device)")
 
-    def curr(t, color, depth):
-        return {'cam': cam, 'im': color, 'depth': depth, 'id': t, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
+    def steps(env):
+        if env.mirror:
+            return None, None, lambda t, data, at, row: (_mirror_row(params, data, t, sil_thres, env.sil_mask, ms_ssim, env.lpips_w), None)
+        eng = env.engine
 
-    repeated = []
-    poses = []
-    saver = None
-    if save_frames:
-        if eval_dir is None or mirror:
-            raise ValueError("save_frames needs eval_dir and an engine (the pictures are formed on the device)")
-        saver = _FrameSaver(eval_dir, dev, int(color0.shape[1]), int(color0.shape[2]))
-    with saver if saver is not None else contextlib.nullcontext():       # (leaving it: every PNG is on disk, the pool shut down)
-        if mirror:
-            rows = []
-            for t in range(num_frames):
-                color, depth, _, pose = _frame(dataset, t)
-                poses.append(pose)
-                if t in frames:
-                    rows.append(_mirror_row(params, curr(t, color, depth), t, sil_thres, sil_mask, ms_ssim, lpips_w))
-            host = torch.stack(rows).numpy()
-        else:
-            engine.relearn_lists(curr(0, color0, depth0), 0)                      # (one read: sizes the list buckets for the map as it is)
-            table = torch.zeros(len(frames), _capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
-            row_of = {t: i for i, t in enumerate(frames)}
-            for t in range(num_frames):
-                color, depth, _, pose = _frame(dataset, t)
-                poses.append(pose)                                               # (every frame's pose feeds the trajectory error)
-                if t in row_of:
-                    engine.evaluate_frame(curr(t, color, depth), t, table[row_of[t]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, **lpips_kw)
-                    if saver is not None:
-                        saver.save(t, engine.buf['out6'], color, depth)
-            host = _read_table(table)
-            for i, t in enumerate(frames):
-                if host[i, _capi.SPLAT_EVAL_FLAGGED] == 0:
-                    continue
-                # this view's lists outgrew the buckets learnt on frame 0: its row was formed on truncated lists.  Re-learn on this view
-                # (exact lists, capacity grown as needed) and evaluate it again
-                repeated.append(t)
-                color, depth, _, _ = _frame(dataset, t)
-                for k in ('status', 'tile_count', 'group_count'):
-                    engine.buf[k].zero_()
-                engine.relearn_lists(curr(t, color, depth), t)
-                again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
-                engine.evaluate_frame(curr(t, color, depth), t, again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, **lpips_kw)
-                host[i] = _read_table(again)
-                if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
-                    raise RuntimeError(f"frame {t}: the per-tile lists could not be sized for its evaluation render")
-                if saver is not None:
-                    saver.save(t, engine.buf['out6'], color, depth)          # (its pictures again, from the complete lists)
-    t_metrics = time.perf_counter() - t_start          # (the table read above waited for the device)
-    out = {'frames': list(frames), 'eval_s': t_metrics, 'eval_ms_per_frame': 1e3 * t_metrics / max(len(frames), 1), 'psnr': host[:, _capi.SPLAT_EVAL_PSNR].copy(), 'depth_rmse': host[:, _capi.SPLAT_EVAL_DEPTH_RMSE].copy(),
-           'depth_l1': host[:, _capi.SPLAT_EVAL_DEPTH_L1].copy(), 'ms_ssim': host[:, _capi.SPLAT_EVAL_MS_SSIM].copy(),
-           'valid_pixels': host[:, _capi.SPLAT_EVAL_VALID].copy(), 'lpips': None, 'repeated': repeated, 'sil_mask': bool(sil_mask)}
-    for k in ('psnr', 'depth_rmse', 'depth_l1', 'ms_ssim'):
-        out['avg_' + k] = float(out[k].mean())
-    if lpips_w is not None:
-        out['lpips'] = host[:, _capi.SPLAT_EVAL_LPIPS].copy()
-        out['avg_lpips'] = float(out['lpips'].mean())
-    out['ate_rmse'] = trajectory_error(params, first_frame_w2c, torch.stack([p.detach().to(dev).float() for p in poses]), num_frames)
-    if eval_dir is not None:
-        os.makedirs(eval_dir, exist_ok=True)
-        for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')):
-            np.savetxt(os.path.join(eval_dir, name), out[k])
-        if lpips_w is not None:
-            np.savetxt(os.path.join(eval_dir, "lpips.txt"), out['lpips'])
+        def learn(t, data, at, again):
+            if again:
+                eng._camera.reset_status()
+            eng.relearn_lists(data, t)
+
+        def score(t, data, at, row):
+            eng.evaluate_frame(data, t, row, sil_thres, sil_mask=env.sil_mask, ms_ssim=ms_ssim, **env.lpips_kw)
+            return None, eng.buf['out6']
+        return None, learn, score
+
+    out, env = _evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every, engine, eval_dir, ms_ssim,
+                         save_frames, lpips_weights, indices=eval_frame_indices, item_of=lambda t: t, every_pose=True, steps=steps, what="frame")
+    # (every frame's pose feeds the trajectory error)
+    out['ate_rmse'] = trajectory_error(params, env.first_frame_w2c, torch.stack([p.detach().to(env.dev).float() for p in env.poses]), len(env.poses))
     return out
 
 
@@ -345,105 +389,38 @@ def evaluate_novel_views(dataset, params, num_frames, sil_thres, mapping_iters, 
     parity target).  On an engine a view camera of the frame's size is moved from pose to pose (``evaluate_view``: the engine's own
     camera, map and optimiser state stay untouched; the poses must be rigid); host synchronisation as in ``evaluate``: one read to
     learn the view's list statistics on the first held-out pose, every frame enqueued, one table read, flagged rows again."""
-    from .fused import FusedEngine, _intrinsics4
-    t_start = time.perf_counter()
-    num_frames = min(int(num_frames), len(dataset))
-    if num_frames < 1:
+    from .fused import _intrinsics4
+    if min(int(num_frames), len(dataset)) < 1:
         raise ValueError("a held-out split starts with the first training frame: the dataset is empty")
-    frames = novel_view_indices(num_frames, eval_every)
-    sil_mask = uses_silhouette_mask(mapping_iters, add_new_gaussians)
-    color0, depth0, intrinsics, pose0 = _frame(dataset, 0)
-    dev = depth0.device
-    H, W = int(color0.shape[1]), int(color0.shape[2])
-    first_frame_w2c = torch.linalg.inv(pose0).to(dev).float().contiguous()
-    mirror = isinstance(engine, str)
-    if mirror and engine != "mirror":
-        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {engine!r})")
-    if not mirror and engine is not None and not isinstance(engine, FusedEngine):
-        raise ValueError(f"engine must be a FusedEngine, None or 'mirror' (got {type(engine).__name__})")
-    if ms_ssim and min(H, W) <= 160:
-        raise ValueError(f"MS-SSIM needs frames with min(H, W) > 160 (got {(H, W)}); pass ms_ssim=False")
-    if save_frames and eval_dir is None:
-        raise ValueError("save_frames needs eval_dir")
-    cam = None
-    if mirror or engine is None:
-        cam = slam.setup_camera(W, H, intrinsics.cpu().numpy(), first_frame_w2c.detach().cpu().numpy(), device=dev)
-    if engine is None:
-        engine = FusedEngine({k: v.detach().float().contiguous() for k, v in params.items()}, cam)
-    lpips_w, lpips_kw = _lpips_arguments(lpips_weights, dev, mirror)
-    k_host = _intrinsics4(intrinsics)                                     # (on the host once: a device matrix would be read per view)
 
-    def curr(t, color, depth):
-        return {'cam': cam, 'im': color, 'depth': depth, 'id': t, 'intrinsics': intrinsics, 'w2c': first_frame_w2c}
+    def steps(env):
+        if env.mirror:
+            return torch.linalg.inv, None, lambda t, data, gt_w2c, row: _mirror_nvs_row(params, data, gt_w2c, sil_thres, env.sil_mask, ms_ssim, env.lpips_w)
+        eng, view = env.engine, env.engine.view_camera(env.W, env.H)
+        k_host = _intrinsics4(env.intrinsics)                             # (on the host once: a device matrix would be read per view)
 
-    repeated = []
-    row_of = {k: i for i, k in enumerate(frames)}
-    saver = _FrameSaver(eval_dir, dev, H, W, rendered_prefix="splatam") if save_frames else None
-    with saver if saver is not None else contextlib.nullcontext():
-        if mirror:
-            rows = []
-            for t in range(1, num_frames):
-                if t - 1 not in row_of:
-                    continue
-                color, depth, _, pose = _frame(dataset, t)
-                row, planes = _mirror_nvs_row(params, curr(t, color, depth), torch.linalg.inv(pose), sil_thres, sil_mask, ms_ssim, lpips_w)
-                rows.append(row)
-                if saver is not None:
-                    saver.save(t - 1, planes, color, depth)
-            host = torch.stack(rows).numpy() if rows else np.zeros((0, _capi.SPLAT_EVAL_ROW))
-        else:
-            view = engine.view_camera(W, H)
-            table = torch.zeros(max(len(frames), 1), _capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)[:len(frames)]
-            learnt = False
-            for t in range(1, num_frames):
-                if t - 1 not in row_of:
-                    continue
-                color, depth, _, pose = _frame(dataset, t)
-                w2c = (first_frame_w2c @ _rigid_inverse(pose.to(dev).float())).contiguous()
-                if not learnt:                                                # (one read: sizes the view's list buckets for the map as it is)
-                    engine.relearn_lists(curr(t, color, depth), 0, view=view, w2c=w2c, intrinsics=k_host)
-                    learnt = True
-                engine.evaluate_view(view, w2c, curr(t, color, depth), table[row_of[t - 1]], sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim,
-                                     holes=True, intrinsics=k_host, **lpips_kw)
-                if saver is not None:
-                    saver.save(t - 1, view.camera.buf['out6'], color, depth)
-            host = _read_table(table)
-            for i, k in enumerate(frames):
-                if host[i, _capi.SPLAT_EVAL_FLAGGED] == 0:
-                    continue
-                # this view's lists outgrew the buckets learnt on the first held-out pose: re-learn on this view and evaluate it again
-                repeated.append(k)
-                color, depth, _, pose = _frame(dataset, k + 1)
-                w2c = (first_frame_w2c @ _rigid_inverse(pose.to(dev).float())).contiguous()
-                for name in ('status', 'tile_count', 'group_count'):
-                    view.camera.buf[name].zero_()
-                engine.relearn_lists(curr(k + 1, color, depth), 0, view=view, w2c=w2c, intrinsics=k_host)
-                again = torch.zeros(_capi.SPLAT_EVAL_ROW, dtype=torch.float64, device=dev)
-                engine.evaluate_view(view, w2c, curr(k + 1, color, depth), again, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=True,
-                                     intrinsics=k_host, **lpips_kw)
-                host[i] = _read_table(again)
-                if host[i, _capi.SPLAT_EVAL_FLAGGED] != 0:
-                    raise RuntimeError(f"held-out frame {k}: the per-tile lists could not be sized for its evaluation render")
-                if saver is not None:
-                    saver.save(k, view.camera.buf['out6'], color, depth)
-    t_metrics = time.perf_counter() - t_start
-    holes = np.rint(host[:, _capi.SPLAT_EVAL_HOLES]).astype(np.int64)
-    percent = percent_holes(holes, H, W)
-    valid = ~(percent > np.float32(0.1))
-    out = {'frames': list(frames), 'eval_s': t_metrics, 'eval_ms_per_frame': 1e3 * t_metrics / max(len(frames), 1), 'psnr': host[:, _capi.SPLAT_EVAL_PSNR].copy(),
-           'depth_rmse': host[:, _capi.SPLAT_EVAL_DEPTH_RMSE].copy(), 'depth_l1': host[:, _capi.SPLAT_EVAL_DEPTH_L1].copy(),
-           'ms_ssim': host[:, _capi.SPLAT_EVAL_MS_SSIM].copy(), 'valid_pixels': host[:, _capi.SPLAT_EVAL_VALID].copy(), 'lpips': None,
-           'repeated': repeated, 'sil_mask': bool(sil_mask), 'holes': holes, 'percent_holes': percent, 'valid_nvs_frames': valid}
-    for k in ('psnr', 'depth_rmse', 'depth_l1', 'ms_ssim'):
-        out['avg_' + k] = float(out[k][valid].mean()) if valid.any() else float("nan")       # (numpy's mean of nothing, without its warning)
-    if lpips_w is not None:                                                                    # (eval_nvs: the valid frames only)
-        out['lpips'] = host[:, _capi.SPLAT_EVAL_LPIPS].copy()
-        out['avg_lpips'] = float(out['lpips'][valid].mean()) if valid.any() else float("nan")
+        def locate(pose):                                                 # (the item's effective world-to-camera: its learn and its score step share it)
+            return (env.first_frame_w2c @ _rigid_inverse(pose.to(env.dev).float())).contiguous()
+
+        def learn(t, data, w2c, again):
+            if again:
+                view.camera.reset_status()
+            eng.relearn_lists(data, 0, view=view, w2c=w2c, intrinsics=k_host)
+
+        def score(t, data, w2c, row):
+            eng.evaluate_view(view, w2c, data, row, sil_thres, sil_mask=env.sil_mask, ms_ssim=ms_ssim, holes=True, intrinsics=k_host, **env.lpips_kw)
+            return None, view.camera.buf['out6']
+        return locate, learn, score
+
+    def validity(out, host, env):
+        out['holes'] = np.rint(host[:, _capi.SPLAT_EVAL_HOLES]).astype(np.int64)
+        out['percent_holes'] = percent_holes(out['holes'], env.H, env.W)
+        out['valid_nvs_frames'] = ~(out['percent_holes'] > np.float32(0.1))
+        return out['valid_nvs_frames']
+
+    out, _ = _evaluate(dataset, params, num_frames, sil_thres, mapping_iters, add_new_gaussians, eval_every, engine, eval_dir, ms_ssim,
+                       save_frames, lpips_weights, indices=novel_view_indices, item_of=lambda k: k + 1, every_pose=False, steps=steps,
+                       what="held-out frame", rendered_prefix="splatam", validity=validity)
     if eval_dir is not None:
-        os.makedirs(eval_dir, exist_ok=True)
-        for name, k in (("psnr.txt", 'psnr'), ("rmse.txt", 'depth_rmse'), ("l1.txt", 'depth_l1'), ("ssim.txt", 'ms_ssim')):
-            np.savetxt(os.path.join(eval_dir, name), out[k])
-        if lpips_w is not None:
-            np.savetxt(os.path.join(eval_dir, "lpips.txt"), out['lpips'])
-        np.save(os.path.join(eval_dir, "valid_nvs_frames.npy"), valid)
+        np.save(os.path.join(eval_dir, "valid_nvs_frames.npy"), out['valid_nvs_frames'])
     return out

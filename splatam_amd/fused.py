@@ -24,6 +24,7 @@ from types import MappingProxyType
 import torch
 
 from . import _capi, slam
+from .map_pass import fit_lists
 from .frames import ingest_frame, ingest_planes, prepare_frame  # noqa: F401  (the frame path lives in frames.py)
 from .rasterizer import _cached_contiguous
 
@@ -152,6 +153,11 @@ class _Camera:
             o = self._natural_order.clone()
         self._orders[view] = o                                      # (most recently visited last)
         self.buf['tile_order'] = o
+
+    def reset_status(self):
+        """Forget what the renders so far flagged: the status words and the list counters they left (before a re-learn, in a digest)."""
+        for key in ('status', 'tile_count', 'group_count'):
+            self.buf[key].zero_()
 
     def keep_lists(self, P, within, only_bucketed):
         """Keep or forget the list statistics for a map of ``P`` rows: kept when the rows moved by less than ``within`` of the rows the
@@ -564,9 +570,7 @@ class FusedEngine:
         self._check_cam(curr_data)
         _check_eval_row(out_row, self.dev)
         cam = self._camera
-        for name, t, c in (("im", curr_data['im'], 3), ("depth", curr_data['depth'], 1)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, cam.H, cam.W)):
-                raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {cam.H}, {cam.W}] on {self.dev}")
+        _check_eval_frame(curr_data, cam.H, cam.W, self.dev)
         fr = self._frame(curr_data, time_idx)
         ews, _ = eval_workspace(self.dev, cam.W, cam.H, ms_ssim)
         cfg = _eval_config(sil_thres, sil_mask, ms_ssim)
@@ -593,9 +597,7 @@ class FusedEngine:
         view's first call; the current camera, the map, its Adam state and ``variables`` stay untouched (``render_view``).  Returns the
         ``ViewImage`` (its ``out6`` holds the planes the row was formed from).  ``lpips``: as in ``evaluate_frame``."""
         _check_eval_row(out_row, self.dev)
-        for name, t, c in (("im", curr_data['im'], 3), ("depth", curr_data['depth'], 1)):
-            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.dev and tuple(t.shape) == (c, view.H, view.W)):
-                raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {view.H}, {view.W}] on {self.dev}")
+        _check_eval_frame(curr_data, view.H, view.W, self.dev)
         img = self.render_view(view, w2c=w2c, intrinsics=curr_data['intrinsics'] if intrinsics is None else intrinsics, rgb8=False)
         o = img.out6
         evaluate_metrics(o[0:3], o[3], o[4], curr_data, out_row, sil_thres, sil_mask=sil_mask, ms_ssim=ms_ssim, holes=holes)
@@ -619,19 +621,10 @@ class FusedEngine:
         if view is not None:
             view.camera.tile_stride, view.camera.max_list_hint = 0, 0
             k = curr_data['intrinsics'] if intrinsics is None else intrinsics
-            return self._fit_lists(lambda: self.render_view(view, w2c=w2c, intrinsics=k, rgb8=False), view.check_overflow, "per-tile lists could not be sized")
+            return fit_lists(lambda: self.render_view(view, w2c=w2c, intrinsics=k, rgb8=False), view.check_overflow, "per-tile lists could not be sized")
         self._check_cam(curr_data)
         self._camera.tile_stride, self._camera.max_list_hint = 0, 0
-        self._fit_lists(lambda: self.render(curr_data, time_idx), self.check_overflow, "per-tile lists could not be sized")
-
-    @staticmethod
-    def _fit_lists(render, digest, message):
-        """``render()`` until its lists fitted -- ``digest()``, which re-sizes them, says whether they overflowed -- three times at most."""
-        for _ in range(3):
-            render()
-            if not digest():
-                return
-        raise RuntimeError(message)
+        fit_lists(lambda: self.render(curr_data, time_idx), self.check_overflow, "per-tile lists could not be sized")
 
     def _append(self, mode, curr_data, time_idx, sil_thres, w2c=None):
         if not self.managed:
@@ -683,8 +676,8 @@ class FusedEngine:
         if depth_sil is None:
             # the densification render must come from complete, sorted lists: a spilled bucket / stale list-length hint would
             # permanently add wrong Gaussians (the status words are overwritten by the next relearn_lists)
-            self._fit_lists(lambda: self.render(curr_data, time_idx), self.check_overflow,
-                            "add_new_gaussians: the per-tile lists could not be sized for the densification render")
+            fit_lists(lambda: self.render(curr_data, time_idx), self.check_overflow,
+                      "add_new_gaussians: the per-tile lists could not be sized for the densification render")
         else:
             out6 = self._camera.buf['out6']
             out6[3], out6[4] = depth_sil[0], depth_sil[1]
@@ -1421,9 +1414,7 @@ class FusedEngine:
             self.skipped_iterations = max(int(skipped), 1)
             b['d_cam'][_REPORT_FLAG] = 0.0
             b['d_cam'][_REPORT_SKIPPED] = 0.0    # (an int32 counter: the bit pattern of 0.0 is 0)
-            b['status'].zero_()
-            b['tile_count'].zero_()
-            b['group_count'].zero_()
+            cam.reset_status()
             self.map_buf['accum'].zero_()
             b['sums'].zero_()
             cam.max_list_hint = 0
@@ -1634,6 +1625,12 @@ def _eval_config(sil_thres, sil_mask, ms_ssim, holes=False):
     c = _capi.SplatEvalConfig()
     c.sil_thres, c.sil_mask, c.ms_ssim, c.holes = float(sil_thres), int(bool(sil_mask)), int(bool(ms_ssim)), int(bool(holes))
     return c
+
+
+def _check_eval_frame(curr_data, H, W, dev):
+    for name, t, c in (("im", curr_data['im'], 3), ("depth", curr_data['depth'], 1)):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev and tuple(t.shape) == (c, H, W)):
+            raise RuntimeError(f"curr_data['{name}'] must be a float32 tensor of shape [{c}, {H}, {W}] on {dev}")
 
 
 def _check_eval_row(out_row, dev):

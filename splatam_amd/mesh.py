@@ -422,40 +422,31 @@ class SparseTsdfVolume(_Surface):
         return dense
 
 
-def _scaled_intrinsics(intrinsics, size, org_size):
-    from .fused import _intrinsics4
-    fx, fy, cx, cy = _intrinsics4(intrinsics)
-    sx, sy = size[0] / org_size[0], size[1] / org_size[1]
-    return fx * sx, fy * sy, cx * sx, cy * sy
-
-
 def _views_pass(frames, run, skipped, view, extra=None):
     """``run(frame)`` (a render and what follows it; returns the ``ViewImage``) for every frame, each view's truncation status kept in a
     device table that is read ONCE at the end, with the ``skipped`` counter and ``extra`` (an int64 [1] tensor made after the loop, or
     None) behind it; the views whose lists did not fit -- turned away on the device -- then get ``view.check_overflow()`` and go
-    again.  Returns (the frames repeated, ``extra``'s value or None)."""
-    dev = skipped.device
-    table = torch.zeros(len(frames) + 2, dtype=torch.int64, device=dev)       # a flag per frame, the skipped counter, ``extra``
-    for n, fr in enumerate(frames):
-        img = run(fr)
-        table[n:n + 1].copy_(img.truncated)
-    table[len(frames):len(frames) + 1].copy_(skipped)
-    if extra is not None:
-        table[len(frames) + 1:].copy_(extra())
-    table = table.cpu().tolist()                            # the one read
-    flagged = [n for n in range(len(frames)) if table[n]]
-    if table[len(frames)] != len(flagged):
-        raise RuntimeError(f"{table[len(frames)]} views were turned away on the device but {len(flagged)} are flagged")
-    if flagged:
-        view.check_overflow()                               # (digests the latest render; clears the camera's status either way)
-    for n in flagged:
-        for _ in range(3):
-            run(frames[n])
-            if not view.check_overflow():                   # (True: the lists are grown, the view goes again)
-                break
-        else:
-            raise RuntimeError(f"frame {frames[n]}: the per-tile lists could not be sized for its view")
-    return [frames[n] for n in flagged], (table[-1] if extra is not None else None)
+    again (``map_pass.run_pass``).  Returns (the frames repeated, ``extra``'s value or None)."""
+    from .map_pass import fit_lists, run_pass
+    table = torch.zeros(len(frames) + 2, dtype=torch.int64, device=skipped.device)       # a flag per frame, the skipped counter, ``extra``
+    host = []
+
+    def read():
+        table[len(frames):len(frames) + 1].copy_(skipped)
+        if extra is not None:
+            table[len(frames) + 1:].copy_(extra())
+        host[:] = table.cpu().tolist()                      # the one read
+        flagged = [n for n in range(len(frames)) if host[n]]
+        if host[len(frames)] != len(flagged):
+            raise RuntimeError(f"{host[len(frames)]} views were turned away on the device but {len(flagged)} are flagged")
+        if flagged:
+            view.check_overflow()                           # (digests the latest render; clears the camera's status either way)
+        return flagged
+
+    repeated = run_pass(frames, lambda n, fr: table[n:n + 1].copy_(run(fr).truncated), read,
+                        lambda n, fr: fit_lists(lambda: run(fr), view.check_overflow,   # (True: the lists are grown, the view goes again)
+                                                f"frame {fr}: the per-tile lists could not be sized for its view"))
+    return repeated, (host[-1] if extra is not None else None)
 
 
 def extract_mesh(engine, frames, size, intrinsics, voxel_size=0.01, trunc=None, bounds=None, max_bytes=DEFAULT_MAX_BYTES, sil_thres=0.99,
@@ -532,14 +523,13 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
     from .export import save_mesh_ply
     from .fused import FusedEngine
     from .mesh_clean import clean_options, format_cleaning
-    from .view import load_map
+    from .view import _scaled_intrinsics, load_map
     check_method(method)
     clean = clean_options(clean)
     found = {} if cleaning is None else cleaning
     dev = torch.device(device)
-    params, variables, k, first_w2c, (W0, H0) = load_map(path, dev)
-    with np.load(path) as z:
-        keyframes = [int(t) for t in z['keyframe_time_indices']] if 'keyframe_time_indices' in z else []
+    params, variables, k, first_w2c, (W0, H0), more = load_map(path, dev, extras=("keyframe_time_indices",))
+    keyframes = [int(t) for t in more["keyframe_time_indices"]] if more["keyframe_time_indices"] is not None else []
     W, H = size or (W0, H0)
     intrinsics = _scaled_intrinsics(k, (W, H), (W0, H0))
     with torch.no_grad():

@@ -210,10 +210,9 @@ def params_poses(path):
     """(w2c [n, 4, 4] float64, intrinsics [3, 3], (width, height)) of a ``params.npz``: the ESTIMATED poses (``post_opt.estimated_w2c``
     seen through the first frame's ``w2c``), in the map's frame -- the frame of a mesh extracted from that map."""
     from .post_opt import estimated_w2c
+    from .view import _check_run_file
     with np.load(path) as z:
-        missing = [k for k in ("cam_unnorm_rots", "cam_trans", "intrinsics", "w2c", "org_width", "org_height") if k not in z]
-        if missing:
-            raise SystemExit(f"{path}: not a params.npz of a run (missing {', '.join(missing)})")
+        _check_run_file(z, path)
         params = {k: torch.from_numpy(np.ascontiguousarray(z[k], dtype=np.float32)) for k in ("cam_unnorm_rots", "cam_trans")}
         k = np.array(z['intrinsics'], dtype=np.float64)[:3, :3]
         first = np.array(z['w2c'], dtype=np.float64).reshape(4, 4)
@@ -250,7 +249,7 @@ def _resolve(parser, args):
         if args.size is None or args.intrinsics is None:
             parser.error("--poses needs --size and --intrinsics")
         return load_poses(args.poses), tuple(args.intrinsics), args.size
-    from .mesh import _scaled_intrinsics
+    from .view import _scaled_intrinsics
     poses, k, size0 = params_poses(args.params)
     size = args.size or size0
     return poses, (tuple(args.intrinsics) if args.intrinsics is not None else _scaled_intrinsics(k, size, size0)), size

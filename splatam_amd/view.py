@@ -174,21 +174,40 @@ class RunOverlay:
         return [(first, count) for first, count in out if count > 0]
 
 
-def load_map(path, device):
-    """(params, variables, intrinsics [3, 3] numpy, first-frame w2c tensor on ``device``, (width, height)) of a ``params.npz``."""
+_RUN_KEYS = ("cam_unnorm_rots", "cam_trans", "intrinsics", "w2c", "org_width", "org_height")     # of a run's params.npz, besides the map
+
+
+def _check_run_file(z, path, keys=_RUN_KEYS):
+    """``z`` (the opened ``path``) holds every one of ``keys``: a ``params.npz`` as a run writes it."""
+    missing = [k for k in keys if k not in z]
+    if missing:
+        raise SystemExit(f"{path}: not a params.npz of a run (missing {', '.join(missing)})")
+
+
+def _scaled_intrinsics(intrinsics, size, org_size):
+    """(fx, fy, cx, cy) of pictures of ``size`` = (width, height) from the intrinsics of pictures of ``org_size``: slam.scale_intrinsics."""
+    from .fused import _intrinsics4
+    fx, fy, cx, cy = _intrinsics4(intrinsics)
+    sx, sy = size[0] / org_size[0], size[1] / org_size[1]
+    return fx * sx, fy * sy, cx * sx, cy * sy
+
+
+def load_map(path, device, extras=None):
+    """(params, variables, intrinsics [3, 3] numpy, first-frame w2c tensor on ``device``, (width, height)) of a ``params.npz``.  With
+    ``extras`` (names of further entries, such as ``keyframe_time_indices`` or ``gt_w2c_all_frames``) a sixth element: a dict of those
+    entries as numpy arrays, None for one the file does not hold."""
     import torch
     from .fused import PARAM_ORDER
     with np.load(path) as z:
-        missing = [k for k in PARAM_ORDER + ("cam_unnorm_rots", "cam_trans", "intrinsics", "w2c", "org_width", "org_height") if k not in z]
-        if missing:
-            raise SystemExit(f"{path}: not a params.npz of a run (missing {', '.join(missing)})")
+        _check_run_file(z, path, PARAM_ORDER + _RUN_KEYS)
         params = {k: torch.from_numpy(np.ascontiguousarray(z[k], dtype=np.float32)).to(device)
                   for k in PARAM_ORDER + ("cam_unnorm_rots", "cam_trans")}
         variables = {'timestep': torch.from_numpy(np.ascontiguousarray(z['timestep'], dtype=np.float32)).to(device)} if 'timestep' in z else None
         k = np.array(z['intrinsics'], dtype=np.float64)[:3, :3]
         w2c = torch.from_numpy(np.ascontiguousarray(z['w2c'], dtype=np.float32)).to(device)
         size = (int(z['org_width']), int(z['org_height']))
-    return params, variables, k, w2c, size
+        more = {name: np.array(z[name]) if name in z else None for name in extras or ()}
+    return (params, variables, k, w2c, size) + ((more,) if extras is not None else ())
 
 
 def render_trajectory(path, out_dir, mode="color", replay=False, every=1, size=None, white=False, device="cuda:0", verbose=True,
@@ -201,44 +220,38 @@ def render_trajectory(path, out_dir, mode="color", replay=False, every=1, size=N
     from PIL import Image
     from . import slam
     from .fused import FusedEngine
+    from .map_pass import fit_lists
     dev = torch.device(device)
-    params, variables, k, first_w2c, (W0, H0) = load_map(path, dev)
+    params, variables, k0, first_w2c, (W0, H0), more = load_map(path, dev, extras=("gt_w2c_all_frames",) if gt_trajectory else ())
     if replay and variables is None:
         raise SystemExit(f"{path}: --replay needs the map's `timestep` entry")
+    gt = more.get("gt_w2c_all_frames")
+    if gt_trajectory and gt is None:
+        raise SystemExit(f"{path}: --gt-trajectory needs the file's `gt_w2c_all_frames` entry")
     W, H = size or (W0, H0)
     os.makedirs(out_dir, exist_ok=True)
     with torch.no_grad():
-        cam = slam.setup_camera(W0, H0, k, first_w2c.cpu().numpy(), device=dev)
-        k0, k = k, k.copy()
-        k[0] *= W / W0                  # (fx, cx and fy, cy of the pictures' size: slam.scale_intrinsics)
-        k[1] *= H / H0
+        cam = slam.setup_camera(W0, H0, k0, first_w2c.cpu().numpy(), device=dev)
+        k = _scaled_intrinsics(k0, (W, H), (W0, H0))
         engine = FusedEngine(params, cam, variables=variables)
         view = engine.view_camera(W, H)
         bg = (1.0, 1.0, 1.0) if white else (0.0, 0.0, 0.0)
         offset = follow_offset() if replay else None
         overlay = None
         if cameras or gt_trajectory:
-            gt = None
-            if gt_trajectory:
-                with np.load(path) as z:
-                    if 'gt_w2c_all_frames' not in z:
-                        raise SystemExit(f"{path}: --gt-trajectory needs the file's `gt_w2c_all_frames` entry")
-                    gt = np.array(z['gt_w2c_all_frames'], dtype=np.float32)
             overlay = RunOverlay(engine, engine.num_frames, first_w2c=first_w2c.contiguous(), frustum_size=frustum_size, intrinsics=k0, size=(W0, H0),
                                  gt_w2c=gt)
             frusta = (("current" if replay else "all") if cameras else "none") if frusta is None else frusta
         written = []
+
         for t in range(0, engine.num_frames, max(int(every), 1)):
-            for _ in range(3):
-                image = engine.render_view(view, time_idx=t, first_w2c=first_w2c, intrinsics=k, mode=mode, background=bg,
-                                           max_timestep=t if replay else None, offset=offset, point_size=point_size, overlay=overlay,
-                                           overlay_upto=t if replay else None, frusta=frusta, line_width=line_width, occlude=occlude)
-                if mode == "centers" or not view.check_overflow():       # (the picture is read right below: the digest's two small reads ride along)
-                    break
-            else:
-                raise RuntimeError(f"frame {t}: the per-tile lists could not be sized for its view")
+            # (the picture is read right below: the digest's two small reads ride along; the centres' picture uses no lists)
+            fit_lists(lambda: engine.render_view(view, time_idx=t, first_w2c=first_w2c, intrinsics=k, mode=mode, background=bg,
+                                                 max_timestep=t if replay else None, offset=offset, point_size=point_size, overlay=overlay,
+                                                 overlay_upto=t if replay else None, frusta=frusta, line_width=line_width, occlude=occlude),
+                      lambda: mode != "centers" and view.check_overflow(), f"frame {t}: the per-tile lists could not be sized for its view")
             name = os.path.join(out_dir, f"view_{t:04d}.png")
-            Image.fromarray(image.rgb8.cpu().numpy()).save(name)
+            Image.fromarray(view.rgb8.cpu().numpy()).save(name)       # (``rgb8`` of the ViewImage: the view's own)
             written.append(name)
             if verbose:
                 print(name, flush=True)

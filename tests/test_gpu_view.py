@@ -390,6 +390,58 @@ def test_saved_frames_decode_to_the_kernels_bytes(tmp_path):
         assert len(os.listdir(os.path.join(tmp_path, "rgb"))) == 3
 
 
+@pytest.mark.parametrize("mode,shrink", (("color", False), ("centers", False), ("color", True)), ids=("color", "centers", "color-retry"))
+def test_render_trajectory_writes_the_bytes_of_render_view(tmp_path, monkeypatch, mode, shrink):
+    """``view.render_trajectory`` on a run's file (400 Gaussians, 3 poses, recorded at 96 x 64, pictured at 48 x 32): every PNG holds the
+    bytes of a direct ``render_view`` at that pose with the intrinsics halved, on an engine that takes the same steps (render, digest).
+    ``centers`` mode uses no lists: it must not digest (``ViewCamera.check_overflow`` is never called); ``color`` digests once a frame.
+    ``color-retry`` forces the loop's retry on the device: after the first digest has learnt the buckets they are shrunk to 16 entries
+    a tile (as tests/test_gpu_novel_view.py forces its repeated rows), so the second frame's first render is flagged and goes again."""
+    from PIL import Image
+    from splatam_amd import fused, slam, view as V
+    W, H = 48, 32
+    params, variables, k, _ = _map(W, H, aniso=False, seed=4)
+    with torch.no_grad():                                    # three distinct poses: a step, then a step with a small rotation
+        params['cam_trans'][0, :, 1] = torch.tensor([0.05, -0.02, 0.1])
+        params['cam_trans'][0, :, 2] = torch.tensor([-0.04, 0.03, 0.2])
+        params['cam_unnorm_rots'][0, :, 2] = torch.tensor([1.0, 0.02, -0.05, 0.03])
+    k0 = np.array(k, dtype=np.float64)
+    k0[:2] *= 2.0                                            # (the run's frames were twice the pictures' size: halving is exact)
+    path = str(tmp_path / "params.npz")
+    np.savez(path, **{n: v.detach().cpu().numpy() for n, v in params.items()}, timestep=variables['timestep'].cpu().numpy(), intrinsics=k0,
+             w2c=np.eye(4, dtype=np.float32), org_width=2 * W, org_height=2 * H)
+    orig = fused.ViewCamera.check_overflow
+
+    def digest(view, log):
+        log.append(orig(view))
+        if shrink and len(log) == 1:
+            assert view.camera.tile_stride > 16
+            view.camera.tile_stride = 16
+        return log[-1]
+    digests = []
+    with monkeypatch.context() as patched:
+        patched.setattr(fused.ViewCamera, "check_overflow", lambda self: digest(self, digests))
+        written = V.render_trajectory(path, str(tmp_path / "out"), mode=mode, size=(W, H), verbose=False)
+    assert [os.path.basename(p) for p in written] == [f"view_{t:04d}.png" for t in range(3)]
+    assert digests == ([] if mode == "centers" else [False, True, False, False] if shrink else [False] * 3), digests
+    loaded, lvars, lk, first_w2c, size0 = V.load_map(path, torch.device("cuda"))
+    assert size0 == (2 * W, 2 * H)
+    steps = []
+    with torch.no_grad():
+        eng = fused.FusedEngine(loaded, slam.setup_camera(2 * W, 2 * H, lk, first_w2c.cpu().numpy(), device="cuda"), variables=lvars)
+        view = eng.view_camera(W, H)
+        for t, name in enumerate(written):
+            for _ in range(3):
+                want = eng.render_view(view, time_idx=t, first_w2c=first_w2c.contiguous(), intrinsics=_intrinsics(W, H), mode=mode).rgb8
+                if mode == "centers" or not digest(view, steps):
+                    break
+            want = want.cpu().numpy()
+            got = np.asarray(Image.open(name))
+            assert got.shape == (H, W, 3) and got.dtype == np.uint8 and np.array_equal(got, want), (mode, t)
+            assert want.min() != want.max()
+    assert steps == digests
+
+
 def test_the_tool_writes_a_picture_per_pose(tmp_path):
     from PIL import Image
     from splatam_amd import pipeline
