@@ -36,6 +36,7 @@ extern "C" {
                                       splat_iter_mapping_step_ex -- the mapping loss of the refinement script (get_loss_gs);
                                       SPLAT_EVAL_LPIPS, SplatLpipsWorkspace, splat_lpips_* -- LPIPS from caller-supplied AlexNet weights (csrc/lpips.hip);
                                       splat_mesh_components, splat_mesh_component_stats -- connected components of a mesh (csrc/meshclean.hip);
+                                      SPLAT_MESH_SIMPLIFY_*, splat_mesh_simplify_keys / _vertices / _quadrics / _place / _faces -- vertex clustering with quadric placement (csrc/meshsimplify.hip);
                                       SplatMeshShade, SPLAT_MESH_SHADE_*, splat_mesh_vertex_normals, splat_mesh_visibility, splat_mesh_shade -- pictures of a mesh (csrc/meshshade.hip);
                                       16: the view layer (SplatViewArgs, splat_view_camera, splat_view_finish, SPLAT_VIEW_COLOR / _DEPTH / _SILHOUETTE);
                                       15: sensor bytes to the loop's planes in one launch (splat_frame_ingest_planes, SPLAT_DEPTH_U16 / _F32);
@@ -1272,6 +1273,54 @@ int splat_icp_solve(const double *partials, int64_t n, int32_t max_iterations, d
 int splat_mesh_components(const int32_t *faces, int32_t num_faces, int32_t num_vertices, int32_t *labels, void *stream);
 int splat_mesh_component_stats(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const int32_t *labels,
                                int32_t *num_v, int32_t *num_f, int64_t *area_q, int32_t *lo, int32_t *hi, void *stream);
+
+/* The mesh simplification layer (csrc/meshsimplify.hip, loop bodies in csrc/meshsimplify_math.h; added within ABI 17): vertex clustering
+ * with quadric placement (P. Lindstrom, "Out-of-core simplification of large polygonal models", SIGGRAPH 2000).  All vertices in one cell
+ * of a uniform grid of edge `cell` (metres) anchored at the WORLD ORIGIN become one vertex, placed where the summed plane quadrics of
+ * the faces around the cell are smallest: flat regions stay flat, edges and corners stay sharp.
+ *
+ * splat_mesh_simplify_keys: keys [num_vertices] int64.  Per axis i = floor((double)x / cell) (negative coordinates count, x = j cell
+ * belongs to cell j), |i| < 2^20; key = (iz + 2^20) << 42 | (iy + 2^20) << 21 | (ix + 2^20); -1 for a vertex that is not finite or
+ * has an index out of range.  The CLUSTER of a vertex is the rank of its key among the distinct keys in ascending order (the caller's
+ * work: a stable sort, a flag where a key differs from its predecessor, a prefix sum), -1 for a key of -1; clusters < num_vertices.
+ *
+ * splat_mesh_simplify_vertices: ADDS, per cluster, to count [num_vertices] int32 and to words 0..5 of sums
+ * [num_vertices][SPLAT_MESH_SIMPLIFY_SUMS] int64: the vertices, the sum of rint(p 2^32) (p = (x - centre) / cell, the vertex local to
+ * its cell, in [-1/2, 1/2)) and, with colors, the sum of rint(colour 2^32).  The caller zeroes count and sums first.
+ *
+ * splat_mesh_simplify_quadrics: ADDS to words 6..15 of sums.  Per face, n = (b - a) x (c - a) in double, n^ = n / |n|, area = |n| / 2; for
+ * every DISTINCT cluster g among the face's three, d = n^ . p of its first corner in g (|d| <= sqrt(3) / 2), and the ten numbers
+ * area {n^ n^T (xx xy xz yy yz zz), d n^ (x y z), d^2} as rint(. 2^SPLAT_MESH_AREA_BITS).  A face adds nothing when it names a vertex
+ * that does not exist or has no cluster, has no area, or has an area not below 2^22 m^2: then *refused is raised to 1 (the caller
+ * zeroes it).  A word holds 2^23 m^2 of faces.
+ *
+ * Both add by 64-bit integer atomics only (a wave adds up runs of lanes that share a cluster by shuffles first): the sums are exact in
+ * their quanta, independent of order and the same bits on every run.
+ *
+ * splat_mesh_simplify_place: per cluster c < num_clusters, from count, sums and cell_keys [num_clusters] (the key of the cluster's
+ * cell): positions [num_clusters][3] float32, colors (the mean; may be NULL), rank, fallback (int32) and value (double).  The mean
+ * m = sum p / count; with SPLAT_MESH_SIMPLIFY_QUADRIC the eigen-decomposition of A (cyclic Jacobi) and
+ * p = m + sum over l_i > 1e-3 max |l| of v_i (v_i . (b - A m)) / l_i; max |l| == 0 or a p outside [-1/2, 1/2]^3 gives p = m and
+ * fallback = 1.  rank: the eigenvalues used (0 with the mean); value: the quadric at p, the sum of area x (distance from the face's plane,
+ * in cells)^2, as it comes out (it may be a few quanta below zero).  The vertex is centre + p cell in double, rounded once.  A cluster with count <= 0 gets zeros.
+ *
+ * splat_mesh_simplify_faces: triples [num_faces][3] int32: the face's three clusters rotated so that the smallest comes first (the winding
+ * is kept), or (-1, -1, -1) for a face that names a vertex that does not exist or has no cluster, or two vertices of one cluster.
+ *
+ * Caller's stream, caller's memory, no allocation, nothing read back.  SPLAT_E_INVALID for negative sizes, a cell that is not positive
+ * and finite, and NULL pointers where something would be read or written; zero sizes succeed without a launch. */
+#define SPLAT_MESH_SIMPLIFY_SUMS 16
+#define SPLAT_MESH_SIMPLIFY_MEAN 0
+#define SPLAT_MESH_SIMPLIFY_QUADRIC 1
+int splat_mesh_simplify_keys(const float *vertices, int32_t num_vertices, double cell, int64_t *keys, void *stream);
+int splat_mesh_simplify_vertices(const float *vertices, const float *colors, int32_t num_vertices, const int32_t *cluster, double cell,
+                                 int32_t *count, int64_t *sums, void *stream);
+int splat_mesh_simplify_quadrics(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const int32_t *cluster,
+                                 double cell, int64_t *sums, int32_t *refused, void *stream);
+int splat_mesh_simplify_place(const int32_t *count, const int64_t *sums, const int64_t *cell_keys, int32_t num_clusters, double cell,
+                              int32_t placement, float *positions, float *colors, int32_t *rank, int32_t *fallback, double *value, void *stream);
+int splat_mesh_simplify_faces(const int32_t *faces, int32_t num_faces, int32_t num_vertices, const int32_t *cluster, int32_t *triples,
+                              void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LPIPS (added within ABI 17; csrc/lpips.hip, arithmetic in csrc/lpips_math.h): what the reference's eval() / eval_nvs() compute with

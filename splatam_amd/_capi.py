@@ -222,6 +222,7 @@ SPLAT_MESH_COMPARE_ROWS, SPLAT_MESH_COMPARE_PARTIALS = 256, 6 * 256
 SPLAT_ICP_STATE, SPLAT_ICP_ROWS, SPLAT_ICP_SUMS = 24, 256, 17      # (added within ABI 17: the ICP layer, csrc/icp.hip)
 SPLAT_MESH_AREA_BITS, SPLAT_MESH_AREA_BAD = 40, 1 << 62            # (added within ABI 17: the mesh cleaning layer, csrc/meshclean.hip)
 SPLAT_MESH_KEY_HIGHEST, SPLAT_MESH_KEY_LOWEST = 2 ** 31 - 1, -2 ** 31
+SPLAT_MESH_SIMPLIFY_SUMS, SPLAT_MESH_SIMPLIFY_MEAN, SPLAT_MESH_SIMPLIFY_QUADRIC = 16, 0, 1      # (added within ABI 17: csrc/meshsimplify.hip)
 SPLAT_MESH_SHADE_COLOR, SPLAT_MESH_SHADE_SHADED, SPLAT_MESH_SHADE_SHADED_COLOR, SPLAT_MESH_SHADE_NORMAL, SPLAT_MESH_SHADE_DEPTH = 0, 1, 2, 3, 4
 SPLAT_ICP_ITERATION, SPLAT_ICP_STATUS, SPLAT_ICP_FITNESS, SPLAT_ICP_RMSE = 16, 17, 18, 19
 SPLAT_ICP_PREV_FITNESS, SPLAT_ICP_PREV_RMSE, SPLAT_ICP_COUNT, SPLAT_ICP_POINTS = 20, 21, 22, 23
@@ -263,6 +264,8 @@ EXPORTS = (
     "splat_mesh_vertex_normals", "splat_mesh_visibility", "splat_mesh_shade",
     "splat_icp_transform", "splat_icp_accumulate", "splat_icp_solve",
     "splat_mesh_components", "splat_mesh_component_stats",
+    "splat_mesh_simplify_keys", "splat_mesh_simplify_vertices", "splat_mesh_simplify_quadrics", "splat_mesh_simplify_place",
+    "splat_mesh_simplify_faces",
     "splat_lpips_weight_floats", "splat_lpips_pack_floats", "splat_lpips_tap_size", "splat_lpips_workspace_layout", "splat_lpips_workspace_bind",
     "splat_lpips_pack", "splat_lpips_conv", "splat_lpips_planes", "splat_lpips_images",
 )
@@ -445,6 +448,11 @@ def lib():
     for name, args in (
         ("splat_mesh_components", [_fp, C.c_int32, C.c_int32, _fp, _fp]),
         ("splat_mesh_component_stats", [_fp, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+        ("splat_mesh_simplify_keys", [_fp, C.c_int32, C.c_double, _fp, _fp]),
+        ("splat_mesh_simplify_vertices", [_fp, _fp, C.c_int32, _fp, C.c_double, _fp, _fp, _fp]),
+        ("splat_mesh_simplify_quadrics", [_fp, C.c_int32, _fp, C.c_int32, _fp, C.c_double, _fp, _fp, _fp]),
+        ("splat_mesh_simplify_place", [_fp, _fp, _fp, C.c_int32, C.c_double, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp]),
+        ("splat_mesh_simplify_faces", [_fp, C.c_int32, C.c_int32, _fp, _fp, _fp]),
     ):
         f = getattr(L, name)
         f.restype = C.c_int

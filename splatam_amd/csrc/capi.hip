@@ -666,6 +666,43 @@ int splat_mesh_component_stats(const float *vertices, int32_t num_vertices, cons
     return check(launch_mesh_component_stats(vertices, num_vertices, faces, num_faces, labels, num_v, num_f, area_q, lo, hi, (hipStream_t)stream));
 }
 
+// the mesh simplification layer (csrc/meshsimplify.hip)
+static bool valid_cell(double cell) { return cell > 0.0 && cell <= 1.7e308; }
+
+int splat_mesh_simplify_keys(const float *vertices, int32_t num_vertices, double cell, int64_t *keys, void *stream) {
+    if (num_vertices < 0 || !valid_cell(cell) || (num_vertices > 0 && (!vertices || !keys))) return SPLAT_E_INVALID;
+    return check(launch_mesh_simplify_keys(vertices, num_vertices, cell, keys, (hipStream_t)stream));
+}
+
+int splat_mesh_simplify_vertices(const float *vertices, const float *colors, int32_t num_vertices, const int32_t *cluster, double cell,
+                                 int32_t *count, int64_t *sums, void *stream) {
+    if (num_vertices < 0 || !valid_cell(cell) || (num_vertices > 0 && (!vertices || !cluster || !count || !sums))) return SPLAT_E_INVALID;
+    return check(launch_mesh_simplify_vertices(vertices, colors, num_vertices, cluster, cell, count, sums, (hipStream_t)stream));
+}
+
+int splat_mesh_simplify_quadrics(const float *vertices, int32_t num_vertices, const int32_t *faces, int32_t num_faces, const int32_t *cluster,
+                                 double cell, int64_t *sums, int32_t *refused, void *stream) {
+    if (!valid_mesh_arrays(vertices, num_vertices, faces, num_faces) || !valid_cell(cell)) return SPLAT_E_INVALID;
+    if (num_vertices > 0 && num_faces > 0 && (!cluster || !sums || !refused)) return SPLAT_E_INVALID;
+    return check(launch_mesh_simplify_quadrics(vertices, num_vertices, faces, num_faces, cluster, cell, sums, refused, (hipStream_t)stream));
+}
+
+int splat_mesh_simplify_place(const int32_t *count, const int64_t *sums, const int64_t *cell_keys, int32_t num_clusters, double cell,
+                              int32_t placement, float *positions, float *colors, int32_t *rank, int32_t *fallback, double *value, void *stream) {
+    if (num_clusters < 0 || !valid_cell(cell) || (placement != SPLAT_MESH_SIMPLIFY_MEAN && placement != SPLAT_MESH_SIMPLIFY_QUADRIC))
+        return SPLAT_E_INVALID;
+    if (num_clusters > 0 && (!count || !sums || !cell_keys || !positions || !rank || !fallback || !value)) return SPLAT_E_INVALID;
+    return check(launch_mesh_simplify_place(count, sums, cell_keys, num_clusters, cell, placement == SPLAT_MESH_SIMPLIFY_QUADRIC, positions, colors,
+                                            rank, fallback, value, (hipStream_t)stream));
+}
+
+int splat_mesh_simplify_faces(const int32_t *faces, int32_t num_faces, int32_t num_vertices, const int32_t *cluster, int32_t *triples,
+                              void *stream) {
+    if (num_faces < 0 || num_vertices < 0 || (num_faces > 0 && (!faces || !triples)) || (num_faces > 0 && num_vertices > 0 && !cluster))
+        return SPLAT_E_INVALID;
+    return check(launch_mesh_simplify_faces(faces, num_faces, num_vertices, cluster, triples, (hipStream_t)stream));
+}
+
 // the mesh render layer (csrc/meshrender.hip)
 static bool finite_f(float x) { return x >= -3.0e38f && x <= 3.0e38f; }
 static bool valid_mesh_view(const SplatMeshView *v) {

@@ -69,21 +69,23 @@ SPLAT_HD void icp_add_terms(double *acc, const double *pm, const float *q, float
         for (int k = 0; k < 3; ++k) acc[8 + 3 * r + k] = ms_addd(acc[8 + 3 * r + k], ms_muld(a[r], b[k]));
 }
 
-// eigenvalues (the diagonal of A afterwards) and eigenvectors (the columns of V) of the symmetric 4 x 4 A, by cyclic Jacobi sweeps
-SPLAT_HD void icp_jacobi4(double A[4][4], double V[4][4]) {
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+// eigenvalues (the diagonal of A afterwards) and eigenvectors (the columns of V) of the symmetric N x N A, by cyclic Jacobi sweeps
+// (the 4 x 4 of Horn's form here, the 3 x 3 of a cluster's quadric in meshsimplify_math.h)
+template <int N>
+SPLAT_HD void icp_jacobi(double (*A)[N], double (*V)[N]) {
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
     double scale = 0.0;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) scale = ms_addd(scale, ms_muld(A[i][j], A[i][j]));
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) scale = ms_addd(scale, ms_muld(A[i][j], A[i][j]));
     const double tiny = ms_muld(scale, 6.223015277861142e-61);          // 2^-200 of the squared Frobenius norm
     for (int sweep = 0; sweep < kIcpMaxSweeps; ++sweep) {
         double off = 0.0;
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j) off = ms_addd(off, ms_muld(A[i][j], A[i][j]));
+        for (int i = 0; i < N; ++i)
+            for (int j = i + 1; j < N; ++j) off = ms_addd(off, ms_muld(A[i][j], A[i][j]));
         if (!(off > tiny)) break;
-        for (int p = 0; p < 3; ++p)
-            for (int q = p + 1; q < 4; ++q) {
+        for (int p = 0; p < N - 1; ++p)
+            for (int q = p + 1; q < N; ++q) {
                 const double apq = A[p][q];
                 if (apq == 0.0) continue;
                 // t = tan of the rotation angle, the smaller root of t^2 + 2 theta t - 1 = 0, theta = (aqq - app) / (2 apq)
@@ -91,18 +93,18 @@ SPLAT_HD void icp_jacobi4(double A[4][4], double V[4][4]) {
                 const double root = ms_sqrtd(ms_addd(ms_muld(theta, theta), 1.0));
                 const double t = theta >= 0.0 ? icp_divd(1.0, ms_addd(theta, root)) : icp_divd(-1.0, ms_subd(root, theta));
                 const double cs = icp_divd(1.0, ms_sqrtd(ms_addd(ms_muld(t, t), 1.0))), sn = ms_muld(t, cs);
-                for (int k = 0; k < 4; ++k) {                           // A <- A J (columns p, q)
+                for (int k = 0; k < N; ++k) {                           // A <- A J (columns p, q)
                     const double akp = A[k][p], akq = A[k][q];
                     A[k][p] = ms_subd(ms_muld(cs, akp), ms_muld(sn, akq));
                     A[k][q] = ms_addd(ms_muld(sn, akp), ms_muld(cs, akq));
                 }
-                for (int k = 0; k < 4; ++k) {                           // A <- J^T A (rows p, q)
+                for (int k = 0; k < N; ++k) {                           // A <- J^T A (rows p, q)
                     const double apk = A[p][k], aqk = A[q][k];
                     A[p][k] = ms_subd(ms_muld(cs, apk), ms_muld(sn, aqk));
                     A[q][k] = ms_addd(ms_muld(sn, apk), ms_muld(cs, aqk));
                 }
                 A[p][q] = A[q][p] = 0.0;
-                for (int k = 0; k < 4; ++k) {                           // V <- V J
+                for (int k = 0; k < N; ++k) {                           // V <- V J
                     const double vkp = V[k][p], vkq = V[k][q];
                     V[k][p] = ms_subd(ms_muld(cs, vkp), ms_muld(sn, vkq));
                     V[k][q] = ms_addd(ms_muld(sn, vkp), ms_muld(cs, vkq));
@@ -110,6 +112,8 @@ SPLAT_HD void icp_jacobi4(double A[4][4], double V[4][4]) {
             }
     }
 }
+
+SPLAT_HD void icp_jacobi4(double A[4][4], double V[4][4]) { icp_jacobi<4>(A, V); }
 
 // the proper rotation U [9] row-major that maximises trace(U M), M [9] row-major = sum (p - a)(q - b)^T
 SPLAT_HD void icp_horn(const double *M, double *U) {

@@ -146,6 +146,15 @@ hipError_t launch_icp_solve(const double *partials, long long n, int32_t max_ite
 hipError_t launch_mesh_components(const int32_t *faces, int32_t F, int32_t V, int32_t *labels, hipStream_t s);
 hipError_t launch_mesh_component_stats(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const int32_t *labels, int32_t *num_v,
                                        int32_t *num_f, int64_t *area_q, int32_t *lo, int32_t *hi, hipStream_t s);
+// meshsimplify.hip: vertex clustering on a world-anchored grid with quadric placement -- keys, per-cluster sums, placement, renamed faces
+hipError_t launch_mesh_simplify_keys(const float *vertices, int32_t V, double cell, int64_t *keys, hipStream_t s);
+hipError_t launch_mesh_simplify_vertices(const float *vertices, const float *colors, int32_t V, const int32_t *cluster, double cell,
+                                         int32_t *count, int64_t *sums, hipStream_t s);
+hipError_t launch_mesh_simplify_quadrics(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const int32_t *cluster, double cell,
+                                         int64_t *sums, int32_t *refused, hipStream_t s);
+hipError_t launch_mesh_simplify_place(const int32_t *count, const int64_t *sums, const int64_t *cell_keys, int32_t n, double cell, int quadric,
+                                      float *positions, float *colors, int32_t *rank, int32_t *fallback, double *value, hipStream_t s);
+hipError_t launch_mesh_simplify_faces(const int32_t *faces, int32_t F, int32_t V, const int32_t *cluster, int32_t *triples, hipStream_t s);
 // meshrender.hip: the depth image of a triangle mesh (z-buffer), views that see each vertex, and the sums of a depth comparison
 hipError_t launch_mesh_depth(const float *vertices, int32_t V, const int32_t *faces, int32_t F, const SplatMeshView &view, float *depth,
                              hipStream_t s);

@@ -22,6 +22,10 @@ view saw and gives the same mesh bit for bit: an apartment at 1 cm, a room at 5 
 ``--clean`` (``extract_mesh(..., clean=True)`` or a dict of ``mesh_clean.clean_mesh`` keywords) removes the mesh's small connected
 components -- the floaters of rendered depth -- on the device before it is returned or written.  Off by default.
 
+``--simplify CELL [--simplify-placement quadric|mean]`` (``mesh_from_params(..., simplify=CELL)``) merges the vertices in each cell of
+a grid of that edge, placed by the cell's quadrics, after the cleaning and before the file (``mesh_simplify.simplify_mesh``).  Off by
+default.
+
 The command loads a ``params.npz`` as ``python -m splatam_amd.run`` writes it; poses come from the map, frames from
 ``keyframe_time_indices`` when present (otherwise every ``--every``-th), size and intrinsics from ``org_width`` / ``org_height`` /
 ``intrinsics``.
@@ -514,19 +518,25 @@ def _cleaned(mesh, clean, device, cleaning=None):
 
 def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None, sil_thres=0.99, depth_max=0.0, bounds=None,
                      max_bytes=DEFAULT_MAX_BYTES, device="cuda:0", verbose=True, sparse=False, clean=None, cleaning=None, method="tetrahedra", views=None,
-                     views_mode="shaded"):
+                     views_mode="shaded", simplify=None, simplification=None):
     """``extract_mesh`` of a ``params.npz`` written to ``out`` (a PLY); returns the ``Mesh``.  ``method``: ``extract_mesh``'s.  ``clean`` (True or a dict of
     ``mesh_clean.clean_mesh`` keywords): the mesh is cleaned before it is written; ``cleaning``, a dict, then receives the report.
+    ``simplify`` (a cell size in metres, or a dict of ``mesh_simplify.simplify_mesh`` keywords that names ``cell``): the mesh is simplified
+    -- after the cleaning, so that no floater is merged into the surface it floats over, and before it is written and pictured;
+    ``simplification``, a dict, then receives the report.
     ``views`` (a directory): pictures ``mesh_%04d.png`` of the mesh that was written, in ``views_mode``, at every ``every``-th estimated
     pose of the run (``mesh_view.render_trajectory``)."""
     from . import slam
     from .export import save_mesh_ply
     from .fused import FusedEngine
     from .mesh_clean import clean_options, format_cleaning
+    from .mesh_simplify import _simplified, format_simplification, simplify_options
     from .view import _scaled_intrinsics, load_map
     check_method(method)
     clean = clean_options(clean)
     found = {} if cleaning is None else cleaning
+    simplify = simplify_options(simplify)
+    simplified = {} if simplification is None else simplification
     dev = torch.device(device)
     params, variables, k, first_w2c, (W0, H0), more = load_map(path, dev, extras=("keyframe_time_indices",))
     keyframes = [int(t) for t in more["keyframe_time_indices"]] if more["keyframe_time_indices"] is not None else []
@@ -539,11 +549,14 @@ def mesh_from_params(path, out, voxel_size=0.01, trunc=None, every=5, size=None,
         mesh = extract_mesh(engine, frames, (W, H), intrinsics, voxel_size=voxel_size, trunc=trunc, bounds=bounds, max_bytes=max_bytes,
                             sil_thres=sil_thres, depth_max=depth_max, first_w2c=first_w2c.contiguous(), sparse=sparse, method=method)
         mesh = _cleaned(mesh, clean, dev, found)            # (not through extract_mesh: the report is wanted)
+        mesh = _simplified(mesh, simplify, dev, simplified)
     save_mesh_ply(out, mesh.vertices.cpu().numpy(), mesh.faces.cpu().numpy(), mesh.colors.cpu().numpy())
     if verbose:
         print(f"{out}: {mesh.vertices.shape[0]} vertices, {mesh.faces.shape[0]} faces from {len(frames)} views", flush=True)
         if clean is not None:
             print(format_cleaning(found), flush=True)
+        if simplify is not None:
+            print(format_simplification(simplified), flush=True)
     if views is not None:
         from . import mesh_view
         poses, _, _ = mesh_view.params_poses(path)
@@ -574,6 +587,9 @@ def _parser():
     parser.add_argument("--min-vertices", type=int, default=None, metavar="N", help="with --clean: components with fewer vertices go (200)")
     parser.add_argument("--min-area", type=float, default=None, metavar="M2", help="with --clean: components with less area in m^2 go (0)")
     parser.add_argument("--keep-largest", type=int, default=None, metavar="K", help="with --clean: keep at most the K components with the most faces")
+    parser.add_argument("--simplify", type=float, default=None, metavar="CELL",
+                        help="merge the vertices in each cell of a grid of this edge (metres) before the mesh is written (python -m splatam_amd.mesh_simplify)")
+    parser.add_argument("--simplify-placement", default=None, choices=("quadric", "mean"), help="with --simplify: where a cell's vertex sits (quadric)")
     parser.add_argument("--views", default=None, metavar="DIR",
                         help="also write pictures mesh_%%04d.png of the mesh at every --every-th estimated pose (python -m splatam_amd.mesh_view)")
     parser.add_argument("--views-mode", default=None, choices=("shaded", "shaded-color", "color", "normal", "depth"), help="with --views (default shaded)")
@@ -589,12 +605,15 @@ def main(argv=None):
         parser.error("--min-vertices, --min-area and --keep-largest need --clean")
     if args.views_mode and not args.views:
         parser.error("--views-mode needs --views")
+    if args.simplify_placement and args.simplify is None:
+        parser.error("--simplify-placement needs --simplify")
+    simplify = {} if args.simplify is None else {"simplify": dict(cell=args.simplify, **({"placement": args.simplify_placement} if args.simplify_placement else {}))}
     bounds = (args.bounds[:3], args.bounds[3:]) if args.bounds else None
     try:
         mesh_from_params(args.params, args.out, voxel_size=args.voxel, trunc=args.trunc, every=args.every, size=args.size,
                          sil_thres=args.sil_thres, depth_max=args.depth_max, bounds=bounds, max_bytes=args.max_bytes, device=args.device,
                          sparse=args.sparse, method=args.method, **({"clean": options or True} if args.clean else {}),
-                         **({"views": args.views, "views_mode": args.views_mode or "shaded"} if args.views else {}))
+                         **({"views": args.views, "views_mode": args.views_mode or "shaded"} if args.views else {}), **simplify)
     except ValueError as e:
         raise SystemExit(str(e)) from None
     return 0

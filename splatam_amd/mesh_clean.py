@@ -15,7 +15,7 @@ from ``extract()`` are welded, a loaded PLY is taken as it is.  A face with a re
 a face that names a vertex that does not exist links nothing and is dropped; a vertex no face names is a component of its own, with 0
 faces.
 
-Not here: welding, hole filling, smoothing, decimation, face-adjacency (edge-sharing) connectivity, a CPU path.
+Not here: welding, hole filling, smoothing, face-adjacency (edge-sharing) connectivity, a CPU path.
 """
 from __future__ import annotations
 

@@ -96,7 +96,10 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
     ``stats['mesh_score']['alignment']`` records what was found.  ``mesh=dict(method="cubes")``: the mesh is extracted by marching
     cubes instead of marching tetrahedra (``mesh.extract_mesh``).  ``mesh=dict(clean=True)`` (or ``clean=`` a dict of
     ``mesh_clean.clean_mesh`` keywords): the mesh's small connected components are removed before it is written and scored;
-    ``stats['mesh_cleaning']`` is the report, and with ``gt_mesh`` it is ``stats['mesh_score']['cleaning']`` too."""
+    ``stats['mesh_cleaning']`` is the report, and with ``gt_mesh`` it is ``stats['mesh_score']['cleaning']`` too.
+    ``mesh=dict(simplify=CELL)`` (or ``simplify=`` a dict of ``mesh_simplify.simplify_mesh`` keywords that names ``cell``): the mesh is
+    simplified after the cleaning and before it is written, so with ``gt_mesh`` the simplified mesh is what is scored;
+    ``stats['mesh_simplification']`` is the report."""
     from . import datasets, pipeline
     separate_densification, separate_tracking = apply_defaults(config)
     check_supported(config)
@@ -148,11 +151,15 @@ def run(config, engine="fused", num_frames=None, evaluate=True, prefetch=4, resu
             stats['mesh'] = os.path.join(os.path.dirname(path), "mesh.ply")
             mesh_options = dict(mesh) if isinstance(mesh, dict) else {}
             cleaning = {} if mesh_options.get("clean") else None
-            mesh_from_params(path, stats['mesh'], device=device, **mesh_options, **({"cleaning": cleaning} if cleaning is not None else {}))
+            simplification = {} if mesh_options.get("simplify") else None
+            mesh_from_params(path, stats['mesh'], device=device, **mesh_options, **({"cleaning": cleaning} if cleaning is not None else {}),
+                             **({"simplification": simplification} if simplification is not None else {}))
             if mesh_options.get("views"):
                 stats['mesh_views'] = mesh_options["views"]
             if cleaning is not None:
                 stats['mesh_cleaning'] = cleaning
+            if simplification is not None:
+                stats['mesh_simplification'] = simplification
             if gt_mesh is not None:
                 from .mesh_score import load_transform, score_culled_in_map_frame, score_mesh
                 transform = load_transform(gt_transform) if isinstance(gt_transform, (str, os.PathLike)) else gt_transform
@@ -193,6 +200,9 @@ def _parser():
                         help="with --mesh: the surface extractor (python -m splatam_amd.mesh --method); cubes: about a third of the triangles")
     parser.add_argument("--clean-mesh", action="store_true",
                         help="with --mesh: remove the mesh's small connected components before it is written and scored (splatam_amd.mesh_clean)")
+    parser.add_argument("--simplify-mesh", type=float, default=None, metavar="CELL",
+                        help="with --mesh: merge the vertices in each cell of a grid of this edge (metres) before the mesh is written and scored "
+                             "(splatam_amd.mesh_simplify)")
     parser.add_argument("--mesh-views", default=None, metavar="DIR",
                         help="with --mesh: pictures of the mesh along the estimated trajectory into DIR (python -m splatam_amd.mesh --views)")
     parser.add_argument("--gt-mesh", default=None, metavar="GT.ply",
@@ -224,9 +234,12 @@ def main(argv=None):
         parser.error("--mesh-method needs --mesh")
     if args.mesh_views and not args.mesh:
         parser.error("--mesh-views needs --mesh")
+    if args.simplify_mesh is not None and not args.mesh:
+        parser.error("--simplify-mesh needs --mesh")
     mesh = args.mesh
-    if args.mesh_sparse or args.clean_mesh or args.mesh_method or args.mesh_views:
+    if args.mesh_sparse or args.clean_mesh or args.mesh_method or args.mesh_views or args.simplify_mesh is not None:
         mesh = dict(**({"sparse": True} if args.mesh_sparse else {}), **({"clean": True} if args.clean_mesh else {}),
+                    **({"simplify": args.simplify_mesh} if args.simplify_mesh is not None else {}),
                     **({"method": args.mesh_method} if args.mesh_method else {}), **({"views": args.mesh_views} if args.mesh_views else {}))
     config = load_experiment(args.experiment)
     seed_everything(config['seed'])

@@ -561,13 +561,17 @@ class SlamSession:
         Further keywords (``voxel_size``, ``trunc``, ``bounds``, ``max_bytes``, ``sil_thres``, ``depth_max``, ``weight_max``,
         ``min_weight``, ``sparse``, ``clean``) go to ``mesh.extract_mesh``, as does ``method`` (``"tetrahedra"``, or ``"cubes"`` for
         marching cubes: about a third of the triangles; anything else is a ValueError); ``clean=True`` (or a dict of ``mesh_clean.clean_mesh``
-        keywords) removes the mesh's small connected components.  ``path``: also written there as a PLY.  ``views`` (a directory): pictures
+        keywords) removes the mesh's small connected components.  ``simplify`` (a cell size in metres, or a dict of
+        ``mesh_simplify.simplify_mesh`` keywords that names ``cell``) merges the vertices in each cell of a grid, after the cleaning.
+        ``path``: also written there as a PLY.  ``views`` (a directory): pictures
         ``mesh_%04d.png`` of the mesh in ``views_mode`` at the estimated poses of ``frames``, numbered by time index
         (``mesh_view.render_trajectory``).  Returns the ``Mesh`` (on the device).
         Between frames and after ``finish()``; engine "fused" only.  The map, the optimiser state and the loop's cameras are left
         as they were."""
         from . import mesh as mesh_mod
+        from .mesh_simplify import _simplified, simplify_options
         mesh_mod.check_method(method)
+        simplify = simplify_options(kwargs.pop("simplify", None))
         if not self.fused:
             raise NotImplementedError("extract_mesh needs engine='fused'")
         if self.engine is None:
@@ -580,6 +584,7 @@ class SlamSession:
             frames = list(self.keyframe_time_indices) or list(range(self.frames_seen))
         with torch.no_grad():
             result = mesh_mod.extract_mesh(self.engine, frames, (W, H), k_view, first_w2c=self.first_frame_w2c.contiguous(), method=method, **kwargs)
+            result = _simplified(result, simplify, self.engine.dev)
         if path is not None:
             from .export import save_mesh_ply
             save_mesh_ply(path, result.vertices.cpu().numpy(), result.faces.cpu().numpy(), result.colors.cpu().numpy())
