@@ -97,8 +97,8 @@ def test_multiview_partition(size):
 @pytest.mark.parametrize("tracking", [False, True])
 def test_view_at_a_real_pose_vs_oracle(view, tracking, monkeypatch):
     """The in-register transform_to_frame of F1 / F6 at a 20-degree pose and at one that puts a fifth of the map behind the near
-    plane (and much of the rest beyond the 1.3 tan(fov) clamp), staged (A)..(D) against the C oracle with the tolerances of
-    tests/test_gpu_configs.py."""
+    plane (the clamped rows of that view carry no gradient: tests/test_gpu_closeup.py covers the 1.3 tan(fov) clamp), staged
+    (A)..(D) against the C oracle with the tolerances of tests/test_gpu_configs.py."""
     from splatam_amd import slam
     from splatam_amd.fused import FusedEngine
     t0 = time.time()

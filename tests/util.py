@@ -291,7 +291,10 @@ MULTIVIEW_SIZES = {
 # keyframe poses (time indices 1..8; 0 stays the identity the map was made at): rotation (degrees about x, about y), translation (m).
 # Every pose turns or moves the camera towards +x, so a strip of the map on that side is seen by no keyframe; x rotations of both
 # signs make the top and bottom rows come and go; view 8 moves 1.4 m forward: the near part of the map (z < ~1.6) is behind the
-# 0.2 near plane and much of the rest projects far outside the image (the 1.3 tan(fov) clamp of the projection's Jacobian).
+# 0.2 near plane (at size B 61 777 rows; 773 live rows at z < 0.4) and much of the rest projects far outside the image.  That view
+# covers the NEAR PLANE, not the 1.3 tan(fov) clamp of the projection's Jacobian: its footprints stay at or below 62 px, a splat
+# centred beyond the clamp needs a radius of 0.15 W (180 px at B) to touch a pixel, so no row with the clamp active carries a
+# gradient, at either size.  The clamp is covered by the walk-through scene of tests/closeup_cases.py.
 MULTIVIEW_POSES = (
     ((0.0, 8.0), (0.10, 0.00, 0.00)),
     ((5.0, 14.0), (0.15, -0.05, 0.05)),
